@@ -15,7 +15,7 @@ The multi-GPU machinery is the library's (include/rpt.h: rpt_create_rank, rpt_re
 rpt_resident_gather_device); torch.distributed (gloo) only carries the 128-byte communicator id, the barriers and the
 max over ranks of the elapsed time.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
        (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
 Prints ONE JSON line on rank 0.
 """
@@ -357,6 +357,36 @@ def rank_tiles_leg(rpt, torch, device, small, world=8):
                     "as fast as this one"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20240601
+
+
+def image_outputs(name, image, limit_bytes):
+    """What --dump-outputs writes of an [H, W, 4] f32 image: the whole image as `name` when it fits in limit_bytes, else a fixed,
+    seeded sample of its pixels as `name`_sample [k, 4] (f32) and their flat indices y * W + x as `name`_sample_index [k] (f64)."""
+    import numpy as np
+    a = image.detach().cpu().numpy() if hasattr(image, "detach") else np.asarray(image)
+    if a.nbytes <= limit_bytes:
+        return {name: a}
+    h, w, c = a.shape
+    k = limit_bytes // (c * a.itemsize + 8)
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(h * w, size=k, replace=False))
+    return {name + "_sample": a.reshape(h * w, c)[idx], name + "_sample_index": idx.astype(np.float64)}
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy for every array (f32 or f64), DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "--dump-outputs: %d bytes" % total
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
+
+
 def timed_steps(torch, tracer, buf, spp, steps):
     """Mean device time of `steps` launches of `spp` samples (HIP events on the launch stream), in seconds."""
     tracer.render_n(buf, spp)
@@ -660,6 +690,11 @@ def main():
     ap.add_argument("--force-multi", action="store_true", help="TEST ONLY: take the N > 1 path with however many ranks there are (one, without a launcher)")
     ap.add_argument("--small", action="store_true", help="TEST ONLY: 1/8-size frames and 1/16 of the samples (control-flow rehearsals)")
     ap.add_argument("--general-kernels-leg", action="store_true", help="INTERNAL: the `general_kernels` secondary leg (a process of its own: see headline_variants)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path handed its caller (the accumulated frame and its frame count; "
+                         "N > 1: rank 0's gathered frame, a fixed sample of its pixels if it is larger than 32 MB; 64 MB in all) as DIR/<name>.npy. "
+                         "The frame accumulates the warmup and the timed steps, (warmup + steps) x spp frames: two runs compare only with the "
+                         "same --warmup and --steps")
     args = ap.parse_args()
     if args.general_kernels_leg:
         return general_kernels_leg(args.small)
@@ -890,6 +925,8 @@ def main():
         elapsed = time.perf_counter() - t0
         kernel_ms = [a.elapsed_time(b) for a, b in evs]
         local_pixels = width * height
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {**image_outputs("pixels", buf.pixels, DUMP_LIMIT_BYTES // 2), "frames": [float(buf.frames)]})
     else:
         # ---- N GPUs: configs[2], strong scaling, gather to rank 0 inside the timed region
         width, height, spp = shrink(C3)
@@ -970,6 +1007,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
         local_pixels = tiling.tile_row_count(height, TILE_ROWS, rank, world) * width
+        if args.dump_outputs and rank == 0 and job:
+            dump_outputs(args.dump_outputs, {**image_outputs("image", job.image, DUMP_LIMIT_BYTES // 2), "frames": [float(job.frames)]})
         # The headline is measured.  What follows are secondary legs on the same communicator: they must never cost the line.
         # A leg that raises is recorded and ends the legs on this rank; ranks that then wait for it in a collective — or a leg that
         # hangs — are cut off by a timer that emits the line with what there is and leaves.

@@ -7,7 +7,7 @@
 // imports tools/).  The shipped path (rust-pathtracer_amd/) never includes,
 // links or loads anything from here, and has no CPU fallback.
 //
-// PARITY UNPINNED: the reference (/root/reference, crate v0.2.4) ships no tests,
+// PARITY UNPINNED: the reference (crate v0.2.4) ships no tests,
 // golden vectors or fixtures, cannot be compiled here (no Rust toolchain), and its
 // RNG (rand::thread_rng, tracer.rs:44) is OS-seeded.  Nothing external pins these
 // results.  What pins them is: this file follows the reference statement by
@@ -1249,6 +1249,10 @@ struct Tracer {
                 uint32_t row_mem = row_end - 1u - (uint32_t)jj;                    // bottom-up like par_rchunks
                 for (uint32_t col = 0; col < width; ++col) {
                     F3 radiance = sample_pixel(col, row_mem, width, height, fkey);
+                    // PROJECT-DEFINED (kernel_common.h, blend): a sample whose radiance is not finite is blended as black, not
+                    // left to make the pixel NaN for good (tracer.rs:105-117 blends whatever the path returned)
+                    if (!std::isfinite(raw(radiance.x)) || !std::isfinite(raw(radiance.y)) || !std::isfinite(raw(radiance.z)))
+                        radiance = F3(0.0f, 0.0f, 0.0f);
                     Raw* pixel = mean + ((size_t)row_mem * width + col) * 4;
                     F color[4] = {radiance.x, radiance.y, radiance.z, F(1.0f)};    // tracer.rs:59,105
                     for (int c = 0; c < 4; ++c)                                    // mix_color, tracer.rs:108-113

@@ -230,9 +230,16 @@ RPT_DEV float4* pixel_address_again(const RenderParams& rp)
     return reinterpret_cast<float4*>(rp.pixels) + pixel_setup(rp, tid).pix_offset;
 }
 
-// mix_color, tracer.rs:108-113, with color = [r, g, b, 1.0] (tracer.rs:59,105)
+// mix_color, tracer.rs:108-113, with color = [r, g, b, 1.0] (tracer.rs:59,105).  PROJECT-DEFINED: a sample whose radiance is not
+// finite is blended as black.  The reference's BSDF returns NaN for a few degenerate directions (configs[1]: about one sample in 10^5..10^6),
+// and tracer.rs blends it, which leaves the pixel NaN for every later frame.  The oracle does the same (rpt_oracle.hpp, render).
+// A bit test, not isfinite: it holds in a fast-math build too.
 RPT_DEV void blend(float4& acc, v3 rad, float v)
 {
+    const uint32_t exp_mask = 0x7f800000u;
+    if ((__float_as_uint(rad.x) & exp_mask) == exp_mask || (__float_as_uint(rad.y) & exp_mask) == exp_mask ||
+        (__float_as_uint(rad.z) & exp_mask) == exp_mask)
+        rad = mk3(0.0f, 0.0f, 0.0f);
     acc.x = (1.0f - v) * acc.x + rad.x * v;
     acc.y = (1.0f - v) * acc.y + rad.y * v;
     acc.z = (1.0f - v) * acc.z + rad.z * v;

@@ -104,7 +104,11 @@ def test_multi_device_render_fans_out(rpt, oracle, torch_cuda, pin):
     before its upload) must precede the event of rank 0's end (recorded behind its kernel) — with one loop doing upload ->
     kernel -> download per device on a pageable buffer (round 2's code) rank 1 begins only after rank 0's download, i.e. after
     rank 0's end.  Run in a child process per setting: RPT_PIN_HOST is read once per process (1: the caller's buffer is
-    page-locked for the call; 0: pageable copies, the two-pass order alone must do it)."""
+    page-locked for the call; 0: pageable copies, the two-pass order alone must do it).
+    As many ranks as the GPU gives the process hardware queues, up to 4: the HIP runtime puts a process's streams on at most
+    GPU_MAX_HW_QUEUES queues (4 by default), and with 2 a third virtual rank's stream shares rank 0's in-order queue, so it begins
+    when rank 0 ends whatever the library enqueues (measured with 2 queues and 4 ranks: begin(rank k) - end(rank 0) = 1.99, -0.20,
+    -2.06 ms for k = 1, 2, 3)."""
     import subprocess
     import sys
     code = r"""
@@ -114,7 +118,7 @@ sys.path.insert(0, %r); sys.path.insert(0, %r)
 import conftest, oracle_lib
 rpt = conftest.load_package()
 os.environ["RPT_GATHER"] = "p2p"
-n, w, h, spp = 4, 512, 384, 64
+n, w, h, spp = %d, 512, 384, 64
 t = rpt.Tracer(rpt.AnalyticalScene(), devices=[0] * n, seed=1)
 buf = rpt.ColorBuffer(w, h)
 t.render_n(buf, 1)                                 # warm: module load, staging allocations
@@ -133,7 +137,8 @@ same = (buf.image().view(np.uint32) == want.view(np.uint32)).all()
 import json
 print("RESULT" + json.dumps([own, gaps, bool(same)]))
 t.close()
-""" % (os.path.dirname(os.path.abspath(__file__)), os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+""" % (os.path.dirname(os.path.abspath(__file__)), os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."),
+       max(2, min(4, int(os.environ.get("GPU_MAX_HW_QUEUES", "4")))))
     env = dict(os.environ, RPT_PIN_HOST=pin)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr

@@ -296,3 +296,22 @@ def test_sdf_object_known_answers(oracle, rpt):
     assert np.abs(a[16:32, 16:32].mean(axis=(0, 1)) - b[16:32, 16:32].mean(axis=(0, 1))).max() < 0.03
     # outside the silhouette both are the constant background
     assert np.allclose(a[0, 0], 0.3, atol=1e-6) and np.array_equal(a[0, 0], b[0, 0])
+
+
+def test_a_sample_that_is_not_finite_is_blended_as_black(oracle):
+    """Sample 188 of pixel (row 177, col 1624) of configs[1]'s 1920x1080 frame (seed 1) is NaN: the reference's BSDF on a
+    degenerate direction.  Rendered, the pixel stays finite: it is the running mean of tracer.rs:105-117 over its 256 samples with
+    that one blended as black (rpt_oracle.hpp render, kernel_common.h blend)."""
+    desc = oracle.scene_analytical()
+    w, h, y, x, spp = 1920, 1080, 177, 1624, 256
+    s = oracle.sample_pixels(desc, np.full(spp, x), np.full(spp, y), np.arange(spp), w, h)
+    assert np.isnan(s[188]).all() and np.isfinite(np.delete(s, 188, axis=0)).all()
+    got = oracle.render_rows(desc, w, h, spp, [y], seed=1)[y, x]
+    one = np.float32(1.0)
+    acc = np.zeros(4, dtype=np.float32)
+    for f in range(spp):
+        v = one / np.float32(f + 1)
+        color = np.array([0.0, 0.0, 0.0, 1.0] if f == 188 else [s[f, 0], s[f, 1], s[f, 2], 1.0], dtype=np.float32)
+        acc = ((one - v) * acc + color * v).astype(np.float32)
+    assert np.isfinite(got).all()
+    assert np.array_equal(got.view(np.uint32), acc.view(np.uint32)), (got, acc)

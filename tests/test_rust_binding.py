@@ -387,23 +387,67 @@ def test_the_rust_surface_the_integration_guide_promises():
         assert m.group(1) or src.count(m.group(2) + "(") >= 2, "%s is declared and never called" % m.group(2)
 
 
-REFERENCE = "/root/reference"
+FINGERPRINT = os.path.join(ROOT, "tests", "golden", "reference_integration_fingerprint.json")
+
+
+def _line_hash(line):
+    import hashlib
+    return hashlib.sha256(line.encode()).hexdigest()
+
+
+def _placeholder(i):
+    return "// line %d of the reference (fingerprint only)" % (i + 1)
+
+
+def _reference_tree_from_fingerprint(tree, fp, patch_text):
+    """What the patch sees of the reference, rebuilt from its fingerprint: every line a hunk shows (context or removed) in
+    its place, checked against the line's hash, a numbered placeholder for every other line, and an empty file for every
+    module of the crate roots."""
+    hunks = {}
+    for part in re.split(r"^diff .*\n", patch_text, flags=re.M)[1:]:
+        path = re.search(r"^\+\+\+ b/(\S+)", part, flags=re.M).group(1)
+        for m in re.finditer(r"^@@ -(\d+)(?:,(\d+))? \+\d+(?:,\d+)? @@[^\n]*\n((?:[ +\-\\][^\n]*\n?)*)", part, flags=re.M):
+            hunks.setdefault(path, []).append((int(m.group(1)), int(m.group(2) or 1), m.group(3).splitlines()))
+    assert set(hunks) == set(fp["files"]), (sorted(hunks), sorted(fp["files"]))
+    for path, entry in fp["files"].items():
+        if entry is None:                              # created by the patch: the reference has no such file
+            assert all(start == 0 and count == 0 for start, count, _ in hunks[path]), path
+            continue
+        lines = [_placeholder(i) for i in range(len(entry["lines"]))]
+        for start, count, body in hunks[path]:
+            old = [l[1:] for l in body if l[:1] in (" ", "-")]
+            assert len(old) == count, (path, start)
+            for j, text in enumerate(old):
+                i = start - 1 + j
+                assert i < len(lines) and _line_hash(text) == entry["lines"][i], \
+                    "%s:%d is not the reference's line: %r" % (path, i + 1, text)
+                lines[i] = text
+        f = tree / path
+        f.parent.mkdir(parents=True, exist_ok=True)
+        f.write_text("\n".join(lines) + ("\n" if entry["final_newline"] else ""))
+    for src, names in fp["modules"].items():
+        for name in names:
+            f = tree / src / name
+            if not f.exists():
+                f.parent.mkdir(parents=True, exist_ok=True)
+                f.write_text("")
 
 
 def test_the_integration_patch_applies_to_the_reference_tree(tmp_path):
     """rust/integration.patch is everything a maintainer changes in the reference beside dropping the two source files in:
     `pub mod gpu_tracer;` (rust-pathtracer/src/lib.rs:12-22), the link stanza (build.rs + Cargo.toml), `mod analytical_gpu;` and
-    the ONE changed statement of renderer/src/main.rs:41-42.  `git apply --check` against a copy of /root/reference (never the
-    tree itself), then the patched tree is looked at the way rustc's module resolution would: every `mod` names a file that
-    exists, the crate that forbids `unsafe` gained none, what main.rs imports is `pub` in gpu_tracer.rs, and `pt.render(&mut buffer)`
-    / `buffer.convert_to_u8(frame)` (main.rs:118-122) are untouched."""
-    import pytest
+    the ONE changed statement of renderer/src/main.rs:41-42.  The reference tree is stood for by its fingerprint
+    (tests/golden/reference_integration_fingerprint.json: the hash of every line of the files the patch touches, the module files
+    of the crate roots; tools/make_reference_fingerprint.py): every line a hunk shows must be the reference's line at that place,
+    then `git apply --check` and `git apply` on the tree rebuilt from it, and the patched tree is looked at the way rustc's module
+    resolution would: every `mod` names a file that exists, the crate that forbids `unsafe` gained none, what main.rs imports is
+    `pub` in gpu_tracer.rs, and `pt.render(&mut buffer)` / `buffer.convert_to_u8(frame)` (main.rs:118-122) are untouched."""
+    import json
     import shutil
-    if not os.path.isdir(REFERENCE):
-        pytest.skip("the reference tree is not on this machine (GPU box)")
-    tree = tmp_path / "reference"
-    shutil.copytree(REFERENCE, tree, ignore=shutil.ignore_patterns("images", ".git"))
+    fp = json.load(open(FINGERPRINT))
     patch = os.path.join(ROOT, "rust", "integration.patch")
+    tree = tmp_path / "reference"
+    _reference_tree_from_fingerprint(tree, fp, open(patch).read())
     before = (tree / "renderer" / "src" / "main.rs").read_text()
     for args in (["--check"], []):
         r = subprocess.run(["git", "apply", "-p1"] + args + [patch], cwd=tree, capture_output=True, text=True)
@@ -429,7 +473,10 @@ def test_the_integration_patch_applies_to_the_reference_tree(tmp_path):
     # the redraw handler is the reference's own, line for line: only additions above it and one statement changed
     changed = [l for l in before.splitlines() if l not in main.splitlines()]
     assert changed == ["    let mut pt = Tracer::new(scene);"], changed
-    assert "pt.render(&mut buffer);" in main and "buffer.convert_to_u8(frame);" in main
+    main_fp = fp["files"]["renderer/src/main.rs"]["lines"]
+    for line in ("                pt.render(&mut buffer);", "                buffer.convert_to_u8(frame);"):
+        assert _line_hash(line) in main_fp, line
+        assert _placeholder(main_fp.index(_line_hash(line))) in main.splitlines(), line
     # the link stanza: a build script the manifest names, asking for the library include/rpt.h is the header of
     cargo = (tree / "rust-pathtracer" / "Cargo.toml").read_text()
     build = (tree / "rust-pathtracer" / "build.rs").read_text()

@@ -1,8 +1,8 @@
 """configs[1] (1920x1080 x 256 spp, seed 1) rendered whole by the strict f32 oracle (= the GPU frame, bit for bit: tests/test_gpu_parity.py)
 and by the oracle over double (liboracle_f64.so): the whole-frame figures bench.py's `f64_reference` (every third row) is a sample of.
 CPU only, ~90 s on 8 cores:   python tools/f64_whole_frame.py > profiles/r6/f64_whole_frame.txt"""
-import sys,time
-sys.path.insert(0,'/root/repo/tests')
+import os,sys,time
+sys.path.insert(0,os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),'tests'))
 import conftest, numpy as np, oracle_lib
 w,h,spp=1920,1080,256
 o64=oracle_lib.Oracle("liboracle_f64.so"); ost=oracle_lib.Oracle("liboracle.so")
