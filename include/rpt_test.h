@@ -17,7 +17,10 @@ extern "C" {
 enum {
     RPT_PROBE_SIN = 0, RPT_PROBE_COS = 1, RPT_PROBE_LOG2 = 2, RPT_PROBE_POW = 3,
     RPT_PROBE_DIV = 4, RPT_PROBE_SQRT = 5, RPT_PROBE_RNG = 6, RPT_PROBE_EXP = 7, RPT_PROBE_LOG = 8,
-    RPT_PROBE_DIV3 = 9                /* three quotients by one denominator, the library's shared-reciprocal form: see dev_math.h */
+    RPT_PROBE_DIV3 = 9,               /* three quotients by one denominator, the library's shared-reciprocal form: see dev_math.h */
+    /* OR'ed into `fn`: the same function from the relaxed-arithmetic build (RPT_RENDER_FAST_MATH's: hipcc's fast divide / sqrt,
+     * FMA contraction; k_probes.hip built a second time with those flags) instead of the strict one */
+    RPT_PROBE_RELAXED = 1u << 8
 };
 int rpt_probe_math(rpt_ctx* ctx, uint32_t fn, const float* a_dev, const float* b_dev,
                    float* out_dev, uint64_t n, void* stream);
@@ -64,7 +67,9 @@ int rpt_debug_sched_read(rpt_ctx* ctx, uint32_t* out, uint32_t capacity_tiles, u
 /* Which instantiation of its kernel class the context's last render launch took on its first device (csrc/launch.h, KernelChoice):
  * bit 0 the table sizes known at compile time, bit 1 the material table (at most 3 primitives), bit 2 its 64-row form (4 primitives),
  * bit 3 the table by class of accepted set (5-12 primitives), bits 8-15 the number of classes then, bits 16-19 the SDF object's
- * compile-time primitive count.  For tests that must know that the kernel they aim at is the one that ran. */
+ * compile-time primitive count, bit 20 the relaxed-arithmetic build (RPT_RENDER_FAST_MATH), bit 21 small scenes' compacting kernel
+ * (else the class's megakernel), bit 22 its dense form (at most 3 072 workgroups), bit 23 the nested-loop kernel.  For tests that must
+ * know that the kernel they aim at is the one that ran. */
 int rpt_debug_kernel_choice(rpt_ctx* ctx, uint32_t* out);
 
 /* Read the environment's knobs (csrc/knobs.h: the library reads them ONCE per process) again: for tests that change one between two

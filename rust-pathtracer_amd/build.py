@@ -37,6 +37,7 @@ OBJECTS = [
     ("capi", "capi.hip", [], "product"),
     ("capi_test", "capi.hip", ["-DRPT_TEST_HOOKS"], "test"),
     ("k_probes", "k_probes.hip", [], "test"),
+    ("k_probes_fast", "k_probes.hip", RELAXED, "test"),            # the math probes of the relaxed build (include/rpt_test.h, RPT_PROBE_RELAXED)
 ]
 # -ffp-contract=off: results are compared bit for bit with a CPU restatement, the only
 # fused operations are the explicit fma calls of rpt_strict_math.h.

@@ -532,7 +532,9 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
         }
         kc.extra_lds = knobs().debug_extra_lds;
         d.last_choice = (kc.sized ? 1u : 0u) | (kc.material_table ? 2u : 0u) | (kc.material_table_wide ? 4u : 0u) | (kc.material_table_mapped ? 8u : 0u) |
-                        ((kc.material_table_mapped ? kc.class_map.n_classes : 0u) << 8) | (kc.sized_sdf << 16);
+                        ((kc.material_table_mapped ? kc.class_map.n_classes : 0u) << 8) | (kc.sized_sdf << 16) |
+                        (fast ? 1u << 20 : 0u) | (rp.compact && !nested ? 1u << 21 : 0u) |
+                        (rp.compact && !nested && nblocks <= kCompactDenseMaxBlocks ? 1u << 22 : 0u) | (nested ? 1u << 23 : 0u);
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
         if (ctx->large) return fast ? rptlaunch_fast::render_large(scl, false, rp, grid, stream) : rptlaunch::render_large(scl, ctx->media, rp, grid, stream);
@@ -1621,10 +1623,13 @@ int rpt_probe_rays(rpt_ctx* ctx, const float* rays_dev, uint32_t* out_dev, uint6
 int rpt_probe_math(rpt_ctx* ctx, uint32_t fn, const float* a_dev, const float* b_dev, float* out_dev, uint64_t n, void* stream)
 {
     if (!ctx) { set_err(nullptr, "rpt_probe_math: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    const bool relaxed = (fn & RPT_PROBE_RELAXED) != 0u;
+    fn &= ~(uint32_t)RPT_PROBE_RELAXED;
     if (!a_dev || !b_dev || !out_dev || fn > RPT_PROBE_DIV3) { set_err(ctx, "rpt_probe_math: invalid argument"); return RPT_ERR_INVALID_ARG; }
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
-    RPT_HIP_CHECK(ctx, rptlaunch::probe_math(fn, a_dev, b_dev, out_dev, n, (hipStream_t)stream));
+    RPT_HIP_CHECK(ctx, relaxed ? rptlaunch_fast::probe_math(fn, a_dev, b_dev, out_dev, n, (hipStream_t)stream)
+                               : rptlaunch::probe_math(fn, a_dev, b_dev, out_dev, n, (hipStream_t)stream));
     return RPT_OK;
 }
 

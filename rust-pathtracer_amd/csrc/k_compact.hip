@@ -229,7 +229,7 @@ hipError_t render_compact(const SceneSmall& sc, bool media, const RenderParams& 
 {
     const dim3 tiles(nblocks), wg(256);
     (void)hipGetLastError();
-    const bool dense = nblocks <= 3072u;                             // (six workgroups per CU: see render_small_compact_dense_kernel)
+    const bool dense = nblocks <= kCompactDenseMaxBlocks;            // (six workgroups per CU: see render_small_compact_dense_kernel)
     if (media) {
 #ifdef RPT_RELAXED_BUILD
         return hipErrorNotSupported;

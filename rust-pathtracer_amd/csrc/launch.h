@@ -23,6 +23,10 @@ struct MatClassMap {
     const uint8_t* cls;                 // [4096] in device memory: accepted spheres | accepted planes << n_spheres (8 + 4 bits at most) -> class
 };
 
+// The compacting kernel of small scenes takes its six-workgroups-per-CU ("dense") form for launches of at most this many workgroups
+// (k_compact.hip, render_small_compact_dense_kernel).
+constexpr uint32_t kCompactDenseMaxBlocks = 3072u;
+
 // Which instantiation of a class's kernel a launch takes (capi.hip decides from the scene and the knobs, knobs.h).
 struct KernelChoice {
     bool sized = false;             // small scenes: the reference scene's table sizes are known at compile time (kernel_common.h, sized_scene)
@@ -75,4 +79,6 @@ hipError_t render_small(const rptdev::SceneSmall& sc, bool media, bool nested, c
 hipError_t render_compact(const rptdev::SceneSmall& sc, bool media, const rptdev::RenderParams& rp, uint32_t nblocks, hipStream_t st, const KernelChoice& kc);
 hipError_t render_sdf(const rptdev::SceneSmallSdf& scs, bool media, const rptdev::RenderParams& rp, uint32_t nblocks, hipStream_t st, const KernelChoice& kc);
 hipError_t render_large(const rptdev::SceneLarge& scl, bool media, const rptdev::RenderParams& rp, uint32_t nblocks, hipStream_t st);
+// test build only (k_probes.hip built with the relaxed flags; include/rpt_test.h, RPT_PROBE_RELAXED)
+hipError_t probe_math(uint32_t fn, const float* a, const float* b, float* out, uint64_t n, hipStream_t st);
 }  // namespace rptlaunch_fast

@@ -26,6 +26,9 @@ out = {"path": rpt._lib.LIB_PATH, "hooks": int(rpt.lib().rpt_build_has_test_hook
 cases = {"small": (rpt.AnalyticalScene(), 96, 54, 5, 0), "compact": (rpt.AnalyticalScene(), 96, 54, 1, 0),
          "nested": (rpt.AnalyticalScene(), 96, 54, 3, rpt._abi.RPT_RENDER_NESTED_LOOPS), "sdf": (scenes.sdf_scene(), 80, 45, 3, 0),
          "large": (scenes.random_spheres_scene(300, 5), 80, 45, 3, 0), "media": (scenes.media_scene(), 64, 36, 3, 0)}
+FAST = rpt._abi.RPT_RENDER_FAST_MATH
+cases.update({"small relaxed": (rpt.AnalyticalScene(), 96, 54, 5, FAST), "compact relaxed": (rpt.AnalyticalScene(), 96, 54, 1, FAST),
+              "sdf relaxed": (scenes.sdf_scene(), 80, 45, 3, FAST), "large relaxed": (scenes.random_spheres_scene(300, 5), 80, 45, 3, FAST)})
 for name, (scene, w, h, spp, flags) in cases.items():
     t = rpt.Tracer(scene, device=0, seed=4)
     t.flags = flags
@@ -50,6 +53,11 @@ def test_the_product_library_renders_what_the_test_build_renders(rpt, oracle):
     cases = {"small": (rpt.AnalyticalScene(), 96, 54, 5, 0), "compact": (rpt.AnalyticalScene(), 96, 54, 1, 0),
              "nested": (rpt.AnalyticalScene(), 96, 54, 3, rpt._abi.RPT_RENDER_NESTED_LOOPS), "sdf": (scenes.sdf_scene(), 80, 45, 3, 0),
              "large": (scenes.random_spheres_scene(300, 5), 80, 45, 3, 0), "media": (scenes.media_scene(), 64, 36, 3, 0)}
+    # the relaxed-arithmetic build of each kernel class (RPT_RENDER_FAST_MATH): not the oracle's frame (tests/test_gpu_relaxed.py holds
+    # it to the f64 oracle), but the same objects in both libraries, so the same frame
+    FAST = rpt._abi.RPT_RENDER_FAST_MATH
+    cases.update({"small relaxed": (rpt.AnalyticalScene(), 96, 54, 5, FAST), "compact relaxed": (rpt.AnalyticalScene(), 96, 54, 1, FAST),
+                  "sdf relaxed": (scenes.sdf_scene(), 80, 45, 3, FAST), "large relaxed": (scenes.random_spheres_scene(300, 5), 80, 45, 3, FAST)})
     for name, (scene, w, h, spp, flags) in cases.items():
         want = oracle.render(scene.describe(), w, h, spp, seed=4)
         t = rpt.Tracer(scene, device=0, seed=4)
@@ -59,5 +67,6 @@ def test_the_product_library_renders_what_the_test_build_renders(rpt, oracle):
         t.close()
         here = buf.image()
         same = (here.view(np.uint32) == want.view(np.uint32)) | (np.isnan(here) & np.isnan(want))
-        assert same.all(), "%s: the test build differs from the oracle" % name
+        assert same.all() or flags & FAST, "%s: the test build differs from the oracle" % name
+        assert not flags & FAST or np.isfinite(here).all(), "%s: non-finite pixels" % name
         assert got[name] == hashlib.sha1(here.tobytes()).hexdigest(), "%s: the product library's frame differs from the test build's" % name
