@@ -68,8 +68,9 @@ int rpt_debug_sched_read(rpt_ctx* ctx, uint32_t* out, uint32_t capacity_tiles, u
  * bit 0 the table sizes known at compile time, bit 1 the material table (at most 3 primitives), bit 2 its 64-row form (4 primitives),
  * bit 3 the table by class of accepted set (5-12 primitives), bits 8-15 the number of classes then, bits 16-19 the SDF object's
  * compile-time primitive count, bit 20 the relaxed-arithmetic build (RPT_RENDER_FAST_MATH), bit 21 small scenes' compacting kernel
- * (else the class's megakernel), bit 22 its dense form (at most 3 072 workgroups), bit 23 the nested-loop kernel.  For tests that must
- * know that the kernel they aim at is the one that ran. */
+ * (else the class's megakernel), bit 22 its dense form (at most 3 072 workgroups), bit 23 the nested-loop kernel, bit 24 the class's
+ * participating-media form (the scene has media: RPT_SCENE_MEDIA).  For tests that must know that the kernel they aim at is the one
+ * that ran. */
 int rpt_debug_kernel_choice(rpt_ctx* ctx, uint32_t* out);
 
 /* Read the environment's knobs (csrc/knobs.h: the library reads them ONCE per process) again: for tests that change one between two

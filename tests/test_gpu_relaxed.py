@@ -16,17 +16,14 @@ Inside the relaxed build there is no tolerance: the same kernel gives the same b
 dispatch, split launches, virtual ranks).  The list of instantiations is checked against the _fast kernels of the loaded library's
 gfx950 code object, so a kernel added without a case fails here."""
 import ctypes as C
-import os
-import re
-import struct
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import conftest
 import f64_compare as F
+from kernel_census import COMPACT_BIT, NESTED_BIT, RELAXED_BIT, kernel_of
+from kernel_census import code_object_kernels as _code_object_kernels
 
 pytestmark = pytest.mark.gpu
 
@@ -43,39 +40,6 @@ def oracle_f64():
     conftest._build_oracle()
     import oracle_lib
     return oracle_lib.Oracle("liboracle_f64.so")
-
-
-# ---- which kernel ran (include/rpt_test.h, rpt_debug_kernel_choice) -------------------------------------------------------------------
-RELAXED_BIT, COMPACT_BIT, DENSE_BIT, NESTED_BIT = 1 << 20, 1 << 21, 1 << 22, 1 << 23
-
-
-def kernel_of(choice, klass):
-    """The relaxed kernel the launchers (k_small / k_compact / k_sdf / k_large.hip) take for rpt_debug_kernel_choice's bits; klass is
-    "small", "sdf" or "large"."""
-    assert choice & RELAXED_BIT, "not the relaxed build: %#x" % choice
-    sized, table, wide, mapped = choice & 1, choice & 2, choice & 4, choice & 8
-    if klass == "large":
-        return "render_large_regen_kernel_fast"
-    if klass == "sdf":
-        n = (choice >> 16) & 0xF
-        if n:
-            return "render_sdf_march2_sized%s_kernel_fast<%d>" % ("_table" if table else "", n)
-        return "render_sdf_march2_table_kernel_fast" if table else "render_sdf_march2_kernel_fast"
-    if choice & NESTED_BIT:
-        return "render_small_nested_kernel_fast"
-    if choice & COMPACT_BIT:
-        dense = "dense_" if choice & DENSE_BIT else ""
-        form = "sized_table_" if sized and table else "sized_" if sized else "table_" if table else ""
-        return "render_small_compact_%s%skernel_fast" % (dense, form)
-    if sized and table:
-        return "render_small_regen_sized_table_kernel_fast"
-    if sized:
-        return "render_small_regen_sized_kernel_fast"
-    if table or wide:
-        return "render_small_regen_table_kernel_fast"
-    if mapped:
-        return "render_small_regen_maptable_kernel_fast"
-    return "render_small_regen_kernel_fast"
 
 
 # ---- scenes ---------------------------------------------------------------------------------------------------------------------
@@ -176,50 +140,6 @@ def test_the_case_list_is_the_library_s_relaxed_kernels(rpt):
     (The code object's metadata, not the host symbol table: the library is built with -fvisibility=hidden.)"""
     names = set(k for k in _code_object_kernels(rpt._lib.LIB_PATH) if k.startswith("render_") and "_fast" in k)
     assert len(names) == 25 and names == set(CASES), "library: %s; cases: %s" % (sorted(names - set(CASES)), sorted(set(CASES) - names))
-
-
-def _code_object_kernels(lib_path):
-    """Kernel names (demangled to name or name<N>) of every gfx950 code object in `lib_path`'s .hip_fatbin section: one offload bundle
-    per translation unit, each unbundled by its header; llvm-readelf --notes reads the kernels' metadata (tools/kernel_meta.py)."""
-    data = open(lib_path, "rb").read()
-    # the ELF section .hip_fatbin
-    shoff, = struct.unpack_from("<Q", data, 0x28)
-    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", data, 0x3A)
-    sec = lambda i: struct.unpack_from("<IIQQQQ", data, shoff + i * shentsize)      # noqa: E731  (name, type, flags, addr, offset, size)
-    strtab = sec(shstrndx)
-    fat = None
-    for i in range(shnum):
-        name_off, _, _, _, off, size = sec(i)
-        name = data[strtab[4] + name_off:data.index(b"\0", strtab[4] + name_off)]
-        if name == b".hip_fatbin":
-            fat = data[off:off + size]
-    assert fat is not None, "no .hip_fatbin in %s" % lib_path
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    names = []
-    readelf = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "llvm-readelf")
-    with tempfile.TemporaryDirectory() as d:
-        for start in [m.start() for m in re.finditer(re.escape(magic), fat)]:
-            n_entries, = struct.unpack_from("<Q", fat, start + len(magic))
-            p = start + len(magic) + 8
-            for _ in range(n_entries):
-                off, size, tlen = struct.unpack_from("<QQQ", fat, p)
-                triple = fat[p + 24:p + 24 + tlen].decode()
-                p += 24 + tlen
-                if triple.endswith("gfx950") and size:
-                    co = os.path.join(d, "co")
-                    open(co, "wb").write(fat[start + off:start + off + size])
-                    txt = subprocess.run([readelf, "--notes", co], check=True, capture_output=True, text=True).stdout
-                    names += re.findall(r"^\s+\.name:\s+(\S+)\s*$", txt, re.M)
-    out = []
-    for n in names:
-        m = re.match(r"_Z(\d+)", n)
-        if not m:
-            out.append(n)
-            continue
-        base = n[m.end():m.end() + int(m.group(1))]
-        t = re.match(r"ILj(\d+)EE", n[m.end() + int(m.group(1)):])
-        out.append(base + ("<%s>" % t.group(1) if t else ""))
-    return out
 
 
 # ---- extensions under relaxed arithmetic ------------------------------------------------------------------------------------------

@@ -24,6 +24,7 @@ rpt = importlib.util.module_from_spec(spec); sys.modules["rust_pathtracer_amd"] 
 from rust_pathtracer_amd import scenes
 out = {"path": rpt._lib.LIB_PATH, "hooks": int(rpt.lib().rpt_build_has_test_hooks()), "has_probe": hasattr(rpt.lib(), "rpt_probe_fn")}
 cases = {"small": (rpt.AnalyticalScene(), 96, 54, 5, 0), "compact": (rpt.AnalyticalScene(), 96, 54, 1, 0),
+         "compact sparse": (rpt.AnalyticalScene(), 1040, 768, 1, 0),
          "nested": (rpt.AnalyticalScene(), 96, 54, 3, rpt._abi.RPT_RENDER_NESTED_LOOPS), "sdf": (scenes.sdf_scene(), 80, 45, 3, 0),
          "large": (scenes.random_spheres_scene(300, 5), 80, 45, 3, 0), "media": (scenes.media_scene(), 64, 36, 3, 0)}
 FAST = rpt._abi.RPT_RENDER_FAST_MATH
@@ -50,7 +51,9 @@ def test_the_product_library_renders_what_the_test_build_renders(rpt, oracle):
     assert r.returncode == 0, r.stderr[-2000:]
     got = json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
     assert os.path.samefile(got["path"], PRODUCT) and got["hooks"] == 0 and not got["has_probe"]
+    # ("compact sparse": 3 120 workgroups, beyond the compacting kernel's dense form)
     cases = {"small": (rpt.AnalyticalScene(), 96, 54, 5, 0), "compact": (rpt.AnalyticalScene(), 96, 54, 1, 0),
+             "compact sparse": (rpt.AnalyticalScene(), 1040, 768, 1, 0),
              "nested": (rpt.AnalyticalScene(), 96, 54, 3, rpt._abi.RPT_RENDER_NESTED_LOOPS), "sdf": (scenes.sdf_scene(), 80, 45, 3, 0),
              "large": (scenes.random_spheres_scene(300, 5), 80, 45, 3, 0), "media": (scenes.media_scene(), 64, 36, 3, 0)}
     # the relaxed-arithmetic build of each kernel class (RPT_RENDER_FAST_MATH): not the oracle's frame (tests/test_gpu_relaxed.py holds
