@@ -1280,6 +1280,7 @@ inline void denoise(const float* in, float* out, uint32_t width, uint32_t height
     float k = edge_k;
     for (uint32_t it = 0; it < iterations; ++it) {
         const int64_t s = (int64_t)1 << it;
+#pragma omp parallel for schedule(static)
         for (int64_t y = 0; y < (int64_t)height; ++y)
             for (int64_t x = 0; x < (int64_t)width; ++x) {
                 const float* cp = &a[((size_t)y * width + x) * 3];
@@ -1293,7 +1294,9 @@ inline void denoise(const float* in, float* out, uint32_t width, uint32_t height
                         // (fused multiply-adds, written out: part of the specification since round 4 — a third fewer operations on a
                         //  pass that was instruction-bound, and nothing here restates the reference)
                         const float d2 = __builtin_fmaf(d0, d0, __builtin_fmaf(d1, d1, d2c * d2c));
-                        if (!(d2 == d2)) continue;
+                        // (not < inf: NaN, or +inf — an endpoint whose compressed colour is infinite, an input of exactly -1; its
+                        //  weight would be 0, but 0 * inf in acc would be NaN)
+                        if (!(d2 < INFINITY)) continue;
                         const float t = __builtin_fmaf(-d2, k, 1.0f);
                         const float g = t > 0.0f ? t : 0.0f;
                         const float wt = (H[dy + 1] * H[dx + 1]) * (g * g);
@@ -1308,7 +1311,9 @@ inline void denoise(const float* in, float* out, uint32_t width, uint32_t height
     }
     for (size_t p = 0; p < n; ++p) {
         const float* i4 = in + p * 4;
-        const bool finite = std::isfinite(i4[0]) && std::isfinite(i4[1]) && std::isfinite(i4[2]);
+        // the compressed colour is finite: no input channel is NaN, +-inf or exactly -1 (c / (1 + c) = -inf)
+        const bool finite = std::isfinite(i4[0]) && std::isfinite(i4[1]) && std::isfinite(i4[2]) && i4[0] != -1.0f && i4[1] != -1.0f &&
+                            i4[2] != -1.0f;
         for (int c = 0; c < 3; ++c) out[p * 4 + c] = finite ? a[p * 3 + c] / (1.0f - a[p * 3 + c]) : i4[c];
         out[p * 4 + 3] = i4[3];
     }

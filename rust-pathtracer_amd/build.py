@@ -32,8 +32,9 @@ OBJECTS = [
     ("k_large_fast", "k_large.hip", RELAXED, "both"),
     ("k_util", "k_util.hip", [], "both"),
     # the denoiser's taps are independent multiply / add sequences: packed f32 instructions halve their issue slots there
-    # (the path kernels lose from SLP: it pins register pairs)
-    ("denoise", "denoise.hip", ["-fslp-vectorize"], "both"),
+    # (the path kernels lose from SLP: it pins register pairs).  PEROP: its divides test their operands next to the operation —
+    # the default form only records them for a render kernel's per-sample recomputation, which the denoiser does not have
+    ("denoise", "denoise.hip", ["-fslp-vectorize"] + PEROP, "both"),
     ("capi", "capi.hip", [], "product"),
     ("capi_test", "capi.hip", ["-DRPT_TEST_HOOKS"], "test"),
     ("k_probes", "k_probes.hip", [], "test"),

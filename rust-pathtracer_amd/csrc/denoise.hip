@@ -9,6 +9,9 @@
 // ping-pong buffers never in cache); the price is 1.48 x the tap arithmetic (halo pixels of the earlier iterations are computed by
 // every tile that needs them — the same operations on the same values: bit-identical).  Later iterations (steps 8 ...: the halo
 // would be as large as the nine taps) read their taps through L1 / L2.  -DRPT_DENOISE_UNFUSED: one pass per iteration (A/B).
+// Built with -DRPT_GUARD_PER_OP (build.py): every divide tests its operands next to the operation and takes hipcc's correctly rounded
+// one outside the short sequence's range — c = 3.4e38 or a subnormal c is an input like any other here, and no kernel of this file
+// recomputes anything (nor has the 256-entry LDS tracker of the default form room for the fused kernel's 1 024 lanes).
 #include <hip/hip_runtime.h>
 
 #include "dev_math.h"
@@ -23,12 +26,12 @@ struct DnSum {
     float wsum;
 };
 
-// one tap of the filter (rpt.h: d2, the NaN skip, the edge-stopping weight)
+// one tap of the filter (rpt.h: d2, the skip of a d2 that is not < inf, the edge-stopping weight)
 RPT_DEV void dn_tap(DnSum& s, v3 cp, v3 cq, float hw, float k)
 {
     const float d0 = cp.x - cq.x, d1 = cp.y - cq.y, d2c = cp.z - cq.z;
     const float d2 = __builtin_fmaf(d0, d0, __builtin_fmaf(d1, d1, d2c * d2c));     // (explicit fmas: the specification's, rpt.h)
-    if (!(d2 == d2)) return;
+    if (!(d2 < __builtin_inff())) return;                                           // NaN, or +inf: an endpoint at c' = -inf (input -1)
     const float t = __builtin_fmaf(-d2, k, 1.0f);
     const float g = t > 0.0f ? t : 0.0f;
     const float wt = hw * (g * g);
@@ -47,11 +50,15 @@ RPT_DEV float4 dn_finish(const DnSum& s, v3 cp, bool last, float4 orig)
     const v3 o = mk3(ok ? m.x : cp.x, ok ? m.y : cp.y, ok ? m.z : cp.z);
     if (!last) return make_float4(o.x, o.y, o.z, 0.0f);
     const float inf = __builtin_inff();
-    const bool finite = (__builtin_fabsf(orig.x) < inf) && (__builtin_fabsf(orig.y) < inf) && (__builtin_fabsf(orig.z) < inf);
+    // the compressed colour is finite: no input channel is NaN, +-inf or exactly -1
+    const bool finite = (__builtin_fabsf(orig.x) < inf) && (__builtin_fabsf(orig.y) < inf) && (__builtin_fabsf(orig.z) < inf) &&
+                        orig.x != -1.0f && orig.y != -1.0f && orig.z != -1.0f;
     if (!finite) return orig;
     return make_float4(fdiv(o.x, 1.0f - o.x), fdiv(o.y, 1.0f - o.y), fdiv(o.z, 1.0f - o.z), orig.w);
 }
 
+#ifdef RPT_DENOISE_UNFUSED
+// (compiled only in the one-pass-per-iteration build, -DRPT_DENOISE_UNFUSED)
 // Steps 1, 2 and 4 through LDS: the workgroup's 16 x 16 pixels plus a halo of STEP — (16 + 2 STEP)^2 loads for 256 pixels (1.3, 1.6,
 // 2.3 per pixel) instead of nine taps each from L1 / L2, which is what bounded the first version (2.5 TB/s of HBM-equivalent at both
 // 1080p and 4K: the taps' L2 traffic, not the arithmetic).  FIRST: the source is the caller's buffer and c' = c / (1 + c) is computed
@@ -100,6 +107,7 @@ __global__ __launch_bounds__(kDnThreads) void denoise_tile_kernel(const float4* 
     if (last) orig = orig_in[p];
     out[p] = dn_finish(s, cp, last != 0u, orig);
 }
+#endif  // RPT_DENOISE_UNFUSED (the default build runs iterations 0-2 in denoise_fused_kernel: there these would be dead code)
 
 // The first K iterations (K = 1, 2, 3; steps 1, 2, 4) in one kernel.  Stage 0 is the loaded region (colours compressed once per loaded
 // pixel), stage j the output of iteration j - 1 on the region later iterations still need; positions outside the image hold NaN at every
@@ -214,7 +222,6 @@ hipError_t denoise(const float* in, float* out, float* scratch, uint32_t width, 
 {
     (void)hipGetLastError();
     const dim3 grid((width + 15u) / 16u, (height + 15u) / 16u), wg(256);
-    const dim3 tgrid((width + (uint32_t)kDnTile - 1u) / (uint32_t)kDnTile, (height + (uint32_t)kDnTile - 1u) / (uint32_t)kDnTile), twg(kDnThreads);
     float k = edge_k;
     const float4* cur = nullptr;
     uint32_t first = 0;
@@ -238,10 +245,18 @@ hipError_t denoise(const float* in, float* out, float* scratch, uint32_t width, 
         float4* dst = (float4*)(((iterations - 1u - i) & 1u) ? scratch : out);
         const float4* orig = (const float4*)in;
         const uint32_t l = last ? 1u : 0u;
-        if (i == 0) hipLaunchKernelGGL((denoise_tile_kernel<1, true>), tgrid, twg, 0, st, orig, orig, dst, width, height, k, l);
-        else if (i == 1) hipLaunchKernelGGL((denoise_tile_kernel<2, false>), tgrid, twg, 0, st, cur, orig, dst, width, height, k, l);
-        else if (i == 2) hipLaunchKernelGGL((denoise_tile_kernel<4, false>), tgrid, twg, 0, st, cur, orig, dst, width, height, k, l);
-        else hipLaunchKernelGGL(denoise_step_kernel, grid, wg, 0, st, cur, orig, dst, width, height, 1 << i, k, l);
+#ifdef RPT_DENOISE_UNFUSED
+        if (i <= 2u) {   // steps 1, 2, 4 through LDS (the default build runs these iterations in denoise_fused_kernel)
+            const dim3 tgrid((width + (uint32_t)kDnTile - 1u) / (uint32_t)kDnTile, (height + (uint32_t)kDnTile - 1u) / (uint32_t)kDnTile), twg(kDnThreads);
+            if (i == 0) hipLaunchKernelGGL((denoise_tile_kernel<1, true>), tgrid, twg, 0, st, orig, orig, dst, width, height, k, l);
+            else if (i == 1) hipLaunchKernelGGL((denoise_tile_kernel<2, false>), tgrid, twg, 0, st, cur, orig, dst, width, height, k, l);
+            else hipLaunchKernelGGL((denoise_tile_kernel<4, false>), tgrid, twg, 0, st, cur, orig, dst, width, height, k, l);
+            cur = dst;
+            k = k * 4.0f;
+            continue;
+        }
+#endif
+        hipLaunchKernelGGL(denoise_step_kernel, grid, wg, 0, st, cur, orig, dst, width, height, 1 << i, k, l);
         cur = dst;
         k = k * 4.0f;
     }

@@ -80,16 +80,31 @@ def code_object_kernels(lib_path):
                     open(co, "wb").write(fat[start + off:start + off + size])
                     txt = subprocess.run([readelf, "--notes", co], check=True, capture_output=True, text=True).stdout
                     names += re.findall(r"^\s+\.name:\s+(\S+)\s*$", txt, re.M)
-    out = []
-    for n in names:
-        m = re.match(r"_Z(\d+)", n)
-        if not m:
-            out.append(n)
-            continue
-        base = n[m.end():m.end() + int(m.group(1))]
-        t = re.match(r"ILj(\d+)EE", n[m.end() + int(m.group(1)):])
-        out.append(base + ("<%s>" % t.group(1) if t else ""))
-    return out
+    return [_demangle(n) for n in names]
+
+
+def _demangle(n):
+    """name or name<N[,true|false]> of a kernel's mangled name: _Z<len><name>, or _ZN<len><scope>...<len><name>E (an anonymous
+    namespace, for one), then integral and bool template arguments."""
+    m = re.match(r"_ZN?", n)
+    if not m:
+        return n
+    p, base = m.end(), None
+    while True:
+        d = re.match(r"\d+", n[p:])
+        if not d:
+            break
+        base = n[p + d.end():p + d.end() + int(d.group())]
+        p += d.end() + int(d.group())
+        if not n.startswith("_ZN"):
+            break
+    if base is None:
+        return n
+    t = re.match(r"I((?:L[ijb]\d+E)+)E", n[p:])
+    if not t:
+        return base
+    args = re.findall(r"L([ijb])(\d+)E", t.group(1))
+    return base + "<%s>" % ",".join(("true" if v == "1" else "false") if c == "b" else v for c, v in args)
 
 
 def render_kernels(lib_path, relaxed):

@@ -37,6 +37,16 @@ for name, (scene, w, h, spp, flags) in cases.items():
     t.render_n(buf, spp)
     out[name] = hashlib.sha1(buf.image().tobytes()).hexdigest()
     t.close()
+import numpy as np
+def image(w, h, seed):
+    img = np.random.default_rng(seed).uniform(0, 3, (h, w, 4)).astype(np.float32)
+    img[h // 2, w // 3, 0], img[1, 1, 1], img[h - 1, w - 1, :3] = -1.0, np.nan, 1e30
+    buf = rpt.ColorBuffer(w, h)
+    buf.pixels[:] = img.reshape(-1)
+    return buf
+for name, (w, h, it) in {"denoise": (200, 150, 3), "denoise 1": (65, 97, 1), "denoise 2": (65, 97, 2)}.items():
+    out[name] = hashlib.sha1(image(w, h, w + it).denoise(it, 2.0).image().tobytes()).hexdigest()
+out["u8"] = hashlib.sha1(image(1021, 3, 5).convert_to_u8().tobytes()).hexdigest()
 print("RESULT " + json.dumps(out))
 '''
 
@@ -73,3 +83,21 @@ def test_the_product_library_renders_what_the_test_build_renders(rpt, oracle):
         assert same.all() or flags & FAST, "%s: the test build differs from the oracle" % name
         assert not flags & FAST or np.isfinite(here).all(), "%s: non-finite pixels" % name
         assert got[name] == hashlib.sha1(here.tobytes()).hexdigest(), "%s: the product library's frame differs from the test build's" % name
+
+    def image(w, h, seed):                                           # (the child's inputs: a pole, a NaN, a saturated pixel)
+        img = np.random.default_rng(seed).uniform(0, 3, (h, w, 4)).astype(np.float32)
+        img[h // 2, w // 3, 0], img[1, 1, 1], img[h - 1, w - 1, :3] = -1.0, np.nan, 1e30
+        buf = rpt.ColorBuffer(w, h)
+        buf.pixels[:] = img.reshape(-1)
+        return buf
+    # the denoiser (denoise_fused_kernel<3>, <1>, <2>) and the u8 conversion: the oracle's, and the same in both libraries
+    for name, (w, h, it) in {"denoise": (200, 150, 3), "denoise 1": (65, 97, 1), "denoise 2": (65, 97, 2)}.items():
+        src = image(w, h, w + it)
+        here = src.denoise(it, 2.0).image()
+        want = oracle.denoise(src.image(), w, h, it, 2.0)
+        assert ((here.view(np.uint32) == want.view(np.uint32)) | (np.isnan(here) & np.isnan(want))).all(), name
+        assert got[name] == hashlib.sha1(here.tobytes()).hexdigest(), "%s: the product library's result differs from the test build's" % name
+    src = image(1021, 3, 5)
+    here = src.convert_to_u8()
+    assert np.array_equal(here, oracle.convert_to_u8(src.image(), 1021, 3))
+    assert got["u8"] == hashlib.sha1(here.tobytes()).hexdigest(), "u8: the product library's frame differs from the test build's"

@@ -58,7 +58,10 @@ VARIANTS = {
     "pair_w4": ["-DRPT_LARGE_PAIR_WAVES_PER_SIMD=4"],
     "pair_w6": ["-DRPT_LARGE_PAIR_WAVES_PER_SIMD=6"],
     # round 4
-    "denoise_tile32": ["-DRPT_DENOISE_TILE=32"],              # the denoiser's LDS tiles 32 x 32 (1 024 threads) instead of 16 x 16: halos 1.32 instead of 1.69 loads per pixel
+    # (the denoiser's one-pass LDS tile kernels, 32 x 32 (1 024 threads) instead of 16 x 16: halos 1.32 instead of 1.69 loads per pixel;
+    #  those kernels exist only under -DRPT_DENOISE_UNFUSED, so this matters only together with dn_unfused below, e.g. ad hoc as
+    #  dn_unfused_tile32=-DRPT_DENOISE_UNFUSED,-DRPT_DENOISE_TILE=32)
+    "denoise_tile32": ["-DRPT_DENOISE_TILE=32"],
     # round 4: code-generation options that cannot change a result (scheduling, register allocation, branch shape)
     "cg_early_ifcvt": ["-mllvm", "-amdgpu-early-ifcvt"],
     "cg_wave_prio": ["-mllvm", "-amdgpu-set-wave-priority"],
