@@ -174,12 +174,27 @@ int oracle_sample_pixels(const rpt_scene_desc* desc, const uint32_t* cols, const
     return 0;
 }
 
-// The rays (closest_hit: max_dist = -1; any_hit: its max_dist) one pixel-sample queries, 7 floats each.
-int oracle_sample_rays(const rpt_scene_desc* desc, uint32_t col, uint32_t row, uint64_t frame, uint32_t width, uint32_t height,
-                       uint64_t seed, float* out, uint32_t max_rays)
+// The same with render flags (RPT_RENDER_RUSSIAN_ROULETTE is the one a single sample reads).
+int oracle_sample_pixels_flags(const rpt_scene_desc* desc, const uint32_t* cols, const uint32_t* rows, const uint64_t* frames,
+                               uint64_t n, uint32_t width, uint32_t height, uint64_t seed, uint32_t render_flags, float* out)
 {
     Scene scene(*desc);
     Tracer tracer(scene);
+    tracer.russian_roulette = (render_flags & RPT_RENDER_RUSSIAN_ROULETTE) != 0;
+    for (uint64_t k = 0; k < n; ++k) {
+        F3 r = tracer.sample_pixel(cols[k], rows[k], width, height, frame_key(seed, frames[k]));
+        out[3 * k + 0] = rawf(r.x); out[3 * k + 1] = rawf(r.y); out[3 * k + 2] = rawf(r.z);
+    }
+    return 0;
+}
+
+// The rays (closest_hit: max_dist = -1; any_hit: its max_dist) one pixel-sample queries, 7 floats each.
+int oracle_sample_rays_flags(const rpt_scene_desc* desc, uint32_t col, uint32_t row, uint64_t frame, uint32_t width, uint32_t height,
+                             uint64_t seed, uint32_t render_flags, float* out, uint32_t max_rays)
+{
+    Scene scene(*desc);
+    Tracer tracer(scene);
+    tracer.russian_roulette = (render_flags & RPT_RENDER_RUSSIAN_ROULETTE) != 0;
     std::vector<float> log;
     g_ray_log = &log;
     tracer.sample_pixel(col, row, width, height, frame_key(seed, frame));
@@ -188,6 +203,12 @@ int oracle_sample_rays(const rpt_scene_desc* desc, uint32_t col, uint32_t row, u
     if (n > max_rays) n = max_rays;
     std::memcpy(out, log.data(), (size_t)n * 7 * sizeof(float));
     return (int)n;
+}
+
+int oracle_sample_rays(const rpt_scene_desc* desc, uint32_t col, uint32_t row, uint64_t frame, uint32_t width, uint32_t height,
+                       uint64_t seed, float* out, uint32_t max_rays)
+{
+    return oracle_sample_rays_flags(desc, col, row, frame, width, height, seed, 0u, out, max_rays);
 }
 
 // Path events (g_event_log) of the samples [frame0, frame0 + spp) of the pixels of the rectangle [col0, col0 + cw) x

@@ -102,10 +102,23 @@ class Oracle:
                                       height, seed, out.ctypes.data)
         return out
 
-    def sample_rays(self, desc, col, row, frame, width, height, seed=1, max_rays=64):
+    def sample_pixels_flags(self, desc, cols, rows, frames, width, height, seed=1, render_flags=0):
+        """sample_pixels with render flags (RPT_RENDER_RUSSIAN_ROULETTE)."""
+        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32)
+        frames = np.ascontiguousarray(frames, dtype=np.uint64)
+        out = np.zeros((len(cols), 3), dtype=np.float32)
+        self.lib.oracle_sample_pixels_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                        C.c_uint64, C.c_uint32, C.c_void_p]
+        self.lib.oracle_sample_pixels_flags(C.byref(desc), cols.ctypes.data, rows.ctypes.data, frames.ctypes.data, len(cols), width,
+                                            height, seed, render_flags, out.ctypes.data)
+        return out
+
+    def sample_rays(self, desc, col, row, frame, width, height, seed=1, max_rays=64, render_flags=0):
         out = np.zeros((max_rays, 7), dtype=np.float32)
-        self.lib.oracle_sample_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint32]
-        n = self.lib.oracle_sample_rays(C.byref(desc), col, row, frame, width, height, seed, out.ctypes.data, max_rays)
+        self.lib.oracle_sample_rays_flags.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                      C.c_uint32, C.c_void_p, C.c_uint32]
+        n = self.lib.oracle_sample_rays_flags(C.byref(desc), col, row, frame, width, height, seed, render_flags, out.ctypes.data, max_rays)
         return out[:n]
 
     def opcount(self, desc, width, height, spp, seed=1):

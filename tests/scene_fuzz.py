@@ -5,14 +5,17 @@ library's short divide / square root are proven for (csrc/dev_math.h)."""
 import numpy as np
 
 
-def random_small_scene(rpt, seed, n_spheres=None, n_lights=None):
+def random_small_scene(rpt, seed, n_spheres=None, n_lights=None, log2_scale=None):
     """-> (scene, log2 of its scale, render flags, rng).  n_spheres / n_lights: fixed table sizes (the reference's are 2 and 1: scenes that
-    take the kernels which know those sizes, kernels.hip sized_scene); None: random."""
+    take the kernels which know those sizes, kernels.hip sized_scene); None: random.  log2_scale: this scale instead of the drawn one
+    (the rest of the scene is the same)."""
     from rust_pathtracer_amd import scenes
     from rust_pathtracer_amd.api import Pinhole, Scene
     A = rpt._abi
     rng = np.random.default_rng(seed)
     log2_k = int(rng.integers(-33, 34))
+    if log2_scale is not None:
+        log2_k = int(log2_scale)
     k = float(2.0 ** log2_k)
     f = lambda x: float(np.float32(x) * np.float32(k))      # noqa: E731
     s = Scene()

@@ -1,0 +1,453 @@
+"""The oracle held to tests/pt_f64.py, a float64 restatement of one pixel-sample written from the reference's source text and
+include/rpt.h (not from oracle/rpt_oracle.hpp), sample by sample.  CPU only.
+
+  * The f64 oracle (liboracle_f64.so: the oracle's statements over double) against the restatement.  Both follow the same
+    statements in double, so a sample agrees to the f32 rounding of oracle_sample_pixels' output (<= 2 ulp(f32) of the value, NaN
+    = NaN), unless a comparison on its path was a near tie (branch margin < 1e-9) that the two orders of evaluation may settle
+    differently.  Scenes: the reference's through both front-ends (oracle_scene_analytical() against AnalyticalRef, and
+    rpt.AnalyticalScene().describe() against DescScene: this also pins oracle_capi.cpp's build_analytical and the product's scene
+    to analytical.rs), 24 fuzzed small scenes at scale 1 (depths 1-8, both any_hit modes, with and without Russian roulette) and a
+    scene of every light type with an emissive sphere and a material that leaves rgb unset.
+  * The oracle's per-function entry points (f64 build) against the restatement's functions, on random inputs and edges.
+  * Teeth: every entry of pt_f64.MUTANTS fails the per-sample check, by name; so does the f64 oracle with its Q5 quirk undone.
+  * The f32 oracle (the device's twin) against the restatement.  Its samples are split at the branch margin TAU: clean samples
+    (margin > TAU) must agree to REL_CLEAN; near-tie samples may take another branch, and at most NEAR_TIE_MAX of them.
+    Calibration: over the 21 000 samples below, 5.4 % lie below TAU = 1e-4 and the largest relative distance of a clean one is
+    3.9e-3 (median 2e-7: paths that bounce between spheres or graze the floor amplify f32 rounding); over the 26 000 samples the
+    GPU leg compares (whole rows of the reference's scene, the horizon among them), 7.8 % and 2.5e-2.  Samples that took another
+    branch were seen up to margin 3.9e-5, none above.  REL_CLEAN = 5e-2 leaves 2x over the largest clean distance, TAU 2.5x over
+    the largest flip, NEAR_TIE_MAX = 12 % 1.5x over 7.8 %.  Large scenes have bounds of their own (TAU_LARGE below).
+    The f64 comparison: 0 of 21 000 samples lay outside the f32-rounding band (so none needed its margin); the smallest margin
+    seen was 3.6e-7.  tests/test_gpu_path_f64.py holds the device to the same TAU and bounds."""
+import numpy as np
+import pytest
+
+import conftest
+import pt_f64 as P
+from scene_fuzz import random_small_scene
+
+TAU = 1e-4                   # branch margin below which an f32 computation may take another branch than the f64 restatement
+REL_CLEAN = 5e-2             # largest relative distance of a clean f32 sample (measured 3.9e-3 here, 2.5e-2 on the GPU leg's set)
+NEAR_TIE_MAX = 0.12          # largest fraction of near-tie samples
+# Large scenes (coordinates ~100, radii ~0.3): an f32 hit point carries ~1e-5 of absolute rounding, its sphere normal ~3e-5 of
+# relative error, and near ties are wider.  Calibration on random_spheres_scene(1000, 16), 3 000 samples: flips seen up to margin
+# 5.6e-5; 55-57 % of the samples lie below TAU_LARGE (every one of the 1 000 spheres' miss tests counts), largest relative distance
+# of the others 1.8e-4.
+TAU_LARGE = 3e-4
+NEAR_TIE_MAX_LARGE = 0.7
+F64_TIE = 1e-9               # branch margin below which the f64 oracle may legitimately disagree with the restatement
+FUZZ_SEEDS = (14, 51, 59, 1, 31, 44, 2, 5, 67, 3, 12, 24, 20, 30, 36, 8, 11, 32, 6, 10, 16, 7, 22, 54)   # three per depth 1-8
+
+
+@pytest.fixture(scope="module")
+def oracle_f64():
+    conftest._build_oracle()
+    import oracle_lib
+    return oracle_lib.Oracle("liboracle_f64.so")
+
+
+def light_types_scene(rpt):
+    """Every light type (include/rpt.h, RPT_SCENE_SAMPLE_ALL_LIGHT_TYPES), an emissive sphere, a sphere whose material sets no rgb
+    (Material::new's 1.5, Q12) and glass, over the checker floor; any_hit honours max_dist."""
+    from rust_pathtracer_amd import scenes
+    from rust_pathtracer_amd.api import Pinhole, Scene
+    A = rpt._abi
+    s = Scene()
+    s.camera = Pinhole((0.4, 1.2, 4.0), (0.0, 0.0, 0.0), 65.0)
+    s.background = dict(kind=A.RPT_BG_GRADIENT_Y, colour_a=(1.0, 1.0, 1.0), colour_b=(0.5, 0.7, 1.0), gamma=2.2, scale=0.5)
+    s.materials = [rpt.Material(roughness=0.3, metallic=0.0),                              # rgb left at Material::new's
+                   scenes.full_material(rgb=(0.9, 0.9, 0.9), roughness=0.05, spec_trans=1.0, ior=1.5, metallic=0.4),   # (Q4 needs both)
+                   rpt.Material(rgb=(0.2, 0.2, 0.2), emission=(2.0, 1.0, 0.5), roughness=0.6),
+                   rpt.Material(roughness=1.0, checker_dir=(0.5, 100.0, 0.25, 0.1))]
+    s.spheres = [((-1.2, 0.0, 0.0), 1.0, 0), ((1.0, -0.2, 0.3), 0.8, 1), ((0.0, -0.6, 1.4), 0.4, 2)]
+    s.planes = [((0.0, 1.0, 0.0), (0.0, -1.0, 0.0), 0.0001, 3)]
+    s.lights = [rpt.AnalyticalLight.spherical((3.0, 2.0, 2.0), 1.0, (3.0, 3.0, 3.0)),
+                rpt.AnalyticalLight.rectangular((-1.0, 3.0, -1.0), (2.0, 0.0, 0.0), (0.0, 0.0, 2.0), (4.0, 4.0, 4.0)),
+                rpt.AnalyticalLight.distant((20.0, 60.0, 30.0), (0.8, 0.8, 0.7))]
+    s.sample_all_light_types = True
+    s.any_hit_uses_max_dist = True
+    s.max_depth = 5
+    return s
+
+
+def occluder_scene(rpt):
+    """The reference's scene with a sphere behind its light, seen from the floor: any_hit ignores max_dist (Q3), so that sphere
+    shadows the light."""
+    s = rpt.AnalyticalScene()
+    s.materials = list(s.materials) + [rpt.Material(rgb=(0.5, 0.5, 0.5), roughness=0.5)]
+    s.spheres = list(s.spheres) + [((4.5, 3.0, 3.0), 0.6, 3)]
+    return s
+
+
+def scene_set(rpt, oracle_f64, n_ref=3000, n_fuzz=500, n_lights=2000, n_occluder=1000):
+    """-> [(name, desc, restated scene, width, height, render flags, items, seed[, scene])], 21 000 samples in all."""
+    A = rpt._abi
+    rng = np.random.default_rng(20261015)
+
+    def items(n, w, h, frames):
+        return list(zip(rng.integers(0, w, n), rng.integers(0, h, n), rng.integers(0, frames, n)))
+
+    out = []
+    d0 = oracle_f64.scene_analytical()
+    out.append(("reference scene, oracle_scene_analytical vs AnalyticalRef", d0, P.AnalyticalRef(), 800, 600, 0, items(n_ref, 800, 600, 8), 1))
+    ref = rpt.AnalyticalScene()
+    d1 = ref.describe()
+    out.append(("reference scene, AnalyticalScene().describe() vs DescScene", d1, P.DescScene(d1), 800, 600, 0, items(n_ref, 800, 600, 8), 7))
+    out[-1] = out[-1] + (ref,)
+    for seed in FUZZ_SEEDS:
+        s, _, flags, _ = random_small_scene(rpt, seed, log2_scale=0)
+        d = s.describe()
+        out.append(("fuzz seed %d (depth %d, max_dist %d, roulette %d)" % (seed, s.max_depth, s.any_hit_uses_max_dist,
+                                                                          bool(flags & A.RPT_RENDER_RUSSIAN_ROULETTE)),
+                    d, P.DescScene(d), 64, 48, flags, items(n_fuzz, 64, 48, 4), 100 + seed, s))
+    s = light_types_scene(rpt)
+    d = s.describe()
+    out.append(("light types", d, P.DescScene(d), 96, 72, 0, items(n_lights, 96, 72, 4), 5, s))
+    s = occluder_scene(rpt)
+    d = s.describe()
+    out.append(("occluder behind the light", d, P.DescScene(d), 64, 48, 0, items(n_occluder, 64, 48, 4), 9, s))
+    return out
+
+
+def in_band(got, want):
+    """got (f64) within 2 ulp(f32) of want (the f32 rounding of a double), NaN = NaN, per sample."""
+    want = np.asarray(want, dtype=np.float32)
+    ulp = np.spacing(np.abs(want)).astype(np.float64)
+    w = want.astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        ok = (np.abs(got - w) <= 2.0 * ulp) | (np.isnan(got) & np.isnan(w)) | (got == w)
+    return ok.all(axis=1)
+
+
+def rel_distance(got, want):
+    """max over channels of |want - got| / max(|got|, 1e-3): relative, with values below 1e-3 measured absolutely; non-finite
+    samples (blended as black) compare as such."""
+    got = np.where(np.isfinite(got), got, 0.0)
+    w = np.where(np.isfinite(want), want, 0.0).astype(np.float64)
+    return (np.abs(w - got) / np.maximum(np.abs(got), 1e-3)).max(axis=1)
+
+
+def restate(entry, oracle, mut=()):
+    name, desc, scene, w, h, flags, items, seed = entry[:8]
+    roulette = bool(flags & P.RENDER_RUSSIAN_ROULETTE)
+    return P.sample_many(scene, oracle, seed, items, w, h, mut=mut, roulette=roulette)
+
+
+def oracle_samples(oracle, entry):
+    name, desc, scene, w, h, flags, items, seed = entry[:8]
+    c, r, f = (np.array([it[k] for it in items]) for k in range(3))
+    return oracle.sample_pixels_flags(desc, c, r, f, w, h, seed=seed, render_flags=flags)
+
+
+def first_diverging_ray(oracle, entry, k, rays):
+    name, desc, scene, w, h, flags, items, seed = entry[:8]
+    c, r, f = items[k]
+    theirs = oracle.sample_rays(desc, int(c), int(r), int(f), w, h, seed=seed, render_flags=flags)
+    mine = np.array(rays[k], dtype=np.float32).reshape(-1, 7)
+    for i in range(max(len(theirs), len(mine))):
+        if i >= len(theirs) or i >= len(mine) or not np.allclose(theirs[i], mine[i], rtol=1e-5, atol=1e-6):
+            return "ray %d: oracle %s, restatement %s" % (i, theirs[i].tolist() if i < len(theirs) else None,
+                                                          mine[i].tolist() if i < len(mine) else None)
+    return "same %d rays" % len(mine)
+
+
+@pytest.fixture(scope="module")
+def scenes_f64(rpt, oracle_f64):
+    return scene_set(rpt, oracle_f64)
+
+
+def test_scene_set_covers_the_statements(rpt, scenes_f64):
+    fuzz = [e[8] for e in scenes_f64 if e[0].startswith("fuzz")]
+    assert len(fuzz) >= 24
+    assert {s.max_depth for s in fuzz} == set(range(1, 9))
+    assert {s.any_hit_uses_max_dist for s in fuzz} == {False, True}
+    flags = {e[5] for e in scenes_f64 if e[0].startswith("fuzz")}
+    assert flags == {0, rpt._abi.RPT_RENDER_RUSSIAN_ROULETTE}
+    assert sum(len(e[6]) for e in scenes_f64) >= 20000
+
+
+def test_f64_oracle_follows_the_restatement(oracle_f64, scenes_f64):
+    """Every sample agrees to the f32 rounding of the oracle's output, or took a near tie (margin < F64_TIE) on its path."""
+    total = outside = 0
+    worst = []
+    for e in scenes_f64:
+        got, marg, rays = restate(e, oracle_f64)
+        want = oracle_samples(oracle_f64, e)
+        ok = in_band(got, want)
+        total += len(ok)
+        outside += int((~ok).sum())
+        bad = np.nonzero(~ok & (marg >= F64_TIE))[0]
+        if bad.size:
+            k = int(bad[0])
+            worst.append("%s: %d samples outside the band with margin >= %g; first: pixel %s, restated %s, oracle %s, margin %.3g; %s"
+                         % (e[0], bad.size, F64_TIE, e[6][k], got[k].tolist(), want[k].tolist(), marg[k],
+                            first_diverging_ray(oracle_f64, e, k, rays)))
+    print("f64 oracle vs restatement: %d samples, %d outside the f32-rounding band" % (total, outside))
+    assert not worst, "\n".join(worst)
+
+
+# ---- per function -------------------------------------------------------------------------------------------------------------
+def close(mine, theirs, ulps=2.0):
+    """mine (f64) against an f32 output of the f64 oracle: within `ulps` ulp(f32), NaN = NaN."""
+    mine = np.asarray(mine, dtype=np.float64)
+    t = np.asarray(theirs, dtype=np.float32)
+    tol = ulps * np.spacing(np.abs(t)).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        return bool(np.all((np.abs(mine - t) <= tol) | (np.isnan(mine) & np.isnan(t)) | (mine == t)))
+
+
+def bsdf_cases(n=1500, seed=3):
+    """(17 material floats, eta, v, n, l) with the edges: roughness 0 and 1, anisotropic +-0.9, metallic 1, spec_trans 1 at eta 1,
+    1.5 and 1 / 1.5, clearcoat 1 at gloss 0 and 1, grazing v.n ~ 1e-6, l below the horizon."""
+    rng = np.random.default_rng(seed)
+    f = lambda x: float(np.float32(x))                                  # noqa: E731
+    out = []
+    edges = [dict(roughness=0.0), dict(roughness=1.0), dict(anisotropic=0.9), dict(anisotropic=-0.9), dict(metallic=1.0),
+             dict(spec_trans=1.0, ior=1.0), dict(spec_trans=1.0, ior=1.5), dict(spec_trans=1.0, ior=f(1 / 1.5)),
+             dict(clearcoat=1.0, clearcoat_gloss=0.0), dict(clearcoat=1.0, clearcoat_gloss=1.0)]
+    for i in range(n):
+        m = np.zeros(17, dtype=np.float32)
+        m[0:3] = rng.uniform(0, 1, 3)
+        m[6] = rng.choice([0.0, 0.5, 0.9])
+        m[7] = rng.choice([0.0, 0.0, 1.0, 0.4])
+        m[8] = rng.uniform(0, 1)
+        m[9], m[10], m[11], m[12] = rng.choice([0, 0.7]), rng.choice([0, 0.5]), rng.choice([0, 1.0]), rng.choice([0, 0.5])
+        m[13], m[14] = rng.choice([0.0, 0.0, 1.0, 0.3]), rng.uniform(0, 1)
+        m[15], m[16] = rng.choice([0.0, 0.0, 1.0, 0.5]), rng.choice([1.45, 1.5, 1.0, 1.33])
+        names = ["rgb"] * 3 + ["emission"] * 3 + ["anisotropic", "metallic", "roughness", "subsurface", "specular_tint", "sheen",
+                                                   "sheen_tint", "clearcoat", "clearcoat_gloss", "spec_trans", "ior"]
+        for k, v in edges[i % len(edges)].items():
+            m[names.index(k)] = v
+        nrm = rng.normal(size=3)
+        nrm /= np.linalg.norm(nrm)
+        if i % 9 == 0:
+            nrm = np.array([0.0, 0.0, rng.choice([-1.0, 1.0])])
+        v = rng.normal(size=3)
+        v /= np.linalg.norm(v)
+        if v @ nrm < 0:
+            v = -v
+        if i % 7 == 0:                                                  # grazing: v.n ~ 1e-6
+            t = np.cross(nrm, rng.normal(size=3))
+            t /= np.linalg.norm(t)
+            v = t + 1e-6 * nrm
+            v /= np.linalg.norm(v)
+        l = rng.normal(size=3)
+        l /= np.linalg.norm(l)                                          # both hemispheres: l below the horizon half the time
+        eta = f(1.0 / m[16]) if i % 4 else f(m[16])
+        out.append((m, eta, v.astype(np.float32), nrm.astype(np.float32), l.astype(np.float32)))
+    return out
+
+
+def widen(a):
+    return tuple(float(x) for x in a)
+
+
+def test_material_finalize_and_defaults(oracle_f64):
+    mat = P.Material()
+    d = oracle_f64.material_defaults()
+    assert widen(d[0:3]) == mat.rgb and widen(d[3:6]) == mat.emission
+    assert (float(d[8]), float(d[16])) == (mat.roughness, mat.ior)
+    for m, *_ in bsdf_cases(400, seed=5):
+        mine = P.Material.from17(m).finalize()
+        theirs = oracle_f64.material_finalize(m)
+        assert close((mine.roughness, mine.clearcoat_roughness, mine.ax, mine.ay), theirs), (m, theirs)
+
+
+def test_disney_eval_per_function(oracle_f64):
+    bad = 0
+    for m, eta, v, n, l in bsdf_cases():
+        M = P.Margin()
+        f, pdf = P.disney_eval(P.Material.from17(m).finalize(), float(eta), widen(v), widen(n), widen(l), M=M)
+        theirs = oracle_f64.disney_eval(m, eta, v, n, l)
+        if not close(f + (pdf,), theirs) and M.m >= F64_TIE:
+            bad += 1
+            assert bad > 3, (m.tolist(), eta, v, n, l, f, pdf, theirs)
+
+
+def pcg_stream(state, inc):
+    """The probes' explicit stream position (state, increment): PCG-RXS-M-XS-32 as tests/test_oracle_kat.py spells it out."""
+    inc |= 1
+
+    def draw():
+        nonlocal state
+        state = (state * 747796405 + inc) & 0xFFFFFFFF
+        word = (((state >> ((state >> 28) + 4)) ^ state) * 277803737) & 0xFFFFFFFF
+        return float(np.float32((((word >> 22) ^ word) & 0xFFFFFFFF) >> 8) * np.float32(2.0 ** -24))
+    return draw
+
+
+def test_disney_sample_per_function(oracle_f64):
+    rng = np.random.default_rng(8)
+    for i, (m, eta, v, n, l) in enumerate(bsdf_cases(seed=4)):
+        stale = (0.0, 0.0, 0.0) if i % 3 == 0 else widen(l)
+        state, inc = int(rng.integers(0, 2 ** 32)), int(rng.integers(0, 2 ** 22))
+        M = P.Margin()
+        calls = [0]
+        dr = pcg_stream(state, inc)
+
+        def draw():
+            calls[0] += 1
+            return dr()
+        f, lo, pdf = P.disney_sample(P.Material.from17(m).finalize(), float(eta), widen(v), widen(n), stale, draw, M=M)
+        theirs = oracle_f64.disney_sample(m, eta, v, n, np.array(stale, dtype=np.float32), state, inc, 0)
+        assert theirs[7] == calls[0]
+        if M.m >= F64_TIE:
+            assert close(f + lo + (pdf,), theirs[:7]), (i, m.tolist(), eta, v, n, stale, f, lo, pdf, theirs)
+
+
+def test_sample_light_per_function(rpt, oracle_f64):
+    A = rpt._abi
+    rng = np.random.default_rng(9)
+    n = 1500
+    rec = np.zeros((n, 32), dtype=np.float32)
+    types = rng.choice([A.RPT_LIGHT_SPHERICAL, A.RPT_LIGHT_SPHERICAL, A.RPT_LIGHT_RECTANGULAR, A.RPT_LIGHT_DISTANT], size=n)
+    rec[:, 0] = types.astype(np.uint32).view(np.float32)
+    rec[:, 1:4] = rng.uniform(-4, 4, size=(n, 3))
+    rec[:, 4:7] = rng.uniform(0, 5, size=(n, 3))
+    rec[:, 7] = rng.choice([1.0, 0.25, 2.0], size=n)
+    rec[:, 8] = (4.0 * np.pi * rec[:, 7] ** 2).astype(np.float32)
+    rec[:, 9:15] = rng.uniform(-2, 2, size=(n, 6))
+    rec[:, 15:18] = rng.uniform(-6, 6, size=(n, 3))
+    on_axis = rng.uniform(size=n) < 0.1                                 # straight above / below the light: the onb's other branch
+    rec[on_axis, 15:17] = rec[on_axis, 1:3]
+    rec[:, 18] = rng.choice([1.0, 3.0, 16.0], size=n)
+    rec[:, 19] = rng.choice([0, A.RPT_SCENE_SAMPLE_ALL_LIGHT_TYPES], size=n).astype(np.uint32).view(np.float32)
+    rec[:, 20] = rng.integers(0, 2 ** 32, size=n, dtype=np.uint64).astype(np.uint32).view(np.float32)
+    rec[:, 21] = rng.integers(0, 2 ** 22, size=n, dtype=np.uint64).astype(np.uint32).view(np.float32)
+    theirs = oracle_f64.probe_fn(A.RPT_PROBE_FN_SAMPLE_LIGHT, rec)
+    for k in range(n):
+        r = rec[k]
+
+        class S:
+            flags = int(r[19:20].view(np.uint32)[0])
+            lights = [None] * int(r[18])
+        light = (int(types[k]), widen(r[1:4]), widen(r[4:7]), widen(r[9:12]), widen(r[12:15]), float(r[7]), float(r[8]))
+        calls = [0]
+        dr = pcg_stream(int(r[20:21].view(np.uint32)[0]), int(r[21:22].view(np.uint32)[0]))
+
+        def draw():
+            calls[0] += 1
+            return dr()
+        M = P.Margin()
+        ls = P.sample_light(S, light, widen(r[15:18]), draw, M)
+        assert theirs[k, 11] == calls[0], k
+        if M.m >= F64_TIE:
+            assert close(ls.normal + ls.emission + ls.direction + (ls.dist, ls.pdf), theirs[k, :11]), (k, r.tolist(), theirs[k])
+
+
+def test_gen_ray_sphere_plane_per_function(rpt, oracle_f64):
+    rng = np.random.default_rng(10)
+    for cam, (w, h) in (((0, 0, 3, 0, 0, 0, 80), (800, 600)), ((0, 6, 14, 0, 2, -40, 70), (4096, 4096)), ((2, 1, -3, 0.5, 0, 1, 35), (1920, 1080))):
+        cam = np.array(cam, dtype=np.float32)
+        c = (widen(cam[0:3]), widen(cam[3:6]), float(cam[6]))
+        for _ in range(300):
+            px, py = float(np.float32(rng.uniform())), float(np.float32(rng.uniform()))
+            ox, oy = float(np.float32(rng.uniform())), float(np.float32(rng.uniform()))
+            o, d = P.gen_ray(c, (px, py), (ox, oy), float(w), float(h))
+            assert close(o + d, oracle_f64.gen_ray(cam, px, py, ox, oy, w, h))
+    A = rpt._abi
+    for i in range(3000):
+        o = rng.uniform(-3, 3, 3).astype(np.float32)
+        d = rng.normal(size=3)
+        d = (d / np.linalg.norm(d)).astype(np.float32)
+        c = rng.uniform(-2, 2, 3).astype(np.float32)
+        r = np.float32(rng.uniform(0.2, 2.0))
+        if i % 5 == 0:
+            o = (c + 0.5 * r * d).astype(np.float32)                      # origin inside the sphere: the far root (Q9)
+        M = P.Margin()
+        t = P.sphere(widen(o), widen(d), widen(c), float(r), M=M)
+        hit, tt = oracle_f64.sphere(o, d, c, float(r))
+        if M.m >= F64_TIE:
+            assert hit == (t is not None), (o, d, c, r)
+            assert not hit or close([t], [tt])
+        pl = A.rpt_plane()
+        pl.normal = A.F3(0.0, 1.0, 0.0)
+        pl.point = A.F3(0.0, float(rng.uniform(-2, 0)), 0.0)
+        pl.min_denom = 0.0001
+        pl.max_t = float(rng.choice([0.0, 3.0]))
+        if i % 6 == 0:
+            d = np.array([d[0], 0.0, d[2]], dtype=np.float32)                # parallel to the plane
+        M = P.Margin()
+        t = P.plane(widen(o), widen(d), (0.0, 1.0, 0.0), widen(pl.point), float(np.float32(0.0001)), float(pl.max_t), M=M)
+        hit, tt = oracle_f64.plane(o, d, pl)
+        if M.m >= F64_TIE:
+            assert hit == (t is not None), (o, d, pl.point[1], pl.max_t)
+            assert not hit or close([t], [tt])
+
+
+# ---- teeth ----------------------------------------------------------------------------------------------------------------------
+def caught(oracle, scenes, mut=(), limit=None):
+    """Does some sample disagree, outside the f32-rounding band, with margin >= F64_TIE?  -> (scene name, pixel) or None."""
+    for e in scenes:
+        its = e[6][:limit] if limit else e[6]
+        e2 = e[:6] + (its,) + e[7:]
+        got, marg, _ = restate(e2, oracle, mut)
+        want = oracle_samples(oracle, e2)
+        bad = np.nonzero(~in_band(got, want) & (marg >= F64_TIE))[0]
+        if bad.size:
+            return e[0], its[int(bad[0])]
+    return None
+
+
+def test_every_mutant_is_caught(oracle_f64, scenes_f64):
+    missed = [m for m in P.MUTANTS if caught(oracle_f64, scenes_f64, (m,), limit=400) is None]
+    assert not missed, "restatement mutants the per-sample check did not catch: %s" % missed
+
+
+def test_undone_q5_is_caught(oracle_f64, scenes_f64):
+    """The f64 oracle with GTR1's ln (the textbook form, oracle_undo_quirks bit 0) must fail on the reference's clearcoat scene."""
+    ref = [e for e in scenes_f64 if e[0].startswith("reference")]
+    assert caught(oracle_f64, ref, limit=600) is None
+    oracle_f64.lib.oracle_undo_quirks(1)
+    try:
+        hit = caught(oracle_f64, ref, limit=600)
+    finally:
+        oracle_f64.lib.oracle_undo_quirks(0)
+    assert hit is not None, "the f64 oracle with Q5 undone passed the per-sample check"
+
+
+# ---- the f32 oracle ------------------------------------------------------------------------------------------------------------
+def split_clean(got, marg, want):
+    """-> (relative distances, near-tie mask)."""
+    return rel_distance(got, want), marg <= TAU
+
+
+def test_f32_oracle_clean_samples_within_bound(oracle, oracle_f64, scenes_f64):
+    """The device's twin: clean samples (margin > TAU) within REL_CLEAN, near-tie samples at most NEAR_TIE_MAX of all, and every
+    sample that disagrees by more than REL_CLEAN a near-tie one."""
+    n = near = 0
+    worst = 0.0
+    for e in scenes_f64:
+        got, marg, rays = restate(e, oracle_f64)
+        want = oracle_samples(oracle, e)
+        rel, tie = split_clean(got, marg, want)
+        n += len(rel)
+        near += int(tie.sum())
+        if (~tie).any():
+            worst = max(worst, float(rel[~tie].max()))
+        bad = np.nonzero((rel > REL_CLEAN) & ~tie)[0]
+        assert not bad.size, "%s: %d clean samples beyond %g, first pixel %s: restated %s, f32 oracle %s, margin %.3g; %s" % (
+            e[0], bad.size, REL_CLEAN, e[6][bad[0]], got[bad[0]].tolist(), want[bad[0]].tolist(), marg[bad[0]],
+            first_diverging_ray(oracle, e, int(bad[0]), rays))
+    print("f32 oracle vs restatement: %d samples, %d near-tie (%.2f %%), largest clean relative distance %.3g" % (n, near, 100.0 * near / n, worst))
+    assert near <= NEAR_TIE_MAX * n
+
+
+def test_large_scene_brute_force(rpt, oracle, oracle_f64):
+    """The large class (1 000 spheres, 16 lights: the numpy brute force over the sphere table) against both oracles: the f64 one to
+    rounding, the f32 one to the large-scene bounds tests/test_gpu_path_f64.py applies to the device."""
+    from rust_pathtracer_amd import scenes
+    s = scenes.random_spheres_scene(1000, 16)
+    d = s.describe()
+    w, h = 96, 64
+    rng = np.random.default_rng(12)
+    items = list(zip(rng.integers(0, w, 1200), rng.integers(0, h, 1200), rng.integers(0, 3, 1200)))
+    e = ("large scene", d, P.DescScene(d), w, h, 0, items, 5)
+    got, marg, rays = restate(e, oracle_f64)
+    bad = np.nonzero(~in_band(got, oracle_samples(oracle_f64, e)) & (marg >= F64_TIE))[0]
+    assert not bad.size, (items[bad[0]], first_diverging_ray(oracle_f64, e, int(bad[0]), rays))
+    rel = rel_distance(got, oracle_samples(oracle, e))
+    tie = marg <= TAU_LARGE
+    assert tie.mean() <= NEAR_TIE_MAX_LARGE
+    assert rel[~tie].max() <= REL_CLEAN, (rel[~tie].max(), items[int(np.argmax(np.where(tie, 0, rel)))])
+    print("large scene, f32 oracle: %.1f %% near-tie, largest clean relative distance %.3g" % (100 * tie.mean(), rel[~tie].max()))
