@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define RPT_ABI_VERSION 4u            /* 4: the A/B-only render flags and the test hooks left this header (include/rpt_test.h) */
+#define RPT_ABI_VERSION 5u            /* 5: triangle meshes (rpt_mesh, rpt_scene_desc.meshes); 4: the A/B-only render flags and the test hooks left this header (include/rpt_test.h) */
 
 typedef enum rpt_status {
     RPT_OK              =  0,
@@ -246,6 +246,59 @@ enum {                                /* rpt_scene_desc.flags */
  * kernel, the SDF march kernel, large scenes' megakernel); RPT_RENDER_FAST_MATH and RPT_RENDER_NESTED_LOOPS do not
  * (RPT_ERR_UNSUPPORTED). */
 
+/* ---- triangle meshes (the reference's Todo "Implement a mesh based example scene", Readme.md) — PROJECT-DEFINED -------------
+ * A mesh is a list of triangles over a vertex array, with ONE material.  The triangles of all meshes form one flattened list:
+ * meshes in order, each mesh's triangles in order; a triangle's index below is its position in that list.
+ *
+ * Triangle test (two-sided Moller-Trumbore), f32 in exactly this operation order; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z,
+ * cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x) (fx.rs:335-344), the divide is the library's
+ * correctly rounded one.  For a ray (o, d) and a triangle (a, b, c):
+ *     e1 = b - a;  e2 = c - a;  p = cross(d, e2);  det = dot(e1, p)
+ *     !(det < 0 || det > 0)          -> miss   (also a NaN det)
+ *     inv = 1 / det;  s = o - a;  u = dot(s, p) * inv
+ *     !(u >= 0 && u <= 1)            -> miss
+ *     q = cross(s, e1);  v = dot(d, q) * inv
+ *     !(v >= 0 && u + v <= 1)        -> miss
+ *     t = dot(e2, q) * inv
+ *     !(t >= 0 && t < F::MAX)        -> miss   (F::MAX = 3.40282347e38: so a hit always has t < the running distance's start value,
+ *                                              and the "first primitive is accepted whenever hit" rule never changes a triangle's result)
+ *     point check, per axis i = x, y, z (min / max of finite numbers):
+ *       lo = a.i + min(min(0, e1.i), e2.i);  hi = a.i + max(max(0, e1.i), e2.i);  w = (max(|lo|, |hi|) + |o.i|) * 2^-16;
+ *       p = o.i + t * d.i;  !(lo - w <= p && p <= hi + w) -> miss
+ *     (A hit whose point lies outside the triangle's box by more than the rounding of the test can produce: what a ray lying in
+ *     the triangle's plane to f32 precision gets, whose det is rounding noise.  The check makes every hit lie near its triangle,
+ *     which is what lets the library's hierarchy give exactly the loop's answer: DESIGN.md 4c.)
+ * Normal: normalize(cross(e1, e2)), NOT turned toward the ray; State::finalize computes ffnormal from it as for planes.
+ *
+ * closest_hit: spheres, then planes, then the triangles in flattened order, then Scene::sample_lights.  A triangle is accepted
+ * when t < dist (dist = the running closest distance), so the result is the nearest triangle nearer than everything before it,
+ * the lowest flattened index on equal t.  any_hit: any triangle hit with (!use_max || t < max_dist).
+ *
+ * Materials: a scene with meshes follows the large scenes' rule — every sphere and mesh material must be a full patch
+ * ((mask & RPT_MAT_ALL) == RPT_MAT_ALL, proc_kind == RPT_PROC_NONE); planes may carry any patch (at most 4 planes).  A triangle
+ * that wins therefore leaves its own material.  A mesh's emission counts when a path hits it, as for spheres; meshes are not
+ * lights (next-event estimation does not sample them).
+ *
+ * Limits: at most RPT_MESH_MAX_TRIANGLES triangles in all, n_spheres + triangles below 2^28 - 1, and the scene's device tables
+ * (spheres, lights, materials, triangles at 48 B, BVH nodes at 64 B: at most one per triangle) below 4 GiB (RPT_ERR_UNSUPPORTED).
+ * rpt_upload_scene answers
+ *   RPT_ERR_INVALID_ARG  a vertex index >= n_vertices, a non-finite vertex, a NULL array with a non-zero count (vertices,
+ *                        indices, or meshes), a material index out of range;
+ *   RPT_ERR_UNSUPPORTED  meshes together with RPT_SCENE_MEDIA or an SDF object, a sphere or mesh material that is not a full patch,
+ *                        more than the limits above;
+ * and rpt_render* answer RPT_ERR_UNSUPPORTED for RPT_RENDER_FAST_MATH, RPT_RENDER_NESTED_LOOPS and RPT_RENDER_SMALL_COMPACT on a
+ * scene with meshes (the scene class has one, strict kernel: like media).  A scene whose meshes hold no triangle at all is not
+ * a mesh scene.  The library builds a bounding volume hierarchy over the triangles at upload; it returns exactly
+ * what the ordered loop above returns, for every ray (a ray with a NaN component hits no triangle; one with an infinite component,
+ * and every ray of a scene with a vertex coordinate beyond 2^60, is served by the loop itself). */
+#define RPT_MESH_MAX_TRIANGLES (1u << 26)
+
+typedef struct rpt_mesh {
+    uint32_t n_vertices;  const float*    vertices;   /* xyz, 3 floats per vertex */
+    uint32_t n_triangles; const uint32_t* indices;    /* 3 vertex indices per triangle */
+    uint32_t material;                                /* index into rpt_scene_desc.materials */
+} rpt_mesh;
+
 typedef struct rpt_scene_desc {
     uint32_t abi_version;             /* RPT_ABI_VERSION */
     uint32_t flags;
@@ -258,6 +311,7 @@ typedef struct rpt_scene_desc {
     uint32_t n_lights;    const rpt_light*    lights;     /* then Scene::sample_lights */
     uint32_t n_materials; const rpt_material* materials;
     rpt_sdf  sdf;                     /* then the SDF object, if any */
+    uint32_t n_meshes;    const rpt_mesh*     meshes;     /* then the meshes' triangles (after the planes: see "triangle meshes") */
 } rpt_scene_desc;
 
 /* Fill `out` with renderer/src/analytical.rs's AnalyticalScene (2 spheres, plane,

@@ -98,6 +98,8 @@ struct Scene {
     uint32_t max_depth = 4;                    // scene.rs:28-30
     bool any_hit_uses_max_dist = false;
     bool sample_all_light_types = false;       // rectangular / distant lights do something (off = the reference)
+    // triangle meshes (include/rpt.h, "triangle meshes"): each points at vertex / index arrays the caller keeps alive
+    std::vector<rpt_mesh> meshes;
     virtual ~Scene() = default;
 
     size_t number_of_lights() const { return lights.size(); }
@@ -121,6 +123,7 @@ struct Scene {
         d.n_planes = (uint32_t)planes.size(); d.planes = planes.data();
         d.n_lights = (uint32_t)lights_flat_.size(); d.lights = lights_flat_.data();
         d.n_materials = (uint32_t)materials.size(); d.materials = materials.data();
+        d.n_meshes = (uint32_t)meshes.size(); d.meshes = meshes.data();
         return d;
     }
 

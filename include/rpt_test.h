@@ -51,6 +51,18 @@ int rpt_probe_fn(rpt_ctx* ctx, uint32_t fn, const float* in_dev, float* out_dev,
  * or 0xFFFFFFFF, any_hit (0/1) with max_dist honoured}.  use_grid = 0 forces the brute-force loops. */
 int rpt_probe_rays(rpt_ctx* ctx, const float* rays_dev, uint32_t* out_dev, uint64_t n, uint32_t use_grid, void* stream);
 
+/* Ray queries against the uploaded MESH scene's triangles (include/rpt.h, "triangle meshes"), through the device functions the mesh
+ * kernel calls: rays_dev = n x {origin[3], direction[3], max_dist}; out_dev = n x {t (f32 bits; +inf's bits when nothing is hit), the
+ * nearest triangle's flattened index or 0xFFFFFFFF, any_hit (0/1)} — closest over the triangles alone, from dist = F::MAX; any_hit
+ * with max_dist honoured when `flags` bit 0 is set.  `flags` bit 1: the ordered loop over every triangle instead of the BVH.
+ * RPT_ERR_NO_SCENE unless the uploaded scene has meshes. */
+enum { RPT_MESH_QUERY_USE_MAX = 1u << 0, RPT_MESH_QUERY_BRUTE = 1u << 1 };
+int rpt_debug_mesh_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
+
+/* The uploaded mesh scene's hierarchy (csrc/host_bvh.h): its interior nodes, the depth of its deepest leaf, and the host time its build
+ * took in rpt_upload_scene.  RPT_ERR_NO_SCENE unless the uploaded scene has meshes.  (tools/mesh_bench.py) */
+int rpt_debug_mesh_stats(rpt_ctx* ctx, uint32_t* n_nodes, uint32_t* depth, float* build_ms);
+
 /* Multi-device contexts, after rpt_render / rpt_resident_render: the time in ms from the moment device index `b` (position in
  * rpt_create_multi's list) BEGAN its part of the last render to the moment device index `a` ENDED its part (HIP events on their
  * streams).  Positive for a != b means the two overlapped: what the fan-out inside render() promises (tracer.rs:29-32).  Events
@@ -69,7 +81,7 @@ int rpt_debug_sched_read(rpt_ctx* ctx, uint32_t* out, uint32_t capacity_tiles, u
  * bit 3 the table by class of accepted set (5-12 primitives), bits 8-15 the number of classes then, bits 16-19 the SDF object's
  * compile-time primitive count, bit 20 the relaxed-arithmetic build (RPT_RENDER_FAST_MATH), bit 21 small scenes' compacting kernel
  * (else the class's megakernel), bit 22 its dense form (at most 3 072 workgroups), bit 23 the nested-loop kernel, bit 24 the class's
- * participating-media form (the scene has media: RPT_SCENE_MEDIA).  For tests that must know that the kernel they aim at is the one
+ * participating-media form (the scene has media: RPT_SCENE_MEDIA), bit 25 the mesh scene class's kernel (k_mesh.hip).  For tests that must know that the kernel they aim at is the one
  * that ran. */
 int rpt_debug_kernel_choice(rpt_ctx* ctx, uint32_t* out);
 

@@ -1,7 +1,7 @@
 """ctypes mirror of include/rpt.h (the C ABI).  Plain data only."""
 import ctypes as C
 
-RPT_ABI_VERSION = 4
+RPT_ABI_VERSION = 5
 
 RPT_OK = 0
 RPT_ERR_INVALID_ARG = -1
@@ -110,6 +110,14 @@ class rpt_sdf(C.Structure):
                 ("hit_eps", C.c_float), ("max_t", C.c_float), ("normal_eps", C.c_float), ("prims", C.POINTER(rpt_sdf_prim))]
 
 
+RPT_MESH_MAX_TRIANGLES = 1 << 26
+
+
+class rpt_mesh(C.Structure):
+    _fields_ = [("n_vertices", C.c_uint32), ("vertices", C.POINTER(C.c_float)),
+                ("n_triangles", C.c_uint32), ("indices", C.POINTER(C.c_uint32)), ("material", C.c_uint32)]
+
+
 class rpt_scene_desc(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("flags", C.c_uint32),
@@ -120,6 +128,7 @@ class rpt_scene_desc(C.Structure):
         ("n_lights", C.c_uint32), ("lights", C.POINTER(rpt_light)),
         ("n_materials", C.c_uint32), ("materials", C.POINTER(rpt_material)),
         ("sdf", rpt_sdf),
+        ("n_meshes", C.c_uint32), ("meshes", C.POINTER(rpt_mesh)),
     ]
 
 
@@ -186,4 +195,8 @@ TEST_SYMBOLS = {
     "rpt_debug_sched_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]),
     "rpt_debug_kernel_choice": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rpt_probe_math": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rpt_debug_mesh_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rpt_debug_mesh_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
 }
+RPT_MESH_QUERY_USE_MAX = 1 << 0
+RPT_MESH_QUERY_BRUTE = 1 << 1

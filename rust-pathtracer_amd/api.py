@@ -132,6 +132,7 @@ class Scene:
         self.sample_all_light_types = False   # rectangular / distant lights do something (project-defined; off = the reference)
         self.media = False       # Material.medium is read: participating media (project-defined, include/rpt.h; off = the reference)
         self.sdf = None          # dict(prims=[(kind, center, (p0, p1))], material, smooth_k, max_steps, hit_eps, max_t, normal_eps)
+        self.meshes = []         # (vertices [N, 3] f32, indices [M, 3] u32, material_index): triangles after the planes (include/rpt.h)
         self._keep = None
 
     def recursion_depth(self):
@@ -189,7 +190,19 @@ class Scene:
             d.sdf.material = self.sdf["material"]; d.sdf.smooth_k = self.sdf.get("smooth_k", 0.5)
             d.sdf.max_steps = self.sdf.get("max_steps", 128); d.sdf.hit_eps = self.sdf.get("hit_eps", 1e-3)
             d.sdf.max_t = self.sdf.get("max_t", 100.0); d.sdf.normal_eps = self.sdf.get("normal_eps", 1e-3)
-        self._keep = (sph, pl, li, ma, sd)
+        me, arrays = None, []
+        if self.meshes:
+            import numpy as np
+            me = (_abi.rpt_mesh * len(self.meshes))()
+            for i, (verts, idx, m) in enumerate(self.meshes):
+                v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
+                t = np.ascontiguousarray(idx, dtype=np.uint32).reshape(-1, 3)
+                arrays += [v, t]
+                me[i].n_vertices = v.shape[0]; me[i].vertices = v.ctypes.data_as(C.POINTER(C.c_float))
+                me[i].n_triangles = t.shape[0]; me[i].indices = t.ctypes.data_as(C.POINTER(C.c_uint32))
+                me[i].material = m
+            d.n_meshes = len(self.meshes); d.meshes = C.cast(me, C.POINTER(_abi.rpt_mesh))
+        self._keep = (sph, pl, li, ma, sd, me, arrays)
         return d
 
 

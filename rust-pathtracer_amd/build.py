@@ -14,9 +14,20 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librpt_hip.so")
 TEST_LIB = os.path.join(HERE, "librpt_hip_test.so")
+# The mesh scene class's kernels (k_mesh.hip) are a code object library of their own, named after the library that loads it through
+# its run path ($ORIGIN) — mesh_lib_of(lib): an experiment build next to the product (tools/) gets its own — so the census of each
+# library's own kernels (tests/test_gpu_image_kernels.py, tests/kernel_census.py) stays what it was; tests/test_mesh_host.py keeps
+# the census of this one.  The test build loads the product's.
+
+
+def mesh_lib_of(lib):
+    return os.path.splitext(os.path.abspath(lib))[0] + "_mesh.so"
+
+
+MESH_LIB = mesh_lib_of(LIB)
 
 # One translation unit per kernel class (csrc/kernel_common.h says what each build of them is):
-#   strict    k_small tracks the range tests of the short divide / sqrt; k_compact, k_sdf, k_large test next to every operation
+#   strict    k_small tracks the range tests of the short divide / sqrt; k_compact, k_sdf, k_large, k_mesh test next to every operation
 #   relaxed   the four render TUs once more with hipcc's fast divide / sqrt and FMA contraction: what RPT_RENDER_FAST_MATH selects
 PEROP = ["-DRPT_GUARD_PER_OP"]
 RELAXED = ["-DRPT_RELAXED_BUILD", "-fno-hip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=fast"]
@@ -26,6 +37,7 @@ OBJECTS = [
     ("k_compact", "k_compact.hip", PEROP, "both"),
     ("k_sdf", "k_sdf.hip", PEROP, "both"),
     ("k_large", "k_large.hip", PEROP, "both"),
+    ("k_mesh", "k_mesh.hip", PEROP, "mesh"),                       # mesh scenes: strict only (include/rpt.h, "triangle meshes"); MESH_LIB
     ("k_small_fast", "k_small.hip", RELAXED, "both"),
     ("k_compact_fast", "k_compact.hip", RELAXED, "both"),
     ("k_sdf_fast", "k_sdf.hip", RELAXED, "both"),
@@ -87,10 +99,12 @@ def _deps():
             [os.path.abspath(__file__)])
 
 
-def needs_build(lib=LIB):
-    if not os.path.exists(lib):
+def needs_build(lib=LIB, mesh_lib=None):
+    """`mesh_lib`: the mesh library `lib` loads (default mesh_lib_of(lib); the test build loads the product's)."""
+    mesh_lib = mesh_lib or mesh_lib_of(lib)
+    if not os.path.exists(lib) or not os.path.exists(mesh_lib):
         return True
-    t = os.path.getmtime(lib)
+    t = min(os.path.getmtime(lib), os.path.getmtime(mesh_lib))
     return any(os.path.getmtime(d) > t for d in _deps())
 
 
@@ -98,7 +112,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
     """Compile csrc/*.hip -> `lib` (and, when `test_lib` is given, the test build beside it).  hipcc cross-compiles gfx950 without a GPU.
     `extra_flags` / `lib` / `objdir_name`: experiment builds next to the product library (tools/); `only`: recompile just these
     objects (the others are taken from `objdir_name`/ as they are — or, if missing there, from the product's build/)."""
-    if not force and not needs_build(lib) and (test_lib is None or not needs_build(test_lib)):
+    if not force and not needs_build(lib) and (test_lib is None or not needs_build(test_lib, mesh_lib_of(lib))):
         return lib
     objdir = os.path.join(HERE, objdir_name)
     os.makedirs(objdir, exist_ok=True)
@@ -127,11 +141,18 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
             failed.append(" ".join(cmd))
     if failed:
         raise RuntimeError("build.py: compilation failed:\n" + "\n".join(failed))
+    mesh_lib = mesh_lib_of(lib)
+    link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w == "mesh"] + [
+        "-Wl,-soname," + os.path.basename(mesh_lib), "-o", mesh_lib]
+    if verbose:
+        print(" ".join(link))
+    subprocess.run(link, check=True, cwd=CSRC)
     for out, kinds in ((lib, ("both", "product")), (test_lib, ("both", "test"))):
         if out is None:
             continue
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-        link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w in kinds] + ["-ldl", "-o", out]
+        link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w in kinds] + [
+            mesh_lib, "-Wl,-rpath,$ORIGIN", "-ldl", "-o", out]
         if verbose:
             print(" ".join(link))
         subprocess.run(link, check=True, cwd=CSRC)

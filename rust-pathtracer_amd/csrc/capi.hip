@@ -9,6 +9,7 @@
 
 #include <dlfcn.h>
 
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "../../include/rpt.h"
+#include "host_bvh.h"
 #include "host_scene.h"
 #include "knobs.h"
 #include "launch.h"
@@ -40,6 +42,8 @@ struct DevState {
     hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_ready = nullptr;
     SceneLarge scene_large;           // device pointers into `tables`
     void* tables = nullptr;           // one allocation holding a large scene's tables
+    SceneMesh scene_mesh;             // a mesh scene's: device pointers into `mesh_tables` (include/rpt.h, "triangle meshes")
+    void* mesh_tables = nullptr;
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -85,6 +89,9 @@ struct rpt_ctx {
     bool has_scene = false;
     bool large = false;               // scene exceeds the kernarg tables: SceneLarge + device tables
     bool media = false;               // RPT_SCENE_MEDIA and some material carries a medium: the media kernels (dev_media.h)
+    bool mesh = false;                // the scene has triangles: SceneMesh + DevState::mesh_tables (k_mesh.hip)
+    uint32_t mesh_nodes = 0, mesh_depth = 0;    // its hierarchy (include/rpt_test.h, rpt_debug_mesh_stats)
+    float mesh_build_ms = 0.0f;
     SceneSmallSdf scene;              // camera part is filled per launch (depends on width/height); sdf.n_prims == 0: plain
     bool class_map_ok = false;        // small scenes of 5-12 primitives: their accepted sets fall into at most 16 classes of equal material
     MatClassMap class_map = {};       // (launch.h; `cls` is filled per device at launch: the 4 096-byte map is DevState::tables of such a scene)
@@ -292,6 +299,7 @@ static void free_dev(DevState& d)
     if (d.fb) (void)hipFree(d.fb);
     if (d.tile) (void)hipFree(d.tile);
     if (d.tables) (void)hipFree(d.tables);
+    if (d.mesh_tables) (void)hipFree(d.mesh_tables);
     if (d.dn) (void)hipFree(d.dn);
     for (DevState::SchedEntry& e : d.sched_cache) if (e.buf) (void)hipFree(e.buf);
     if (d.sched_done) (void)hipEventDestroy(d.sched_done);
@@ -480,8 +488,10 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     }
     SceneSmallSdf scs = ctx->scene;
     SceneLarge scl = d.scene_large;
-    scs.cam = scl.cam = make_camera(ctx->camera, (float)width, (float)height);
-    const bool has_sdf = !ctx->large && scs.sdf.n_prims > 0;
+    SceneMesh scm = d.scene_mesh;
+    scs.cam = scl.cam = scm.cam = make_camera(ctx->camera, (float)width, (float)height);
+    const bool in_hbm = ctx->large || ctx->mesh;                    // the scene's tables are in device memory (large and mesh scenes)
+    const bool has_sdf = !in_hbm && scs.sdf.n_prims > 0;
     const bool nested = (flags & RPT_RENDER_NESTED_LOOPS) != 0;
     const bool fast = (flags & RPT_RENDER_FAST_MATH) != 0;
 
@@ -497,8 +507,8 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     // (small scenes' megakernel only; 8 ... 48 are within 2 % of each other, +5.9 % over finishing un-voted)
     rp.finish_threshold = knobs().finish_threshold;
     rp.march_min_lanes = knobs().sdf_march_min_lanes;
-    rp.compact = (!ctx->large && !has_sdf && ((flags & RPT_RENDER_SMALL_COMPACT) || spp <= knobs().compact_max_spp)) ? 1u : 0u;
-    if (flags & RPT_RENDER_RUSSIAN_ROULETTE) { scs.flags |= kSceneFlagRussianRoulette; scl.flags |= kSceneFlagRussianRoulette; }
+    rp.compact = (!in_hbm && !has_sdf && ((flags & RPT_RENDER_SMALL_COMPACT) || spp <= knobs().compact_max_spp)) ? 1u : 0u;
+    if (flags & RPT_RENDER_RUSSIAN_ROULETTE) { scs.flags |= kSceneFlagRussianRoulette; scl.flags |= kSceneFlagRussianRoulette; scm.flags |= kSceneFlagRussianRoulette; }
     if (rp.rows_local == 0) return RPT_OK;
     const uint32_t tiles_y = (rp.rows_local + 15u) / 16u;
     const uint64_t nblocks = (uint64_t)rp.tiles_x * tiles_y;
@@ -506,6 +516,10 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     // The nested-loop kernel is the differential baseline of the reference's own scene class; the other classes have one form.
     if (nested && (ctx->large || has_sdf || ctx->media)) {
         set_err(ctx, "render: RPT_RENDER_NESTED_LOOPS exists for small scenes without an SDF object or media only");
+        return RPT_ERR_UNSUPPORTED;
+    }
+    if (ctx->mesh && (flags & (RPT_RENDER_FAST_MATH | RPT_RENDER_NESTED_LOOPS | RPT_RENDER_SMALL_COMPACT))) {
+        set_err(ctx, "render: scenes with meshes have one kernel form (strict, path-regenerating): no RPT_RENDER_FAST_MATH, NESTED_LOOPS or SMALL_COMPACT");
         return RPT_ERR_UNSUPPORTED;
     }
     if (ctx->media && fast) {
@@ -518,13 +532,13 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     KernelChoice kc;
     {
         const SceneSmall& sc = scs;
-        const bool can_size = !knobs().no_sized_kernels && !ctx->media && !ctx->large && !nested;
+        const bool can_size = !knobs().no_sized_kernels && !ctx->media && !in_hbm && !nested;
         kc.sized = can_size && !has_sdf && sc.n_spheres == 2u && sc.n_planes == 1u && sc.n_lights == 1u;      // (kernel_common.h, RPT_REFERENCE_SIZES)
         kc.sized_sdf = (can_size && has_sdf && sc.n_planes == 1u && sc.n_lights == 1u && scs.sdf.n_prims <= 4u) ? scs.sdf.n_prims : 0u;
-        kc.material_table = !knobs().no_material_table && !ctx->media && !ctx->large && !nested && rptlaunch::material_table_fits_small(scs, has_sdf);      // (with or without the sizes)
-        kc.material_table_wide = !knobs().no_material_table && !ctx->media && !ctx->large && !nested && !has_sdf && !rp.compact && rptlaunch::material_table_fits_small(scs, false, 4u);
+        kc.material_table = !knobs().no_material_table && !ctx->media && !in_hbm && !nested && rptlaunch::material_table_fits_small(scs, has_sdf);      // (with or without the sizes)
+        kc.material_table_wide = !knobs().no_material_table && !ctx->media && !in_hbm && !nested && !has_sdf && !rp.compact && rptlaunch::material_table_fits_small(scs, false, 4u);
         // five to twelve primitives: the table by class of accepted set (launch.h, MatClassMap), in the megakernel of small scenes
-        if (!kc.material_table && !kc.material_table_wide && !knobs().no_material_table && !ctx->media && !ctx->large && !nested && !has_sdf && !rp.compact &&
+        if (!kc.material_table && !kc.material_table_wide && !knobs().no_material_table && !ctx->media && !in_hbm && !nested && !has_sdf && !rp.compact &&
             ctx->class_map_ok && d.tables) {
             kc.material_table_mapped = true;
             kc.class_map = ctx->class_map;
@@ -535,9 +549,10 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
                         ((kc.material_table_mapped ? kc.class_map.n_classes : 0u) << 8) | (kc.sized_sdf << 16) |
                         (fast ? 1u << 20 : 0u) | (rp.compact && !nested ? 1u << 21 : 0u) |
                         (rp.compact && !nested && nblocks <= kCompactDenseMaxBlocks ? 1u << 22 : 0u) | (nested ? 1u << 23 : 0u) |
-                        (ctx->media ? 1u << 24 : 0u);
+                        (ctx->media ? 1u << 24 : 0u) | (ctx->mesh ? 1u << 25 : 0u);
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
+        if (ctx->mesh) return rptlaunch::render_mesh(scm, rp, grid, stream);
         if (ctx->large) return fast ? rptlaunch_fast::render_large(scl, false, rp, grid, stream) : rptlaunch::render_large(scl, ctx->media, rp, grid, stream);
         if (has_sdf) return fast ? rptlaunch_fast::render_sdf(scs, false, rp, grid, stream, kc) : rptlaunch::render_sdf(scs, ctx->media, rp, grid, stream, kc);
         if (rp.compact && !nested) return fast ? rptlaunch_fast::render_compact(scs, false, rp, grid, stream, kc) : rptlaunch::render_compact(scs, ctx->media, rp, grid, stream, kc);
@@ -733,6 +748,7 @@ int rpt_scene_analytical(rpt_scene_desc* out)
     out->n_planes = 1; out->planes = planes;
     out->n_lights = 1; out->lights = lights;
     out->n_materials = 3; out->materials = mats;
+    out->n_meshes = 0; out->meshes = nullptr;                         // (the reference's scene has no triangles)
     return RPT_OK;
 }
 
@@ -869,6 +885,221 @@ void rpt_destroy(rpt_ctx* ctx)
     delete ctx;
 }
 
+// The device tables of a large scene (dev_scene_large.h), in one host buffer: spheres, their materials, lights, materials, the spherical
+// lights' records for Scene::sample_lights, the grid; `extra` more bytes at the end (a mesh scene's triangles and nodes).
+struct LargeTables {
+    std::vector<unsigned char> host;
+    size_t sz_sph = 0, sz_smat = 0, sz_lights = 0, sz_mats = 0, off_lsph = 0, sz_lsph = 0, sz_tables = 0, sz_accel = 0;
+    uint32_t n_light_spheres = 0;
+    bool lights_fast = true, use_accel = false;
+    HostAccel accel;
+    size_t end() const { return (sz_tables + sz_accel + 15) & ~(size_t)15; }     // where `extra` begins
+};
+
+static int prepare_large_tables(rpt_ctx* ctx, const rpt_scene_desc* s, uint64_t extra, LargeTables& lt)
+{
+    lt.sz_sph = sizeof(float4) * s->n_spheres;
+    lt.sz_smat = (sizeof(uint32_t) * s->n_spheres + 15) & ~(size_t)15;
+    lt.sz_lights = (sizeof(DevLight) * (s->n_lights ? s->n_lights : 1) + 15) & ~(size_t)15;
+    lt.sz_mats = (sizeof(DevMaterial) * (s->n_materials ? s->n_materials : 1) + 15) & ~(size_t)15;
+    lt.use_accel = s->n_spheres >= 64 && !knobs().no_grid;
+    if (lt.use_accel) {
+        std::string why;
+        if (!build_accel(s->spheres, s->n_spheres, lt.accel, why)) { set_err(ctx, "rpt_upload_scene: %s", why.c_str()); return RPT_ERR_UNSUPPORTED; }
+    }
+    // The spherical lights once more as {centre, radius * radius} records with their indices, padded to whole groups of four: what
+    // Scene::sample_lights' loop streams (dev_scene_large.h, closest_geom_finish).  Only when every light that DOES something
+    // in sample_lights is spherical: always, unless the scene samples the other light types and has a rectangular one.
+    std::vector<float> lsph;
+    std::vector<uint32_t> lids;
+    for (uint32_t i = 0; i < s->n_lights; ++i) {
+        const rpt_light& l = s->lights[i];
+        if (l.type == RPT_LIGHT_SPHERICAL) { lsph.insert(lsph.end(), {l.position[0], l.position[1], l.position[2], l.radius * l.radius}); lids.push_back(i); }
+        else if (l.type == RPT_LIGHT_RECTANGULAR && (s->flags & RPT_SCENE_SAMPLE_ALL_LIGHT_TYPES)) lt.lights_fast = false;
+    }
+    lt.n_light_spheres = (uint32_t)lids.size();
+    while (lids.size() % 4u) { lsph.insert(lsph.end(), {0.0f, 0.0f, 0.0f, 0.0f}); lids.push_back(0u); }
+    lt.sz_lsph = sizeof(float) * lsph.size();
+    const size_t sz_lids = (sizeof(uint32_t) * lids.size() + 15) & ~(size_t)15;
+    lt.sz_tables = lt.sz_sph + lt.sz_smat + lt.sz_lights + lt.sz_mats + lt.sz_lsph + sz_lids;
+    lt.sz_accel = lt.accel.bytes();
+    // every table is addressed with 32-bit byte offsets from its own base (dev_scene_large.h, gather32)
+    if ((uint64_t)lt.end() + extra >= (1ull << 32)) { set_err(ctx, "rpt_upload_scene: the scene's tables exceed 4 GiB"); return RPT_ERR_UNSUPPORTED; }
+    lt.host.assign(extra ? lt.end() + extra : lt.sz_tables + lt.sz_accel, 0);
+    float4* h_sph = reinterpret_cast<float4*>(lt.host.data());
+    uint32_t* h_smat = reinterpret_cast<uint32_t*>(lt.host.data() + lt.sz_sph);
+    DevLight* h_lights = reinterpret_cast<DevLight*>(lt.host.data() + lt.sz_sph + lt.sz_smat);
+    DevMaterial* h_mats = reinterpret_cast<DevMaterial*>(lt.host.data() + lt.sz_sph + lt.sz_smat + lt.sz_lights);
+    for (uint32_t i = 0; i < s->n_spheres; ++i) {
+        h_sph[i] = make_float4(s->spheres[i].center[0], s->spheres[i].center[1], s->spheres[i].center[2], s->spheres[i].radius);
+        h_smat[i] = s->spheres[i].material;
+    }
+    for (uint32_t i = 0; i < s->n_lights; ++i) h_lights[i] = dev_light(s->lights[i]);
+    for (uint32_t i = 0; i < s->n_materials; ++i) h_mats[i] = dev_material(s->materials[i]);
+    lt.off_lsph = lt.sz_sph + lt.sz_smat + lt.sz_lights + lt.sz_mats;
+    if (!lsph.empty()) memcpy(lt.host.data() + lt.off_lsph, lsph.data(), lt.sz_lsph);
+    if (!lids.empty()) memcpy(lt.host.data() + lt.off_lsph + lt.sz_lsph, lids.data(), sizeof(uint32_t) * lids.size());
+    if (lt.use_accel) lt.accel.write(lt.host.data() + lt.sz_tables);
+    return RPT_OK;
+}
+
+// The SceneLarge over a copy of lt.host at `base` on a device.
+static void bind_large_tables(SceneLarge& L, const rpt_scene_desc* s, const LargeTables& lt, unsigned char* base)
+{
+    memset(&L, 0, sizeof(L));
+    L.n_spheres = s->n_spheres; L.n_planes = s->n_planes; L.n_lights = s->n_lights; L.n_materials = s->n_materials;
+    L.flags = s->flags; L.max_depth = s->max_depth; L.eps = s->eps; L.n_lights_f = (float)s->n_lights;
+    L.bg = dev_background(s->background);
+    L.spheres = reinterpret_cast<const float4*>(base);
+    L.sphere_material = reinterpret_cast<const uint32_t*>(base + lt.sz_sph);
+    L.lights = reinterpret_cast<const DevLight*>(base + lt.sz_sph + lt.sz_smat);
+    L.materials = reinterpret_cast<const DevMaterial*>(base + lt.sz_sph + lt.sz_smat + lt.sz_lights);
+    L.light_spheres = reinterpret_cast<const float4*>(base + lt.off_lsph);
+    L.light_sphere_ids = reinterpret_cast<const uint32_t*>(base + lt.off_lsph + lt.sz_lsph);
+    L.n_light_spheres = lt.lights_fast ? lt.n_light_spheres : 0xFFFFFFFFu;
+    for (uint32_t i = 0; i < s->n_planes; ++i) L.planes[i] = dev_plane(s->planes[i]);
+    L.use_accel = lt.use_accel ? 1u : 0u;
+    if (lt.use_accel) lt.accel.bind(L, base + lt.sz_tables);
+}
+
+// ---- mesh scenes (include/rpt.h, "triangle meshes") ----
+static uint64_t mesh_triangles(const rpt_scene_desc* s)
+{
+    uint64_t n = 0;
+    for (uint32_t m = 0; m < s->n_meshes; ++m) n += s->meshes[m].n_triangles;
+    return n;
+}
+
+// The checks that hold for every scene's meshes (also an empty one's): include/rpt.h's RPT_ERR_INVALID_ARG cases.
+static int validate_meshes(rpt_ctx* ctx, const rpt_scene_desc* s)
+{
+    if (s->n_meshes && !s->meshes) { set_err(ctx, "rpt_upload_scene: meshes is NULL"); return RPT_ERR_INVALID_ARG; }
+    for (uint32_t m = 0; m < s->n_meshes; ++m) {
+        const rpt_mesh& me = s->meshes[m];
+        if ((me.n_vertices && !me.vertices) || (me.n_triangles && !me.indices)) { set_err(ctx, "rpt_upload_scene: mesh %u: a table pointer is NULL", m); return RPT_ERR_INVALID_ARG; }
+        if (me.material >= s->n_materials) { set_err(ctx, "rpt_upload_scene: mesh %u material out of range", m); return RPT_ERR_INVALID_ARG; }
+        for (uint64_t k = 0; k < 3ull * me.n_vertices; ++k)
+            if (!std::isfinite(me.vertices[k])) { set_err(ctx, "rpt_upload_scene: mesh %u vertex %llu is not finite", m, (unsigned long long)(k / 3)); return RPT_ERR_INVALID_ARG; }
+        for (uint64_t k = 0; k < 3ull * me.n_triangles; ++k)
+            if (me.indices[k] >= me.n_vertices) { set_err(ctx, "rpt_upload_scene: mesh %u triangle %llu: vertex index out of range", m, (unsigned long long)(k / 3)); return RPT_ERR_INVALID_ARG; }
+    }
+    return RPT_OK;
+}
+
+// Validate, flatten, build the hierarchy once, upload to every device; the context's scene changes only when every device has its
+// tables (a failure leaves the previous scene as it was).
+static int upload_mesh_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
+{
+    const uint64_t n64 = mesh_triangles(s);
+    if (n64 > RPT_MESH_MAX_TRIANGLES) { set_err(ctx, "rpt_upload_scene: at most %u triangles", RPT_MESH_MAX_TRIANGLES); return RPT_ERR_UNSUPPORTED; }
+    if (s->flags & RPT_SCENE_MEDIA) { set_err(ctx, "rpt_upload_scene: meshes and participating media (RPT_SCENE_MEDIA) do not go together"); return RPT_ERR_UNSUPPORTED; }
+    if (s->sdf.n_prims) { set_err(ctx, "rpt_upload_scene: meshes and the SDF object do not go together"); return RPT_ERR_UNSUPPORTED; }
+    const uint32_t n = (uint32_t)n64;
+    if ((uint64_t)s->n_spheres + n >= kNoSphere) { set_err(ctx, "rpt_upload_scene: spheres + triangles must stay below 2^28 - 1"); return RPT_ERR_UNSUPPORTED; }
+    auto full_patch = [&](uint32_t mi) { const rpt_material& m = s->materials[mi]; return (m.mask & RPT_MAT_ALL) == RPT_MAT_ALL && m.proc_kind == RPT_PROC_NONE; };
+    for (uint32_t i = 0; i < s->n_spheres; ++i) {
+        const rpt_sphere& sp = s->spheres[i];
+        if (!full_patch(sp.material)) { set_err(ctx, "rpt_upload_scene: a scene with meshes needs full sphere materials; sphere %u's is not", i); return RPT_ERR_UNSUPPORTED; }
+        if (!std::isfinite(sp.center[0]) || !std::isfinite(sp.center[1]) || !std::isfinite(sp.center[2]) || !std::isfinite(sp.radius) || sp.radius < 0.0f) {
+            set_err(ctx, "rpt_upload_scene: sphere %u has a non-finite centre or a negative / non-finite radius", i);
+            return RPT_ERR_INVALID_ARG;
+        }
+    }
+    for (uint32_t m = 0; m < s->n_meshes; ++m)
+        if (!full_patch(s->meshes[m].material)) { set_err(ctx, "rpt_upload_scene: mesh %u's material is not a full patch (mask == RPT_MAT_ALL, no procedural part)", m); return RPT_ERR_UNSUPPORTED; }
+
+    // flatten: meshes in order, each mesh's triangles in order
+    std::vector<float> tv(9 * (size_t)n);
+    std::vector<uint32_t> tmat(n);
+    {
+        size_t k = 0;
+        for (uint32_t m = 0; m < s->n_meshes; ++m) {
+            const rpt_mesh& me = s->meshes[m];
+            for (uint32_t t = 0; t < me.n_triangles; ++t, ++k) {
+                for (int v = 0; v < 3; ++v)
+                    for (int a = 0; a < 3; ++a) tv[9 * k + 3 * v + a] = me.vertices[3 * (size_t)me.indices[3 * (size_t)t + v] + a];
+                tmat[k] = me.material;
+            }
+        }
+    }
+    rpthost::HostBvh bvh;
+    const auto t_build = std::chrono::steady_clock::now();
+    rpthost::build_bvh(tv.data(), n, bvh);
+    const float build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build).count();
+    // the walk's exactness argument needs finite widened slab bounds (dev_scene_mesh.h): beyond 2^60 the ordered loop serves every ray
+    bool coords_ok = true;
+    for (float x : tv) coords_ok = coords_ok && std::fabs(x) <= 0x1p60f;
+    const size_t sz_tris = 48 * (size_t)n, sz_nodes = sizeof(rpthost::BvhNode) * bvh.nodes.size();
+    LargeTables lt;
+    RPT_CHECK_RC(prepare_large_tables(ctx, s, (uint64_t)sz_tris + sz_nodes, lt));
+    {   // triangles in leaf order: {a, flattened index}, {b - a, -}, {c - a, material} (dev_scene_mesh.h, tri_at)
+        float* h = reinterpret_cast<float*>(lt.host.data() + lt.end());
+        for (uint32_t slot = 0; slot < n; ++slot) {
+            const uint32_t i = bvh.order[slot];
+            const float* v = &tv[9 * (size_t)i];
+            float* r = h + 12 * (size_t)slot;
+            r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; memcpy(&r[3], &i, 4);
+            r[4] = v[3] - v[0]; r[5] = v[4] - v[1]; r[6] = v[5] - v[2]; r[7] = 0.0f;
+            r[8] = v[6] - v[0]; r[9] = v[7] - v[1]; r[10] = v[8] - v[2]; memcpy(&r[11], &tmat[i], 4);
+        }
+        memcpy(lt.host.data() + lt.end() + sz_tris, bvh.nodes.data(), sz_nodes);
+    }
+    // every device first; only then does the context change
+    std::vector<void*> fresh(ctx->devs.size(), nullptr);
+    auto undo = [&]() { for (size_t i = 0; i < fresh.size(); ++i) if (fresh[i]) { DeviceGuard g(ctx->devs[i].device); (void)hipFree(fresh[i]); } };
+    for (size_t i = 0; i < ctx->devs.size(); ++i) {
+        DeviceGuard guard(ctx->devs[i].device);
+        hipError_t e = guard.status;
+        if (e == hipSuccess) e = hipMalloc(&fresh[i], lt.host.size());
+        if (e == hipSuccess) e = hipMemcpy(fresh[i], lt.host.data(), lt.host.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            set_err(ctx, "rpt_upload_scene: uploading the mesh tables to device %d failed: %s", ctx->devs[i].device, hipGetErrorString(e));
+            undo();
+            return RPT_ERR_HIP;
+        }
+    }
+    for (size_t i = 0; i < ctx->devs.size(); ++i) {
+        DevState& d = ctx->devs[i];
+        DeviceGuard guard(d.device);
+        (void)hipStreamSynchronize(d.stream);                       // a running launch may still read the old tables
+        if (d.tables) { (void)hipFree(d.tables); d.tables = nullptr; }
+        if (d.mesh_tables) (void)hipFree(d.mesh_tables);
+        d.mesh_tables = fresh[i];
+        unsigned char* base = reinterpret_cast<unsigned char*>(d.mesh_tables);
+        SceneMesh& M = d.scene_mesh;
+        memset(&M, 0, sizeof(M));
+        bind_large_tables(M, s, lt, base);
+        M.tris = reinterpret_cast<const float4*>(base + lt.end());
+        M.nodes = reinterpret_cast<const float4*>(base + lt.end() + sz_tris);
+        M.n_tris = n;
+        M.use_bvh = coords_ok ? 1u : 0u;
+    }
+    ctx->mesh_nodes = (uint32_t)bvh.nodes.size();
+    ctx->mesh_depth = bvh.depth;
+    ctx->mesh_build_ms = build_ms;
+    ctx->camera = s->camera;
+    ctx->class_map_ok = false;
+    ctx->large = false;
+    ctx->media = false;
+    ctx->mesh = true;
+    ctx->has_scene = true;
+    for (DevState& dv : ctx->devs) { dv.sched_launches = 0; for (DevState::SchedEntry& e : dv.sched_cache) e.launches = 0; }
+    return RPT_OK;
+}
+
+// A mesh scene's tables (DevState::mesh_tables) go when another scene is committed.
+static void drop_mesh_tables(rpt_ctx* ctx)
+{
+    for (DevState& d : ctx->devs) {
+        if (!d.mesh_tables) continue;
+        DeviceGuard guard(d.device);
+        (void)hipStreamSynchronize(d.stream);
+        (void)hipFree(d.mesh_tables);
+        d.mesh_tables = nullptr;
+    }
+    ctx->mesh = false;
+}
+
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
 {
     if (!ctx || !s) { set_err(ctx, "rpt_upload_scene: NULL argument"); return RPT_ERR_INVALID_ARG; }
@@ -916,6 +1147,8 @@ int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
             if (s->sdf.prims[i].kind > RPT_SDF_TORUS_Y) { set_err(ctx, "rpt_upload_scene: unknown SDF primitive kind"); return RPT_ERR_INVALID_ARG; }
         if (large) { set_err(ctx, "rpt_upload_scene: the SDF object is only supported in small scenes"); return RPT_ERR_UNSUPPORTED; }
     }
+    RPT_CHECK_RC(validate_meshes(ctx, s));
+    if (mesh_triangles(s) > 0) return upload_mesh_scene(ctx, s);
     if (large) {
         if (s->n_spheres >= kNoSphere) { set_err(ctx, "rpt_upload_scene: at most 2^28 - 2 spheres"); return RPT_ERR_UNSUPPORTED; }
         // Layered patches need a bit per primitive; large scenes must use full sphere materials.
@@ -939,73 +1172,18 @@ int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
                 return RPT_ERR_INVALID_ARG;
             }
         }
-        const size_t sz_sph = sizeof(float4) * s->n_spheres;
-        const size_t sz_smat = (sizeof(uint32_t) * s->n_spheres + 15) & ~(size_t)15;
-        const size_t sz_lights = (sizeof(DevLight) * (s->n_lights ? s->n_lights : 1) + 15) & ~(size_t)15;
-        const size_t sz_mats = (sizeof(DevMaterial) * (s->n_materials ? s->n_materials : 1) + 15) & ~(size_t)15;
-        const bool use_accel = s->n_spheres >= 64 && !knobs().no_grid;
-        HostAccel accel;
-        if (use_accel) {
-            std::string why;
-            if (!build_accel(s->spheres, s->n_spheres, accel, why)) { set_err(ctx, "rpt_upload_scene: %s", why.c_str()); return RPT_ERR_UNSUPPORTED; }
-        }
-        // The spherical lights once more as {centre, radius * radius} records with their indices, padded to whole groups of four: what
-        // Scene::sample_lights' loop streams (dev_scene_large.h, closest_geom_finish).  Only when every light that DOES something
-        // in sample_lights is spherical: always, unless the scene samples the other light types and has a rectangular one.
-        bool lights_fast = true;
-        std::vector<float> lsph;
-        std::vector<uint32_t> lids;
-        for (uint32_t i = 0; i < s->n_lights; ++i) {
-            const rpt_light& l = s->lights[i];
-            if (l.type == RPT_LIGHT_SPHERICAL) { lsph.insert(lsph.end(), {l.position[0], l.position[1], l.position[2], l.radius * l.radius}); lids.push_back(i); }
-            else if (l.type == RPT_LIGHT_RECTANGULAR && (s->flags & RPT_SCENE_SAMPLE_ALL_LIGHT_TYPES)) lights_fast = false;
-        }
-        const uint32_t n_light_spheres = (uint32_t)lids.size();
-        while (lids.size() % 4u) { lsph.insert(lsph.end(), {0.0f, 0.0f, 0.0f, 0.0f}); lids.push_back(0u); }
-        const size_t sz_lsph = sizeof(float) * lsph.size(), sz_lids = (sizeof(uint32_t) * lids.size() + 15) & ~(size_t)15;
-        const size_t sz_tables = sz_sph + sz_smat + sz_lights + sz_mats + sz_lsph + sz_lids;
-        const size_t sz_accel = accel.bytes();
-        // every table is addressed with 32-bit byte offsets from its own base (dev_scene_large.h, gather32)
-        if ((uint64_t)sz_tables + sz_accel >= (1ull << 32)) { set_err(ctx, "rpt_upload_scene: the scene's tables exceed 4 GiB"); return RPT_ERR_UNSUPPORTED; }
-        std::vector<unsigned char> host(sz_tables + sz_accel, 0);
-        float4* h_sph = reinterpret_cast<float4*>(host.data());
-        uint32_t* h_smat = reinterpret_cast<uint32_t*>(host.data() + sz_sph);
-        DevLight* h_lights = reinterpret_cast<DevLight*>(host.data() + sz_sph + sz_smat);
-        DevMaterial* h_mats = reinterpret_cast<DevMaterial*>(host.data() + sz_sph + sz_smat + sz_lights);
-        for (uint32_t i = 0; i < s->n_spheres; ++i) {
-            h_sph[i] = make_float4(s->spheres[i].center[0], s->spheres[i].center[1], s->spheres[i].center[2], s->spheres[i].radius);
-            h_smat[i] = s->spheres[i].material;
-        }
-        for (uint32_t i = 0; i < s->n_lights; ++i) h_lights[i] = dev_light(s->lights[i]);
-        for (uint32_t i = 0; i < s->n_materials; ++i) h_mats[i] = dev_material(s->materials[i]);
-        const size_t off_lsph = sz_sph + sz_smat + sz_lights + sz_mats;
-        if (!lsph.empty()) memcpy(host.data() + off_lsph, lsph.data(), sz_lsph);
-        if (!lids.empty()) memcpy(host.data() + off_lsph + sz_lsph, lids.data(), sizeof(uint32_t) * lids.size());
-        if (use_accel) accel.write(host.data() + sz_tables);
+        LargeTables lt;
+        RPT_CHECK_RC(prepare_large_tables(ctx, s, 0, lt));
         for (DevState& d : ctx->devs) {
             DeviceGuard guard(d.device);
             RPT_HIP_CHECK(ctx, guard.status);
             RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));       // a running launch may still read the old tables
             if (d.tables) { RPT_HIP_CHECK(ctx, hipFree(d.tables)); d.tables = nullptr; }
-            RPT_HIP_CHECK(ctx, hipMalloc(&d.tables, host.size()));
-            RPT_HIP_CHECK(ctx, hipMemcpy(d.tables, host.data(), host.size(), hipMemcpyHostToDevice));
-            unsigned char* base = reinterpret_cast<unsigned char*>(d.tables);
-            SceneLarge& L = d.scene_large;
-            memset(&L, 0, sizeof(L));
-            L.n_spheres = s->n_spheres; L.n_planes = s->n_planes; L.n_lights = s->n_lights; L.n_materials = s->n_materials;
-            L.flags = s->flags; L.max_depth = s->max_depth; L.eps = s->eps; L.n_lights_f = (float)s->n_lights;
-            L.bg = dev_background(s->background);
-            L.spheres = reinterpret_cast<const float4*>(base);
-            L.sphere_material = reinterpret_cast<const uint32_t*>(base + sz_sph);
-            L.lights = reinterpret_cast<const DevLight*>(base + sz_sph + sz_smat);
-            L.materials = reinterpret_cast<const DevMaterial*>(base + sz_sph + sz_smat + sz_lights);
-            L.light_spheres = reinterpret_cast<const float4*>(base + off_lsph);
-            L.light_sphere_ids = reinterpret_cast<const uint32_t*>(base + off_lsph + sz_lsph);
-            L.n_light_spheres = lights_fast ? n_light_spheres : 0xFFFFFFFFu;
-            for (uint32_t i = 0; i < s->n_planes; ++i) L.planes[i] = dev_plane(s->planes[i]);
-            L.use_accel = use_accel ? 1u : 0u;
-            if (use_accel) accel.bind(L, base + sz_tables);
+            RPT_HIP_CHECK(ctx, hipMalloc(&d.tables, lt.host.size()));
+            RPT_HIP_CHECK(ctx, hipMemcpy(d.tables, lt.host.data(), lt.host.size(), hipMemcpyHostToDevice));
+            bind_large_tables(d.scene_large, s, lt, reinterpret_cast<unsigned char*>(d.tables));
         }
+        drop_mesh_tables(ctx);
         ctx->camera = s->camera;
         ctx->class_map_ok = false;
         ctx->large = true;
@@ -1056,6 +1234,7 @@ int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
             RPT_HIP_CHECK(ctx, hipMemcpy(dv.tables, cls.data(), cls.size(), hipMemcpyHostToDevice));
         }
     }
+    drop_mesh_tables(ctx);
     ctx->camera = s->camera;
     ctx->large = false;
     ctx->media = media;
@@ -1618,6 +1797,25 @@ int rpt_probe_rays(rpt_ctx* ctx, const float* rays_dev, uint32_t* out_dev, uint6
     SceneLarge sc = ctx->devs[0].scene_large;
     if (!use_grid) sc.use_accel = 0;
     RPT_HIP_CHECK(ctx, rptlaunch::probe_rays(sc, rays_dev, out_dev, n, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_debug_mesh_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->has_scene || !ctx->mesh) { set_err(ctx, "rpt_debug_mesh_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    if (!rays_dev || !out_dev || (flags & ~(uint32_t)(RPT_MESH_QUERY_USE_MAX | RPT_MESH_QUERY_BRUTE))) { set_err(ctx, "rpt_debug_mesh_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (n == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_query(ctx->devs[0].scene_mesh, rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_debug_mesh_stats(rpt_ctx* ctx, uint32_t* n_nodes, uint32_t* depth, float* build_ms)
+{
+    if (!ctx || !n_nodes || !depth || !build_ms) { set_err(ctx, "rpt_debug_mesh_stats: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->has_scene || !ctx->mesh) { set_err(ctx, "rpt_debug_mesh_stats: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    *n_nodes = ctx->mesh_nodes; *depth = ctx->mesh_depth; *build_ms = ctx->mesh_build_ms;
     return RPT_OK;
 }
 

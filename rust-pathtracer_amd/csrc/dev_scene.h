@@ -171,6 +171,15 @@ struct SceneLarge {
     uint32_t n_light_spheres;
 };
 
+// Mesh scenes (include/rpt.h, "triangle meshes"; dev_scene_mesh.h): a large scene's tables plus the triangles and their bounding
+// volume hierarchy (host_bvh.h), in HBM.
+struct SceneMesh : SceneLarge {
+    const float4* tris;               // 3 per triangle slot, in the hierarchy's leaf order: {a, flattened index}, {b - a, -}, {c - a, material}
+    const float4* nodes;              // 4 per node (host_bvh.h, BvhNode)
+    uint32_t n_tris;
+    uint32_t use_bvh;                 // 0: every triangle, in slot order (rpt_debug_mesh_query's RPT_MESH_QUERY_BRUTE)
+};
+
 // (seed, frame) -> the key of a frame's random streams (dev_math.h, Rng): host and device
 __host__ __device__ inline uint32_t pcg_hash_hd(uint32_t v)
 {

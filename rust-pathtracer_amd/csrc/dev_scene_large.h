@@ -434,6 +434,8 @@ RPT_DEV bool grid_any_sphere(const SceneLarge& sc, const RayD& ray, bool use_max
 // accepted planes above.  (rpt_upload_scene refuses tables with 2^28 spheres or more.)
 constexpr uint32_t kNoSphere = 0x0FFFFFFFu;
 
+RPT_DEV bool sample_lights_large(const SceneLarge& sc, const RayD& ray, PathState& ps, EmitterHit& e, bool hit);
+
 // Geometry pass of AnalyticalScene::closest_hit + Scene::sample_lights, as in dev_integrator.h, for N spheres:
 // the part after the sphere loop (dist / best / hit are the loop's result, however it was run).
 RPT_DEV bool closest_geom_finish(const SceneLarge& sc, const RayD& ray, PathState& ps, float dist, uint32_t best, bool hit, GeomHit& g, EmitterHit& e)
@@ -452,8 +454,12 @@ RPT_DEV bool closest_geom_finish(const SceneLarge& sc, const RayD& ray, PathStat
     }
     if (hit) ps.hit_dist = dist;
     g.code = (best == 0xFFFFFFFFu ? kNoSphere : best) | (accepted_planes << 28);
+    return sample_lights_large(sc, ray, ps, e, hit);
+}
 
-    // Scene::sample_lights, scene.rs:65-85
+// Scene::sample_lights, scene.rs:65-85: the end of closest_hit after every surface (`hit`: one was accepted; ps.hit_dist its distance).
+RPT_DEV bool sample_lights_large(const SceneLarge& sc, const RayD& ray, PathState& ps, EmitterHit& e, bool hit)
+{
     float ldist = ps.hit_dist;
     if (sc.n_light_spheres == 0xFFFFFFFFu) {
         for (uint32_t i = 0; i < sc.n_lights; ++i) {

@@ -1,5 +1,5 @@
 // launch.h — the seam between the host-side C ABI (capi.hip) and the kernels: one translation unit per kernel class
-// (k_small.hip, k_compact.hip, k_sdf.hip, k_large.hip: each holds its kernels and the function that launches them), the utility
+// (k_small.hip, k_compact.hip, k_sdf.hip, k_large.hip, k_mesh.hip: each holds its kernels and the function that launches them), the utility
 // kernels (k_util.hip), the denoiser (denoise.hip) and, in the test build only, the probes (k_probes.hip).
 #pragma once
 
@@ -49,6 +49,11 @@ hipError_t render_small(const rptdev::SceneSmall& sc, bool media, bool nested, c
 hipError_t render_compact(const rptdev::SceneSmall& sc, bool media, const rptdev::RenderParams& rp, uint32_t nblocks, hipStream_t st, const KernelChoice& kc);
 hipError_t render_sdf(const rptdev::SceneSmallSdf& scs, bool media, const rptdev::RenderParams& rp, uint32_t nblocks, hipStream_t st, const KernelChoice& kc);
 hipError_t render_large(const rptdev::SceneLarge& scl, bool media, const rptdev::RenderParams& rp, uint32_t nblocks, hipStream_t st);
+
+// Mesh scenes (k_mesh.hip; strict arithmetic, no media: include/rpt.h "triangle meshes").  mesh_query: rpt_debug_mesh_query's walks
+// (include/rpt_test.h; `flags` its RPT_MESH_QUERY_* bits).
+hipError_t render_mesh(const rptdev::SceneMesh& sc, const rptdev::RenderParams& rp, uint32_t nblocks, hipStream_t st);
+hipError_t mesh_query(const rptdev::SceneMesh& sc, const float* rays, uint32_t* out, uint64_t n, uint32_t flags, hipStream_t st);
 
 // Cost-ordered dispatch (kernel_common.h, block_tile): `cost` holds 4 dwords per tile, `order` one; init = bottom rows first and no
 // costs; order = the tiles sorted by the costs the last launch left, most expensive first.

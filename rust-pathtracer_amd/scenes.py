@@ -136,3 +136,63 @@ def sdf_scene():
                         (_abi.RPT_SDF_TORUS_Y, (-0.3, -0.55, 0.1), (1.25, 0.22))],
                  material=0, smooth_k=0.35, max_steps=128, hit_eps=1e-3, max_t=60.0, normal_eps=1e-3)
     return s
+
+
+def icosphere(subdivisions=3, center=(0.0, 0.0, 0.0), radius=1.0):
+    """-> (vertices [N, 3] f32, indices [M, 3] u32): the icosahedron, each triangle cut into four `subdivisions` times, the vertices
+    pushed out to the sphere (20 * 4^subdivisions triangles, shared vertices)."""
+    import numpy as np
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = np.array([[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t],
+                  [t, 0, -1], [t, 0, 1], [-t, 0, -1], [-t, 0, 1]], dtype=np.float64)
+    f = np.array([[0, 11, 5], [0, 5, 1], [0, 1, 7], [0, 7, 10], [0, 10, 11], [1, 5, 9], [5, 11, 4], [11, 10, 2], [10, 7, 6],
+                  [7, 1, 8], [3, 9, 4], [3, 4, 2], [3, 2, 6], [3, 6, 8], [3, 8, 9], [4, 9, 5], [2, 4, 11], [6, 2, 10], [8, 6, 7],
+                  [9, 8, 1]])
+    tri = v[f]
+    tri /= np.linalg.norm(tri, axis=2, keepdims=True)
+    for _ in range(subdivisions):
+        a, b, c = tri[:, 0], tri[:, 1], tri[:, 2]
+        ab, bc, ca = (a + b) * 0.5, (b + c) * 0.5, (c + a) * 0.5
+        ab, bc, ca = (x / np.linalg.norm(x, axis=1, keepdims=True) for x in (ab, bc, ca))
+        tri = np.stack([np.stack([a, ab, ca], 1), np.stack([ab, b, bc], 1), np.stack([ca, bc, c], 1), np.stack([ab, bc, ca], 1)], 1).reshape(-1, 3, 3)
+    pts = (tri.reshape(-1, 3) * radius + np.asarray(center, dtype=np.float64)).astype(np.float32)
+    verts, inv = np.unique(pts, axis=0, return_inverse=True)
+    return verts, inv.reshape(-1, 3).astype(np.uint32)
+
+
+def torus(major=0.7, minor=0.3, n_major=128, n_minor=64, center=(0.0, 0.0, 0.0)):
+    """-> (vertices, indices): a torus around the z axis (the ring in the xy plane), n_major x n_minor quads as two triangles each."""
+    import numpy as np
+    u = np.arange(n_major) * (2.0 * np.pi / n_major)
+    w = np.arange(n_minor) * (2.0 * np.pi / n_minor)
+    uu, ww = np.meshgrid(u, w, indexing="ij")
+    ring = major + minor * np.cos(ww)
+    pts = np.stack([ring * np.cos(uu), ring * np.sin(uu), minor * np.sin(ww)], -1).reshape(-1, 3) + np.asarray(center)
+    i, j = np.meshgrid(np.arange(n_major), np.arange(n_minor), indexing="ij")
+    a = i * n_minor + j
+    b = ((i + 1) % n_major) * n_minor + j
+    c = ((i + 1) % n_major) * n_minor + (j + 1) % n_minor
+    d = i * n_minor + (j + 1) % n_minor
+    idx = np.concatenate([np.stack([a, b, c], -1).reshape(-1, 3), np.stack([a, c, d], -1).reshape(-1, 3)])
+    return pts.astype(np.float32), idx.astype(np.uint32)
+
+
+def mesh_scene(subdivisions=7, n_major=256, n_minor=128):
+    """A triangle-mesh scene (include/rpt.h, "triangle meshes"; the reference's Todo "Implement a mesh based example scene"): the
+    reference's scene with its two spheres replaced by meshes — a metal icosphere on the left, a red clearcoat torus on the right —
+    over the reference's checker floor, under its light and camera.  Defaults: 327 680 + 65 536 triangles."""
+    s = Scene()
+    s.camera = Pinhole((0.0, 0.0, 3.0), (0.0, 0.0, 0.0), 80.0)
+    s.background = dict(kind=_abi.RPT_BG_GRADIENT_Y, colour_a=(1.0, 1.0, 1.0), colour_b=(0.5, 0.7, 1.0), gamma=2.2, scale=0.5)
+    s.lights = [AnalyticalLight.spherical((3.0, 2.0, 2.0), 1.0, (3.0, 3.0, 3.0))]
+    s.materials = [
+        full_material(rgb=(1.0, 1.0, 1.0), roughness=0.05, metallic=1.0),                        # icosphere
+        full_material(rgb=(1.0, 0.186, 0.0), clearcoat=1.0, clearcoat_gloss=1.0, roughness=0.1),  # torus
+        Material(roughness=1.0, checker_dir=(0.5, 100.0, 0.25, 0.1)),                            # floor (analytical.rs:107-116)
+    ]
+    s.planes = [((0.0, 1.0, 0.0), (0.0, -1.0, 0.0), 0.0001, 2)]
+    v, t = icosphere(subdivisions, (-1.1, 0.0, 0.0), 1.0)
+    s.meshes.append((v, t, 0))
+    v, t = torus(0.7, 0.3, n_major, n_minor, (1.1, 0.0, 0.0))
+    s.meshes.append((v, t, 1))
+    return s

@@ -39,6 +39,12 @@ pub struct RptSdf {
     pub prims: *const RptSdfPrim,
 }
 #[repr(C)] #[derive(Clone, Copy)]
+pub struct RptMesh {
+    pub n_vertices: u32, pub vertices: *const f32,
+    pub n_triangles: u32, pub indices: *const u32,
+    pub material: u32,
+}
+#[repr(C)] #[derive(Clone, Copy)]
 pub struct RptSceneDesc {
     pub abi_version: u32, pub flags: u32,
     pub camera: RptCamera, pub background: RptBackground,
@@ -48,10 +54,12 @@ pub struct RptSceneDesc {
     pub n_lights: u32, pub lights: *const RptLight,
     pub n_materials: u32, pub materials: *const RptMaterial,
     pub sdf: RptSdf,
+    // triangle meshes (include/rpt.h, ABI 5).  SceneDescBuilder does not fill them yet (a `mesh` method is a follow-up): zero here.
+    pub n_meshes: u32, pub meshes: *const RptMesh,
 }
 #[repr(C)] #[derive(Clone, Copy)] pub struct RptUniqueId { pub bytes: [c_char; 128] }
 
-pub const RPT_ABI_VERSION: u32 = 4;
+pub const RPT_ABI_VERSION: u32 = 5;
 // Constants of include/rpt.h (tests/test_rust_binding.py compares every one of them with the header).
 pub const RPT_OK: i32 = 0;
 pub const RPT_ERR_INVALID_ARG: i32 = -1;
