@@ -9,7 +9,6 @@
 
 #include <dlfcn.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -20,8 +19,7 @@
 #include <vector>
 
 #include "../../include/rpt.h"
-#include "host_bvh.h"
-#include "host_scene.h"
+#include "host_upload.h"
 #include "knobs.h"
 #include "launch.h"
 #ifdef RPT_TEST_HOOKS
@@ -29,8 +27,8 @@
 #endif
 
 using namespace rptdev;
-using rpthost::HostAccel;
-using rpthost::build_accel;
+using rpthost::SceneImage;
+using rpthost::SceneKind;
 using rpthost::make_camera;
 using rpthost::knobs;
 
@@ -40,10 +38,8 @@ struct DevState {
     int rank = 0;                     // this device's rank in the world (row blocks b with b % world == rank)
     hipStream_t stream = nullptr;
     hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_ready = nullptr;
-    SceneLarge scene_large;           // device pointers into `tables`
-    void* tables = nullptr;           // one allocation holding a large scene's tables
-    SceneMesh scene_mesh;             // a mesh scene's: device pointers into `mesh_tables` (include/rpt.h, "triangle meshes")
-    void* mesh_tables = nullptr;
+    void* tables = nullptr;           // the scene's device tables (host_upload.h, SceneImage::bytes): a large or mesh scene's, a small one's class map
+    SceneMesh scene;                  // a large or mesh scene's kernel argument: device pointers into `tables` (rpthost::bind_scene)
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -86,16 +82,7 @@ struct rpt_ctx {
     bool peer_gather = false;         // single process, RPT_GATHER=p2p: hipMemcpyPeerAsync instead of RCCL
     uint32_t tile_rows = 2;
     uint32_t dispatch[4] = {0xFFFFFFFFu, 0, 0, 0};   // rpt_set_dispatch: cost_order (0xFFFFFFFF: the environment's defaults), unit_rounds, unit_min_spp, unit_slots
-    bool has_scene = false;
-    bool large = false;               // scene exceeds the kernarg tables: SceneLarge + device tables
-    bool media = false;               // RPT_SCENE_MEDIA and some material carries a medium: the media kernels (dev_media.h)
-    bool mesh = false;                // the scene has triangles: SceneMesh + DevState::mesh_tables (k_mesh.hip)
-    uint32_t mesh_nodes = 0, mesh_depth = 0;    // its hierarchy (include/rpt_test.h, rpt_debug_mesh_stats)
-    float mesh_build_ms = 0.0f;
-    SceneSmallSdf scene;              // camera part is filled per launch (depends on width/height); sdf.n_prims == 0: plain
-    bool class_map_ok = false;        // small scenes of 5-12 primitives: their accepted sets fall into at most 16 classes of equal material
-    MatClassMap class_map = {};       // (launch.h; `cls` is filled per device at launch: the 4 096-byte map is DevState::tables of such a scene)
-    rpt_camera camera;
+    rpthost::SceneState scene;        // its class, camera, small scenes' kernel argument (host_upload.h); every device's tables: DevState
     // resident ColorBuffer (buffer.rs:6-14): pixels as per-rank tiles + frames
     uint32_t res_w = 0, res_h = 0, res_tile_rows = 0, res_rows_padded = 0;
     uint64_t res_frames = 0;
@@ -268,38 +255,12 @@ static uint32_t unit_chunks(const DispatchPolicy& pol, uint64_t nblocks, uint32_
 constexpr uint32_t kOrderAlwaysFromSpp = 16;
 // Small scenes: launches of at most knobs().compact_max_spp samples per pixel take the compacting kernel (k_compact.hip).
 // (1 since round 3: 1080p, 1 spp 7.12 vs 6.83 Gsamples/s for the megakernel, 2 spp 7.01 vs 7.39: profiles/r3/spp_curve.txt)
-// ---- descriptor -> device tables ---------------------------------------------------------------------------
-static DevPlane dev_plane(const rpt_plane& a) { return DevPlane{a.normal[0], a.normal[1], a.normal[2], a.point[0], a.point[1], a.point[2], a.min_denom, a.material, a.max_t}; }
-static DevLight dev_light(const rpt_light& a)
-{
-    return DevLight{a.type, a.position[0], a.position[1], a.position[2], a.emission[0], a.emission[1], a.emission[2], a.radius, a.area,
-                    a.u[0], a.u[1], a.u[2], a.v[0], a.v[1], a.v[2]};
-}
-static DevMaterial dev_material(const rpt_material& a)
-{
-    DevMaterial m;
-    m.mask = a.mask; m.proc_kind = a.proc_kind;
-    for (int k = 0; k < 3; ++k) { m.rgb[k] = a.rgb[k]; m.emission[k] = a.emission[k]; }
-    m.anisotropic = a.anisotropic; m.metallic = a.metallic; m.roughness = a.roughness; m.subsurface = a.subsurface;
-    m.specular_tint = a.specular_tint; m.sheen = a.sheen; m.sheen_tint = a.sheen_tint; m.clearcoat = a.clearcoat;
-    m.clearcoat_gloss = a.clearcoat_gloss; m.spec_trans = a.spec_trans; m.ior = a.ior;
-    for (int k = 0; k < 4; ++k) m.proc_params[k] = a.proc_params[k];
-    m.medium_type = a.medium_type; m.medium_density = a.medium_density; m.medium_anisotropy = a.medium_anisotropy;
-    for (int k = 0; k < 3; ++k) m.medium_color[k] = a.medium_color[k];
-    return m;
-}
-static DevBackground dev_background(const rpt_background& b)
-{
-    return DevBackground{b.kind, b.colour_a[0], b.colour_a[1], b.colour_a[2], b.colour_b[0], b.colour_b[1], b.colour_b[2], b.gamma, b.scale};
-}
-
 static void free_dev(DevState& d)
 {
     DeviceGuard guard(d.device);
     if (d.fb) (void)hipFree(d.fb);
     if (d.tile) (void)hipFree(d.tile);
     if (d.tables) (void)hipFree(d.tables);
-    if (d.mesh_tables) (void)hipFree(d.mesh_tables);
     if (d.dn) (void)hipFree(d.dn);
     for (DevState::SchedEntry& e : d.sched_cache) if (e.buf) (void)hipFree(e.buf);
     if (d.sched_done) (void)hipEventDestroy(d.sched_done);
@@ -438,45 +399,6 @@ static int sched_for(rpt_ctx* ctx, DevState& d, uint32_t nblocks, uint32_t width
     return RPT_OK;
 }
 
-// The classes of accepted sets of a small scene of 5-12 primitives (launch.h, MatClassMap).  The material of a hit is Material::new()
-// overwritten field by field by the accepted primitives in order (apply_patch_fields; a procedural patch writes rgb whatever its
-// mask says: apply_patch_row), so two sets give the same material when every field has the same last writer in both.  False: the
-// scene is not one the mapped table serves (fewer than 5 primitives, two procedural materials, more than 16 classes).
-static bool material_class_map(const SceneSmall& sc, MatClassMap& map, std::vector<uint8_t>& cls)
-{
-    const uint32_t ns = sc.n_spheres, np = sc.n_planes, nb = ns + np;
-    if (nb < 5u || nb > 12u) return false;
-    uint32_t n_procedural = 0;
-    uint32_t mask_of[kMaxSpheres + kMaxPlanes];
-    for (uint32_t i = 0; i < nb; ++i) {
-        const DevMaterial& m = sc.materials[i < ns ? sc.spheres[i].material : sc.planes[i - ns].material];
-        n_procedural += m.proc_kind != 0u;
-        mask_of[i] = (m.mask & (uint32_t)RPT_MAT_ALL) | (m.proc_kind == RPT_PROC_CHECKER_DIR ? (uint32_t)RPT_MAT_RGB : 0u);
-    }
-    if (n_procedural > 1u) return false;
-    memset(&map, 0, sizeof(map));
-    cls.assign(4096, 0);
-    struct Signature { uint8_t last[13]; bool operator==(const Signature& o) const { return memcmp(last, o.last, sizeof(last)) == 0; } };
-    std::vector<Signature> classes;
-    for (uint32_t set = 0; set < (1u << nb); ++set) {
-        Signature sig;
-        memset(sig.last, 0xFF, sizeof(sig.last));
-        for (uint32_t i = 0; i < nb; ++i)
-            if ((set >> i) & 1u)
-                for (uint32_t f = 0; f < 13u; ++f) if ((mask_of[i] >> f) & 1u) sig.last[f] = (uint8_t)i;
-        size_t c = 0;
-        while (c < classes.size() && !(classes[c] == sig)) ++c;
-        if (c == classes.size()) {
-            if (classes.size() == kMatClasses) return false;
-            classes.push_back(sig);
-            map.class_set[c] = (uint16_t)((set & ((1u << ns) - 1u)) | ((set >> ns) << kMaxSpheres));      // (GeomHit.code's layout: planes from bit 8)
-        }
-        cls[set] = (uint8_t)c;
-    }
-    map.n_classes = (uint32_t)classes.size();
-    return true;
-}
-
 // One render launch sequence on one device.
 static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t width, uint32_t height, uint64_t frames_done, uint32_t spp,
                          uint64_t seed, uint32_t flags, uint32_t tile_rows, uint32_t rank, uint32_t world, hipStream_t stream)
@@ -486,11 +408,13 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
         set_err(ctx, "render: unknown flag bits 0x%x (bits 2-4, 6-7, 9-10 named A/B kernel forms until ABI 3; they are gone, include/rpt.h)", flags & ~(uint32_t)RPT_RENDER_ALL_FLAGS);
         return RPT_ERR_INVALID_ARG;
     }
-    SceneSmallSdf scs = ctx->scene;
-    SceneLarge scl = d.scene_large;
-    SceneMesh scm = d.scene_mesh;
-    scs.cam = scl.cam = scm.cam = make_camera(ctx->camera, (float)width, (float)height);
-    const bool in_hbm = ctx->large || ctx->mesh;                    // the scene's tables are in device memory (large and mesh scenes)
+    const SceneKind kind = ctx->scene.kind;
+    const bool media = ctx->scene.media;
+    SceneSmallSdf scs = ctx->scene.small;
+    SceneLarge scl = d.scene;
+    SceneMesh scm = d.scene;
+    scs.cam = scl.cam = scm.cam = make_camera(ctx->scene.camera, (float)width, (float)height);
+    const bool in_hbm = kind == SceneKind::large || kind == SceneKind::mesh;     // the scene's tables are in device memory
     const bool has_sdf = !in_hbm && scs.sdf.n_prims > 0;
     const bool nested = (flags & RPT_RENDER_NESTED_LOOPS) != 0;
     const bool fast = (flags & RPT_RENDER_FAST_MATH) != 0;
@@ -503,7 +427,7 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     rp.tile_rows = tile_rows; rp.rank = rank; rp.world = world;
     rp.seed = seed;
     rp.tiles_x = (width + 15u) / 16u;
-    rp.shade_threshold = has_sdf ? knobs().sdf_shade_room : knobs().shade_threshold;      // (k_sdf.hip: the second room's threshold, 0 = one block)
+    rp.shade_threshold = has_sdf ? knobs().sdf_shade_room : knobs().shade_threshold;      // (k_sdf.hip: the second room's threshold; knobs.h keeps both in 1..64)
     // (small scenes' megakernel only; 8 ... 48 are within 2 % of each other, +5.9 % over finishing un-voted)
     rp.finish_threshold = knobs().finish_threshold;
     rp.march_min_lanes = knobs().sdf_march_min_lanes;
@@ -514,15 +438,15 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     const uint64_t nblocks = (uint64_t)rp.tiles_x * tiles_y;
     if (nblocks > 0x7FFFFFFFull) { set_err(ctx, "render: grid too large"); return RPT_ERR_INVALID_ARG; }
     // The nested-loop kernel is the differential baseline of the reference's own scene class; the other classes have one form.
-    if (nested && (ctx->large || has_sdf || ctx->media)) {
+    if (nested && (kind == SceneKind::large || has_sdf || media)) {
         set_err(ctx, "render: RPT_RENDER_NESTED_LOOPS exists for small scenes without an SDF object or media only");
         return RPT_ERR_UNSUPPORTED;
     }
-    if (ctx->mesh && (flags & (RPT_RENDER_FAST_MATH | RPT_RENDER_NESTED_LOOPS | RPT_RENDER_SMALL_COMPACT))) {
+    if (kind == SceneKind::mesh && (flags & (RPT_RENDER_FAST_MATH | RPT_RENDER_NESTED_LOOPS | RPT_RENDER_SMALL_COMPACT))) {
         set_err(ctx, "render: scenes with meshes have one kernel form (strict, path-regenerating): no RPT_RENDER_FAST_MATH, NESTED_LOOPS or SMALL_COMPACT");
         return RPT_ERR_UNSUPPORTED;
     }
-    if (ctx->media && fast) {
+    if (media && fast) {
         set_err(ctx, "render: scenes with participating media (RPT_SCENE_MEDIA) have no relaxed-arithmetic kernel form");
         return RPT_ERR_UNSUPPORTED;
     }
@@ -532,16 +456,16 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     KernelChoice kc;
     {
         const SceneSmall& sc = scs;
-        const bool can_size = !knobs().no_sized_kernels && !ctx->media && !in_hbm && !nested;
+        const bool can_size = !knobs().no_sized_kernels && !media && !in_hbm && !nested;
         kc.sized = can_size && !has_sdf && sc.n_spheres == 2u && sc.n_planes == 1u && sc.n_lights == 1u;      // (kernel_common.h, RPT_REFERENCE_SIZES)
         kc.sized_sdf = (can_size && has_sdf && sc.n_planes == 1u && sc.n_lights == 1u && scs.sdf.n_prims <= 4u) ? scs.sdf.n_prims : 0u;
-        kc.material_table = !knobs().no_material_table && !ctx->media && !in_hbm && !nested && rptlaunch::material_table_fits_small(scs, has_sdf);      // (with or without the sizes)
-        kc.material_table_wide = !knobs().no_material_table && !ctx->media && !in_hbm && !nested && !has_sdf && !rp.compact && rptlaunch::material_table_fits_small(scs, false, 4u);
+        kc.material_table = !knobs().no_material_table && !media && !in_hbm && !nested && rptlaunch::material_table_fits_small(scs, has_sdf);      // (with or without the sizes)
+        kc.material_table_wide = !knobs().no_material_table && !media && !in_hbm && !nested && !has_sdf && !rp.compact && rptlaunch::material_table_fits_small(scs, false, 4u);
         // five to twelve primitives: the table by class of accepted set (launch.h, MatClassMap), in the megakernel of small scenes
-        if (!kc.material_table && !kc.material_table_wide && !knobs().no_material_table && !ctx->media && !in_hbm && !nested && !has_sdf && !rp.compact &&
-            ctx->class_map_ok && d.tables) {
+        if (!kc.material_table && !kc.material_table_wide && !knobs().no_material_table && !media && !in_hbm && !nested && !has_sdf && !rp.compact &&
+            ctx->scene.class_map_ok && d.tables) {
             kc.material_table_mapped = true;
-            kc.class_map = ctx->class_map;
+            kc.class_map = ctx->scene.class_map;
             kc.class_map.cls = reinterpret_cast<const uint8_t*>(d.tables);
         }
         kc.extra_lds = knobs().debug_extra_lds;
@@ -549,14 +473,14 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
                         ((kc.material_table_mapped ? kc.class_map.n_classes : 0u) << 8) | (kc.sized_sdf << 16) |
                         (fast ? 1u << 20 : 0u) | (rp.compact && !nested ? 1u << 21 : 0u) |
                         (rp.compact && !nested && nblocks <= kCompactDenseMaxBlocks ? 1u << 22 : 0u) | (nested ? 1u << 23 : 0u) |
-                        (ctx->media ? 1u << 24 : 0u) | (ctx->mesh ? 1u << 25 : 0u);
+                        (media ? 1u << 24 : 0u) | (kind == SceneKind::mesh ? 1u << 25 : 0u);
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
-        if (ctx->mesh) return rptlaunch::render_mesh(scm, rp, grid, stream);
-        if (ctx->large) return fast ? rptlaunch_fast::render_large(scl, false, rp, grid, stream) : rptlaunch::render_large(scl, ctx->media, rp, grid, stream);
-        if (has_sdf) return fast ? rptlaunch_fast::render_sdf(scs, false, rp, grid, stream, kc) : rptlaunch::render_sdf(scs, ctx->media, rp, grid, stream, kc);
-        if (rp.compact && !nested) return fast ? rptlaunch_fast::render_compact(scs, false, rp, grid, stream, kc) : rptlaunch::render_compact(scs, ctx->media, rp, grid, stream, kc);
-        return fast ? rptlaunch_fast::render_small(scs, false, nested, rp, grid, stream, kc) : rptlaunch::render_small(scs, ctx->media, nested, rp, grid, stream, kc);
+        if (kind == SceneKind::mesh) return rptlaunch::render_mesh(scm, rp, grid, stream);
+        if (kind == SceneKind::large) return fast ? rptlaunch_fast::render_large(scl, false, rp, grid, stream) : rptlaunch::render_large(scl, media, rp, grid, stream);
+        if (has_sdf) return fast ? rptlaunch_fast::render_sdf(scs, false, rp, grid, stream, kc) : rptlaunch::render_sdf(scs, media, rp, grid, stream, kc);
+        if (rp.compact && !nested) return fast ? rptlaunch_fast::render_compact(scs, false, rp, grid, stream, kc) : rptlaunch::render_compact(scs, media, rp, grid, stream, kc);
+        return fast ? rptlaunch_fast::render_small(scs, false, nested, rp, grid, stream, kc) : rptlaunch::render_small(scs, media, nested, rp, grid, stream, kc);
     };
 
     // Dispatch (kernel_common.h): this device's launches of `nblocks` tiles run most expensive tile first, as measured by the previous
@@ -885,361 +809,58 @@ void rpt_destroy(rpt_ctx* ctx)
     delete ctx;
 }
 
-// The device tables of a large scene (dev_scene_large.h), in one host buffer: spheres, their materials, lights, materials, the spherical
-// lights' records for Scene::sample_lights, the grid; `extra` more bytes at the end (a mesh scene's triangles and nodes).
-struct LargeTables {
-    std::vector<unsigned char> host;
-    size_t sz_sph = 0, sz_smat = 0, sz_lights = 0, sz_mats = 0, off_lsph = 0, sz_lsph = 0, sz_tables = 0, sz_accel = 0;
-    uint32_t n_light_spheres = 0;
-    bool lights_fast = true, use_accel = false;
-    HostAccel accel;
-    size_t end() const { return (sz_tables + sz_accel + 15) & ~(size_t)15; }     // where `extra` begins
-};
-
-static int prepare_large_tables(rpt_ctx* ctx, const rpt_scene_desc* s, uint64_t extra, LargeTables& lt)
+// rpt_upload_scene stages the new scene's tables on every device first (stage_scene: the context is untouched until every device
+// has them), then commits (commit_scene).  Staging holds the old and the new tables together for a moment.
+static int stage_scene(rpt_ctx* ctx, const SceneImage& img, std::vector<void*>& fresh)
 {
-    lt.sz_sph = sizeof(float4) * s->n_spheres;
-    lt.sz_smat = (sizeof(uint32_t) * s->n_spheres + 15) & ~(size_t)15;
-    lt.sz_lights = (sizeof(DevLight) * (s->n_lights ? s->n_lights : 1) + 15) & ~(size_t)15;
-    lt.sz_mats = (sizeof(DevMaterial) * (s->n_materials ? s->n_materials : 1) + 15) & ~(size_t)15;
-    lt.use_accel = s->n_spheres >= 64 && !knobs().no_grid;
-    if (lt.use_accel) {
-        std::string why;
-        if (!build_accel(s->spheres, s->n_spheres, lt.accel, why)) { set_err(ctx, "rpt_upload_scene: %s", why.c_str()); return RPT_ERR_UNSUPPORTED; }
-    }
-    // The spherical lights once more as {centre, radius * radius} records with their indices, padded to whole groups of four: what
-    // Scene::sample_lights' loop streams (dev_scene_large.h, closest_geom_finish).  Only when every light that DOES something
-    // in sample_lights is spherical: always, unless the scene samples the other light types and has a rectangular one.
-    std::vector<float> lsph;
-    std::vector<uint32_t> lids;
-    for (uint32_t i = 0; i < s->n_lights; ++i) {
-        const rpt_light& l = s->lights[i];
-        if (l.type == RPT_LIGHT_SPHERICAL) { lsph.insert(lsph.end(), {l.position[0], l.position[1], l.position[2], l.radius * l.radius}); lids.push_back(i); }
-        else if (l.type == RPT_LIGHT_RECTANGULAR && (s->flags & RPT_SCENE_SAMPLE_ALL_LIGHT_TYPES)) lt.lights_fast = false;
-    }
-    lt.n_light_spheres = (uint32_t)lids.size();
-    while (lids.size() % 4u) { lsph.insert(lsph.end(), {0.0f, 0.0f, 0.0f, 0.0f}); lids.push_back(0u); }
-    lt.sz_lsph = sizeof(float) * lsph.size();
-    const size_t sz_lids = (sizeof(uint32_t) * lids.size() + 15) & ~(size_t)15;
-    lt.sz_tables = lt.sz_sph + lt.sz_smat + lt.sz_lights + lt.sz_mats + lt.sz_lsph + sz_lids;
-    lt.sz_accel = lt.accel.bytes();
-    // every table is addressed with 32-bit byte offsets from its own base (dev_scene_large.h, gather32)
-    if ((uint64_t)lt.end() + extra >= (1ull << 32)) { set_err(ctx, "rpt_upload_scene: the scene's tables exceed 4 GiB"); return RPT_ERR_UNSUPPORTED; }
-    lt.host.assign(extra ? lt.end() + extra : lt.sz_tables + lt.sz_accel, 0);
-    float4* h_sph = reinterpret_cast<float4*>(lt.host.data());
-    uint32_t* h_smat = reinterpret_cast<uint32_t*>(lt.host.data() + lt.sz_sph);
-    DevLight* h_lights = reinterpret_cast<DevLight*>(lt.host.data() + lt.sz_sph + lt.sz_smat);
-    DevMaterial* h_mats = reinterpret_cast<DevMaterial*>(lt.host.data() + lt.sz_sph + lt.sz_smat + lt.sz_lights);
-    for (uint32_t i = 0; i < s->n_spheres; ++i) {
-        h_sph[i] = make_float4(s->spheres[i].center[0], s->spheres[i].center[1], s->spheres[i].center[2], s->spheres[i].radius);
-        h_smat[i] = s->spheres[i].material;
-    }
-    for (uint32_t i = 0; i < s->n_lights; ++i) h_lights[i] = dev_light(s->lights[i]);
-    for (uint32_t i = 0; i < s->n_materials; ++i) h_mats[i] = dev_material(s->materials[i]);
-    lt.off_lsph = lt.sz_sph + lt.sz_smat + lt.sz_lights + lt.sz_mats;
-    if (!lsph.empty()) memcpy(lt.host.data() + lt.off_lsph, lsph.data(), lt.sz_lsph);
-    if (!lids.empty()) memcpy(lt.host.data() + lt.off_lsph + lt.sz_lsph, lids.data(), sizeof(uint32_t) * lids.size());
-    if (lt.use_accel) lt.accel.write(lt.host.data() + lt.sz_tables);
-    return RPT_OK;
-}
-
-// The SceneLarge over a copy of lt.host at `base` on a device.
-static void bind_large_tables(SceneLarge& L, const rpt_scene_desc* s, const LargeTables& lt, unsigned char* base)
-{
-    memset(&L, 0, sizeof(L));
-    L.n_spheres = s->n_spheres; L.n_planes = s->n_planes; L.n_lights = s->n_lights; L.n_materials = s->n_materials;
-    L.flags = s->flags; L.max_depth = s->max_depth; L.eps = s->eps; L.n_lights_f = (float)s->n_lights;
-    L.bg = dev_background(s->background);
-    L.spheres = reinterpret_cast<const float4*>(base);
-    L.sphere_material = reinterpret_cast<const uint32_t*>(base + lt.sz_sph);
-    L.lights = reinterpret_cast<const DevLight*>(base + lt.sz_sph + lt.sz_smat);
-    L.materials = reinterpret_cast<const DevMaterial*>(base + lt.sz_sph + lt.sz_smat + lt.sz_lights);
-    L.light_spheres = reinterpret_cast<const float4*>(base + lt.off_lsph);
-    L.light_sphere_ids = reinterpret_cast<const uint32_t*>(base + lt.off_lsph + lt.sz_lsph);
-    L.n_light_spheres = lt.lights_fast ? lt.n_light_spheres : 0xFFFFFFFFu;
-    for (uint32_t i = 0; i < s->n_planes; ++i) L.planes[i] = dev_plane(s->planes[i]);
-    L.use_accel = lt.use_accel ? 1u : 0u;
-    if (lt.use_accel) lt.accel.bind(L, base + lt.sz_tables);
-}
-
-// ---- mesh scenes (include/rpt.h, "triangle meshes") ----
-static uint64_t mesh_triangles(const rpt_scene_desc* s)
-{
-    uint64_t n = 0;
-    for (uint32_t m = 0; m < s->n_meshes; ++m) n += s->meshes[m].n_triangles;
-    return n;
-}
-
-// The checks that hold for every scene's meshes (also an empty one's): include/rpt.h's RPT_ERR_INVALID_ARG cases.
-static int validate_meshes(rpt_ctx* ctx, const rpt_scene_desc* s)
-{
-    if (s->n_meshes && !s->meshes) { set_err(ctx, "rpt_upload_scene: meshes is NULL"); return RPT_ERR_INVALID_ARG; }
-    for (uint32_t m = 0; m < s->n_meshes; ++m) {
-        const rpt_mesh& me = s->meshes[m];
-        if ((me.n_vertices && !me.vertices) || (me.n_triangles && !me.indices)) { set_err(ctx, "rpt_upload_scene: mesh %u: a table pointer is NULL", m); return RPT_ERR_INVALID_ARG; }
-        if (me.material >= s->n_materials) { set_err(ctx, "rpt_upload_scene: mesh %u material out of range", m); return RPT_ERR_INVALID_ARG; }
-        for (uint64_t k = 0; k < 3ull * me.n_vertices; ++k)
-            if (!std::isfinite(me.vertices[k])) { set_err(ctx, "rpt_upload_scene: mesh %u vertex %llu is not finite", m, (unsigned long long)(k / 3)); return RPT_ERR_INVALID_ARG; }
-        for (uint64_t k = 0; k < 3ull * me.n_triangles; ++k)
-            if (me.indices[k] >= me.n_vertices) { set_err(ctx, "rpt_upload_scene: mesh %u triangle %llu: vertex index out of range", m, (unsigned long long)(k / 3)); return RPT_ERR_INVALID_ARG; }
-    }
-    return RPT_OK;
-}
-
-// Validate, flatten, build the hierarchy once, upload to every device; the context's scene changes only when every device has its
-// tables (a failure leaves the previous scene as it was).
-static int upload_mesh_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
-{
-    const uint64_t n64 = mesh_triangles(s);
-    if (n64 > RPT_MESH_MAX_TRIANGLES) { set_err(ctx, "rpt_upload_scene: at most %u triangles", RPT_MESH_MAX_TRIANGLES); return RPT_ERR_UNSUPPORTED; }
-    if (s->flags & RPT_SCENE_MEDIA) { set_err(ctx, "rpt_upload_scene: meshes and participating media (RPT_SCENE_MEDIA) do not go together"); return RPT_ERR_UNSUPPORTED; }
-    if (s->sdf.n_prims) { set_err(ctx, "rpt_upload_scene: meshes and the SDF object do not go together"); return RPT_ERR_UNSUPPORTED; }
-    const uint32_t n = (uint32_t)n64;
-    if ((uint64_t)s->n_spheres + n >= kNoSphere) { set_err(ctx, "rpt_upload_scene: spheres + triangles must stay below 2^28 - 1"); return RPT_ERR_UNSUPPORTED; }
-    auto full_patch = [&](uint32_t mi) { const rpt_material& m = s->materials[mi]; return (m.mask & RPT_MAT_ALL) == RPT_MAT_ALL && m.proc_kind == RPT_PROC_NONE; };
-    for (uint32_t i = 0; i < s->n_spheres; ++i) {
-        const rpt_sphere& sp = s->spheres[i];
-        if (!full_patch(sp.material)) { set_err(ctx, "rpt_upload_scene: a scene with meshes needs full sphere materials; sphere %u's is not", i); return RPT_ERR_UNSUPPORTED; }
-        if (!std::isfinite(sp.center[0]) || !std::isfinite(sp.center[1]) || !std::isfinite(sp.center[2]) || !std::isfinite(sp.radius) || sp.radius < 0.0f) {
-            set_err(ctx, "rpt_upload_scene: sphere %u has a non-finite centre or a negative / non-finite radius", i);
-            return RPT_ERR_INVALID_ARG;
-        }
-    }
-    for (uint32_t m = 0; m < s->n_meshes; ++m)
-        if (!full_patch(s->meshes[m].material)) { set_err(ctx, "rpt_upload_scene: mesh %u's material is not a full patch (mask == RPT_MAT_ALL, no procedural part)", m); return RPT_ERR_UNSUPPORTED; }
-
-    // flatten: meshes in order, each mesh's triangles in order
-    std::vector<float> tv(9 * (size_t)n);
-    std::vector<uint32_t> tmat(n);
-    {
-        size_t k = 0;
-        for (uint32_t m = 0; m < s->n_meshes; ++m) {
-            const rpt_mesh& me = s->meshes[m];
-            for (uint32_t t = 0; t < me.n_triangles; ++t, ++k) {
-                for (int v = 0; v < 3; ++v)
-                    for (int a = 0; a < 3; ++a) tv[9 * k + 3 * v + a] = me.vertices[3 * (size_t)me.indices[3 * (size_t)t + v] + a];
-                tmat[k] = me.material;
-            }
-        }
-    }
-    rpthost::HostBvh bvh;
-    const auto t_build = std::chrono::steady_clock::now();
-    rpthost::build_bvh(tv.data(), n, bvh);
-    const float build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build).count();
-    // the walk's exactness argument needs finite widened slab bounds (dev_scene_mesh.h): beyond 2^60 the ordered loop serves every ray
-    bool coords_ok = true;
-    for (float x : tv) coords_ok = coords_ok && std::fabs(x) <= 0x1p60f;
-    const size_t sz_tris = 48 * (size_t)n, sz_nodes = sizeof(rpthost::BvhNode) * bvh.nodes.size();
-    LargeTables lt;
-    RPT_CHECK_RC(prepare_large_tables(ctx, s, (uint64_t)sz_tris + sz_nodes, lt));
-    {   // triangles in leaf order: {a, flattened index}, {b - a, -}, {c - a, material} (dev_scene_mesh.h, tri_at)
-        float* h = reinterpret_cast<float*>(lt.host.data() + lt.end());
-        for (uint32_t slot = 0; slot < n; ++slot) {
-            const uint32_t i = bvh.order[slot];
-            const float* v = &tv[9 * (size_t)i];
-            float* r = h + 12 * (size_t)slot;
-            r[0] = v[0]; r[1] = v[1]; r[2] = v[2]; memcpy(&r[3], &i, 4);
-            r[4] = v[3] - v[0]; r[5] = v[4] - v[1]; r[6] = v[5] - v[2]; r[7] = 0.0f;
-            r[8] = v[6] - v[0]; r[9] = v[7] - v[1]; r[10] = v[8] - v[2]; memcpy(&r[11], &tmat[i], 4);
-        }
-        memcpy(lt.host.data() + lt.end() + sz_tris, bvh.nodes.data(), sz_nodes);
-    }
-    // every device first; only then does the context change
-    std::vector<void*> fresh(ctx->devs.size(), nullptr);
-    auto undo = [&]() { for (size_t i = 0; i < fresh.size(); ++i) if (fresh[i]) { DeviceGuard g(ctx->devs[i].device); (void)hipFree(fresh[i]); } };
+    static const char* const kind_name[] = {"", "class map", "large scene", "mesh"};
+    fresh.assign(ctx->devs.size(), nullptr);
+    if (img.bytes.empty()) return RPT_OK;
     for (size_t i = 0; i < ctx->devs.size(); ++i) {
         DeviceGuard guard(ctx->devs[i].device);
         hipError_t e = guard.status;
-        if (e == hipSuccess) e = hipMalloc(&fresh[i], lt.host.size());
-        if (e == hipSuccess) e = hipMemcpy(fresh[i], lt.host.data(), lt.host.size(), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMalloc(&fresh[i], img.bytes.size());
+        if (e == hipSuccess) e = hipMemcpy(fresh[i], img.bytes.data(), img.bytes.size(), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
-            set_err(ctx, "rpt_upload_scene: uploading the mesh tables to device %d failed: %s", ctx->devs[i].device, hipGetErrorString(e));
-            undo();
+            set_err(ctx, "rpt_upload_scene: uploading the %s tables to device %d failed: %s", kind_name[(int)img.state.kind], ctx->devs[i].device,
+                    hipGetErrorString(e));
+            for (size_t k = 0; k <= i; ++k)
+                if (fresh[k]) { DeviceGuard g(ctx->devs[k].device); (void)hipFree(fresh[k]); }
             return RPT_ERR_HIP;
         }
     }
-    for (size_t i = 0; i < ctx->devs.size(); ++i) {
-        DevState& d = ctx->devs[i];
-        DeviceGuard guard(d.device);
-        (void)hipStreamSynchronize(d.stream);                       // a running launch may still read the old tables
-        if (d.tables) { (void)hipFree(d.tables); d.tables = nullptr; }
-        if (d.mesh_tables) (void)hipFree(d.mesh_tables);
-        d.mesh_tables = fresh[i];
-        unsigned char* base = reinterpret_cast<unsigned char*>(d.mesh_tables);
-        SceneMesh& M = d.scene_mesh;
-        memset(&M, 0, sizeof(M));
-        bind_large_tables(M, s, lt, base);
-        M.tris = reinterpret_cast<const float4*>(base + lt.end());
-        M.nodes = reinterpret_cast<const float4*>(base + lt.end() + sz_tris);
-        M.n_tris = n;
-        M.use_bvh = coords_ok ? 1u : 0u;
-    }
-    ctx->mesh_nodes = (uint32_t)bvh.nodes.size();
-    ctx->mesh_depth = bvh.depth;
-    ctx->mesh_build_ms = build_ms;
-    ctx->camera = s->camera;
-    ctx->class_map_ok = false;
-    ctx->large = false;
-    ctx->media = false;
-    ctx->mesh = true;
-    ctx->has_scene = true;
-    for (DevState& dv : ctx->devs) { dv.sched_launches = 0; for (DevState::SchedEntry& e : dv.sched_cache) e.launches = 0; }
     return RPT_OK;
 }
 
-// A mesh scene's tables (DevState::mesh_tables) go when another scene is committed.
-static void drop_mesh_tables(rpt_ctx* ctx)
+// Every device drops its old tables and takes its staged ones; then the context's scene is replaced, and the dispatch order of every
+// launch shape is learned again.
+static void commit_scene(rpt_ctx* ctx, const SceneImage& img, const std::vector<void*>& fresh)
 {
-    for (DevState& d : ctx->devs) {
-        if (!d.mesh_tables) continue;
+    for (size_t i = 0; i < ctx->devs.size(); ++i) {
+        DevState& d = ctx->devs[i];
         DeviceGuard guard(d.device);
-        (void)hipStreamSynchronize(d.stream);
-        (void)hipFree(d.mesh_tables);
-        d.mesh_tables = nullptr;
+        if (d.tables) {
+            (void)hipStreamSynchronize(d.stream);                   // a running launch may still read the old tables
+            (void)hipFree(d.tables);                                // (and hipFree waits for the device: launches on other streams)
+        }
+        d.tables = fresh[i];
+        rpthost::bind_scene(img, static_cast<unsigned char*>(d.tables), d.scene);
+        d.sched_launches = 0;
+        for (DevState::SchedEntry& e : d.sched_cache) e.launches = 0;
     }
-    ctx->mesh = false;
+    ctx->scene = img.state;
 }
 
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
 {
     if (!ctx || !s) { set_err(ctx, "rpt_upload_scene: NULL argument"); return RPT_ERR_INVALID_ARG; }
-    if (s->abi_version != RPT_ABI_VERSION) { set_err(ctx, "rpt_upload_scene: abi_version %u != %u", s->abi_version, RPT_ABI_VERSION); return RPT_ERR_INVALID_ARG; }
-    if ((s->n_spheres && !s->spheres) || (s->n_planes && !s->planes) || (s->n_lights && !s->lights) || (s->n_materials && !s->materials)) {
-        set_err(ctx, "rpt_upload_scene: a table pointer is NULL");
-        return RPT_ERR_INVALID_ARG;
-    }
-    // bounded loop counts: a wave must always reach the end of its kernel
-    if (s->max_depth > 4096u) { set_err(ctx, "rpt_upload_scene: max_depth %u exceeds the supported 4096", s->max_depth); return RPT_ERR_INVALID_ARG; }
-    if (s->sdf.n_prims && s->sdf.max_steps > 65536u) { set_err(ctx, "rpt_upload_scene: sdf.max_steps %u exceeds the supported 65536", s->sdf.max_steps); return RPT_ERR_INVALID_ARG; }
-    const bool large = s->n_spheres > (uint32_t)kMaxSpheres || s->n_lights > (uint32_t)kMaxLights || s->n_materials > (uint32_t)kMaxMaterials;
-    if (s->n_planes > (uint32_t)kMaxPlanes) {
-        set_err(ctx, "rpt_upload_scene: at most %d planes are supported", kMaxPlanes);
-        return RPT_ERR_UNSUPPORTED;
-    }
-    for (uint32_t i = 0; i < s->n_spheres; ++i)
-        if (s->spheres[i].material >= s->n_materials) { set_err(ctx, "rpt_upload_scene: sphere %u material out of range", i); return RPT_ERR_INVALID_ARG; }
-    for (uint32_t i = 0; i < s->n_planes; ++i)
-        if (s->planes[i].material >= s->n_materials) { set_err(ctx, "rpt_upload_scene: plane %u material out of range", i); return RPT_ERR_INVALID_ARG; }
-    for (uint32_t i = 0; i < s->n_lights; ++i)
-        if (s->lights[i].type > RPT_LIGHT_DISTANT) { set_err(ctx, "rpt_upload_scene: light %u has an unknown type", i); return RPT_ERR_INVALID_ARG; }
-    // participating media (include/rpt.h): used only under RPT_SCENE_MEDIA, and then only when some material carries one
-    bool media = false;
-    if (s->flags & RPT_SCENE_MEDIA) {
-        for (uint32_t i = 0; i < s->n_materials; ++i) {
-            const rpt_material& m = s->materials[i];
-            if (!(m.mask & RPT_MAT_MEDIUM)) continue;
-            if (m.medium_type > RPT_MEDIUM_EMISSIVE) { set_err(ctx, "rpt_upload_scene: material %u has an unknown medium type", i); return RPT_ERR_INVALID_ARG; }
-            if (!(m.medium_density >= 0.0f) || !std::isfinite(m.medium_density)) {
-                set_err(ctx, "rpt_upload_scene: material %u: the medium's density must be finite and >= 0", i);
-                return RPT_ERR_INVALID_ARG;
-            }
-            media = media || m.medium_type != RPT_MEDIUM_NONE;
-        }
-        if (media && s->n_materials > kMaxMediaMaterials) { set_err(ctx, "rpt_upload_scene: scenes with media can have at most %u materials", kMaxMediaMaterials); return RPT_ERR_UNSUPPORTED; }
-    }
-
-    if (s->sdf.n_prims) {
-        if (s->sdf.n_prims > (uint32_t)kMaxSdfPrims || !s->sdf.prims || s->sdf.material >= s->n_materials || !(s->sdf.smooth_k > 0.0f)) {
-            set_err(ctx, "rpt_upload_scene: bad SDF object (1..%d prims, material in range, smooth_k > 0)", kMaxSdfPrims);
-            return RPT_ERR_INVALID_ARG;
-        }
-        for (uint32_t i = 0; i < s->sdf.n_prims; ++i)
-            if (s->sdf.prims[i].kind > RPT_SDF_TORUS_Y) { set_err(ctx, "rpt_upload_scene: unknown SDF primitive kind"); return RPT_ERR_INVALID_ARG; }
-        if (large) { set_err(ctx, "rpt_upload_scene: the SDF object is only supported in small scenes"); return RPT_ERR_UNSUPPORTED; }
-    }
-    RPT_CHECK_RC(validate_meshes(ctx, s));
-    if (mesh_triangles(s) > 0) return upload_mesh_scene(ctx, s);
-    if (large) {
-        if (s->n_spheres >= kNoSphere) { set_err(ctx, "rpt_upload_scene: at most 2^28 - 2 spheres"); return RPT_ERR_UNSUPPORTED; }
-        // Layered patches need a bit per primitive; large scenes must use full sphere materials.
-        for (uint32_t i = 0; i < s->n_spheres; ++i) {
-            const rpt_material& m = s->materials[s->spheres[i].material];
-            if (media && !(m.mask & RPT_MAT_MEDIUM)) {
-                // (with patches a nearer sphere WITHOUT a medium would inherit the medium of a farther one accepted before it)
-                set_err(ctx, "rpt_upload_scene: in a large scene with media every sphere material must set RPT_MAT_MEDIUM "
-                             "(medium_type RPT_MEDIUM_NONE for none); sphere %u does not", i);
-                return RPT_ERR_UNSUPPORTED;
-            }
-            if ((m.mask & RPT_MAT_ALL) != RPT_MAT_ALL || m.proc_kind != RPT_PROC_NONE) {
-                set_err(ctx, "rpt_upload_scene: scenes beyond %d spheres / %d lights / %d materials need full sphere materials "
-                             "(mask == RPT_MAT_ALL, no procedural part); sphere %u does not", kMaxSpheres, kMaxLights, kMaxMaterials, i);
-                return RPT_ERR_UNSUPPORTED;
-            }
-            // the acceleration structure is built from these numbers: they must be numbers
-            const rpt_sphere& sp = s->spheres[i];
-            if (!std::isfinite(sp.center[0]) || !std::isfinite(sp.center[1]) || !std::isfinite(sp.center[2]) || !std::isfinite(sp.radius) || sp.radius < 0.0f) {
-                set_err(ctx, "rpt_upload_scene: sphere %u has a non-finite centre or a negative / non-finite radius", i);
-                return RPT_ERR_INVALID_ARG;
-            }
-        }
-        LargeTables lt;
-        RPT_CHECK_RC(prepare_large_tables(ctx, s, 0, lt));
-        for (DevState& d : ctx->devs) {
-            DeviceGuard guard(d.device);
-            RPT_HIP_CHECK(ctx, guard.status);
-            RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));       // a running launch may still read the old tables
-            if (d.tables) { RPT_HIP_CHECK(ctx, hipFree(d.tables)); d.tables = nullptr; }
-            RPT_HIP_CHECK(ctx, hipMalloc(&d.tables, lt.host.size()));
-            RPT_HIP_CHECK(ctx, hipMemcpy(d.tables, lt.host.data(), lt.host.size(), hipMemcpyHostToDevice));
-            bind_large_tables(d.scene_large, s, lt, reinterpret_cast<unsigned char*>(d.tables));
-        }
-        drop_mesh_tables(ctx);
-        ctx->camera = s->camera;
-        ctx->class_map_ok = false;
-        ctx->large = true;
-        ctx->media = media;
-        ctx->has_scene = true;
-        for (DevState& dv : ctx->devs) { dv.sched_launches = 0; for (DevState::SchedEntry& e : dv.sched_cache) e.launches = 0; }   // a new scene: the dispatch order is learned again
-        return RPT_OK;
-    }
-
-    for (DevState& d : ctx->devs) {                                 // drop the previous scene's tables (a large scene's, or a small one's class map)
-        if (!d.tables) continue;
-        DeviceGuard guard(d.device);
-        RPT_HIP_CHECK(ctx, guard.status);
-        RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
-        RPT_HIP_CHECK(ctx, hipFree(d.tables)); d.tables = nullptr;
-    }
-    SceneSmallSdf& d = ctx->scene;
-    memset(&d, 0, sizeof(d));
-    d.n_spheres = s->n_spheres; d.n_planes = s->n_planes; d.n_lights = s->n_lights; d.n_materials = s->n_materials;
-    d.flags = s->flags;
-    d.max_depth = s->max_depth;
-    d.eps = s->eps;
-    d.n_lights_f = (float)s->n_lights;
-    d.bg = dev_background(s->background);
-    for (uint32_t i = 0; i < s->n_spheres; ++i) {
-        const rpt_sphere& a = s->spheres[i];
-        d.spheres[i] = DevSphere{a.center[0], a.center[1], a.center[2], a.radius, a.material};
-    }
-    for (uint32_t i = 0; i < s->n_planes; ++i) d.planes[i] = dev_plane(s->planes[i]);
-    for (uint32_t i = 0; i < s->n_lights; ++i) d.lights[i] = dev_light(s->lights[i]);
-    for (uint32_t i = 0; i < s->n_materials; ++i) d.materials[i] = dev_material(s->materials[i]);
-    d.sdf.n_prims = s->sdf.n_prims; d.sdf.max_steps = s->sdf.max_steps; d.sdf.material = s->sdf.material;
-    d.sdf.smooth_k = s->sdf.smooth_k; d.sdf.hit_eps = s->sdf.hit_eps; d.sdf.max_t = s->sdf.max_t; d.sdf.normal_eps = s->sdf.normal_eps;
-    d.sdf.inv_smooth_k = s->sdf.n_prims ? 1.0f / s->sdf.smooth_k : 0.0f;
-    for (uint32_t i = 0; i < s->sdf.n_prims; ++i) {
-        const rpt_sdf_prim& a = s->sdf.prims[i];
-        d.sdf.prims[i] = DevSdfPrim{a.center[0], a.center[1], a.center[2], a.params[0], a.params[1], a.kind, {0u, 0u}};
-    }
-    // five to twelve primitives: the classes of accepted sets the material table is indexed by (launch.h, MatClassMap), once per scene;
-    // the 4 096-byte map lives in each device's `tables`
-    std::vector<uint8_t> cls;
-    ctx->class_map_ok = s->sdf.n_prims == 0 && !media && material_class_map(static_cast<const SceneSmall&>(d), ctx->class_map, cls);
-    if (ctx->class_map_ok) {
-        for (DevState& dv : ctx->devs) {
-            DeviceGuard guard(dv.device);
-            RPT_HIP_CHECK(ctx, guard.status);
-            RPT_HIP_CHECK(ctx, hipMalloc(&dv.tables, cls.size()));
-            RPT_HIP_CHECK(ctx, hipMemcpy(dv.tables, cls.data(), cls.size(), hipMemcpyHostToDevice));
-        }
-    }
-    drop_mesh_tables(ctx);
-    ctx->camera = s->camera;
-    ctx->large = false;
-    ctx->media = media;
-    ctx->has_scene = true;
-    for (DevState& dv : ctx->devs) dv.sched_launches = 0;
+    SceneImage img;
+    std::string why;
+    const int rc = rpthost::prepare_scene(s, img, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    std::vector<void*> fresh;
+    RPT_CHECK_RC(stage_scene(ctx, img, fresh));
+    commit_scene(ctx, img, fresh);
     return RPT_OK;
 }
 
@@ -1269,7 +890,7 @@ int rpt_render_device(rpt_ctx* ctx, float* pixels_dev, uint32_t width, uint32_t 
                       uint64_t seed, uint32_t flags, uint32_t tile_rows, uint32_t rank, uint32_t world, void* stream)
 {
     if (!ctx) { set_err(nullptr, "rpt_render_device: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->has_scene) { set_err(ctx, "rpt_render_device: no scene uploaded"); return RPT_ERR_NO_SCENE; }
+    if (ctx->scene.kind == SceneKind::none) { set_err(ctx, "rpt_render_device: no scene uploaded"); return RPT_ERR_NO_SCENE; }
     if (!pixels_dev || width == 0 || height == 0 || world == 0 || rank >= world || tile_rows == 0) {
         set_err(ctx, "rpt_render_device: invalid argument (pixels=%p width=%u height=%u tile_rows=%u rank=%u world=%u)",
                 (void*)pixels_dev, width, height, tile_rows, rank, world);
@@ -1288,7 +909,7 @@ int rpt_render(rpt_ctx* ctx, float* pixels, uint32_t width, uint32_t height, uin
     if (!ctx) { set_err(nullptr, "rpt_render: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
     if (!pixels || width == 0 || height == 0) { set_err(ctx, "rpt_render: invalid argument"); return RPT_ERR_INVALID_ARG; }
     if ((uint64_t)width * height > 0xFFFFFFFFull) { set_err(ctx, "rpt_render: image too large for 32-bit pixel indices"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->has_scene) { set_err(ctx, "rpt_render: no scene uploaded"); return RPT_ERR_NO_SCENE; }
+    if (ctx->scene.kind == SceneKind::none) { set_err(ctx, "rpt_render: no scene uploaded"); return RPT_ERR_NO_SCENE; }
     if ((size_t)ctx->world != ctx->devs.size()) {
         set_err(ctx, "rpt_render: a host ColorBuffer needs every rank in this process (rpt_create / rpt_create_multi); "
                      "with one process per GPU use the resident buffer (rpt_resident_*)");
@@ -1430,7 +1051,7 @@ int rpt_resident_render(rpt_ctx* ctx, uint32_t width, uint32_t height, uint32_t 
     if (!ctx) { set_err(nullptr, "rpt_resident_render: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
     if (width == 0 || height == 0) { set_err(ctx, "rpt_resident_render: invalid argument"); return RPT_ERR_INVALID_ARG; }
     if ((uint64_t)width * height > 0xFFFFFFFFull) { set_err(ctx, "rpt_resident_render: image too large for 32-bit pixel indices"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->has_scene) { set_err(ctx, "rpt_resident_render: no scene uploaded"); return RPT_ERR_NO_SCENE; }
+    if (ctx->scene.kind == SceneKind::none) { set_err(ctx, "rpt_resident_render: no scene uploaded"); return RPT_ERR_NO_SCENE; }
     int rc = resident_begin(ctx, width, height);
     if (rc != RPT_OK) return rc;
     DeviceGuard guard(ctx->devs[0].device);
@@ -1790,11 +1411,11 @@ int rpt_synchronize(rpt_ctx* ctx, void* stream)
 int rpt_probe_rays(rpt_ctx* ctx, const float* rays_dev, uint32_t* out_dev, uint64_t n, uint32_t use_grid, void* stream)
 {
     if (!ctx) { set_err(nullptr, "rpt_probe_rays: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->has_scene || !ctx->large) { set_err(ctx, "rpt_probe_rays: needs an uploaded large scene"); return RPT_ERR_NO_SCENE; }
+    if (ctx->scene.kind != SceneKind::large) { set_err(ctx, "rpt_probe_rays: needs an uploaded large scene"); return RPT_ERR_NO_SCENE; }
     if (!rays_dev || !out_dev) { set_err(ctx, "rpt_probe_rays: invalid argument"); return RPT_ERR_INVALID_ARG; }
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
-    SceneLarge sc = ctx->devs[0].scene_large;
+    SceneLarge sc = ctx->devs[0].scene;
     if (!use_grid) sc.use_accel = 0;
     RPT_HIP_CHECK(ctx, rptlaunch::probe_rays(sc, rays_dev, out_dev, n, (hipStream_t)stream));
     return RPT_OK;
@@ -1803,19 +1424,19 @@ int rpt_probe_rays(rpt_ctx* ctx, const float* rays_dev, uint32_t* out_dev, uint6
 int rpt_debug_mesh_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
 {
     if (!ctx) { set_err(nullptr, "rpt_debug_mesh_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->has_scene || !ctx->mesh) { set_err(ctx, "rpt_debug_mesh_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
     if (!rays_dev || !out_dev || (flags & ~(uint32_t)(RPT_MESH_QUERY_USE_MAX | RPT_MESH_QUERY_BRUTE))) { set_err(ctx, "rpt_debug_mesh_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
-    RPT_HIP_CHECK(ctx, rptlaunch::mesh_query(ctx->devs[0].scene_mesh, rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_query(ctx->devs[0].scene, rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
 }
 
 int rpt_debug_mesh_stats(rpt_ctx* ctx, uint32_t* n_nodes, uint32_t* depth, float* build_ms)
 {
     if (!ctx || !n_nodes || !depth || !build_ms) { set_err(ctx, "rpt_debug_mesh_stats: invalid argument"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->has_scene || !ctx->mesh) { set_err(ctx, "rpt_debug_mesh_stats: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    *n_nodes = ctx->mesh_nodes; *depth = ctx->mesh_depth; *build_ms = ctx->mesh_build_ms;
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_stats: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    *n_nodes = ctx->scene.mesh_nodes; *depth = ctx->scene.mesh_depth; *build_ms = ctx->scene.mesh_build_ms;
     return RPT_OK;
 }
 
@@ -1839,9 +1460,9 @@ int rpt_probe_fn(rpt_ctx* ctx, uint32_t fn, const float* in_dev, float* out_dev,
     DevCamera cam;
     memset(&cam, 0, sizeof(cam));
     if (fn == RPT_PROBE_FN_GEN_RAY) {
-        if (!ctx->has_scene) { set_err(ctx, "rpt_probe_fn: GEN_RAY uses the uploaded scene's camera"); return RPT_ERR_NO_SCENE; }
+        if (ctx->scene.kind == SceneKind::none) { set_err(ctx, "rpt_probe_fn: GEN_RAY uses the uploaded scene's camera"); return RPT_ERR_NO_SCENE; }
         if (!params) { set_err(ctx, "rpt_probe_fn: GEN_RAY needs params = {width, height}"); return RPT_ERR_INVALID_ARG; }
-        cam = make_camera(ctx->camera, params[0], params[1]);
+        cam = make_camera(ctx->scene.camera, params[0], params[1]);
     }
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);

@@ -1,5 +1,5 @@
 // host_bvh.h — the bounding volume hierarchy of mesh scenes (include/rpt.h, "triangle meshes"), built on the host at upload.  Plain
-// C++ with no HIP type in it, like host_grid.h: capi.hip includes it, and tests/test_mesh_host.py compiles it alone with
+// C++ with no HIP type in it, like host_grid.h: host_upload.h includes it, and tests/test_mesh_host.py compiles it alone with
 // g++ -fsanitize=address,undefined (tests/bvh_harness.cpp).  Single-threaded, so the same triangles give the same bytes.
 //
 // A binary tree, binned SAH (16 bins per axis over the centroids).  An interior node holds the boxes of its two children, so the

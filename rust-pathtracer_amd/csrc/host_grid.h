@@ -1,5 +1,5 @@
 // host_grid.h — the uniform grid of large scenes, built on the host at upload.  Plain C++ with no HIP type in it (compiled with
-// -ffp-contract=off like everything else): capi.hip includes it through host_scene.h, and tests/host_harness.cpp compiles it
+// -ffp-contract=off like everything else): host_upload.h includes it through host_scene.h, and tests/host_harness.cpp compiles it
 // alone with g++ -fsanitize=address,undefined (oracle/Makefile, `make asan`).
 #pragma once
 

@@ -15,7 +15,7 @@
 // checker colour and side do not fit the LDS beyond four primitives — but a row is a MATERIAL, and the material of a hit depends on the
 // accepted set only through which primitive wrote each field last (analytical.rs:56-58, 82-85, 115-116 are field writes): accepted sets
 // with the same last writers are one class, and a scene whose primitives carry whole materials has n + 1 of them.  The host sorts the
-// 2^n sets into classes (capi.hip, material_class_map); up to 16 classes x 2 colours x 2 sides = 64 rows fit.
+// 2^n sets into classes (host_upload.h, material_class_map); up to 16 classes x 2 colours x 2 sides = 64 rows fit.
 constexpr uint32_t kMatClasses = 16u;
 struct MatClassMap {
     uint32_t n_classes;
