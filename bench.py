@@ -15,9 +15,11 @@ The multi-GPU machinery is the library's (include/rpt.h: rpt_create_rank, rpt_re
 rpt_resident_gather_device); torch.distributed (gloo) only carries the 128-byte communicator id, the barriers and the
 max over ranks of the elapsed time.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline; everything else the line
+can carry (rooflines and committed counters, the other configs and kernel variants, the CPU baselines, the f64 comparison; N > 1:
+weak scaling, the one-GPU frame, configs[4]) is measured only with --full.
 """
 import argparse
 import json
@@ -682,8 +684,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU leg (profiling runs)")
-    ap.add_argument("--headline-only", action="store_true", help="skip the secondary configs[3] / configs[4] legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else the line can carry: rooflines, other configs and kernel variants, "
+                         "CPU baselines, the f64 comparison (N > 1: weak scaling, the one-GPU frame, configs[4])")
     ap.add_argument("--smoke-shared-gpu", action="store_true",
                     help="TEST ONLY: every rank drives cuda:0 and the tiles are gathered with peer copies (RCCL rejects "
                          "duplicate devices), to exercise the N>1 control flow on a 1-GPU box; the numbers mean nothing")
@@ -765,6 +768,36 @@ def main():
     def emit_locked():
         samples = width * height * spp * args.steps
         value = samples / elapsed / 1e6
+        out = {
+            "metric": "Msamples/s (pixels x spp) on AnalyticalScene 1920x1080 f32; 1/2/4/8-GPU scaling",
+            "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
+            "scaling": "none" if not multi else "strong",     # one GPU: nothing scales; N > 1: configs[2]'s frame is the same for every N
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": ("AnalyticalScene %dx%d x %d spp per step, f32, seed 1 (BASELINE.json configs[1])" % (width, height, spp)) if not multi else
+                                   ("AnalyticalScene %dx%d x %d spp per step, f32, seed 1 (BASELINE.json configs[2]): cyclic %d-row tiles over %d GPUs, "
+                                    "RCCL gather to rank 0 + scatter per step inside the timed region" % (width, height, spp, TILE_ROWS, world)),
+                       "spp_per_step": spp, "width": width, "height": height, "parallelism": "rows%d" % world,
+                       **({"gather": gather_mode} if multi else {})},
+        }
+        if args.full:
+            out.update(rooflines())
+        out.update(dict(extra))
+        if args.full and not multi:
+            out.update(other_configs(rpt, torch, local_rank, args.small))
+            if not args.small:
+                cpu = cpu_baseline(width, height)
+                out["cpu_baseline"] = cpu
+                out["gpu_over_cpu"] = round(value / cpu["value"], 1)
+                out["config1"] = config1_line(rpt, torch, local_rank, cpu["cores"])
+                try:
+                    out["f64_reference"] = f64_reference(rpt, torch, local_rank, cpu["cores"])
+                except Exception as e:      # noqa: BLE001 - a secondary leg must not cost the line
+                    out["f64_reference"] = {"error": "%s: %s" % (type(e).__name__, e)}
+        print(json.dumps(out))
+
+    def rooflines():
+        """--full: the FP32-VALU and HBM rooflines of the timed launches (op counts from the oracle, committed PMC counters)."""
         avg_kernel_s = sum(kernel_ms) / len(kernel_ms) / 1e3
         ops = op_counts()
         # FP32-VALU roofline of the megakernel: this rank's pixels x spp per step over the step's measured launch time
@@ -800,35 +833,10 @@ def main():
                             "nominal issue peak; frac_of_dual_issue_peak is the issue figure, x lane_utilisation = the share of the ALU lanes' "
                             "issue capacity doing path work; a stream of nothing but independent v_fma_f32 issues fma_stream_at_5_waves "
                             "at this occupancy (profiles/r5/valu_issue_peak.txt)"}
-        out = {
-            "metric": "Msamples/s (pixels x spp) on AnalyticalScene 1920x1080 f32; 1/2/4/8-GPU scaling",
-            "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "none" if not multi else "strong",     # one GPU: nothing scales; N > 1: configs[2]'s frame is the same for every N
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": ("AnalyticalScene %dx%d x %d spp per step, f32, seed 1 (BASELINE.json configs[1])" % (width, height, spp)) if not multi else
-                                   ("AnalyticalScene %dx%d x %d spp per step, f32, seed 1 (BASELINE.json configs[2]): cyclic %d-row tiles over %d GPUs, "
-                                    "RCCL gather to rank 0 + scatter per step inside the timed region" % (width, height, spp, TILE_ROWS, world)),
-                       "spp_per_step": spp, "width": width, "height": height, "parallelism": "rows%d" % world,
-                       **({"gather": gather_mode} if multi else {})},
-            "roofline": roofline,
-            "roofline_hbm": {"bound": "hbm", "achieved": round(hbm, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(hbm / HBM_PEAK_GBS, 6),
-                             "algorithmic_bytes_per_step": algo_bytes,
-                             "note": "32/S bytes per pixel-sample: the honest signature of an ALU-bound path, not the binding roofline"},
-        }
-        out.update(dict(extra))
-        if not multi and not args.headline_only:
-            out.update(other_configs(rpt, torch, local_rank, args.small))
-        if not multi and not args.no_cpu_baseline and not args.small:
-            cpu = cpu_baseline(width, height)
-            out["cpu_baseline"] = cpu
-            out["gpu_over_cpu"] = round(value / cpu["value"], 1)
-            out["config1"] = config1_line(rpt, torch, local_rank, cpu["cores"])
-            try:
-                out["f64_reference"] = f64_reference(rpt, torch, local_rank, cpu["cores"])
-            except Exception as e:      # noqa: BLE001 - a secondary leg must not cost the line
-                out["f64_reference"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        print(json.dumps(out))
+        return {"roofline": roofline,
+                "roofline_hbm": {"bound": "hbm", "achieved": round(hbm, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(hbm / HBM_PEAK_GBS, 6),
+                                 "algorithmic_bytes_per_step": algo_bytes,
+                                 "note": "32/S bytes per pixel-sample: the honest signature of an ALU-bound path, not the binding roofline"}}
 
     def secondary_legs():
         if os.environ.get("RPT_BENCH_TEST_STALL") == str(rank):         # tests: this rank never reaches the legs' first collective
@@ -903,6 +911,32 @@ def main():
             if tracer:
                 tracer._scene = scene
                 tracer.upload_scene()
+
+    def watched_secondary_legs():
+        # The headline is measured.  What follows are secondary legs on the same communicator: they must never cost the line.
+        # A leg that raises is recorded and ends the legs on this rank; ranks that then wait for it in a collective — or a leg that
+        # hangs — are cut off by a timer that emits the line with what there is and leaves.
+        def cut_off():
+            # The legs hang (or a rank never reached them): the line goes out with what there is, and the process ends with a
+            # status that says so — a hung rank must not look like success to the launcher.
+            with emit_lock:
+                if not emitted:
+                    extra["secondary_legs"] = "cut off after %d s" % SECONDARY_LIMIT_S
+            emit()
+            sys.stdout.flush()
+            sys.stderr.flush()
+            os._exit(3)
+
+        watchdog = threading.Timer(SECONDARY_LIMIT_S, cut_off)
+        watchdog.daemon = True
+        watchdog.start()
+        try:
+            secondary_legs()
+        except Exception as e:              # noqa: BLE001
+            with emit_lock:
+                extra["secondary_legs"] = "stopped by %s: %s" % (type(e).__name__, e)
+        dist.barrier()
+        watchdog.cancel()
 
     if not multi:
         # ---- one GPU: configs[1].  The frame is a torch tensor, the launches go to torch's current stream, and
@@ -1009,30 +1043,8 @@ def main():
         local_pixels = tiling.tile_row_count(height, TILE_ROWS, rank, world) * width
         if args.dump_outputs and rank == 0 and job:
             dump_outputs(args.dump_outputs, {**image_outputs("image", job.image, DUMP_LIMIT_BYTES // 2), "frames": [float(job.frames)]})
-        # The headline is measured.  What follows are secondary legs on the same communicator: they must never cost the line.
-        # A leg that raises is recorded and ends the legs on this rank; ranks that then wait for it in a collective — or a leg that
-        # hangs — are cut off by a timer that emits the line with what there is and leaves.
-        def cut_off():
-            # The legs hang (or a rank never reached them): the line goes out with what there is, and the process ends with a
-            # status that says so — a hung rank must not look like success to the launcher.
-            with emit_lock:
-                if not emitted:
-                    extra["secondary_legs"] = "cut off after %d s" % SECONDARY_LIMIT_S
-            emit()
-            sys.stdout.flush()
-            sys.stderr.flush()
-            os._exit(3)
-
-        watchdog = threading.Timer(SECONDARY_LIMIT_S, cut_off)
-        watchdog.daemon = True
-        watchdog.start()
-        try:
-            secondary_legs()
-        except Exception as e:              # noqa: BLE001
-            with emit_lock:
-                extra["secondary_legs"] = "stopped by %s: %s" % (type(e).__name__, e)
-        dist.barrier()
-        watchdog.cancel()
+        if args.full:
+            watched_secondary_legs()
 
     emit()
     if multi:

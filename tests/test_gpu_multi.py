@@ -292,7 +292,7 @@ def test_bench_runs_the_multi_gpu_control_flow_on_one_gpu(rpt, torch_cuda):
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29517", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--small",
-                        "--smoke-shared-gpu"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--smoke-shared-gpu", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
@@ -317,7 +317,7 @@ def test_bench_keeps_its_line_when_a_secondary_leg_hangs(rpt, torch_cuda):
     env["RPT_BENCH_TEST_STALL"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29519", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--small",
-                        "--smoke-shared-gpu"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--smoke-shared-gpu", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode != 0, "a cut-off run must not report success"
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, "ONE JSON line:\n" + r.stdout[-2000:] + r.stderr[-4000:]
@@ -340,7 +340,7 @@ def test_bench_multi_gpu_path_with_the_library_communicator_and_one_rank(rpt, to
         env.pop(k, None)
     env["MASTER_ADDR"] = "127.0.0.1"
     env["MASTER_PORT"] = "29533"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--small", "--force-multi"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--small", "--force-multi", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
