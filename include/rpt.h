@@ -421,6 +421,54 @@ int rpt_set_dispatch(rpt_ctx* ctx, uint32_t cost_order, uint32_t unit_rounds, ui
 /* Copy the scene into the context (Tracer owns its scene: tracer.rs:8). */
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* scene);
 
+/* ---- moving meshes — PROJECT-DEFINED ------------------------------------------------------------------------------------------
+ * New vertex positions for meshes of the uploaded scene, without the upload: the scene's meshes keep their indices, materials
+ * and triangle order, and each mesh named in `updates` gets the positions given — all of its vertices.  Afterwards the context
+ * renders exactly what it would render after rpt_upload_scene of the same descriptor with those vertex arrays: the same frames
+ * bit for bit, the same errors from rpt_render*.
+ *
+ * The hierarchy keeps its shape and gets new boxes, computed on the device (a refit: DESIGN.md 4c).  No result depends on that;
+ * speed can: the shape was chosen for the uploaded positions, and after a large deformation a fresh rpt_upload_scene walks
+ * faster.  Measured on an MI355X, scenes.mesh_scene (393 216 triangles) at 1920x1080 (tools/mesh_bench.py --update,
+ * profiles/NOTES.md): an update takes 0.62-0.65 ms (the context's first one 2.2 ms: it allocates) where the upload of the same
+ * moved scene takes 184-191 ms; and after a ripple of 1.25 % of the icosphere's radius with the torus turned by 0.05 rad a fresh
+ * upload rendered 1.4 % faster than the refitted hierarchy, after 12.5 % and 0.5 rad 35 % faster, after 25 % and 2 rad 74 % faster.
+ * Update while a mesh only moves; upload again once its shape has changed.
+ *
+ * The call blocks until every device of the context has finished its earlier work and holds the new tables (like
+ * rpt_upload_scene, whose hipFree waits for the device); launches the caller has put on streams of its own through
+ * rpt_render_device must be ordered by the caller, as for an upload.  The resident ColorBuffer is left alone, as rpt_upload_scene
+ * leaves it: the caller resets it.  The learned dispatch order is kept (it never changes a pixel, and a small move leaves the
+ * tile costs good predictors).  A context of several devices (rpt_create_multi) updates every one; with one process per GPU
+ * (rpt_create_rank) every rank makes the call itself, as for an upload.
+ *
+ * n_updates == 0 is RPT_OK and does nothing.  A mesh without triangles may be named: its count is checked and nothing else
+ * happens.  Everything below but RPT_ERR_HIP is checked on the host before any device is touched, in this order, so that a
+ * rejected call leaves the context exactly as it was:
+ *   RPT_ERR_INVALID_ARG  ctx is NULL; updates is NULL with a non-zero count;
+ *   RPT_ERR_NO_SCENE     no scene is uploaded, or the uploaded scene is not a mesh scene (it holds no triangle);
+ *   RPT_ERR_UNSUPPORTED  the scene's meshes hold 2^32 vertices or more in all;
+ *   RPT_ERR_INVALID_ARG  per update, in order: mesh >= the scene's n_meshes; a mesh named twice; n_vertices different from the
+ *                        uploaded mesh's; vertices NULL with a non-zero count; a non-finite coordinate (rpt_last_error names the
+ *                        mesh and the vertex);
+ *   RPT_ERR_HIP          a runtime call failed part-way.  The tables may then be half written, so the context is left with NO
+ *                        scene (its tables freed; rpt_render* answer RPT_ERR_NO_SCENE until the next rpt_upload_scene).
+ * As at upload, while a coordinate some triangle uses lies beyond 2^60 the ordered loop serves every ray; an update that brings
+ * all of them back turns the hierarchy's walk on again.
+ *
+ * Memory.  On the host a mesh scene keeps, from its upload to the context's first update, a copy of its vertices and indices
+ * (12 B per vertex + 12 B per triangle + 4 B per hierarchy node), and for its whole life 1 B per vertex.  The first update
+ * allocates on every device, until the next rpt_upload_scene, 12 B per vertex + 36 B per triangle + 4 B per hierarchy node (the
+ * vertices, each triangle's vertex indices and box, the refit order) — about half of the scene's own triangle and node tables —
+ * and releases the host copy.  A context that is never updated allocates nothing on a device. */
+typedef struct rpt_mesh_vertices {
+    uint32_t mesh;                    /* index into the uploaded scene's rpt_scene_desc.meshes */
+    uint32_t n_vertices;              /* must equal that mesh's n_vertices */
+    const float* vertices;            /* xyz, 3 floats per vertex: the mesh's new positions, all of them */
+} rpt_mesh_vertices;
+
+int rpt_update_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n_updates);
+
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)
  *   frames_done ColorBuffer.frames before the call; the caller adds `spp` afterwards

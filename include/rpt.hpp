@@ -199,6 +199,12 @@ public:
     /// Return the scene (tracer.rs:629); call sync_scene() after mutating it.
     Scene* scene() { return scene_; }
     void sync_scene() { rpt_scene_desc d = scene_->describe(); check(rpt_upload_scene(ctx_, &d), ctx_); }
+    /// New vertex positions for meshes of the uploaded scene without the upload (rpt.h, "moving meshes"): the frames of a fresh
+    /// sync_scene() of the moved scene, from a refit of the hierarchy on the device.  The caller's Scene keeps its own arrays:
+    /// point its rpt_mesh entries at the new positions before the next sync_scene().
+    void update_meshes(const std::vector<rpt_mesh_vertices>& updates) {
+        check(rpt_update_meshes(ctx_, updates.data(), (uint32_t)updates.size()), ctx_);
+    }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

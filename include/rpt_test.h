@@ -63,6 +63,12 @@ int rpt_debug_mesh_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32
  * took in rpt_upload_scene.  RPT_ERR_NO_SCENE unless the uploaded scene has meshes.  (tools/mesh_bench.py) */
 int rpt_debug_mesh_stats(rpt_ctx* ctx, uint32_t* n_nodes, uint32_t* depth, float* build_ms);
 
+/* Copy the uploaded mesh scene's triangle rows (which = 0: 48 B per triangle, in leaf order) or hierarchy nodes (which = 1: 64 B each,
+ * csrc/host_bvh.h BvhNode) from the context's first device to the host, as rpt_update_meshes (include/rpt.h) left them.  *bytes = the
+ * table's size; RPT_ERR_INVALID_ARG when `out` is NULL or holds fewer than that (*bytes is still set).  RPT_ERR_NO_SCENE unless the
+ * uploaded scene has meshes.  Waits for the device. */
+int rpt_debug_mesh_tables(rpt_ctx* ctx, uint32_t which, void* out, uint64_t capacity_bytes, uint64_t* bytes);
+
 /* Multi-device contexts, after rpt_render / rpt_resident_render: the time in ms from the moment device index `b` (position in
  * rpt_create_multi's list) BEGAN its part of the last render to the moment device index `a` ENDED its part (HIP events on their
  * streams).  Positive for a != b means the two overlapped: what the fan-out inside render() promises (tracer.rs:29-32).  Events

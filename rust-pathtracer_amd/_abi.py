@@ -118,6 +118,10 @@ class rpt_mesh(C.Structure):
                 ("n_triangles", C.c_uint32), ("indices", C.POINTER(C.c_uint32)), ("material", C.c_uint32)]
 
 
+class rpt_mesh_vertices(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("n_vertices", C.c_uint32), ("vertices", C.POINTER(C.c_float))]
+
+
 class rpt_scene_desc(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("flags", C.c_uint32),
@@ -163,6 +167,7 @@ SYMBOLS = {
     "rpt_last_error": (C.c_char_p, [C.c_void_p]),
     "rpt_abi_version": (C.c_uint32, []),
     "rpt_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(rpt_scene_desc)]),
+    "rpt_update_meshes": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_vertices), C.c_uint32]),
     "rpt_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -197,6 +202,7 @@ TEST_SYMBOLS = {
     "rpt_probe_math": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rpt_debug_mesh_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rpt_debug_mesh_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "rpt_debug_mesh_tables": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 RPT_MESH_QUERY_USE_MAX = 1 << 0
 RPT_MESH_QUERY_BRUTE = 1 << 1

@@ -381,6 +381,21 @@ class Tracer:
         desc = self._scene.describe()
         check(lib().rpt_upload_scene(self._h, C.byref(desc)), self._h)
 
+    def update_meshes(self, updates):
+        """New vertex positions for meshes of the uploaded scene without the upload (include/rpt.h, "moving meshes"): `updates` maps
+        a mesh's index in scene().meshes to an array of shape (n_vertices, 3).  The frames are those of upload_scene() of the moved
+        scene, bit for bit; the hierarchy is refitted on the device, not rebuilt.  On success the scene's vertex arrays are
+        replaced too, so a later upload_scene() uploads the moved scene."""
+        items = sorted(updates.items())
+        arrays = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3) for _, v in items]
+        ups = (_abi.rpt_mesh_vertices * max(1, len(items)))()
+        for u, (m, _), v in zip(ups, items, arrays):
+            u.mesh, u.n_vertices, u.vertices = int(m), v.shape[0], v.ctypes.data_as(C.POINTER(C.c_float))
+        check(lib().rpt_update_meshes(self._h, ups, len(items)), self._h)
+        for (m, _), v in zip(items, arrays):
+            _, idx, mat = self._scene.meshes[m]
+            self._scene.meshes[m] = (v, idx, mat)
+
     def scene(self):                                               # tracer.rs:629-631
         return self._scene
 

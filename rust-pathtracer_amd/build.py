@@ -26,6 +26,15 @@ def mesh_lib_of(lib):
 
 MESH_LIB = mesh_lib_of(LIB)
 
+
+# The refit kernels of rpt_update_meshes (k_refit.hip) are a third code object library, named, linked and found the same way:
+# tests/test_mesh_update_host.py keeps its census.
+def refit_lib_of(lib):
+    return os.path.splitext(os.path.abspath(lib))[0] + "_refit.so"
+
+
+REFIT_LIB = refit_lib_of(LIB)
+
 # One translation unit per kernel class (csrc/kernel_common.h says what each build of them is):
 #   strict    k_small tracks the range tests of the short divide / sqrt; k_compact, k_sdf, k_large, k_mesh test next to every operation
 #   relaxed   the four render TUs once more with hipcc's fast divide / sqrt and FMA contraction: what RPT_RENDER_FAST_MATH selects
@@ -38,6 +47,7 @@ OBJECTS = [
     ("k_sdf", "k_sdf.hip", PEROP, "both"),
     ("k_large", "k_large.hip", PEROP, "both"),
     ("k_mesh", "k_mesh.hip", PEROP, "mesh"),                       # mesh scenes: strict only (include/rpt.h, "triangle meshes"); MESH_LIB
+    ("k_refit", "k_refit.hip", [], "refit"),                       # rpt_update_meshes' refit of a mesh scene's tables; REFIT_LIB
     ("k_small_fast", "k_small.hip", RELAXED, "both"),
     ("k_compact_fast", "k_compact.hip", RELAXED, "both"),
     ("k_sdf_fast", "k_sdf.hip", RELAXED, "both"),
@@ -99,12 +109,14 @@ def _deps():
             [os.path.abspath(__file__)])
 
 
-def needs_build(lib=LIB, mesh_lib=None):
-    """`mesh_lib`: the mesh library `lib` loads (default mesh_lib_of(lib); the test build loads the product's)."""
+def needs_build(lib=LIB, mesh_lib=None, refit_lib=None):
+    """`mesh_lib`, `refit_lib`: the code object libraries `lib` loads (default mesh_lib_of(lib), refit_lib_of(lib); the test build loads
+    the product's)."""
     mesh_lib = mesh_lib or mesh_lib_of(lib)
-    if not os.path.exists(lib) or not os.path.exists(mesh_lib):
+    refit_lib = refit_lib or refit_lib_of(lib)
+    if not os.path.exists(lib) or not os.path.exists(mesh_lib) or not os.path.exists(refit_lib):
         return True
-    t = min(os.path.getmtime(lib), os.path.getmtime(mesh_lib))
+    t = min(os.path.getmtime(lib), os.path.getmtime(mesh_lib), os.path.getmtime(refit_lib))
     return any(os.path.getmtime(d) > t for d in _deps())
 
 
@@ -112,7 +124,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
     """Compile csrc/*.hip -> `lib` (and, when `test_lib` is given, the test build beside it).  hipcc cross-compiles gfx950 without a GPU.
     `extra_flags` / `lib` / `objdir_name`: experiment builds next to the product library (tools/); `only`: recompile just these
     objects (the others are taken from `objdir_name`/ as they are — or, if missing there, from the product's build/)."""
-    if not force and not needs_build(lib) and (test_lib is None or not needs_build(test_lib, mesh_lib_of(lib))):
+    if not force and not needs_build(lib) and (test_lib is None or not needs_build(test_lib, mesh_lib_of(lib), refit_lib_of(lib))):
         return lib
     objdir = os.path.join(HERE, objdir_name)
     os.makedirs(objdir, exist_ok=True)
@@ -141,18 +153,19 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
             failed.append(" ".join(cmd))
     if failed:
         raise RuntimeError("build.py: compilation failed:\n" + "\n".join(failed))
-    mesh_lib = mesh_lib_of(lib)
-    link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w == "mesh"] + [
-        "-Wl,-soname," + os.path.basename(mesh_lib), "-o", mesh_lib]
-    if verbose:
-        print(" ".join(link))
-    subprocess.run(link, check=True, cwd=CSRC)
+    mesh_lib, refit_lib = mesh_lib_of(lib), refit_lib_of(lib)
+    for part, kind in ((mesh_lib, "mesh"), (refit_lib, "refit")):
+        link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w == kind] + [
+            "-Wl,-soname," + os.path.basename(part), "-o", part]
+        if verbose:
+            print(" ".join(link))
+        subprocess.run(link, check=True, cwd=CSRC)
     for out, kinds in ((lib, ("both", "product")), (test_lib, ("both", "test"))):
         if out is None:
             continue
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w in kinds] + [
-            mesh_lib, "-Wl,-rpath,$ORIGIN", "-ldl", "-o", out]
+            mesh_lib, refit_lib, "-Wl,-rpath,$ORIGIN", "-ldl", "-o", out]
         if verbose:
             print(" ".join(link))
         subprocess.run(link, check=True, cwd=CSRC)

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/rpt.h"
+#include "host_refit.h"
 #include "host_upload.h"
 #include "knobs.h"
 #include "launch.h"
@@ -40,6 +41,7 @@ struct DevState {
     hipEvent_t ev_begin = nullptr, ev_end = nullptr, ev_ready = nullptr;
     void* tables = nullptr;           // the scene's device tables (host_upload.h, SceneImage::bytes): a large or mesh scene's, a small one's class map
     SceneMesh scene;                  // a large or mesh scene's kernel argument: device pointers into `tables` (rpthost::bind_scene)
+    void* refit = nullptr;            // a mesh scene's refit tables (host_refit.h, RefitLayout): from the first rpt_update_meshes to the next upload
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -83,6 +85,7 @@ struct rpt_ctx {
     uint32_t tile_rows = 2;
     uint32_t dispatch[4] = {0xFFFFFFFFu, 0, 0, 0};   // rpt_set_dispatch: cost_order (0xFFFFFFFF: the environment's defaults), unit_rounds, unit_min_spp, unit_slots
     rpthost::SceneState scene;        // its class, camera, small scenes' kernel argument (host_upload.h); every device's tables: DevState
+    rpthost::RefitPlan refit;         // a mesh scene's plan for rpt_update_meshes (host_refit.h)
     // resident ColorBuffer (buffer.rs:6-14): pixels as per-rank tiles + frames
     uint32_t res_w = 0, res_h = 0, res_tile_rows = 0, res_rows_padded = 0;
     uint64_t res_frames = 0;
@@ -261,6 +264,7 @@ static void free_dev(DevState& d)
     if (d.fb) (void)hipFree(d.fb);
     if (d.tile) (void)hipFree(d.tile);
     if (d.tables) (void)hipFree(d.tables);
+    if (d.refit) (void)hipFree(d.refit);
     if (d.dn) (void)hipFree(d.dn);
     for (DevState::SchedEntry& e : d.sched_cache) if (e.buf) (void)hipFree(e.buf);
     if (d.sched_done) (void)hipEventDestroy(d.sched_done);
@@ -834,7 +838,7 @@ static int stage_scene(rpt_ctx* ctx, const SceneImage& img, std::vector<void*>& 
 
 // Every device drops its old tables and takes its staged ones; then the context's scene is replaced, and the dispatch order of every
 // launch shape is learned again.
-static void commit_scene(rpt_ctx* ctx, const SceneImage& img, const std::vector<void*>& fresh)
+static void commit_scene(rpt_ctx* ctx, SceneImage& img, const std::vector<void*>& fresh)
 {
     for (size_t i = 0; i < ctx->devs.size(); ++i) {
         DevState& d = ctx->devs[i];
@@ -843,12 +847,14 @@ static void commit_scene(rpt_ctx* ctx, const SceneImage& img, const std::vector<
             (void)hipStreamSynchronize(d.stream);                   // a running launch may still read the old tables
             (void)hipFree(d.tables);                                // (and hipFree waits for the device: launches on other streams)
         }
+        if (d.refit) { (void)hipFree(d.refit); d.refit = nullptr; } // (written by rpt_update_meshes only, which waits for its own work)
         d.tables = fresh[i];
         rpthost::bind_scene(img, static_cast<unsigned char*>(d.tables), d.scene);
         d.sched_launches = 0;
         for (DevState::SchedEntry& e : d.sched_cache) e.launches = 0;
     }
     ctx->scene = img.state;
+    ctx->refit = std::move(img.refit);
 }
 
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
@@ -861,6 +867,88 @@ int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
     std::vector<void*> fresh;
     RPT_CHECK_RC(stage_scene(ctx, img, fresh));
     commit_scene(ctx, img, fresh);
+    return RPT_OK;
+}
+
+// ---- rpt_update_meshes (include/rpt.h, "moving meshes") --------------------------------------------------------------------------
+// A runtime failure part-way through an update may leave tables half written: the context drops its scene, on every device.
+static void drop_scene(rpt_ctx* ctx)
+{
+    for (DevState& d : ctx->devs) {
+        DeviceGuard guard(d.device);
+        (void)hipDeviceSynchronize();
+        if (d.tables) { (void)hipFree(d.tables); d.tables = nullptr; }
+        if (d.refit) { (void)hipFree(d.refit); d.refit = nullptr; }
+        d.scene = SceneMesh();
+    }
+    ctx->scene = rpthost::SceneState();
+    ctx->refit = rpthost::RefitPlan();
+}
+
+// One device's part of an update: wait for its earlier work, make its refit tables if this is the context's first update, copy the
+// named meshes' vertices in, refit every triangle row and slot box, then the nodes level by level, deepest first (kernel boundaries
+// on one stream order the levels), and wait.
+static int update_device(rpt_ctx* ctx, DevState& d, const rpt_mesh_vertices* updates, uint32_t n_updates)
+{
+    const rpthost::RefitPlan& plan = ctx->refit;
+    const rpthost::RefitLayout lay(plan.n_vertices(), plan.n_slots, plan.n_nodes);
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    unsigned char* base = static_cast<unsigned char*>(d.refit);
+    if (!base) {
+        RPT_HIP_CHECK(ctx, hipMalloc(&d.refit, lay.total));
+        base = static_cast<unsigned char*>(d.refit);
+        if (!plan.vertices.empty()) RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_vertices, plan.vertices.data(), sizeof(float) * plan.vertices.size(), hipMemcpyHostToDevice, d.stream));
+        RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_slot_vertex, plan.slot_vertex.data(), sizeof(uint32_t) * plan.slot_vertex.size(), hipMemcpyHostToDevice, d.stream));
+        RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_level_nodes, plan.level_nodes.data(), sizeof(uint32_t) * plan.level_nodes.size(), hipMemcpyHostToDevice, d.stream));
+    }
+    for (uint32_t u = 0; u < n_updates; ++u) {
+        if (updates[u].n_vertices == 0) continue;
+        RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_vertices + 12 * (size_t)plan.mesh_first[updates[u].mesh], updates[u].vertices,
+                                          12 * (size_t)updates[u].n_vertices, hipMemcpyHostToDevice, d.stream));
+    }
+    float4* tris = const_cast<float4*>(d.scene.tris);
+    float4* nodes = const_cast<float4*>(d.scene.nodes);
+    const float* slot_box = reinterpret_cast<const float*>(base + lay.off_slot_box);
+    const uint32_t* level_nodes = reinterpret_cast<const uint32_t*>(base + lay.off_level_nodes);
+    RPT_HIP_CHECK(ctx, rptlaunch::refit_triangles(reinterpret_cast<const float*>(base + lay.off_vertices), reinterpret_cast<const uint32_t*>(base + lay.off_slot_vertex),
+                                                  tris, reinterpret_cast<float*>(base + lay.off_slot_box), plan.n_slots, d.stream));
+    for (uint32_t level = plan.n_levels(); level-- > 0;)
+        RPT_HIP_CHECK(ctx, rptlaunch::refit_nodes(nodes, slot_box, level_nodes + plan.level_first[level], plan.level_first[level + 1u] - plan.level_first[level], d.stream));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    return RPT_OK;
+}
+
+int rpt_update_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n_updates)
+{
+    if (!ctx) { set_err(nullptr, "rpt_update_meshes: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (n_updates == 0) return RPT_OK;
+    std::vector<float> max_abs;
+    std::string why;
+    const int rc = rpthost::check_mesh_update(ctx->refit, ctx->scene.kind == SceneKind::mesh, updates, n_updates, max_abs, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    bool any = false;                                               // (meshes without vertices only: nothing moves)
+    for (uint32_t u = 0; u < n_updates; ++u) any = any || updates[u].n_vertices != 0;
+    if (!any) return RPT_OK;
+    {
+        DeviceGuard guard(ctx->devs[0].device);
+        int rc_dev = RPT_OK;
+        for (DevState& d : ctx->devs) {
+            if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_update_meshes: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
+            else rc_dev = update_device(ctx, d, updates, n_updates);
+            if (rc_dev != RPT_OK) break;
+        }
+        if (rc_dev != RPT_OK) {
+            const std::string first = ctx->err;
+            drop_scene(ctx);
+            set_err(ctx, "%s; the context now holds no scene", first.c_str());
+            return rc_dev;
+        }
+    }
+    // every device holds the moved scene: the host's record follows
+    ctx->refit.release_staging();
+    ctx->refit.mesh_max_abs = max_abs;
+    const uint32_t use_bvh = rpthost::refit_use_bvh(max_abs) ? 1u : 0u;
+    for (DevState& d : ctx->devs) d.scene.use_bvh = use_bvh;
     return RPT_OK;
 }
 
@@ -1437,6 +1525,19 @@ int rpt_debug_mesh_stats(rpt_ctx* ctx, uint32_t* n_nodes, uint32_t* depth, float
     if (!ctx || !n_nodes || !depth || !build_ms) { set_err(ctx, "rpt_debug_mesh_stats: invalid argument"); return RPT_ERR_INVALID_ARG; }
     if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_stats: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
     *n_nodes = ctx->scene.mesh_nodes; *depth = ctx->scene.mesh_depth; *build_ms = ctx->scene.mesh_build_ms;
+    return RPT_OK;
+}
+
+int rpt_debug_mesh_tables(rpt_ctx* ctx, uint32_t which, void* out, uint64_t capacity_bytes, uint64_t* bytes)
+{
+    if (!ctx || !bytes || which > 1u) { set_err(ctx, "rpt_debug_mesh_tables: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_tables: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    const DevState& d = ctx->devs[0];
+    *bytes = which == 0u ? 48ull * d.scene.n_tris : 64ull * ctx->scene.mesh_nodes;
+    if (!out || capacity_bytes < *bytes) { set_err(ctx, "rpt_debug_mesh_tables: %llu bytes do not fit", (unsigned long long)*bytes); return RPT_ERR_INVALID_ARG; }
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    RPT_HIP_CHECK(ctx, hipMemcpy(out, which == 0u ? d.scene.tris : d.scene.nodes, (size_t)*bytes, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 

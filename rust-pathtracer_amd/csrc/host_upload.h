@@ -14,6 +14,7 @@
 
 #include "../../include/rpt.h"
 #include "host_bvh.h"
+#include "host_refit.h"
 #include "host_scene.h"
 #include "launch.h"
 
@@ -55,6 +56,7 @@ struct SceneImage {
     std::vector<unsigned char> bytes; // what every device holds (DevState::tables); empty: nothing (a small scene without a class map)
     SceneMesh tables = {};            // large and mesh scenes: the kernel argument but for its device pointers (bind_scene)
     HostAccel accel;
+    RefitPlan refit;                  // mesh scenes: what rpt_update_meshes needs beyond `bytes` (host_refit.h); the context keeps it
     size_t off_smat = 0, off_lights = 0, off_mats = 0, off_lsph = 0, off_lids = 0, off_accel = 0, off_tris = 0, off_nodes = 0;
 };
 
@@ -280,6 +282,7 @@ inline int prepare_scene(const rpt_scene_desc* s, SceneImage& img, std::string& 
         st.mesh_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build).count();
         st.mesh_nodes = (uint32_t)bvh.nodes.size();
         st.mesh_depth = bvh.depth;
+        build_refit_plan(s, bvh, img.refit);
     }
     const size_t sz_tris = 48 * (size_t)n, sz_nodes = sizeof(BvhNode) * bvh.nodes.size();
 

@@ -55,6 +55,13 @@ hipError_t render_large(const rptdev::SceneLarge& scl, bool media, const rptdev:
 hipError_t render_mesh(const rptdev::SceneMesh& sc, const rptdev::RenderParams& rp, uint32_t nblocks, hipStream_t st);
 hipError_t mesh_query(const rptdev::SceneMesh& sc, const float* rays, uint32_t* out, uint64_t n, uint32_t flags, hipStream_t st);
 
+// The refit of a mesh scene's tables from new vertex positions (k_refit.hip, a code object library of its own; host_refit.h has the
+// tables and the host reference; include/rpt.h "moving meshes").  refit_triangles: the float part of every triangle row and every
+// slot's box; refit_nodes: the boxes of the `count` interior nodes `level_nodes` lists, one level of the hierarchy — launched once
+// per level, deepest first, on one stream.
+hipError_t refit_triangles(const float* vertices, const uint32_t* slot_vertex, float4* tris, float* slot_box, uint32_t n_slots, hipStream_t st);
+hipError_t refit_nodes(float4* nodes, const float* slot_box, const uint32_t* level_nodes, uint32_t count, hipStream_t st);
+
 // Cost-ordered dispatch (kernel_common.h, block_tile): `cost` holds 4 dwords per tile, `order` one; init = bottom rows first and no
 // costs; order = the tiles sorted by the costs the last launch left, most expensive first.
 hipError_t sched_init(uint32_t* cost, uint32_t* order, uint32_t n_tiles, hipStream_t st);

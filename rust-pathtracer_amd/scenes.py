@@ -196,3 +196,30 @@ def mesh_scene(subdivisions=7, n_major=256, n_minor=128):
     v, t = torus(0.7, 0.3, n_major, n_minor, (1.1, 0.0, 0.0))
     s.meshes.append((v, t, 1))
     return s
+
+
+def mesh_scene_moved(scene, phase, seed=0x5EED0006):
+    """-> new vertex arrays for `scene` (a mesh_scene(): the icosphere, then the torus), one per mesh, for Tracer.update_meshes: a
+    radial ripple travelling over the icosphere — amplitude 0.25 * min(phase, 1) of its radius, six waves from pole to pole, a seeded
+    phase offset — and the torus turned by `phase` radians about its own axis (z, through its centre).  Meshes beyond the second
+    keep their positions.  phase = 0 returns the scene's arrays as they are, bit for bit; 0.05 is a small move, 0.5 a medium one,
+    2.0 a large one (tools/mesh_bench.py --update)."""
+    import numpy as np
+    out = [np.array(v, dtype=np.float32, copy=True) for v, _, _ in scene.meshes]
+    if phase == 0:
+        return out
+    offset = _U(seed)(0.0, 2.0 * np.pi)
+    for k, v in enumerate(out[:2]):
+        p = v.astype(np.float64)
+        c = 0.5 * (p.min(0) + p.max(0))
+        q = p - c
+        if k == 0:
+            r = np.sqrt((q * q).sum(1, keepdims=True))
+            r = np.where(r > 0.0, r, 1.0)
+            wave = np.sin(6.0 * np.pi * q[:, 1:2] / r + offset + 4.0 * phase)
+            q = q * (1.0 + 0.25 * min(phase, 1.0) * wave)
+        else:
+            cs, sn = np.cos(phase), np.sin(phase)
+            q = np.stack([cs * q[:, 0] - sn * q[:, 1], sn * q[:, 0] + cs * q[:, 1], q[:, 2]], 1)
+        out[k] = (q + c).astype(np.float32)
+    return out

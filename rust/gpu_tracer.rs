@@ -44,6 +44,12 @@ pub struct RptMesh {
     pub n_triangles: u32, pub indices: *const u32,
     pub material: u32,
 }
+// rpt_update_meshes (include/rpt.h, "moving meshes"): one mesh's new vertex positions
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct RptMeshVertices {
+    pub mesh: u32, pub n_vertices: u32,
+    pub vertices: *const f32,
+}
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct RptSceneDesc {
     pub abi_version: u32, pub flags: u32,
@@ -124,6 +130,9 @@ extern "C" {
     fn rpt_destroy(ctx: *mut RptCtx);
     fn rpt_last_error(ctx: *const RptCtx) -> *const c_char;
     fn rpt_upload_scene(ctx: *mut RptCtx, scene: *const RptSceneDesc) -> c_int;
+    // (SceneDescBuilder fills no meshes yet, so nothing here can move one: declared for the `mesh` follow-up)
+    #[allow(dead_code)]
+    fn rpt_update_meshes(ctx: *mut RptCtx, updates: *const RptMeshVertices, n_updates: u32) -> c_int;
     fn rpt_scene_analytical(out: *mut RptSceneDesc) -> c_int;
     fn rpt_render(ctx: *mut RptCtx, pixels: *mut f32, width: u32, height: u32,
                   frames_done: u64, spp: u32, seed: u64, flags: u32) -> c_int;

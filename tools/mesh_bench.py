@@ -2,7 +2,12 @@
 Gsamples/s of the resident render, the triangle and BVH node counts, the BVH's depth and build time (host, inside the upload) and the
 whole upload's time.  Loads the test build (its rpt_debug_mesh_stats, include/rpt_test.h).
 
-    python tools/mesh_bench.py [--spp 16] [--reps 5]
+--update: one JSON line more, for rpt_update_meshes (include/rpt.h, "moving meshes").  For a small, a medium and a large move of the
+scene (scenes.mesh_scene_moved, phases 0.05 / 0.5 / 2.0), alternating, `--reps` times each in one process: the wall time of
+update_meshes (the host's clock around the blocking call) from the uploaded scene to the moved one; the wall time of upload_scene()
+of the same moved scene (the existing path: the yardstick); and the resident render rate after each, from resident_kernel_ms.
+
+    python tools/mesh_bench.py [--spp 16] [--reps 5] [--update]
 """
 import argparse
 import ctypes as C
@@ -21,6 +26,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--spp", type=int, default=16)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--update", action="store_true")
     a = ap.parse_args()
     os.environ.setdefault("RPT_LIB", os.path.join(ROOT, "rust-pathtracer_amd", "librpt_hip_test.so"))     # (the product has no hooks)
     import __graft_entry__
@@ -42,10 +48,63 @@ def main():
         t.render_resident(a.width, a.height, a.spp)
         ms = t.resident_kernel_ms()
         rates.append(a.width * a.height * a.spp / (ms * 1e-3) / 1e9)
+    update = measure_updates(pkg, t, s, a) if a.update else None
     t.close()
     print(json.dumps({"workload": "mesh_scene %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "triangles": n_tris,
                       "gsamples_per_s_median": sorted(rates)[len(rates) // 2], "gsamples_per_s": rates,
                       "bvh_nodes": nodes.value, "bvh_depth": depth.value, "bvh_build_ms": build_ms.value, "upload_s": upload_s}))
+    if update:
+        print(json.dumps(update))
+
+
+def measure_updates(pkg, t, s, a):
+    """-> the --update line.  `t` holds `s` uploaded and warmed up; it is never uploaded to again, so every update refits the
+    ORIGINAL scene's hierarchy.  The yardstick runs on a second context of the same process."""
+    import numpy as np
+    from rust_pathtracer_amd import scenes
+    original = [np.array(v, np.float32, copy=True) for v, _, _ in s.meshes]
+
+    def rate(tr):
+        tr.resident_reset()
+        tr.render_resident(a.width, a.height, a.spp)                # the dispatch order's first costs after an upload
+        tr.render_resident(a.width, a.height, a.spp)
+        return a.width * a.height * a.spp / (tr.resident_kernel_ms() * 1e-3) / 1e9
+
+    def stats(xs):
+        xs = sorted(xs)
+        return {"median": xs[len(xs) // 2], "min": xs[0], "max": xs[-1]}
+
+    phases = (("small", 0.05), ("medium", 0.5), ("large", 2.0))
+    moved = {name: scenes.mesh_scene_moved(s, phase) for name, phase in phases}
+    res = {name: {"update_ms": [], "upload_ms": [], "rate_update": [], "rate_upload": []} for name, _ in phases}
+    fresh_scene = scenes.mesh_scene()
+    fresh = pkg.Tracer(fresh_scene, device=0, seed=1)
+    t0 = time.perf_counter()
+    t.update_meshes(dict(enumerate(original)))                      # the context's first update: allocates the device's refit tables
+    first_ms = (time.perf_counter() - t0) * 1e3
+    reps = max(5, a.reps)
+    for _ in range(reps):
+        for name, _ in phases:
+            r = res[name]
+            t0 = time.perf_counter()
+            t.update_meshes(dict(enumerate(moved[name])))
+            r["update_ms"].append((time.perf_counter() - t0) * 1e3)
+            r["rate_update"].append(rate(t))
+            fresh_scene.meshes = [(v, idx, m) for v, (_, idx, m) in zip(moved[name], fresh_scene.meshes)]
+            t0 = time.perf_counter()
+            fresh.upload_scene()                                    # the same moved scene through the existing path
+            r["upload_ms"].append((time.perf_counter() - t0) * 1e3)
+            r["rate_upload"].append(rate(fresh))
+    fresh.close()
+    out = {"workload": "mesh_scene update %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "reps": reps, "first_update_ms": first_ms}
+    for name, phase in phases:
+        r = res[name]
+        up, full = stats(r["update_ms"]), stats(r["upload_ms"])
+        ru, rf = stats(r["rate_update"]), stats(r["rate_upload"])
+        out[name] = {"phase": phase, "update_ms": up, "upload_ms": full, "upload_over_update": full["median"] / up["median"],
+                     "gsamples_per_s_after_update": ru, "gsamples_per_s_after_upload": rf,
+                     "fresh_upload_renders_faster_by_percent": (rf["median"] / ru["median"] - 1.0) * 100.0}
+    return out
 
 
 if __name__ == "__main__":
