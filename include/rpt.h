@@ -469,6 +469,42 @@ typedef struct rpt_mesh_vertices {
 
 int rpt_update_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n_updates);
 
+/* ---- rebuilding a moved mesh's hierarchy — PROJECT-DEFINED ---------------------------------------------------------------------
+ * rpt_update_meshes, and then a NEW hierarchy: the meshes named in `updates` get the positions given, and every device of the
+ * context builds a hierarchy over all triangles of the scene on the device — new shape, new leaf order, new boxes (DESIGN.md 4c:
+ * the triangles sorted by a Morton code of their centroids, split top-down where the code's highest differing bit changes, under
+ * the upload's depth rule).  Afterwards the context renders exactly what it would render after rpt_upload_scene of the same
+ * descriptor with those vertex arrays: the same frames bit for bit, the same errors from rpt_render*.
+ *
+ * Arguments and checks are rpt_update_meshes', in its order, all on the host before any device is touched, so that a rejected
+ * call leaves the context exactly as it was; rpt_last_error names this call.  One difference: n_updates == 0 is not a no-op — it
+ * rebuilds over the positions the context holds (`updates` may then be NULL), and only RPT_ERR_NO_SCENE and RPT_ERR_UNSUPPORTED
+ * (2^32 vertices) can reject it.  RPT_ERR_HIP: a runtime call failed part-way, an allocation among them, or the build did not end
+ * within the walk's 24 levels (the depth rule excludes it; such a table is never bound): the context is left with NO scene.
+ * The 2^60 rule is unchanged: whether the walk or the ordered loop serves the rays follows the positions, and the tables a
+ * rebuild leaves are valid either way.
+ *
+ * A later rpt_update_meshes refits the rebuilt shape; a later rebuild starts from whatever is there; rpt_upload_scene drops
+ * everything a rebuild allocated.  Blocking, streams, the resident ColorBuffer, the learned dispatch order, contexts of several
+ * devices and one process per GPU: all as for rpt_update_meshes.  The same positions give the same tables, byte for byte, on every
+ * device and at every call.
+ *
+ * Memory.  The context's first rebuild allocates on every device, until the next rpt_upload_scene: the refit's tables with room
+ * for any hierarchy (12 B per vertex + 40 B per triangle), a node table of its own (64 B per triangle; the upload's stays where
+ * it is, unused), and the build's work area (76 B per triangle and the sort's temporary storage) — for scenes.mesh_scene
+ * about 80 MB beside the scene's own 34 MB.
+ *
+ * When to use which.  Measured on an MI355X, scenes.mesh_scene (393 216 triangles) at 1920x1080 x 16 spp (tools/mesh_bench.py
+ * --rebuild, profiles/NOTES.md; medians of 5, alternating): a rebuild takes 1.10-1.11 ms (the context's first one 8.6 ms: it
+ * allocates) where an update takes 0.62 ms and the upload of the same moved scene 188-192 ms.  Render rates afterwards, in
+ * Gsamples/s, refit / rebuilt / fresh upload: after a ripple of 1.25 % of the icosphere's radius with the torus turned by 0.05 rad
+ * 0.803 / 0.705 / 0.814; after 12.5 % and 0.5 rad 0.460 / 0.537 / 0.623; after 25 % and 2 rad 0.278 / 0.418 / 0.483.  A rebuilt
+ * (Morton-order) hierarchy walks at 86-87 % of the upload's binned-SAH one whatever the move, a refitted one at 99 % down to 58 %:
+ * update while a mesh only moves or ripples; rebuild once its shape has changed — somewhere before the medium move here —, every
+ * frame if need be; and upload again only where the scene then stays put for long, since the host build's extra 190 ms buy 15 %
+ * of the render rate (here: from about twenty such frames on). */
+int rpt_rebuild_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n_updates);
+
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)
  *   frames_done ColorBuffer.frames before the call; the caller adds `spp` afterwards

@@ -205,6 +205,11 @@ public:
     void update_meshes(const std::vector<rpt_mesh_vertices>& updates) {
         check(rpt_update_meshes(ctx_, updates.data(), (uint32_t)updates.size()), ctx_);
     }
+    /// ... and a new hierarchy over all triangles, built on the device (rpt.h, "rebuilding a moved mesh's hierarchy"): for a mesh
+    /// whose shape has changed.  No updates: a rebuild over the positions the context holds.
+    void rebuild_meshes(const std::vector<rpt_mesh_vertices>& updates = {}) {
+        check(rpt_rebuild_meshes(ctx_, updates.data(), (uint32_t)updates.size()), ctx_);
+    }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

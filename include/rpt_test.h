@@ -60,11 +60,12 @@ enum { RPT_MESH_QUERY_USE_MAX = 1u << 0, RPT_MESH_QUERY_BRUTE = 1u << 1 };
 int rpt_debug_mesh_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
 
 /* The uploaded mesh scene's hierarchy (csrc/host_bvh.h): its interior nodes, the depth of its deepest leaf, and the host time its build
- * took in rpt_upload_scene.  RPT_ERR_NO_SCENE unless the uploaded scene has meshes.  (tools/mesh_bench.py) */
+ * took in rpt_upload_scene — after rpt_rebuild_meshes the rebuilt hierarchy's, and the wall time of that call's device part.
+ * RPT_ERR_NO_SCENE unless the uploaded scene has meshes.  (tools/mesh_bench.py) */
 int rpt_debug_mesh_stats(rpt_ctx* ctx, uint32_t* n_nodes, uint32_t* depth, float* build_ms);
 
 /* Copy the uploaded mesh scene's triangle rows (which = 0: 48 B per triangle, in leaf order) or hierarchy nodes (which = 1: 64 B each,
- * csrc/host_bvh.h BvhNode) from the context's first device to the host, as rpt_update_meshes (include/rpt.h) left them.  *bytes = the
+ * csrc/host_bvh.h BvhNode) from the context's first device to the host, as rpt_update_meshes / rpt_rebuild_meshes (include/rpt.h) left them.  *bytes = the
  * table's size; RPT_ERR_INVALID_ARG when `out` is NULL or holds fewer than that (*bytes is still set).  RPT_ERR_NO_SCENE unless the
  * uploaded scene has meshes.  Waits for the device. */
 int rpt_debug_mesh_tables(rpt_ctx* ctx, uint32_t which, void* out, uint64_t capacity_bytes, uint64_t* bytes);

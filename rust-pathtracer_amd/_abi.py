@@ -168,6 +168,7 @@ SYMBOLS = {
     "rpt_abi_version": (C.c_uint32, []),
     "rpt_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(rpt_scene_desc)]),
     "rpt_update_meshes": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_vertices), C.c_uint32]),
+    "rpt_rebuild_meshes": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_vertices), C.c_uint32]),
     "rpt_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

@@ -386,12 +386,21 @@ class Tracer:
         a mesh's index in scene().meshes to an array of shape (n_vertices, 3).  The frames are those of upload_scene() of the moved
         scene, bit for bit; the hierarchy is refitted on the device, not rebuilt.  On success the scene's vertex arrays are
         replaced too, so a later upload_scene() uploads the moved scene."""
+        self._move_meshes(lib().rpt_update_meshes, updates)
+
+    def rebuild_meshes(self, updates=None):
+        """update_meshes, then a new hierarchy over all triangles, built on the device (include/rpt.h, "rebuilding a moved mesh's
+        hierarchy"): for meshes whose shape has changed.  The frames are again those of upload_scene() of the moved scene, bit
+        for bit.  Without `updates`: a rebuild over the positions the context holds."""
+        self._move_meshes(lib().rpt_rebuild_meshes, updates or {})
+
+    def _move_meshes(self, call, updates):
         items = sorted(updates.items())
         arrays = [np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3) for _, v in items]
         ups = (_abi.rpt_mesh_vertices * max(1, len(items)))()
         for u, (m, _), v in zip(ups, items, arrays):
             u.mesh, u.n_vertices, u.vertices = int(m), v.shape[0], v.ctypes.data_as(C.POINTER(C.c_float))
-        check(lib().rpt_update_meshes(self._h, ups, len(items)), self._h)
+        check(call(self._h, ups, len(items)), self._h)
         for (m, _), v in zip(items, arrays):
             _, idx, mat = self._scene.meshes[m]
             self._scene.meshes[m] = (v, idx, mat)

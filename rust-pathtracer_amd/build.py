@@ -35,6 +35,15 @@ def refit_lib_of(lib):
 
 REFIT_LIB = refit_lib_of(LIB)
 
+
+# The hierarchy build of rpt_rebuild_meshes (k_build.hip: its bvhbuild_* kernels and the rocPRIM kernels of its sort and prefix sums)
+# is a fourth, again named, linked and found the same way: tests/test_mesh_rebuild_host.py keeps its census.
+def build_lib_of(lib):
+    return os.path.splitext(os.path.abspath(lib))[0] + "_build.so"
+
+
+BUILD_LIB = build_lib_of(LIB)
+
 # One translation unit per kernel class (csrc/kernel_common.h says what each build of them is):
 #   strict    k_small tracks the range tests of the short divide / sqrt; k_compact, k_sdf, k_large, k_mesh test next to every operation
 #   relaxed   the four render TUs once more with hipcc's fast divide / sqrt and FMA contraction: what RPT_RENDER_FAST_MATH selects
@@ -48,6 +57,7 @@ OBJECTS = [
     ("k_large", "k_large.hip", PEROP, "both"),
     ("k_mesh", "k_mesh.hip", PEROP, "mesh"),                       # mesh scenes: strict only (include/rpt.h, "triangle meshes"); MESH_LIB
     ("k_refit", "k_refit.hip", [], "refit"),                       # rpt_update_meshes' refit of a mesh scene's tables; REFIT_LIB
+    ("k_build", "k_build.hip", [], "bvhbuild"),                    # rpt_rebuild_meshes' new slot order and shape; BUILD_LIB
     ("k_small_fast", "k_small.hip", RELAXED, "both"),
     ("k_compact_fast", "k_compact.hip", RELAXED, "both"),
     ("k_sdf_fast", "k_sdf.hip", RELAXED, "both"),
@@ -109,14 +119,13 @@ def _deps():
             [os.path.abspath(__file__)])
 
 
-def needs_build(lib=LIB, mesh_lib=None, refit_lib=None):
-    """`mesh_lib`, `refit_lib`: the code object libraries `lib` loads (default mesh_lib_of(lib), refit_lib_of(lib); the test build loads
-    the product's)."""
-    mesh_lib = mesh_lib or mesh_lib_of(lib)
-    refit_lib = refit_lib or refit_lib_of(lib)
-    if not os.path.exists(lib) or not os.path.exists(mesh_lib) or not os.path.exists(refit_lib):
+def needs_build(lib=LIB, mesh_lib=None, refit_lib=None, build_lib=None):
+    """`mesh_lib`, `refit_lib`, `build_lib`: the code object libraries `lib` loads (default mesh_lib_of(lib), refit_lib_of(lib),
+    build_lib_of(lib); the test build loads the product's)."""
+    parts = [lib, mesh_lib or mesh_lib_of(lib), refit_lib or refit_lib_of(lib), build_lib or build_lib_of(lib)]
+    if not all(os.path.exists(p) for p in parts):
         return True
-    t = min(os.path.getmtime(lib), os.path.getmtime(mesh_lib), os.path.getmtime(refit_lib))
+    t = min(os.path.getmtime(p) for p in parts)
     return any(os.path.getmtime(d) > t for d in _deps())
 
 
@@ -124,7 +133,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
     """Compile csrc/*.hip -> `lib` (and, when `test_lib` is given, the test build beside it).  hipcc cross-compiles gfx950 without a GPU.
     `extra_flags` / `lib` / `objdir_name`: experiment builds next to the product library (tools/); `only`: recompile just these
     objects (the others are taken from `objdir_name`/ as they are — or, if missing there, from the product's build/)."""
-    if not force and not needs_build(lib) and (test_lib is None or not needs_build(test_lib, mesh_lib_of(lib), refit_lib_of(lib))):
+    if not force and not needs_build(lib) and (test_lib is None or not needs_build(test_lib, mesh_lib_of(lib), refit_lib_of(lib), build_lib_of(lib))):
         return lib
     objdir = os.path.join(HERE, objdir_name)
     os.makedirs(objdir, exist_ok=True)
@@ -153,8 +162,8 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
             failed.append(" ".join(cmd))
     if failed:
         raise RuntimeError("build.py: compilation failed:\n" + "\n".join(failed))
-    mesh_lib, refit_lib = mesh_lib_of(lib), refit_lib_of(lib)
-    for part, kind in ((mesh_lib, "mesh"), (refit_lib, "refit")):
+    mesh_lib, refit_lib, build_lib = mesh_lib_of(lib), refit_lib_of(lib), build_lib_of(lib)
+    for part, kind in ((mesh_lib, "mesh"), (refit_lib, "refit"), (build_lib, "bvhbuild")):
         link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w == kind] + [
             "-Wl,-soname," + os.path.basename(part), "-o", part]
         if verbose:
@@ -165,7 +174,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
             continue
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w in kinds] + [
-            mesh_lib, refit_lib, "-Wl,-rpath,$ORIGIN", "-ldl", "-o", out]
+            mesh_lib, refit_lib, build_lib, "-Wl,-rpath,$ORIGIN", "-ldl", "-o", out]
         if verbose:
             print(" ".join(link))
         subprocess.run(link, check=True, cwd=CSRC)

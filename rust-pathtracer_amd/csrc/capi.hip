@@ -19,10 +19,12 @@
 #include <vector>
 
 #include "../../include/rpt.h"
+#include "host_build.h"
 #include "host_refit.h"
 #include "host_upload.h"
 #include "knobs.h"
 #include "launch.h"
+#include "launch_build.h"
 #ifdef RPT_TEST_HOOKS
 #include "../../include/rpt_test.h"
 #endif
@@ -42,6 +44,10 @@ struct DevState {
     void* tables = nullptr;           // the scene's device tables (host_upload.h, SceneImage::bytes): a large or mesh scene's, a small one's class map
     SceneMesh scene;                  // a large or mesh scene's kernel argument: device pointers into `tables` (rpthost::bind_scene)
     void* refit = nullptr;            // a mesh scene's refit tables (host_refit.h, RefitLayout): from the first rpt_update_meshes to the next upload
+    bool refit_full = false;          // ... allocated by rpt_rebuild_meshes: their level order has room for every hierarchy over the scene's triangles
+    void* build = nullptr;            // rpt_rebuild_meshes' own tables (host_build.h, BuildLayout) and the node table it binds: from the
+    void* build_nodes = nullptr;      // context's first rebuild to the next upload
+    size_t build_temp_bytes = 0;
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -258,13 +264,24 @@ static uint32_t unit_chunks(const DispatchPolicy& pol, uint64_t nblocks, uint32_
 constexpr uint32_t kOrderAlwaysFromSpp = 16;
 // Small scenes: launches of at most knobs().compact_max_spp samples per pixel take the compacting kernel (k_compact.hip).
 // (1 since round 3: 1080p, 1 spp 7.12 vs 6.83 Gsamples/s for the megakernel, 2 spp 7.01 vs 7.39: profiles/r3/spp_curve.txt)
+
+// what rpt_update_meshes and rpt_rebuild_meshes allocated on a device (its current device; nothing of the scene may still run)
+static void free_mesh_work(DevState& d)
+{
+    if (d.refit) { (void)hipFree(d.refit); d.refit = nullptr; }
+    if (d.build) { (void)hipFree(d.build); d.build = nullptr; }
+    if (d.build_nodes) { (void)hipFree(d.build_nodes); d.build_nodes = nullptr; }
+    d.refit_full = false;
+    d.build_temp_bytes = 0;
+}
+
 static void free_dev(DevState& d)
 {
     DeviceGuard guard(d.device);
     if (d.fb) (void)hipFree(d.fb);
     if (d.tile) (void)hipFree(d.tile);
     if (d.tables) (void)hipFree(d.tables);
-    if (d.refit) (void)hipFree(d.refit);
+    free_mesh_work(d);
     if (d.dn) (void)hipFree(d.dn);
     for (DevState::SchedEntry& e : d.sched_cache) if (e.buf) (void)hipFree(e.buf);
     if (d.sched_done) (void)hipEventDestroy(d.sched_done);
@@ -847,7 +864,8 @@ static void commit_scene(rpt_ctx* ctx, SceneImage& img, const std::vector<void*>
             (void)hipStreamSynchronize(d.stream);                   // a running launch may still read the old tables
             (void)hipFree(d.tables);                                // (and hipFree waits for the device: launches on other streams)
         }
-        if (d.refit) { (void)hipFree(d.refit); d.refit = nullptr; } // (written by rpt_update_meshes only, which waits for its own work)
+        free_mesh_work(d);                                          // (written by rpt_update_meshes / rpt_rebuild_meshes only, which wait for their own work;
+                                                                    //  a rebuilt node table is read by launches: the wait above covers it)
         d.tables = fresh[i];
         rpthost::bind_scene(img, static_cast<unsigned char*>(d.tables), d.scene);
         d.sched_launches = 0;
@@ -878,7 +896,7 @@ static void drop_scene(rpt_ctx* ctx)
         DeviceGuard guard(d.device);
         (void)hipDeviceSynchronize();
         if (d.tables) { (void)hipFree(d.tables); d.tables = nullptr; }
-        if (d.refit) { (void)hipFree(d.refit); d.refit = nullptr; }
+        free_mesh_work(d);
         d.scene = SceneMesh();
     }
     ctx->scene = rpthost::SceneState();
@@ -948,6 +966,156 @@ int rpt_update_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n
     ctx->refit.release_staging();
     ctx->refit.mesh_max_abs = max_abs;
     const uint32_t use_bvh = rpthost::refit_use_bvh(max_abs) ? 1u : 0u;
+    for (DevState& d : ctx->devs) d.scene.use_bvh = use_bvh;
+    return RPT_OK;
+}
+
+// ---- rpt_rebuild_meshes (include/rpt.h, "rebuilding a moved mesh's hierarchy") -----------------------------------------------------
+// One device's part of a rebuild: wait for its earlier work; make the refit tables as a first update does, but with a level order
+// that has room for any hierarchy over the scene's triangles (tables an update made are copied into larger ones); make the build's
+// tables and the new node table if this is the context's first rebuild; copy the named meshes' vertices in; then, on the device's
+// stream, the slots' boxes in the present order, the new order (k_build.hip, build_order), the rows and boxes in the new order, the
+// new shape (build_shape).  The host reads the levels' counts back once, launches the refit of the nodes level by level, deepest
+// first, and waits.  `levels`: host_build.h's kBuildLevelWords words, as the device left them.
+static int rebuild_device(rpt_ctx* ctx, DevState& d, const rpt_mesh_vertices* updates, uint32_t n_updates, uint32_t* levels)
+{
+    using namespace rpthost;
+    const RefitPlan& plan = ctx->refit;
+    const uint32_t n = plan.n_slots, max_nodes = build_max_nodes(n);
+    const RefitLayout lay(plan.n_vertices(), n, max_nodes);
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    if (!d.refit) {
+        RPT_HIP_CHECK(ctx, hipMalloc(&d.refit, lay.total));
+        d.refit_full = true;
+        unsigned char* base = static_cast<unsigned char*>(d.refit);
+        if (!plan.vertices.empty()) RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_vertices, plan.vertices.data(), sizeof(float) * plan.vertices.size(), hipMemcpyHostToDevice, d.stream));
+        RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_slot_vertex, plan.slot_vertex.data(), sizeof(uint32_t) * plan.slot_vertex.size(), hipMemcpyHostToDevice, d.stream));
+    } else if (!d.refit_full) {
+        void* larger = nullptr;
+        RPT_HIP_CHECK(ctx, hipMalloc(&larger, lay.total));
+        hipError_t e = hipMemcpyAsync(larger, d.refit, lay.off_slot_box, hipMemcpyDeviceToDevice, d.stream);      // the vertices and the slots' vertex indices
+        if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+        if (e != hipSuccess) (void)hipFree(larger);
+        RPT_HIP_CHECK(ctx, e);
+        (void)hipFree(d.refit);
+        d.refit = larger;
+        d.refit_full = true;
+    }
+    if (!d.build) {
+        RPT_HIP_CHECK(ctx, rptlaunch::build_temp_bytes(n, &d.build_temp_bytes));
+        const BuildLayout bl(n, max_nodes, build_level_bound(n, kBvhMaxDepth - 1u), d.build_temp_bytes);
+        RPT_HIP_CHECK(ctx, hipMalloc(&d.build, bl.total));
+    }
+    if (!d.build_nodes) RPT_HIP_CHECK(ctx, hipMalloc(&d.build_nodes, sizeof(BvhNode) * (size_t)max_nodes));
+    unsigned char* base = static_cast<unsigned char*>(d.refit);
+    unsigned char* work = static_cast<unsigned char*>(d.build);
+    for (uint32_t u = 0; u < n_updates; ++u) {
+        if (updates[u].n_vertices == 0) continue;
+        RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_vertices + 12 * (size_t)plan.mesh_first[updates[u].mesh], updates[u].vertices,
+                                          12 * (size_t)updates[u].n_vertices, hipMemcpyHostToDevice, d.stream));
+    }
+    const BuildLayout bl(n, max_nodes, build_level_bound(n, kBvhMaxDepth - 1u), d.build_temp_bytes);
+    rptlaunch::BuildTables t;
+    t.n_slots = n; t.max_nodes = max_nodes;
+    t.tris = const_cast<float4*>(d.scene.tris);
+    t.nodes = static_cast<float4*>(d.build_nodes);
+    t.slot_box = reinterpret_cast<const float*>(base + lay.off_slot_box);
+    t.slot_vertex = reinterpret_cast<uint32_t*>(base + lay.off_slot_vertex);
+    t.level_nodes = reinterpret_cast<uint32_t*>(base + lay.off_level_nodes);
+    t.keys_in = reinterpret_cast<uint64_t*>(work + bl.off_keys_in); t.keys_out = reinterpret_cast<uint64_t*>(work + bl.off_keys_out);
+    t.vals_in = reinterpret_cast<uint32_t*>(work + bl.off_vals_in); t.vals_out = reinterpret_cast<uint32_t*>(work + bl.off_vals_out);
+    t.gather = reinterpret_cast<uint32_t*>(work + bl.off_gather);
+    t.range = reinterpret_cast<uint2*>(work + bl.off_range);
+    t.mid = reinterpret_cast<uint32_t*>(work + bl.off_mid);
+    t.flags = reinterpret_cast<uint32_t*>(work + bl.off_flags); t.offsets = reinterpret_cast<uint32_t*>(work + bl.off_offsets);
+    t.levels = reinterpret_cast<uint32_t*>(work + bl.off_levels);
+    t.bounds = reinterpret_cast<uint32_t*>(work + bl.off_bounds);
+    t.temp = work + bl.off_temp; t.temp_bytes = d.build_temp_bytes;
+    const float* vertices = reinterpret_cast<const float*>(base + lay.off_vertices);
+    float* slot_box = reinterpret_cast<float*>(base + lay.off_slot_box);
+    RPT_HIP_CHECK(ctx, rptlaunch::refit_triangles(vertices, t.slot_vertex, t.tris, slot_box, n, d.stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::build_order(t, d.stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::refit_triangles(vertices, t.slot_vertex, t.tris, slot_box, n, d.stream));
+    const uint32_t leaf = knobs().build_leaf < 1u ? 1u : (knobs().build_leaf > kBvhLeafMax ? kBvhLeafMax : knobs().build_leaf);
+    RPT_HIP_CHECK(ctx, rptlaunch::build_shape(t, leaf, d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(levels, t.levels, sizeof(uint32_t) * kBuildLevelWords, hipMemcpyDeviceToHost, d.stream));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    // the table is bound only if it is one the walk can use: at most kBvhMaxDepth levels, each where the last one ended
+    uint32_t n_levels = 0, n_nodes = 0;
+    bool sound = levels[kBuildStatus] == 0u && levels[kBuildLevelCount] == 1u && levels[kBuildLevelCount + kBvhMaxDepth] == 0u;
+    for (uint32_t k = 0; sound && k < kBvhMaxDepth && levels[kBuildLevelCount + k]; ++k) {
+        sound = levels[k] == n_nodes && levels[kBuildLevelCount + k] <= max_nodes - n_nodes;
+        n_nodes += levels[kBuildLevelCount + k];
+        n_levels = k + 1u;
+    }
+    if (!sound) {
+        set_err(ctx, "rpt_rebuild_meshes: the build on device %d did not finish within %u levels (status %u)", d.device, kBvhMaxDepth, levels[kBuildStatus]);
+        return RPT_ERR_HIP;
+    }
+    for (uint32_t level = n_levels; level-- > 0;)
+        RPT_HIP_CHECK(ctx, rptlaunch::refit_nodes(t.nodes, t.slot_box, t.level_nodes + levels[level], levels[kBuildLevelCount + level], d.stream));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    d.scene.nodes = t.nodes;
+    return RPT_OK;
+}
+
+int rpt_rebuild_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n_updates)
+{
+    using namespace rpthost;
+    if (!ctx) { set_err(nullptr, "rpt_rebuild_meshes: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    std::vector<float> max_abs;
+    if (n_updates == 0) {                                           // a rebuild over the positions the context holds
+        if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_rebuild_meshes: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+        if (!ctx->refit.ok) { set_err(ctx, "rpt_rebuild_meshes: the scene's meshes hold 2^32 vertices or more"); return RPT_ERR_UNSUPPORTED; }
+        max_abs = ctx->refit.mesh_max_abs;
+    } else {
+        std::string why;
+        const int rc = check_mesh_update(ctx->refit, ctx->scene.kind == SceneKind::mesh, updates, n_updates, max_abs, why);
+        if (rc != RPT_OK) {
+            const std::string theirs = "rpt_update_meshes: ";       // (host_refit.h, update_error: the checks are an update's, the call is this one)
+            if (why.compare(0, theirs.size(), theirs) == 0) why = "rpt_rebuild_meshes: " + why.substr(theirs.size());
+            set_err(ctx, "%s", why.c_str());
+            return rc;
+        }
+    }
+    uint32_t levels[kBuildLevelWords] = {}, first_levels[kBuildLevelWords] = {};
+    const auto t_build = std::chrono::steady_clock::now();
+    {
+        DeviceGuard guard(ctx->devs[0].device);
+        int rc_dev = RPT_OK;
+        for (size_t i = 0; i < ctx->devs.size(); ++i) {
+            DevState& d = ctx->devs[i];
+            if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_rebuild_meshes: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
+            else rc_dev = rebuild_device(ctx, d, updates, n_updates, levels);
+            if (rc_dev == RPT_OK && i == 0) memcpy(first_levels, levels, sizeof(levels));
+            if (rc_dev == RPT_OK && memcmp(first_levels, levels, sizeof(levels)) != 0) {
+                set_err(ctx, "rpt_rebuild_meshes: device %d built another hierarchy than device %d", d.device, ctx->devs[0].device);
+                rc_dev = RPT_ERR_HIP;
+            }
+            if (rc_dev != RPT_OK) break;
+        }
+        if (rc_dev != RPT_OK) {
+            const std::string first = ctx->err;
+            drop_scene(ctx);
+            set_err(ctx, "%s; the context now holds no scene", first.c_str());
+            return rc_dev;
+        }
+    }
+    // every device holds the rebuilt scene: the host's record follows
+    RefitPlan& plan = ctx->refit;
+    plan.release_staging();
+    plan.mesh_max_abs = max_abs;
+    plan.level_first.clear();
+    plan.n_nodes = 0;
+    for (uint32_t k = 0; k < kBvhMaxDepth && levels[kBuildLevelCount + k]; ++k) {
+        plan.level_first.push_back(levels[k]);
+        plan.n_nodes += levels[kBuildLevelCount + k];
+    }
+    plan.level_first.push_back(plan.n_nodes);
+    ctx->scene.mesh_nodes = plan.n_nodes;
+    ctx->scene.mesh_depth = plan.n_levels();                        // (breadth-first: the deepest level's children are leaves)
+    ctx->scene.mesh_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build).count();
+    const uint32_t use_bvh = refit_use_bvh(max_abs) ? 1u : 0u;
     for (DevState& d : ctx->devs) d.scene.use_bvh = use_bvh;
     return RPT_OK;
 }

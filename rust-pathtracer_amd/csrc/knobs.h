@@ -32,6 +32,8 @@ struct Knobs {
     float grid_near_reach = 1.5f;        // RPT_GRID_NEAR_REACH      near tier's reach in half-diagonals of the grid box (0: no near tier)
     float grid_spheres_per_cell = 1.0f;  // RPT_GRID_SPHERES_PER_CELL
     bool grid_box_lists = false;         // RPT_GRID_BOX_LISTS       cell lists by box-cell overlap instead of ball-cell overlap (A/B)
+    // -- the hierarchy rpt_rebuild_meshes builds (host_build.h)
+    uint32_t build_leaf = 2;             // RPT_BUILD_LEAF           a child of this many triangles or fewer is a leaf (1..8; development: the default is the measured one)
     // -- host side
     std::string gather;                  // RPT_GATHER               "p2p": single-process multi-device contexts gather with peer copies instead of RCCL
     bool pin_host = true;                // RPT_PIN_HOST             0: rpt_render does not page-lock the caller's buffer for the call
@@ -63,6 +65,7 @@ inline Knobs read_knobs()
     v.grid_near_reach = knob_f32("RPT_GRID_NEAR_REACH", v.grid_near_reach);
     v.grid_spheres_per_cell = knob_f32("RPT_GRID_SPHERES_PER_CELL", v.grid_spheres_per_cell);
     v.grid_box_lists = knob_flag("RPT_GRID_BOX_LISTS", false);
+    v.build_leaf = knob_u32("RPT_BUILD_LEAF", v.build_leaf);
     v.gather = knob_str("RPT_GATHER");
     v.pin_host = knob_flag("RPT_PIN_HOST", true);
     v.rccl_lib = knob_str("RPT_RCCL_LIB");

@@ -133,6 +133,7 @@ extern "C" {
     // (SceneDescBuilder fills no meshes yet, so nothing here can move one: declared for the `mesh` follow-up)
     #[allow(dead_code)]
     fn rpt_update_meshes(ctx: *mut RptCtx, updates: *const RptMeshVertices, n_updates: u32) -> c_int;
+    fn rpt_rebuild_meshes(ctx: *mut RptCtx, updates: *const RptMeshVertices, n_updates: u32) -> c_int;
     fn rpt_scene_analytical(out: *mut RptSceneDesc) -> c_int;
     fn rpt_render(ctx: *mut RptCtx, pixels: *mut f32, width: u32, height: u32,
                   frames_done: u64, spp: u32, seed: u64, flags: u32) -> c_int;
@@ -455,6 +456,13 @@ impl GpuTracer {
     /// How the launches are scheduled (include/rpt.h, rpt_set_dispatch); never changes a pixel.
     pub fn set_dispatch(&mut self, cost_order: u32, unit_rounds: u32, unit_min_spp: u32, unit_slots: u32) {
         unsafe { rpt_set_dispatch(self.ctx, cost_order, unit_rounds, unit_min_spp, unit_slots); }
+    }
+
+    /// New positions for the named meshes of the uploaded scene (all of a mesh's vertices; none: the positions the context
+    /// holds), then a new hierarchy over every triangle, built on the device (include/rpt.h, "rebuilding a moved mesh's
+    /// hierarchy"): the frames of a fresh upload of the moved scene.  The pointers are read during the call only.
+    pub fn rebuild_meshes(&mut self, updates: &[RptMeshVertices]) -> Result<(), RptError> {
+        self.check(unsafe { rpt_rebuild_meshes(self.ctx, updates.as_ptr(), updates.len() as u32) })
     }
 
     /// Continue a host ColorBuffer (pixels + frames) in the resident buffer.

@@ -7,7 +7,14 @@ scene (scenes.mesh_scene_moved, phases 0.05 / 0.5 / 2.0), alternating, `--reps` 
 update_meshes (the host's clock around the blocking call) from the uploaded scene to the moved one; the wall time of upload_scene()
 of the same moved scene (the existing path: the yardstick); and the resident render rate after each, from resident_kernel_ms.
 
-    python tools/mesh_bench.py [--spp 16] [--reps 5] [--update]
+--rebuild: one JSON line more, for rpt_rebuild_meshes (include/rpt.h, "rebuilding a moved mesh's hierarchy"), in the same shape.  For
+the same three moves, alternating, `--reps` times each (at least 5) in one process: the wall time of rebuild_meshes, of upload_scene()
+of the same moved scene on a second context (the unchanged path: the yardstick) and of update_meshes on a third (which refits the
+ORIGINAL scene's hierarchy); the resident render rate after each of the three; the rebuilt node count and depth; the context's first
+rebuild apart (it allocates); and the rates of the unmoved scene, rebuilt and uploaded.  RPT_BUILD_LEAF (csrc/knobs.h) sets the
+leaf target of the run.
+
+    python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild]
 """
 import argparse
 import ctypes as C
@@ -27,6 +34,7 @@ def main():
     ap.add_argument("--spp", type=int, default=16)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--update", action="store_true")
+    ap.add_argument("--rebuild", action="store_true")
     a = ap.parse_args()
     os.environ.setdefault("RPT_LIB", os.path.join(ROOT, "rust-pathtracer_amd", "librpt_hip_test.so"))     # (the product has no hooks)
     import __graft_entry__
@@ -49,12 +57,15 @@ def main():
         ms = t.resident_kernel_ms()
         rates.append(a.width * a.height * a.spp / (ms * 1e-3) / 1e9)
     update = measure_updates(pkg, t, s, a) if a.update else None
+    rebuild = measure_rebuilds(pkg, s, a) if a.rebuild else None
     t.close()
     print(json.dumps({"workload": "mesh_scene %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "triangles": n_tris,
                       "gsamples_per_s_median": sorted(rates)[len(rates) // 2], "gsamples_per_s": rates,
                       "bvh_nodes": nodes.value, "bvh_depth": depth.value, "bvh_build_ms": build_ms.value, "upload_s": upload_s}))
     if update:
         print(json.dumps(update))
+    if rebuild:
+        print(json.dumps(rebuild))
 
 
 def measure_updates(pkg, t, s, a):
@@ -104,6 +115,82 @@ def measure_updates(pkg, t, s, a):
         out[name] = {"phase": phase, "update_ms": up, "upload_ms": full, "upload_over_update": full["median"] / up["median"],
                      "gsamples_per_s_after_update": ru, "gsamples_per_s_after_upload": rf,
                      "fresh_upload_renders_faster_by_percent": (rf["median"] / ru["median"] - 1.0) * 100.0}
+    return out
+
+
+def measure_rebuilds(pkg, s, a):
+    """-> the --rebuild line.  Three contexts of this process over the same scene: one that rebuilds, one that is uploaded to (the
+    yardstick), one that only ever updates (every update refits the ORIGINAL hierarchy, as in --update)."""
+    import numpy as np
+    from rust_pathtracer_amd import scenes
+    original = [np.array(v, np.float32, copy=True) for v, _, _ in s.meshes]
+
+    def rate(tr):
+        tr.resident_reset()
+        tr.render_resident(a.width, a.height, a.spp)                # the dispatch order's first costs
+        tr.render_resident(a.width, a.height, a.spp)
+        return a.width * a.height * a.spp / (tr.resident_kernel_ms() * 1e-3) / 1e9
+
+    def stats(xs):
+        xs = sorted(xs)
+        return {"median": xs[len(xs) // 2], "min": xs[0], "max": xs[-1]}
+
+    def mesh_stats(tr):
+        nodes, depth, ms = C.c_uint32(0), C.c_uint32(0), C.c_float(0.0)
+        pkg._lib.check(pkg.lib().rpt_debug_mesh_stats(tr._h, C.byref(nodes), C.byref(depth), C.byref(ms)), tr._h)
+        return nodes.value, depth.value
+
+    phases = (("small", 0.05), ("medium", 0.5), ("large", 2.0))
+    moved = {name: scenes.mesh_scene_moved(s, phase) for name, phase in phases}
+    keys = ("rebuild_ms", "upload_ms", "update_ms", "rate_rebuild", "rate_upload", "rate_update")
+    res = {name: {k: [] for k in keys} for name, _ in phases}
+    built = pkg.Tracer(scenes.mesh_scene(), device=0, seed=1)
+    fresh_scene = scenes.mesh_scene()
+    fresh = pkg.Tracer(fresh_scene, device=0, seed=1)
+    refit = pkg.Tracer(scenes.mesh_scene(), device=0, seed=1)
+    uploaded_stats = mesh_stats(fresh)
+    rate_unmoved_upload = rate(fresh)
+    t0 = time.perf_counter()
+    built.rebuild_meshes()                                          # the context's first rebuild: allocates the device's tables
+    first_ms = (time.perf_counter() - t0) * 1e3
+    rate_unmoved_rebuild = rate(built)
+    unmoved_stats = mesh_stats(built)
+    refit.update_meshes(dict(enumerate(original)))
+    reps = max(5, a.reps)
+    shape = {}
+    for _ in range(reps):
+        for name, _ in phases:
+            r = res[name]
+            t0 = time.perf_counter()
+            built.rebuild_meshes(dict(enumerate(moved[name])))
+            r["rebuild_ms"].append((time.perf_counter() - t0) * 1e3)
+            r["rate_rebuild"].append(rate(built))
+            shape[name] = mesh_stats(built)
+            fresh_scene.meshes = [(v, idx, m) for v, (_, idx, m) in zip(moved[name], fresh_scene.meshes)]
+            t0 = time.perf_counter()
+            fresh.upload_scene()
+            r["upload_ms"].append((time.perf_counter() - t0) * 1e3)
+            r["rate_upload"].append(rate(fresh))
+            t0 = time.perf_counter()
+            refit.update_meshes(dict(enumerate(moved[name])))
+            r["update_ms"].append((time.perf_counter() - t0) * 1e3)
+            r["rate_update"].append(rate(refit))
+    for tr in (built, fresh, refit):
+        tr.close()
+    out = {"workload": "mesh_scene rebuild %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "reps": reps,
+           "leaf_target": os.environ.get("RPT_BUILD_LEAF", "default"), "first_rebuild_ms": first_ms,
+           "unmoved": {"gsamples_per_s_after_rebuild": rate_unmoved_rebuild, "gsamples_per_s_after_upload": rate_unmoved_upload,
+                       "rebuild_over_upload_rate": rate_unmoved_rebuild / rate_unmoved_upload,
+                       "rebuilt_nodes": unmoved_stats[0], "rebuilt_depth": unmoved_stats[1],
+                       "uploaded_nodes": uploaded_stats[0], "uploaded_depth": uploaded_stats[1]}}
+    for name, phase in phases:
+        r = res[name]
+        rb, full, up = stats(r["rebuild_ms"]), stats(r["upload_ms"]), stats(r["update_ms"])
+        rr, rf, ru = stats(r["rate_rebuild"]), stats(r["rate_upload"]), stats(r["rate_update"])
+        out[name] = {"phase": phase, "rebuild_ms": rb, "upload_ms": full, "update_ms": up, "upload_over_rebuild": full["median"] / rb["median"],
+                     "gsamples_per_s_after_rebuild": rr, "gsamples_per_s_after_upload": rf, "gsamples_per_s_after_update": ru,
+                     "rebuild_over_upload_rate": rr["median"] / rf["median"], "rebuild_over_update_rate": rr["median"] / ru["median"],
+                     "rebuilt_nodes": shape[name][0], "rebuilt_depth": shape[name][1]}
     return out
 
 
