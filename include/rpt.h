@@ -505,6 +505,83 @@ int rpt_update_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n
  * of the render rate (here: from about twenty such frames on). */
 int rpt_rebuild_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n_updates);
 
+/* ---- moving meshes from device memory — PROJECT-DEFINED -------------------------------------------------------------------------
+ * rpt_update_meshes and rpt_rebuild_meshes for positions that already live in device memory (a skinning, cloth or simulation
+ * step's output), with an optional affine transform per mesh applied on the device while they are read: a caller who keeps a
+ * rest pose in device memory moves a mesh rigidly with that array and twelve floats per frame — the library keeps no rest pose of
+ * its own, and nothing drifts.
+ *
+ * Meaning.  Let P(m) be, for each mesh m named in `sources`, the positions computed from vertices_dev and transform as written
+ * below.  The two calls leave the context in the state rpt_update_meshes / rpt_rebuild_meshes would leave it in, given P as host
+ * arrays: the same frames bit for bit, the same triangle and node tables byte for byte, the same errors from rpt_render* — and so
+ * the frames of a fresh rpt_upload_scene of the descriptor with P.
+ *
+ * The transform: 12 floats in HOST memory, the rows of a 3x4 matrix t; f32 in exactly this operation order, nothing contracted:
+ *     out[c] = ((t[4c]*x + t[4c+1]*y) + t[4c+2]*z) + t[4c+3]        c = 0, 1, 2
+ * transform == NULL copies a vertex's three words unchanged, so a -0 stays -0.  An identity matrix is NOT the same thing: it
+ * turns -0 into +0 (-0*1 + 0*0 = +0).  The statement is written once, csrc/host_move.h, for the kernel and the host reference.
+ *
+ * Checks, in this order.  On the host first:
+ *   RPT_ERR_INVALID_ARG  ctx is NULL; sources is NULL with a non-zero count;
+ *   RPT_ERR_NO_SCENE     no scene is uploaded, or the uploaded scene is not a mesh scene;
+ *   RPT_ERR_UNSUPPORTED  the scene's meshes hold 2^32 vertices or more in all;
+ *   RPT_ERR_INVALID_ARG  per source, in order: mesh >= the scene's n_meshes; a mesh named twice; n_vertices different from the
+ *                        uploaded mesh's; vertices_dev NULL with a non-zero count; vertices_dev not device memory — whatever
+ *                        hipPointerGetAttributes does not report as hipMemoryTypeDevice: an error from the query, host memory
+ *                        whether page-locked or not, managed memory —, before any kernel is launched; vertices_dev's allocation
+ *                        ending before 12 * n_vertices bytes from the pointer on (hipMemGetAddressRange; where the runtime
+ *                        reports no range for the memory, and inside a larger allocation such as a pooling allocator's block,
+ *                        the extent is the caller's responsibility: the kernels read 3 * n_vertices floats); a non-finite
+ *                        entry in transform (rpt_last_error names the mesh and the entry).
+ * Then on the device: every coordinate of every named mesh's P must be finite.  A NaN or infinity in the source, or an overflow
+ * through the transform, answers RPT_ERR_INVALID_ARG; rpt_last_error names the mesh (the first such source in `sources`) and its
+ * lowest offending vertex.  A vertex no triangle references is checked too, as on the host path.
+ * A rejected call leaves the context exactly as it was: the check pass transforms in registers and stores no position; only when
+ * every source has passed does a second pass compute the same positions again and store them.  A later
+ * rpt_rebuild_meshes(ctx, NULL, 0) after a rejection sees the old positions.
+ *   RPT_ERR_HIP          a runtime call failed part-way: the context is left with NO scene, as for rpt_update_meshes.
+ * The 2^60 rule is unchanged; the per-mesh largest |coordinate| over referenced vertices now comes from the device check.
+ *
+ * Where the source lives.  vertices_dev may lie on any device of the process.  The check runs on the context's first device; each
+ * device of the context reads a source that lies on itself in place, and one that lies elsewhere from a copy into its own memory
+ * (hipMemcpyAsync, hipMemcpyDefault).  A context of several devices (rpt_create_multi, also with a device listed twice) brings
+ * every one to the same state; with one process per GPU every rank makes the call itself, as for an update.  (The copy of a source
+ * from another device is unverified on hardware: the tests run on one GPU, where a context with the device listed twice is what
+ * exercises the several-devices loop.)
+ *
+ * Ordering.  The calls block, like their host forms.  Before a source is read, all earlier work on the device that holds it has
+ * finished (hipDeviceSynchronize there): a producer kernel enqueued on any stream before the call is complete.  When the call
+ * returns the source has been consumed: the caller may overwrite it at once.  There is no stream argument.
+ *
+ * n_sources == 0: rpt_update_meshes_device answers RPT_OK and does nothing; rpt_rebuild_meshes_device is
+ * rpt_rebuild_meshes(ctx, NULL, 0).  Streams of the caller's own, the resident ColorBuffer, the learned dispatch order: as for
+ * rpt_update_meshes.
+ *
+ * rpt_download_mesh_vertices copies the positions the context holds for one mesh — all its vertices — to host memory: before the
+ * context's first update of any kind from the host's copy of the upload, afterwards from its first device's vertex table.  It
+ * answers RPT_ERR_INVALID_ARG for a NULL ctx, NULL vertices with a non-zero count, mesh >= n_meshes or n_vertices different from
+ * the mesh's, RPT_ERR_NO_SCENE without a mesh scene, RPT_ERR_UNSUPPORTED for 2^32 vertices, and never changes anything.
+ *
+ * Memory.  The context's first device-source call allocates on its first device, until the next rpt_upload_scene, 1 B per vertex
+ * (which vertices a triangle references) + 8 B per mesh (the check's words); a device that reads a source lying on another device
+ * keeps 12 B per vertex for the copies.  The refit's and the rebuild's tables are those of rpt_update_meshes /
+ * rpt_rebuild_meshes, allocated as there.  No staging copy of the positions exists: the check stores nothing.
+ *
+ * Timings: tools/mesh_bench.py --device times both forms on scenes.mesh_scene (393 216 triangles, 196 610 vertices) next to
+ * the host forms (medians of 5, alternating); no figures are recorded here yet.  What the device forms leave out of the host forms'
+ * 0.62 ms and 1.10 ms is the host's scan of 2.4 MB of coordinates and one pageable copy per mesh; what they add is two kernel
+ * launches per named mesh, one 8-byte-per-mesh read-back and one more wait. */
+typedef struct rpt_mesh_source {
+    uint32_t mesh;                    /* index into the uploaded scene's rpt_scene_desc.meshes */
+    uint32_t n_vertices;              /* must equal that mesh's n_vertices */
+    const float* vertices_dev;        /* DEVICE memory, xyz, 3 floats per vertex: all of the mesh's vertices */
+    const float* transform;           /* HOST memory, 12 floats, rows of a 3x4 matrix; NULL = take the positions as they are */
+} rpt_mesh_source;
+
+int rpt_update_meshes_device(rpt_ctx* ctx, const rpt_mesh_source* sources, uint32_t n_sources);
+int rpt_rebuild_meshes_device(rpt_ctx* ctx, const rpt_mesh_source* sources, uint32_t n_sources);
+int rpt_download_mesh_vertices(rpt_ctx* ctx, uint32_t mesh, float* vertices /* host */, uint32_t n_vertices);
+
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)
  *   frames_done ColorBuffer.frames before the call; the caller adds `spp` afterwards

@@ -210,6 +210,20 @@ public:
     void rebuild_meshes(const std::vector<rpt_mesh_vertices>& updates = {}) {
         check(rpt_rebuild_meshes(ctx_, updates.data(), (uint32_t)updates.size()), ctx_);
     }
+    /// The two calls for positions in DEVICE memory, each mesh through an optional 3x4 transform applied on the device (rpt.h,
+    /// "moving meshes from device memory").  They block and have consumed the sources when they return.
+    void update_meshes_device(const std::vector<rpt_mesh_source>& sources) {
+        check(rpt_update_meshes_device(ctx_, sources.data(), (uint32_t)sources.size()), ctx_);
+    }
+    void rebuild_meshes_device(const std::vector<rpt_mesh_source>& sources = {}) {
+        check(rpt_rebuild_meshes_device(ctx_, sources.data(), (uint32_t)sources.size()), ctx_);
+    }
+    /// The positions the context holds for one mesh of the uploaded scene (xyz per vertex).
+    std::vector<float> mesh_vertices(uint32_t mesh, uint32_t n_vertices) {
+        std::vector<float> out(3 * (size_t)n_vertices);
+        check(rpt_download_mesh_vertices(ctx_, mesh, out.data(), n_vertices), ctx_);
+        return out;
+    }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

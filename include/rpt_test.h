@@ -64,6 +64,11 @@ int rpt_debug_mesh_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32
  * RPT_ERR_NO_SCENE unless the uploaded scene has meshes.  (tools/mesh_bench.py) */
 int rpt_debug_mesh_stats(rpt_ctx* ctx, uint32_t* n_nodes, uint32_t* depth, float* build_ms);
 
+/* On how many of the context's devices the hierarchy's walk serves the uploaded mesh scene's rays: all of them, or — while a coordinate
+ * some triangle uses lies beyond 2^60 (include/rpt.h, "triangle meshes") — none: the ordered loop serves them.  RPT_ERR_NO_SCENE
+ * unless the uploaded scene has meshes. */
+int rpt_debug_mesh_walk(rpt_ctx* ctx, uint32_t* walk);
+
 /* Copy the uploaded mesh scene's triangle rows (which = 0: 48 B per triangle, in leaf order) or hierarchy nodes (which = 1: 64 B each,
  * csrc/host_bvh.h BvhNode) from the context's first device to the host, as rpt_update_meshes / rpt_rebuild_meshes (include/rpt.h) left them.  *bytes = the
  * table's size; RPT_ERR_INVALID_ARG when `out` is NULL or holds fewer than that (*bytes is still set).  RPT_ERR_NO_SCENE unless the

@@ -122,6 +122,10 @@ class rpt_mesh_vertices(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("n_vertices", C.c_uint32), ("vertices", C.POINTER(C.c_float))]
 
 
+class rpt_mesh_source(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("n_vertices", C.c_uint32), ("vertices_dev", C.c_void_p), ("transform", C.POINTER(C.c_float))]
+
+
 class rpt_scene_desc(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("flags", C.c_uint32),
@@ -169,6 +173,9 @@ SYMBOLS = {
     "rpt_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(rpt_scene_desc)]),
     "rpt_update_meshes": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_vertices), C.c_uint32]),
     "rpt_rebuild_meshes": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_vertices), C.c_uint32]),
+    "rpt_update_meshes_device": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_source), C.c_uint32]),
+    "rpt_rebuild_meshes_device": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_source), C.c_uint32]),
+    "rpt_download_mesh_vertices": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "rpt_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -203,6 +210,7 @@ TEST_SYMBOLS = {
     "rpt_probe_math": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rpt_debug_mesh_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rpt_debug_mesh_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "rpt_debug_mesh_walk": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rpt_debug_mesh_tables": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
 }
 RPT_MESH_QUERY_USE_MAX = 1 << 0

@@ -348,6 +348,7 @@ class Tracer:
         self.seed = int(seed)
         self.flags = 0                 # RPT_RENDER_* bits (0 = the strict, bit-exact regenerating kernel)
         self._frame = None             # resident_to_u8's page-locked frame
+        self._stale_meshes = set()     # meshes whose scene().meshes arrays a device-source call has left behind (update_meshes_device)
         self._h = C.c_void_p()
         if devices is not None:
             ids = (C.c_int * len(devices))(*devices)
@@ -378,6 +379,7 @@ class Tracer:
 
     def upload_scene(self):
         """Call after mutating the scene returned by scene()."""
+        self._refresh_stale_meshes()
         desc = self._scene.describe()
         check(lib().rpt_upload_scene(self._h, C.byref(desc)), self._h)
 
@@ -400,10 +402,66 @@ class Tracer:
         ups = (_abi.rpt_mesh_vertices * max(1, len(items)))()
         for u, (m, _), v in zip(ups, items, arrays):
             u.mesh, u.n_vertices, u.vertices = int(m), v.shape[0], v.ctypes.data_as(C.POINTER(C.c_float))
-        check(call(self._h, ups, len(items)), self._h)
+        self._checked_move(call(self._h, ups, len(items)))
         for (m, _), v in zip(items, arrays):
             _, idx, mat = self._scene.meshes[m]
             self._scene.meshes[m] = (v, idx, mat)
+            self._stale_meshes.discard(int(m))
+
+    def _checked_move(self, status):
+        """check() for the calls that move meshes: one that failed part-way (RPT_ERR_HIP) has left the context without a scene, so
+        there is nothing left to read stale arrays back from — the next upload_scene() uploads the scene as the wrapper has it."""
+        if status == _abi.RPT_ERR_HIP:
+            self._stale_meshes.clear()
+        check(status, self._h)
+
+    def update_meshes_device(self, sources):
+        """update_meshes for positions that live in device memory (include/rpt.h, "moving meshes from device memory"): `sources`
+        maps a mesh's index to a CUDA float32 contiguous tensor of shape (n_vertices, 3), or to a pair (tensor, transform) —
+        `transform` anything np.asarray(..., np.float32).reshape(3, 4) takes, applied on the device while the positions are read.
+        The call blocks and has consumed the tensors when it returns.  scene().meshes[m]'s vertex array is stale afterwards;
+        mesh_vertices(m) reads the positions the context holds, and upload_scene() refreshes the stale ones first."""
+        self._move_meshes_device(lib().rpt_update_meshes_device, sources)
+
+    def rebuild_meshes_device(self, sources=None):
+        """rebuild_meshes from device memory: update_meshes_device's arguments.  Without `sources`: a rebuild over the positions
+        the context holds."""
+        self._move_meshes_device(lib().rpt_rebuild_meshes_device, sources or {})
+
+    def _move_meshes_device(self, call, sources):
+        import torch
+        items = sorted(sources.items())
+        srcs = (_abi.rpt_mesh_source * max(1, len(items)))()
+        keep = []
+        for s, (m, v) in zip(srcs, items):
+            xf = None
+            if isinstance(v, (tuple, list)):
+                v, xf = v
+            if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.dim() == 2 and
+                    v.shape[1] == 3):
+                raise ValueError("mesh %d: the source must be a CUDA float32 contiguous tensor of shape (n, 3)" % m)
+            s.mesh, s.n_vertices, s.vertices_dev = int(m), v.shape[0], v.data_ptr() if v.shape[0] else None
+            if xf is not None:
+                xf = np.ascontiguousarray(np.asarray(xf, np.float32).reshape(3, 4))
+                s.transform = xf.ctypes.data_as(C.POINTER(C.c_float))
+            keep.append((v, xf))
+        self._checked_move(call(self._h, srcs, len(items)))
+        self._stale_meshes.update(int(m) for m, _ in items)
+
+    def mesh_vertices(self, m):
+        """The positions the context holds for mesh `m` (rpt_download_mesh_vertices): a new float32 array of shape (n_vertices, 3)."""
+        n = np.asarray(self._scene.meshes[m][0]).reshape(-1, 3).shape[0]
+        out = np.empty((n, 3), np.float32)
+        check(lib().rpt_download_mesh_vertices(self._h, int(m), out.ctypes.data, n), self._h)
+        return out
+
+    def _refresh_stale_meshes(self):
+        """scene().meshes' vertex arrays that a device-source call left stale, read back once (only before an upload)."""
+        for m in sorted(self._stale_meshes):
+            if m < len(getattr(self._scene, "meshes", ())):
+                _, idx, mat = self._scene.meshes[m]
+                self._scene.meshes[m] = (self.mesh_vertices(m), idx, mat)
+        self._stale_meshes.clear()
 
     def scene(self):                                               # tracer.rs:629-631
         return self._scene

@@ -20,11 +20,13 @@
 
 #include "../../include/rpt.h"
 #include "host_build.h"
+#include "host_move.h"
 #include "host_refit.h"
 #include "host_upload.h"
 #include "knobs.h"
 #include "launch.h"
 #include "launch_build.h"
+#include "launch_move.h"
 #ifdef RPT_TEST_HOOKS
 #include "../../include/rpt_test.h"
 #endif
@@ -48,6 +50,9 @@ struct DevState {
     void* build = nullptr;            // rpt_rebuild_meshes' own tables (host_build.h, BuildLayout) and the node table it binds: from the
     void* build_nodes = nullptr;      // context's first rebuild to the next upload
     size_t build_temp_bytes = 0;
+    void* move = nullptr;             // the device-source calls' check tables (host_move.h, MoveLayout): on the context's first device, from its
+                                      // first rpt_update_meshes_device / rpt_rebuild_meshes_device to the next upload
+    void* move_stage = nullptr;       // ... and copies of sources that lie on another device (12 B per vertex of the scene), made on demand
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -271,6 +276,8 @@ static void free_mesh_work(DevState& d)
     if (d.refit) { (void)hipFree(d.refit); d.refit = nullptr; }
     if (d.build) { (void)hipFree(d.build); d.build = nullptr; }
     if (d.build_nodes) { (void)hipFree(d.build_nodes); d.build_nodes = nullptr; }
+    if (d.move) { (void)hipFree(d.move); d.move = nullptr; }
+    if (d.move_stage) { (void)hipFree(d.move_stage); d.move_stage = nullptr; }
     d.refit_full = false;
     d.build_temp_bytes = 0;
 }
@@ -903,10 +910,53 @@ static void drop_scene(rpt_ctx* ctx)
     ctx->refit = rpthost::RefitPlan();
 }
 
+// Where the named meshes' new positions come from: host arrays (rpt_update_meshes, rpt_rebuild_meshes) or device arrays through a
+// transform (their _device forms, checked before: check_positions_device).  The only thing in which the two forms' device work differs.
+struct MeshPositions {
+    const rpt_mesh_vertices* host = nullptr;
+    uint32_t n_host = 0;
+    const rpt_mesh_source* dev = nullptr;
+    uint32_t n_dev = 0;
+    const int* dev_device = nullptr;  // per source: the device that holds it (host_move.h, check_mesh_sources)
+};
+
+// `*src`: source `so` where device `d` (the current one) can read it — in place when it lies there, else copied into d's own memory,
+// on d's stream.
+static int source_on_device(rpt_ctx* ctx, DevState& d, const rpt_mesh_source& so, int so_device, const float** src)
+{
+    if (so_device == d.device) { *src = so.vertices_dev; return RPT_OK; }
+    const rpthost::RefitPlan& plan = ctx->refit;
+    if (!d.move_stage) RPT_HIP_CHECK(ctx, hipMalloc(&d.move_stage, 12 * (size_t)plan.n_vertices()));
+    float* at = static_cast<float*>(d.move_stage) + 3 * (size_t)plan.mesh_first[so.mesh];
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(at, so.vertices_dev, 12 * (size_t)so.n_vertices, hipMemcpyDefault, d.stream));
+    *src = at;
+    return RPT_OK;
+}
+
+// The named meshes' positions into `vertices`, device d's concatenated vertex table, on d's stream.
+static int put_positions(rpt_ctx* ctx, DevState& d, const MeshPositions& pos, unsigned char* vertices)
+{
+    const rpthost::RefitPlan& plan = ctx->refit;
+    for (uint32_t u = 0; u < pos.n_host; ++u) {
+        if (pos.host[u].n_vertices == 0) continue;
+        RPT_HIP_CHECK(ctx, hipMemcpyAsync(vertices + 12 * (size_t)plan.mesh_first[pos.host[u].mesh], pos.host[u].vertices,
+                                          12 * (size_t)pos.host[u].n_vertices, hipMemcpyHostToDevice, d.stream));
+    }
+    for (uint32_t u = 0; u < pos.n_dev; ++u) {
+        const rpt_mesh_source& so = pos.dev[u];
+        if (so.n_vertices == 0) continue;
+        const float* src = nullptr;
+        RPT_CHECK_RC(source_on_device(ctx, d, so, pos.dev_device[u], &src));
+        RPT_HIP_CHECK(ctx, rptlaunch::move_apply(src, rpthost::move_transform_of(so.transform),
+                                                 reinterpret_cast<float*>(vertices) + 3 * (size_t)plan.mesh_first[so.mesh], so.n_vertices, d.stream));
+    }
+    return RPT_OK;
+}
+
 // One device's part of an update: wait for its earlier work, make its refit tables if this is the context's first update, copy the
 // named meshes' vertices in, refit every triangle row and slot box, then the nodes level by level, deepest first (kernel boundaries
 // on one stream order the levels), and wait.
-static int update_device(rpt_ctx* ctx, DevState& d, const rpt_mesh_vertices* updates, uint32_t n_updates)
+static int update_device(rpt_ctx* ctx, DevState& d, const MeshPositions& pos)
 {
     const rpthost::RefitPlan& plan = ctx->refit;
     const rpthost::RefitLayout lay(plan.n_vertices(), plan.n_slots, plan.n_nodes);
@@ -919,11 +969,7 @@ static int update_device(rpt_ctx* ctx, DevState& d, const rpt_mesh_vertices* upd
         RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_slot_vertex, plan.slot_vertex.data(), sizeof(uint32_t) * plan.slot_vertex.size(), hipMemcpyHostToDevice, d.stream));
         RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_level_nodes, plan.level_nodes.data(), sizeof(uint32_t) * plan.level_nodes.size(), hipMemcpyHostToDevice, d.stream));
     }
-    for (uint32_t u = 0; u < n_updates; ++u) {
-        if (updates[u].n_vertices == 0) continue;
-        RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_vertices + 12 * (size_t)plan.mesh_first[updates[u].mesh], updates[u].vertices,
-                                          12 * (size_t)updates[u].n_vertices, hipMemcpyHostToDevice, d.stream));
-    }
+    RPT_CHECK_RC(put_positions(ctx, d, pos, base + lay.off_vertices));
     float4* tris = const_cast<float4*>(d.scene.tris);
     float4* nodes = const_cast<float4*>(d.scene.nodes);
     const float* slot_box = reinterpret_cast<const float*>(base + lay.off_slot_box);
@@ -936,23 +982,15 @@ static int update_device(rpt_ctx* ctx, DevState& d, const rpt_mesh_vertices* upd
     return RPT_OK;
 }
 
-int rpt_update_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n_updates)
+// Every device's update_device with checked positions, then the host's record: what rpt_update_meshes and rpt_update_meshes_device share.
+static int run_update(rpt_ctx* ctx, const MeshPositions& pos, const std::vector<float>& max_abs, const char* call)
 {
-    if (!ctx) { set_err(nullptr, "rpt_update_meshes: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (n_updates == 0) return RPT_OK;
-    std::vector<float> max_abs;
-    std::string why;
-    const int rc = rpthost::check_mesh_update(ctx->refit, ctx->scene.kind == SceneKind::mesh, updates, n_updates, max_abs, why);
-    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
-    bool any = false;                                               // (meshes without vertices only: nothing moves)
-    for (uint32_t u = 0; u < n_updates; ++u) any = any || updates[u].n_vertices != 0;
-    if (!any) return RPT_OK;
     {
         DeviceGuard guard(ctx->devs[0].device);
         int rc_dev = RPT_OK;
         for (DevState& d : ctx->devs) {
-            if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_update_meshes: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
-            else rc_dev = update_device(ctx, d, updates, n_updates);
+            if (guard.to(d.device) != hipSuccess) { set_err(ctx, "%s: cannot select device %d", call, d.device); rc_dev = RPT_ERR_HIP; }
+            else rc_dev = update_device(ctx, d, pos);
             if (rc_dev != RPT_OK) break;
         }
         if (rc_dev != RPT_OK) {
@@ -970,6 +1008,22 @@ int rpt_update_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n
     return RPT_OK;
 }
 
+int rpt_update_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n_updates)
+{
+    if (!ctx) { set_err(nullptr, "rpt_update_meshes: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (n_updates == 0) return RPT_OK;
+    std::vector<float> max_abs;
+    std::string why;
+    const int rc = rpthost::check_mesh_update(ctx->refit, ctx->scene.kind == SceneKind::mesh, updates, n_updates, max_abs, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    bool any = false;                                               // (meshes without vertices only: nothing moves)
+    for (uint32_t u = 0; u < n_updates; ++u) any = any || updates[u].n_vertices != 0;
+    if (!any) return RPT_OK;
+    MeshPositions pos;
+    pos.host = updates; pos.n_host = n_updates;
+    return run_update(ctx, pos, max_abs, "rpt_update_meshes");
+}
+
 // ---- rpt_rebuild_meshes (include/rpt.h, "rebuilding a moved mesh's hierarchy") -----------------------------------------------------
 // One device's part of a rebuild: wait for its earlier work; make the refit tables as a first update does, but with a level order
 // that has room for any hierarchy over the scene's triangles (tables an update made are copied into larger ones); make the build's
@@ -977,7 +1031,7 @@ int rpt_update_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n
 // stream, the slots' boxes in the present order, the new order (k_build.hip, build_order), the rows and boxes in the new order, the
 // new shape (build_shape).  The host reads the levels' counts back once, launches the refit of the nodes level by level, deepest
 // first, and waits.  `levels`: host_build.h's kBuildLevelWords words, as the device left them.
-static int rebuild_device(rpt_ctx* ctx, DevState& d, const rpt_mesh_vertices* updates, uint32_t n_updates, uint32_t* levels)
+static int rebuild_device(rpt_ctx* ctx, DevState& d, const MeshPositions& pos, uint32_t* levels)
 {
     using namespace rpthost;
     const RefitPlan& plan = ctx->refit;
@@ -1009,11 +1063,7 @@ static int rebuild_device(rpt_ctx* ctx, DevState& d, const rpt_mesh_vertices* up
     if (!d.build_nodes) RPT_HIP_CHECK(ctx, hipMalloc(&d.build_nodes, sizeof(BvhNode) * (size_t)max_nodes));
     unsigned char* base = static_cast<unsigned char*>(d.refit);
     unsigned char* work = static_cast<unsigned char*>(d.build);
-    for (uint32_t u = 0; u < n_updates; ++u) {
-        if (updates[u].n_vertices == 0) continue;
-        RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_vertices + 12 * (size_t)plan.mesh_first[updates[u].mesh], updates[u].vertices,
-                                          12 * (size_t)updates[u].n_vertices, hipMemcpyHostToDevice, d.stream));
-    }
+    RPT_CHECK_RC(put_positions(ctx, d, pos, base + lay.off_vertices));
     const BuildLayout bl(n, max_nodes, build_level_bound(n, kBvhMaxDepth - 1u), d.build_temp_bytes);
     rptlaunch::BuildTables t;
     t.n_slots = n; t.max_nodes = max_nodes;
@@ -1059,25 +1109,10 @@ static int rebuild_device(rpt_ctx* ctx, DevState& d, const rpt_mesh_vertices* up
     return RPT_OK;
 }
 
-int rpt_rebuild_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n_updates)
+// Every device's rebuild_device with checked positions, then the host's record: what rpt_rebuild_meshes and rpt_rebuild_meshes_device share.
+static int run_rebuild(rpt_ctx* ctx, const MeshPositions& pos, const std::vector<float>& max_abs, const char* call)
 {
     using namespace rpthost;
-    if (!ctx) { set_err(nullptr, "rpt_rebuild_meshes: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    std::vector<float> max_abs;
-    if (n_updates == 0) {                                           // a rebuild over the positions the context holds
-        if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_rebuild_meshes: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-        if (!ctx->refit.ok) { set_err(ctx, "rpt_rebuild_meshes: the scene's meshes hold 2^32 vertices or more"); return RPT_ERR_UNSUPPORTED; }
-        max_abs = ctx->refit.mesh_max_abs;
-    } else {
-        std::string why;
-        const int rc = check_mesh_update(ctx->refit, ctx->scene.kind == SceneKind::mesh, updates, n_updates, max_abs, why);
-        if (rc != RPT_OK) {
-            const std::string theirs = "rpt_update_meshes: ";       // (host_refit.h, update_error: the checks are an update's, the call is this one)
-            if (why.compare(0, theirs.size(), theirs) == 0) why = "rpt_rebuild_meshes: " + why.substr(theirs.size());
-            set_err(ctx, "%s", why.c_str());
-            return rc;
-        }
-    }
     uint32_t levels[kBuildLevelWords] = {}, first_levels[kBuildLevelWords] = {};
     const auto t_build = std::chrono::steady_clock::now();
     {
@@ -1085,11 +1120,11 @@ int rpt_rebuild_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t 
         int rc_dev = RPT_OK;
         for (size_t i = 0; i < ctx->devs.size(); ++i) {
             DevState& d = ctx->devs[i];
-            if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_rebuild_meshes: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
-            else rc_dev = rebuild_device(ctx, d, updates, n_updates, levels);
+            if (guard.to(d.device) != hipSuccess) { set_err(ctx, "%s: cannot select device %d", call, d.device); rc_dev = RPT_ERR_HIP; }
+            else rc_dev = rebuild_device(ctx, d, pos, levels);
             if (rc_dev == RPT_OK && i == 0) memcpy(first_levels, levels, sizeof(levels));
             if (rc_dev == RPT_OK && memcmp(first_levels, levels, sizeof(levels)) != 0) {
-                set_err(ctx, "rpt_rebuild_meshes: device %d built another hierarchy than device %d", d.device, ctx->devs[0].device);
+                set_err(ctx, "%s: device %d built another hierarchy than device %d", call, d.device, ctx->devs[0].device);
                 rc_dev = RPT_ERR_HIP;
             }
             if (rc_dev != RPT_OK) break;
@@ -1117,6 +1152,167 @@ int rpt_rebuild_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t 
     ctx->scene.mesh_build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build).count();
     const uint32_t use_bvh = refit_use_bvh(max_abs) ? 1u : 0u;
     for (DevState& d : ctx->devs) d.scene.use_bvh = use_bvh;
+    return RPT_OK;
+}
+
+int rpt_rebuild_meshes(rpt_ctx* ctx, const rpt_mesh_vertices* updates, uint32_t n_updates)
+{
+    using namespace rpthost;
+    if (!ctx) { set_err(nullptr, "rpt_rebuild_meshes: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    std::vector<float> max_abs;
+    if (n_updates == 0) {                                           // a rebuild over the positions the context holds
+        if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_rebuild_meshes: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+        if (!ctx->refit.ok) { set_err(ctx, "rpt_rebuild_meshes: the scene's meshes hold 2^32 vertices or more"); return RPT_ERR_UNSUPPORTED; }
+        max_abs = ctx->refit.mesh_max_abs;
+    } else {
+        std::string why;
+        const int rc = check_mesh_update(ctx->refit, ctx->scene.kind == SceneKind::mesh, updates, n_updates, max_abs, why);
+        if (rc != RPT_OK) {
+            const std::string theirs = "rpt_update_meshes: ";       // (host_refit.h, update_error: the checks are an update's, the call is this one)
+            if (why.compare(0, theirs.size(), theirs) == 0) why = "rpt_rebuild_meshes: " + why.substr(theirs.size());
+            set_err(ctx, "%s", why.c_str());
+            return rc;
+        }
+    }
+    MeshPositions pos;
+    pos.host = updates; pos.n_host = n_updates;
+    return run_rebuild(ctx, pos, max_abs, "rpt_rebuild_meshes");
+}
+
+// ---- rpt_update_meshes_device / rpt_rebuild_meshes_device (include/rpt.h, "moving meshes from device memory") ----------------------
+// host_move.h's MoveSourceQuery: device memory is what hipPointerGetAttributes reports as hipMemoryTypeDevice, and nothing else; and
+// `bytes` from `p` on must lie inside the allocation `p` points into (hipMemGetAddressRange), so that no kernel reads beyond it
+static int query_source(const void* p, size_t bytes, int* device)
+{
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof(attr));
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return rpthost::kMoveSourceNotDevice; }
+    if (attr.type != hipMemoryTypeDevice || attr.isManaged) return rpthost::kMoveSourceNotDevice;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) == hipSuccess) {
+        const uintptr_t at = reinterpret_cast<uintptr_t>(p), lo = reinterpret_cast<uintptr_t>(base);
+        if (at < lo || at - lo > size || size - (at - lo) < bytes) return rpthost::kMoveSourceShort;
+    } else (void)hipGetLastError();                                 // (memory whose range the runtime does not report: the extent is the caller's word)
+    *device = attr.device;
+    return rpthost::kMoveSourceOk;
+}
+
+// The device check of a call whose host checks have passed, on the context's first device (the current one): its check tables if this
+// is the context's first device-source call, the words zeroed, one check launch per source, the words read back.  Nothing the
+// context's scene consists of is written.  RPT_OK: `max_abs` has the named meshes' new values.
+static int check_positions_device(rpt_ctx* ctx, const rpt_mesh_source* sources, uint32_t n_sources, const int* devices, const char* call,
+                                  std::vector<float>& max_abs)
+{
+    using namespace rpthost;
+    DevState& d = ctx->devs[0];
+    const RefitPlan& plan = ctx->refit;
+    const MoveLayout ml(plan.n_meshes(), plan.n_vertices());
+    if (!d.move) {
+        void* fresh = nullptr;
+        RPT_HIP_CHECK(ctx, hipMalloc(&fresh, ml.total));
+        hipError_t e = plan.referenced.empty() ? hipSuccess
+                                               : hipMemcpy(static_cast<unsigned char*>(fresh) + ml.off_referenced, plan.referenced.data(), plan.referenced.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) (void)hipFree(fresh);
+        RPT_HIP_CHECK(ctx, e);
+        d.move = fresh;
+    }
+    unsigned char* base = static_cast<unsigned char*>(d.move);
+    uint32_t* words = reinterpret_cast<uint32_t*>(base + ml.off_words);
+    const size_t word_bytes = sizeof(uint32_t) * kMoveWords * plan.n_meshes();
+    RPT_HIP_CHECK(ctx, hipMemsetAsync(words, 0, word_bytes, d.stream));
+    for (uint32_t u = 0; u < n_sources; ++u) {
+        const rpt_mesh_source& so = sources[u];
+        if (so.n_vertices == 0) continue;
+        const float* src = nullptr;
+        RPT_CHECK_RC(source_on_device(ctx, d, so, devices[u], &src));
+        RPT_HIP_CHECK(ctx, rptlaunch::move_check(src, move_transform_of(so.transform), base + ml.off_referenced + plan.mesh_first[so.mesh],
+                                                 words + kMoveWords * (size_t)so.mesh, so.n_vertices, d.stream));
+    }
+    std::vector<uint32_t> got(kMoveWords * (size_t)plan.n_meshes(), 0u);
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(got.data(), words, word_bytes, hipMemcpyDeviceToHost, d.stream));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    for (uint32_t u = 0; u < n_sources; ++u) {
+        const rpt_mesh_source& so = sources[u];
+        float big = 0.0f;
+        std::string why;
+        if (so.n_vertices != 0 && move_check_result(so, &got[kMoveWords * (size_t)so.mesh], call, big, why) != RPT_OK) {
+            set_err(ctx, "%s", why.c_str());
+            return RPT_ERR_INVALID_ARG;
+        }
+        max_abs[so.mesh] = big;
+    }
+    return RPT_OK;
+}
+
+static int move_meshes_device(rpt_ctx* ctx, const rpt_mesh_source* sources, uint32_t n_sources, bool rebuild)
+{
+    const char* call = rebuild ? "rpt_rebuild_meshes_device" : "rpt_update_meshes_device";
+    if (!ctx) { set_err(nullptr, "%s: ctx is NULL", call); return RPT_ERR_INVALID_ARG; }
+    if (n_sources == 0) {                                           // nothing to do, or a rebuild over the positions the context holds
+        if (!rebuild) return RPT_OK;
+        if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "%s: needs an uploaded scene with meshes", call); return RPT_ERR_NO_SCENE; }
+        if (!ctx->refit.ok) { set_err(ctx, "%s: the scene's meshes hold 2^32 vertices or more", call); return RPT_ERR_UNSUPPORTED; }
+        return run_rebuild(ctx, MeshPositions(), ctx->refit.mesh_max_abs, call);
+    }
+    std::vector<int> devices;
+    std::string why;
+    const int rc = rpthost::check_mesh_sources(ctx->refit, ctx->scene.kind == SceneKind::mesh, sources, n_sources, query_source, call, devices, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    bool any = false;                                               // (meshes without vertices only: nothing moves)
+    for (uint32_t u = 0; u < n_sources; ++u) any = any || sources[u].n_vertices != 0;
+    if (!any && !rebuild) return RPT_OK;
+    std::vector<float> max_abs = ctx->refit.mesh_max_abs;
+    {
+        // everything enqueued on a device that holds a source has finished before the source is read; then the check
+        DeviceGuard guard(ctx->devs[0].device);
+        int rc_dev = RPT_OK;
+        for (uint32_t u = 0; u < n_sources && rc_dev == RPT_OK; ++u) {
+            bool seen = devices[u] < 0;
+            for (uint32_t k = 0; k < u; ++k) seen = seen || devices[k] == devices[u];
+            if (seen) continue;
+            if (guard.to(devices[u]) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+                (void)hipGetLastError();
+                set_err(ctx, "%s: cannot wait for device %d, which holds mesh %u's source", call, devices[u], sources[u].mesh);
+                rc_dev = RPT_ERR_HIP;
+            }
+        }
+        if (rc_dev == RPT_OK && guard.to(ctx->devs[0].device) != hipSuccess) { set_err(ctx, "%s: cannot select device %d", call, ctx->devs[0].device); rc_dev = RPT_ERR_HIP; }
+        if (rc_dev == RPT_OK) rc_dev = check_positions_device(ctx, sources, n_sources, devices.data(), call, max_abs);
+        if (rc_dev == RPT_ERR_HIP) {
+            const std::string first = ctx->err;
+            drop_scene(ctx);
+            set_err(ctx, "%s; the context now holds no scene", first.c_str());
+        }
+        if (rc_dev != RPT_OK) return rc_dev;
+    }
+    MeshPositions pos;
+    pos.dev = sources; pos.n_dev = n_sources; pos.dev_device = devices.data();
+    return rebuild ? run_rebuild(ctx, pos, max_abs, call) : run_update(ctx, pos, max_abs, call);
+}
+
+int rpt_update_meshes_device(rpt_ctx* ctx, const rpt_mesh_source* sources, uint32_t n_sources) { return move_meshes_device(ctx, sources, n_sources, false); }
+int rpt_rebuild_meshes_device(rpt_ctx* ctx, const rpt_mesh_source* sources, uint32_t n_sources) { return move_meshes_device(ctx, sources, n_sources, true); }
+
+int rpt_download_mesh_vertices(rpt_ctx* ctx, uint32_t mesh, float* vertices, uint32_t n_vertices)
+{
+    if (!ctx) { set_err(nullptr, "rpt_download_mesh_vertices: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_mesh_vertices: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    const rpthost::RefitPlan& plan = ctx->refit;
+    if (!plan.ok) { set_err(ctx, "rpt_download_mesh_vertices: the scene's meshes hold 2^32 vertices or more"); return RPT_ERR_UNSUPPORTED; }
+    if (mesh >= plan.n_meshes()) { set_err(ctx, "rpt_download_mesh_vertices: mesh %u out of range (the scene has %u)", mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
+    const uint32_t first = plan.mesh_first[mesh], count = plan.mesh_first[mesh + 1u] - first;
+    if (n_vertices != count) { set_err(ctx, "rpt_download_mesh_vertices: mesh %u: n_vertices %u != the uploaded mesh's %u", mesh, n_vertices, count); return RPT_ERR_INVALID_ARG; }
+    if (count == 0) return RPT_OK;
+    if (!vertices) { set_err(ctx, "rpt_download_mesh_vertices: vertices is NULL"); return RPT_ERR_INVALID_ARG; }
+    const DevState& d = ctx->devs[0];
+    if (!d.refit) {                                                 // no update yet: the upload's positions, still on the host
+        memcpy(vertices, &plan.vertices[3 * (size_t)first], 12 * (size_t)count);
+        return RPT_OK;
+    }
+    RPT_ON_DEVICE(ctx);
+    const rpthost::RefitLayout lay(plan.n_vertices(), 0, 0);        // (the vertices come first whatever follows them)
+    RPT_HIP_CHECK(ctx, hipMemcpy(vertices, static_cast<const unsigned char*>(d.refit) + lay.off_vertices + 12 * (size_t)first, 12 * (size_t)count, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
@@ -1693,6 +1889,15 @@ int rpt_debug_mesh_stats(rpt_ctx* ctx, uint32_t* n_nodes, uint32_t* depth, float
     if (!ctx || !n_nodes || !depth || !build_ms) { set_err(ctx, "rpt_debug_mesh_stats: invalid argument"); return RPT_ERR_INVALID_ARG; }
     if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_stats: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
     *n_nodes = ctx->scene.mesh_nodes; *depth = ctx->scene.mesh_depth; *build_ms = ctx->scene.mesh_build_ms;
+    return RPT_OK;
+}
+
+int rpt_debug_mesh_walk(rpt_ctx* ctx, uint32_t* walk)
+{
+    if (!ctx || !walk) { set_err(ctx, "rpt_debug_mesh_walk: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_walk: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    *walk = 0u;
+    for (const DevState& d : ctx->devs) *walk += d.scene.use_bvh ? 1u : 0u;
     return RPT_OK;
 }
 

@@ -44,6 +44,14 @@ pub struct RptMesh {
     pub n_triangles: u32, pub indices: *const u32,
     pub material: u32,
 }
+// rpt_update_meshes_device (include/rpt.h, "moving meshes from device memory"): one mesh's new positions in DEVICE memory and an
+// optional 3x4 transform (12 floats in host memory; null: the positions as they are)
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct RptMeshSource {
+    pub mesh: u32, pub n_vertices: u32,
+    pub vertices_dev: *const f32,
+    pub transform: *const f32,
+}
 // rpt_update_meshes (include/rpt.h, "moving meshes"): one mesh's new vertex positions
 #[repr(C)] #[derive(Clone, Copy)]
 pub struct RptMeshVertices {
@@ -134,6 +142,9 @@ extern "C" {
     #[allow(dead_code)]
     fn rpt_update_meshes(ctx: *mut RptCtx, updates: *const RptMeshVertices, n_updates: u32) -> c_int;
     fn rpt_rebuild_meshes(ctx: *mut RptCtx, updates: *const RptMeshVertices, n_updates: u32) -> c_int;
+    fn rpt_update_meshes_device(ctx: *mut RptCtx, sources: *const RptMeshSource, n_sources: u32) -> c_int;
+    fn rpt_rebuild_meshes_device(ctx: *mut RptCtx, sources: *const RptMeshSource, n_sources: u32) -> c_int;
+    fn rpt_download_mesh_vertices(ctx: *mut RptCtx, mesh: u32, vertices: *mut f32, n_vertices: u32) -> c_int;
     fn rpt_scene_analytical(out: *mut RptSceneDesc) -> c_int;
     fn rpt_render(ctx: *mut RptCtx, pixels: *mut f32, width: u32, height: u32,
                   frames_done: u64, spp: u32, seed: u64, flags: u32) -> c_int;
@@ -463,6 +474,22 @@ impl GpuTracer {
     /// hierarchy"): the frames of a fresh upload of the moved scene.  The pointers are read during the call only.
     pub fn rebuild_meshes(&mut self, updates: &[RptMeshVertices]) -> Result<(), RptError> {
         self.check(unsafe { rpt_rebuild_meshes(self.ctx, updates.as_ptr(), updates.len() as u32) })
+    }
+
+    /// New positions for the named meshes from DEVICE memory, each through its optional transform, and a refit of the hierarchy
+    /// (include/rpt.h, "moving meshes from device memory").  Blocks; the sources are consumed when it returns.
+    pub fn update_meshes_device(&mut self, sources: &[RptMeshSource]) -> Result<(), RptError> {
+        self.check(unsafe { rpt_update_meshes_device(self.ctx, sources.as_ptr(), sources.len() as u32) })
+    }
+
+    /// ... and a new hierarchy over every triangle (none: a rebuild over the positions the context holds).
+    pub fn rebuild_meshes_device(&mut self, sources: &[RptMeshSource]) -> Result<(), RptError> {
+        self.check(unsafe { rpt_rebuild_meshes_device(self.ctx, sources.as_ptr(), sources.len() as u32) })
+    }
+
+    /// The positions the context holds for mesh `mesh`: `vertices.len()` must be three times its vertex count.
+    pub fn download_mesh_vertices(&mut self, mesh: u32, vertices: &mut [f32]) -> Result<(), RptError> {
+        self.check(unsafe { rpt_download_mesh_vertices(self.ctx, mesh, vertices.as_mut_ptr(), (vertices.len() / 3) as u32) })
     }
 
     /// Continue a host ColorBuffer (pixels + frames) in the resident buffer.

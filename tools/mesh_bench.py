@@ -14,7 +14,13 @@ ORIGINAL scene's hierarchy); the resident render rate after each of the three; t
 rebuild apart (it allocates); and the rates of the unmoved scene, rebuilt and uploaded.  RPT_BUILD_LEAF (csrc/knobs.h) sets the
 leaf target of the run.
 
-    python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild]
+--device: one JSON line more, for rpt_update_meshes_device / rpt_rebuild_meshes_device (include/rpt.h, "moving meshes from device
+memory").  For the same three moves, alternating, `--reps` times each (at least 5) in one process, one context per column: the wall
+time of update_meshes and rebuild_meshes from host arrays (unchanged code: the yardsticks, to be compared with the figures
+include/rpt.h records for them); of the two device forms without a transform on the same positions held in CUDA tensors; of the two
+device forms moving the torus alone, rigidly, from a rest tensor by a matrix; and each device form's first call apart (it allocates).
+
+    python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild] [--device]
 """
 import argparse
 import ctypes as C
@@ -35,6 +41,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--update", action="store_true")
     ap.add_argument("--rebuild", action="store_true")
+    ap.add_argument("--device", action="store_true")
     a = ap.parse_args()
     os.environ.setdefault("RPT_LIB", os.path.join(ROOT, "rust-pathtracer_amd", "librpt_hip_test.so"))     # (the product has no hooks)
     import __graft_entry__
@@ -58,6 +65,7 @@ def main():
         rates.append(a.width * a.height * a.spp / (ms * 1e-3) / 1e9)
     update = measure_updates(pkg, t, s, a) if a.update else None
     rebuild = measure_rebuilds(pkg, s, a) if a.rebuild else None
+    device = measure_device_sources(pkg, s, a) if a.device else None
     t.close()
     print(json.dumps({"workload": "mesh_scene %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "triangles": n_tris,
                       "gsamples_per_s_median": sorted(rates)[len(rates) // 2], "gsamples_per_s": rates,
@@ -66,6 +74,8 @@ def main():
         print(json.dumps(update))
     if rebuild:
         print(json.dumps(rebuild))
+    if device:
+        print(json.dumps(device))
 
 
 def measure_updates(pkg, t, s, a):
@@ -191,6 +201,67 @@ def measure_rebuilds(pkg, s, a):
                      "gsamples_per_s_after_rebuild": rr, "gsamples_per_s_after_upload": rf, "gsamples_per_s_after_update": ru,
                      "rebuild_over_upload_rate": rr["median"] / rf["median"], "rebuild_over_update_rate": rr["median"] / ru["median"],
                      "rebuilt_nodes": shape[name][0], "rebuilt_depth": shape[name][1]}
+    return out
+
+
+def measure_device_sources(pkg, s, a):
+    """-> the --device line.  Six contexts of this process over the same scene, one per column, so that every column's calls follow
+    calls of its own kind; within a repetition the columns alternate."""
+    import numpy as np
+    import torch
+    from rust_pathtracer_amd import scenes
+    original = [np.array(v, np.float32, copy=True) for v, _, _ in s.meshes]
+
+    def stats(xs):
+        xs = sorted(xs)
+        return {"median": xs[len(xs) // 2], "min": xs[0], "max": xs[-1]}
+
+    def timed(call, arg):
+        t0 = time.perf_counter()
+        call(arg)
+        return (time.perf_counter() - t0) * 1e3
+
+    phases = (("small", 0.05), ("medium", 0.5), ("large", 2.0))
+    moved = {name: scenes.mesh_scene_moved(s, phase) for name, phase in phases}
+    on_device = {name: [torch.from_numpy(np.ascontiguousarray(v, np.float32)).to("cuda:0") for v in moved[name]] for name, _ in phases}
+    rest = torch.from_numpy(original[1]).to("cuda:0")               # the torus's rest pose, and a turn about its own axis per move
+    centre = 0.5 * (original[1].min(0) + original[1].max(0)).astype(np.float64)
+    matrix = {}
+    for name, phase in phases:
+        c, si = np.cos(phase), np.sin(phase)
+        rot = np.array([[c, -si, 0.0], [si, c, 0.0], [0.0, 0.0, 1.0]])
+        matrix[name] = np.concatenate([rot, (centre - rot @ centre)[:, None]], axis=1).astype(np.float32)
+    torch.cuda.synchronize()
+    columns = ("update_host", "rebuild_host", "update_device", "rebuild_device", "update_device_rigid", "rebuild_device_rigid")
+    ctx = {c: pkg.Tracer(scenes.mesh_scene(), device=0, seed=1) for c in columns}
+    first = {"update_host": timed(ctx["update_host"].update_meshes, dict(enumerate(original))),
+             "rebuild_host": timed(ctx["rebuild_host"].rebuild_meshes, dict(enumerate(original))),
+             "update_device": timed(ctx["update_device"].update_meshes_device, dict(enumerate(on_device["small"]))),
+             "rebuild_device": timed(ctx["rebuild_device"].rebuild_meshes_device, dict(enumerate(on_device["small"]))),
+             "update_device_rigid": timed(ctx["update_device_rigid"].update_meshes_device, {1: (rest, matrix["small"])}),
+             "rebuild_device_rigid": timed(ctx["rebuild_device_rigid"].rebuild_meshes_device, {1: (rest, matrix["small"])})}
+    res = {name: {c: [] for c in columns} for name, _ in phases}
+    reps = max(5, a.reps)
+    for _ in range(reps):
+        for name, _ in phases:
+            r = res[name]
+            r["update_host"].append(timed(ctx["update_host"].update_meshes, dict(enumerate(moved[name]))))
+            r["update_device"].append(timed(ctx["update_device"].update_meshes_device, dict(enumerate(on_device[name]))))
+            r["update_device_rigid"].append(timed(ctx["update_device_rigid"].update_meshes_device, {1: (rest, matrix[name])}))
+            r["rebuild_host"].append(timed(ctx["rebuild_host"].rebuild_meshes, dict(enumerate(moved[name]))))
+            r["rebuild_device"].append(timed(ctx["rebuild_device"].rebuild_meshes_device, dict(enumerate(on_device[name]))))
+            r["rebuild_device_rigid"].append(timed(ctx["rebuild_device_rigid"].rebuild_meshes_device, {1: (rest, matrix[name])}))
+    # the device forms hold what the host forms hold (the timing ran the same moves)
+    same = all(np.array_equal(ctx["update_host"].mesh_vertices(m).view(np.uint32), ctx["update_device"].mesh_vertices(m).view(np.uint32)) and
+               np.array_equal(ctx["rebuild_host"].mesh_vertices(m).view(np.uint32), ctx["rebuild_device"].mesh_vertices(m).view(np.uint32))
+               for m in range(len(original)))
+    for tr in ctx.values():
+        tr.close()
+    out = {"workload": "mesh_scene device sources, %d vertices" % sum(len(v) for v in original), "reps": reps,
+           "first_call_ms": first, "device_forms_hold_the_host_forms_positions": bool(same)}
+    for name, phase in phases:
+        out[name] = {"phase": phase}
+        out[name].update({c + "_ms": stats(res[name][c]) for c in columns})
     return out
 
 
