@@ -582,6 +582,80 @@ int rpt_update_meshes_device(rpt_ctx* ctx, const rpt_mesh_source* sources, uint3
 int rpt_rebuild_meshes_device(rpt_ctx* ctx, const rpt_mesh_source* sources, uint32_t n_sources);
 int rpt_download_mesh_vertices(rpt_ctx* ctx, uint32_t mesh, float* vertices /* host */, uint32_t n_vertices);
 
+/* ---- smooth mesh shading — PROJECT-DEFINED --------------------------------------------------------------------------------------
+ * Per mesh, a winning triangle is shaded with the interpolated normals of its three vertices instead of normalize(cross(e1, e2)).
+ * The library computes the vertex normals on the device from the f32 positions the context holds, and computes them again inside
+ * every call that moves a mesh; nothing crosses the host.  Every operation order is stated, so that normals and frames stay
+ * checkable bit for bit (tests/test_gpu_mesh_smooth.py holds both to a numpy float32 restatement).  dot, cross and F::MAX are those
+ * of "triangle meshes"; the square root and the divides are the library's correctly rounded ones.
+ *
+ * Vertex normals of a SMOOTH mesh.  Let the mesh's triangles be k = 0, 1, ... in the mesh's own order, (a, b, c) the positions of
+ * triangle k's corners.
+ *     face vector      g_k = cross(b - a, c - a)      (the e1, e2 and cross of the triangle test; not normalised: area-weighted)
+ *     vertex vector    s_j = the sum of g_k over the triangles that name vertex j at one or more corners, each such triangle
+ *                      counted ONCE, in ascending k; per component, f32, left to right, starting with the first term.
+ *                      No triangle names j: s_j = (0, 0, 0).
+ *     l2 = dot(s_j, s_j);  !(l2 > 0 && l2 <= F::MAX)  ->  n_j = (0, 0, 0)     (also a NaN from overflowing edges)
+ *     otherwise        n_j = s_j / sqrt(l2), per component: one root, three divides (the reference's normalize)
+ * The order is by triangle index within the mesh, never by slot of the hierarchy: rpt_rebuild_meshes reorders slots and leaves
+ * every normal bit for bit where it was.
+ *
+ * Normal of a winning triangle of a SMOOTH mesh.  u and v are the values the triangle test computed for this ray and triangle
+ * (the library recomputes them from the unchanged ray and row: the same operations, the same bits); na, nb, nc the vertex
+ * normals of its corners a, b, c.
+ *     w = (1 - u) - v
+ *     m.i = (w * na.i + u * nb.i) + v * nc.i          i = x, y, z
+ *     l2 = dot(m, m);  !(l2 > 0 && l2 <= F::MAX)  ->  the flat normal normalize(cross(e1, e2))
+ *     otherwise        m / sqrt(l2): one root, three divides
+ * Like the flat normal it is NOT turned toward the ray, and everything downstream treats it as today's normal: ffnormal, eta's
+ * side, the offset of the next-event ray.  The known cost of that choice: near silhouettes and near the terminator an
+ * interpolated normal can face away from the ray that hit the front of its triangle, or lean over a neighbouring facet — the
+ * hit is then shaded from the other side, or a shadow ray starts below the neighbour.  The library does not bend the normal.
+ * Triangle test, acceptance order, any_hit and materials are unchanged.
+ *
+ * rpt_set_mesh_shading sets the mode of the named meshes of the uploaded scene, before or after any number of moves or rebuilds;
+ * meshes not named keep theirs, and rpt_upload_scene leaves every mesh RPT_MESH_SHADING_FLAT.  On return every SMOOTH mesh's
+ * normals are current on every device of the context (rpt_create_multi: all of them; one process per GPU: every rank makes the
+ * call itself, as for rpt_update_meshes).  A mesh without triangles may be named.  The checks, in this order, all on the host
+ * before any device is touched — a rejected call changes nothing, and rpt_last_error names the item:
+ *   RPT_ERR_INVALID_ARG  ctx is NULL;
+ *   RPT_ERR_NO_SCENE     no scene with meshes is uploaded;
+ *   RPT_ERR_UNSUPPORTED  the scene's meshes hold 2^32 vertices or more;
+ *   RPT_ERR_INVALID_ARG  items NULL with a non-zero count; then per item: mesh >= n_meshes, a mesh named twice, a mode that is
+ *                        neither constant;
+ *   RPT_OK               n_items == 0: nothing is done;
+ *   RPT_ERR_HIP          a runtime call failed part-way: the context is left with NO scene, as for rpt_update_meshes.
+ * While some mesh is SMOOTH the scene renders through a kernel of its own (the mesh kernel's body with the normal above); when
+ * the last SMOOTH mesh goes back to FLAT the context renders exactly as if the call had never been made — the same kernel, the
+ * same tables.  A scene on which the call was never made is untouched by all of this.
+ *
+ * Moves.  rpt_update_meshes, rpt_rebuild_meshes and both _device forms recompute the normals of every SMOOTH mesh on the device
+ * before they return RPT_OK (two more kernel launches per device, whatever the number of meshes); a rejected move leaves them as
+ * they were.
+ *
+ * rpt_download_mesh_normals copies the normals the context holds for one SMOOTH mesh — all its vertices, xyz — to host memory from
+ * its first device.  It takes rpt_download_mesh_vertices' arguments and gives its answers; a FLAT mesh answers
+ * RPT_ERR_INVALID_ARG and says so.  It never changes anything.
+ *
+ * Memory.  The call brings the refit's tables to every device as the context's first rpt_update_meshes does (and reads the
+ * triangles' corners back from the first device once per call: 60 B per triangle over the link; the call is rare).  While a mesh
+ * is SMOOTH every device holds, until the last mesh is FLAT again or the next rpt_upload_scene: 20 B per vertex of the SCENE
+ * (a 16-byte normal and a 4-byte list offset), per triangle of the SMOOTH meshes 28 B (its face vector, 16 B, and its corners,
+ * 12 B) + 4 B per distinct corner (the vertices' lists: 12 B for a proper triangle), and one bit per triangle of the scene.
+ *
+ * Timings: not measured yet.  tools/mesh_bench.py --smooth alternates, in one process, flat and smooth frames of
+ * scenes.mesh_scene and the four move calls with both meshes smooth against flat.  What the normals add to a move is two
+ * launches per device over the tables above (scenes.mesh_scene: about 25 MB read and written). */
+enum { RPT_MESH_SHADING_FLAT = 0, RPT_MESH_SHADING_SMOOTH = 1 };
+
+typedef struct rpt_mesh_shading {
+    uint32_t mesh;                    /* index into the uploaded scene's rpt_scene_desc.meshes */
+    uint32_t mode;                    /* RPT_MESH_SHADING_FLAT or RPT_MESH_SHADING_SMOOTH */
+} rpt_mesh_shading;
+
+int rpt_set_mesh_shading(rpt_ctx* ctx, const rpt_mesh_shading* items, uint32_t n_items);
+int rpt_download_mesh_normals(rpt_ctx* ctx, uint32_t mesh, float* normals /* host, xyz per vertex */, uint32_t n_vertices);
+
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)
  *   frames_done ColorBuffer.frames before the call; the caller adds `spp` afterwards

@@ -224,6 +224,17 @@ public:
         check(rpt_download_mesh_vertices(ctx_, mesh, out.data(), n_vertices), ctx_);
         return out;
     }
+    /// Per-mesh shading (rpt.h, "smooth mesh shading"): RPT_MESH_SHADING_SMOOTH interpolates vertex normals the library computes
+    /// on the device and keeps current through every call above; sync_scene() leaves every mesh flat again.
+    void set_mesh_shading(const std::vector<rpt_mesh_shading>& items) {
+        check(rpt_set_mesh_shading(ctx_, items.data(), (uint32_t)items.size()), ctx_);
+    }
+    /// The vertex normals the context holds for one SMOOTH mesh (xyz per vertex).
+    std::vector<float> mesh_normals(uint32_t mesh, uint32_t n_vertices) {
+        std::vector<float> out(3 * (size_t)n_vertices);
+        check(rpt_download_mesh_normals(ctx_, mesh, out.data(), n_vertices), ctx_);
+        return out;
+    }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

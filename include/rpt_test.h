@@ -59,6 +59,12 @@ int rpt_probe_rays(rpt_ctx* ctx, const float* rays_dev, uint32_t* out_dev, uint6
 enum { RPT_MESH_QUERY_USE_MAX = 1u << 0, RPT_MESH_QUERY_BRUTE = 1u << 1 };
 int rpt_debug_mesh_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
 
+/* The normal a winning triangle is shaded with (include/rpt.h, "smooth mesh shading"), through the hit_normal the smooth scenes' render
+ * kernel calls: rays_dev as for rpt_debug_mesh_query (max_dist is not read); out_dev = n x 4 dwords {the nearest triangle's flattened
+ * index or 0xFFFFFFFF, the normal's three words (zeros when nothing is hit)}.  `flags`: RPT_MESH_QUERY_BRUTE or 0.
+ * RPT_ERR_NO_SCENE unless the uploaded scene has meshes; RPT_ERR_INVALID_ARG while no mesh is SMOOTH (that kernel does not run then). */
+int rpt_debug_mesh_normal_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
+
 /* The uploaded mesh scene's hierarchy (csrc/host_bvh.h): its interior nodes, the depth of its deepest leaf, and the host time its build
  * took in rpt_upload_scene — after rpt_rebuild_meshes the rebuilt hierarchy's, and the wall time of that call's device part.
  * RPT_ERR_NO_SCENE unless the uploaded scene has meshes.  (tools/mesh_bench.py) */
@@ -93,7 +99,7 @@ int rpt_debug_sched_read(rpt_ctx* ctx, uint32_t* out, uint32_t capacity_tiles, u
  * bit 3 the table by class of accepted set (5-12 primitives), bits 8-15 the number of classes then, bits 16-19 the SDF object's
  * compile-time primitive count, bit 20 the relaxed-arithmetic build (RPT_RENDER_FAST_MATH), bit 21 small scenes' compacting kernel
  * (else the class's megakernel), bit 22 its dense form (at most 3 072 workgroups), bit 23 the nested-loop kernel, bit 24 the class's
- * participating-media form (the scene has media: RPT_SCENE_MEDIA), bit 25 the mesh scene class's kernel (k_mesh.hip).  For tests that must know that the kernel they aim at is the one
+ * participating-media form (the scene has media: RPT_SCENE_MEDIA), bit 25 the mesh scene class's kernel (k_mesh.hip), bit 26 beside it its smooth-shading form (k_smooth.hip: some mesh is SMOOTH).  For tests that must know that the kernel they aim at is the one
  * that ran. */
 int rpt_debug_kernel_choice(rpt_ctx* ctx, uint32_t* out);
 

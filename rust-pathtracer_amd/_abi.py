@@ -126,6 +126,13 @@ class rpt_mesh_source(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("n_vertices", C.c_uint32), ("vertices_dev", C.c_void_p), ("transform", C.POINTER(C.c_float))]
 
 
+RPT_MESH_SHADING_FLAT, RPT_MESH_SHADING_SMOOTH = 0, 1
+
+
+class rpt_mesh_shading(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("mode", C.c_uint32)]
+
+
 class rpt_scene_desc(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("flags", C.c_uint32),
@@ -176,6 +183,8 @@ SYMBOLS = {
     "rpt_update_meshes_device": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_source), C.c_uint32]),
     "rpt_rebuild_meshes_device": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_source), C.c_uint32]),
     "rpt_download_mesh_vertices": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "rpt_set_mesh_shading": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_shading), C.c_uint32]),
+    "rpt_download_mesh_normals": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "rpt_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -209,6 +218,7 @@ TEST_SYMBOLS = {
     "rpt_debug_kernel_choice": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rpt_probe_math": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rpt_debug_mesh_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rpt_debug_mesh_normal_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rpt_debug_mesh_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "rpt_debug_mesh_walk": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rpt_debug_mesh_tables": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

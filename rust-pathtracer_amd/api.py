@@ -455,6 +455,27 @@ class Tracer:
         check(lib().rpt_download_mesh_vertices(self._h, int(m), out.ctypes.data, n), self._h)
         return out
 
+    def set_mesh_shading(self, modes):
+        """Per-mesh shading (include/rpt.h, "smooth mesh shading"): `modes` maps a mesh's index in scene().meshes to "smooth" —
+        interpolated vertex normals, which the library computes on the device and keeps current through every call that moves
+        the mesh — or "flat".  Meshes not named keep their mode; upload_scene() leaves every mesh flat again, as in C."""
+        names = {"flat": _abi.RPT_MESH_SHADING_FLAT, "smooth": _abi.RPT_MESH_SHADING_SMOOTH}
+        items = sorted(modes.items())
+        its = (_abi.rpt_mesh_shading * max(1, len(items)))()
+        for it, (m, mode) in zip(its, items):
+            if mode not in names:
+                raise ValueError("mesh %d: the mode must be \"smooth\" or \"flat\", not %r" % (m, mode))
+            it.mesh, it.mode = int(m), names[mode]
+        self._checked_move(lib().rpt_set_mesh_shading(self._h, its, len(items)))
+
+    def mesh_normals(self, m):
+        """The vertex normals the context holds for the smooth mesh `m` (rpt_download_mesh_normals): a new float32 array of shape
+        (n_vertices, 3)."""
+        n = np.asarray(self._scene.meshes[m][0]).reshape(-1, 3).shape[0]
+        out = np.empty((n, 3), np.float32)
+        check(lib().rpt_download_mesh_normals(self._h, int(m), out.ctypes.data, n), self._h)
+        return out
+
     def _refresh_stale_meshes(self):
         """scene().meshes' vertex arrays that a device-source call left stale, read back once (only before an upload)."""
         for m in sorted(self._stale_meshes):

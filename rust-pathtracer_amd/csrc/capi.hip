@@ -22,11 +22,13 @@
 #include "host_build.h"
 #include "host_move.h"
 #include "host_refit.h"
+#include "host_smooth.h"
 #include "host_upload.h"
 #include "knobs.h"
 #include "launch.h"
 #include "launch_build.h"
 #include "launch_move.h"
+#include "launch_smooth.h"
 #ifdef RPT_TEST_HOOKS
 #include "../../include/rpt_test.h"
 #endif
@@ -53,6 +55,7 @@ struct DevState {
     void* move = nullptr;             // the device-source calls' check tables (host_move.h, MoveLayout): on the context's first device, from its
                                       // first rpt_update_meshes_device / rpt_rebuild_meshes_device to the next upload
     void* move_stage = nullptr;       // ... and copies of sources that lie on another device (12 B per vertex of the scene), made on demand
+    void* smooth = nullptr;           // smooth shading's tables (host_smooth.h, SmoothLayout): while some mesh is SMOOTH (rpt_set_mesh_shading)
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -97,6 +100,7 @@ struct rpt_ctx {
     uint32_t dispatch[4] = {0xFFFFFFFFu, 0, 0, 0};   // rpt_set_dispatch: cost_order (0xFFFFFFFF: the environment's defaults), unit_rounds, unit_min_spp, unit_slots
     rpthost::SceneState scene;        // its class, camera, small scenes' kernel argument (host_upload.h); every device's tables: DevState
     rpthost::RefitPlan refit;         // a mesh scene's plan for rpt_update_meshes (host_refit.h)
+    rpthost::SmoothPlan smooth;       // its meshes' shading modes and the sizes of every device's smooth tables (host_smooth.h)
     // resident ColorBuffer (buffer.rs:6-14): pixels as per-rank tiles + frames
     uint32_t res_w = 0, res_h = 0, res_tile_rows = 0, res_rows_padded = 0;
     uint64_t res_frames = 0;
@@ -278,6 +282,7 @@ static void free_mesh_work(DevState& d)
     if (d.build_nodes) { (void)hipFree(d.build_nodes); d.build_nodes = nullptr; }
     if (d.move) { (void)hipFree(d.move); d.move = nullptr; }
     if (d.move_stage) { (void)hipFree(d.move_stage); d.move_stage = nullptr; }
+    if (d.smooth) { (void)hipFree(d.smooth); d.smooth = nullptr; }
     d.refit_full = false;
     d.build_temp_bytes = 0;
 }
@@ -427,6 +432,22 @@ static int sched_for(rpt_ctx* ctx, DevState& d, uint32_t nblocks, uint32_t width
     return RPT_OK;
 }
 
+// A mesh scene's kernel argument while some mesh is SMOOTH: device d's scene plus pointers into its refit and smooth tables.
+static SceneMeshSmooth smooth_scene_of(const rpt_ctx* ctx, const DevState& d)
+{
+    const rpthost::SmoothPlan& sp = ctx->smooth;
+    const rpthost::RefitLayout rl(ctx->refit.n_vertices(), 0, 0);   // (the vertices and slot_vertex come first whatever follows them)
+    const rpthost::SmoothLayout sl(sp.n_vertices, sp.n_tris, sp.n_faces, sp.n_adj);
+    const unsigned char* refit = static_cast<const unsigned char*>(d.refit);
+    const unsigned char* base = static_cast<const unsigned char*>(d.smooth);
+    SceneMeshSmooth s{};
+    static_cast<SceneMesh&>(s) = d.scene;
+    s.slot_vertex = reinterpret_cast<const uint32_t*>(refit + rl.off_slot_vertex);
+    s.vnormals = reinterpret_cast<const float4*>(base + sl.off_normals);
+    s.smooth_bits = reinterpret_cast<const uint32_t*>(base + sl.off_bits);
+    return s;
+}
+
 // One render launch sequence on one device.
 static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t width, uint32_t height, uint64_t frames_done, uint32_t spp,
                          uint64_t seed, uint32_t flags, uint32_t tile_rows, uint32_t rank, uint32_t world, hipStream_t stream)
@@ -441,6 +462,7 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     SceneSmallSdf scs = ctx->scene.small;
     SceneLarge scl = d.scene;
     SceneMesh scm = d.scene;
+    const bool smooth = kind == SceneKind::mesh && d.smooth && d.refit && ctx->smooth.any();      // some mesh is SMOOTH: k_smooth.hip's form
     scs.cam = scl.cam = scm.cam = make_camera(ctx->scene.camera, (float)width, (float)height);
     const bool in_hbm = kind == SceneKind::large || kind == SceneKind::mesh;     // the scene's tables are in device memory
     const bool has_sdf = !in_hbm && scs.sdf.n_prims > 0;
@@ -501,9 +523,15 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
                         ((kc.material_table_mapped ? kc.class_map.n_classes : 0u) << 8) | (kc.sized_sdf << 16) |
                         (fast ? 1u << 20 : 0u) | (rp.compact && !nested ? 1u << 21 : 0u) |
                         (rp.compact && !nested && nblocks <= kCompactDenseMaxBlocks ? 1u << 22 : 0u) | (nested ? 1u << 23 : 0u) |
-                        (media ? 1u << 24 : 0u) | (kind == SceneKind::mesh ? 1u << 25 : 0u);
+                        (media ? 1u << 24 : 0u) | (kind == SceneKind::mesh ? 1u << 25 : 0u) |
+                        (smooth ? 1u << 26 : 0u);
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
+        if (smooth) {
+            SceneMeshSmooth sms = smooth_scene_of(ctx, d);
+            static_cast<SceneMesh&>(sms) = scm;
+            return rptlaunch::render_mesh_smooth(sms, rp, grid, stream);
+        }
         if (kind == SceneKind::mesh) return rptlaunch::render_mesh(scm, rp, grid, stream);
         if (kind == SceneKind::large) return fast ? rptlaunch_fast::render_large(scl, false, rp, grid, stream) : rptlaunch::render_large(scl, media, rp, grid, stream);
         if (has_sdf) return fast ? rptlaunch_fast::render_sdf(scs, false, rp, grid, stream, kc) : rptlaunch::render_sdf(scs, media, rp, grid, stream, kc);
@@ -880,6 +908,7 @@ static void commit_scene(rpt_ctx* ctx, SceneImage& img, const std::vector<void*>
     }
     ctx->scene = img.state;
     ctx->refit = std::move(img.refit);
+    ctx->smooth = rpthost::SmoothPlan();                            // every mesh FLAT
 }
 
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
@@ -908,6 +937,7 @@ static void drop_scene(rpt_ctx* ctx)
     }
     ctx->scene = rpthost::SceneState();
     ctx->refit = rpthost::RefitPlan();
+    ctx->smooth = rpthost::SmoothPlan();
 }
 
 // Where the named meshes' new positions come from: host arrays (rpt_update_meshes, rpt_rebuild_meshes) or device arrays through a
@@ -956,19 +986,43 @@ static int put_positions(rpt_ctx* ctx, DevState& d, const MeshPositions& pos, un
 // One device's part of an update: wait for its earlier work, make its refit tables if this is the context's first update, copy the
 // named meshes' vertices in, refit every triangle row and slot box, then the nodes level by level, deepest first (kernel boundaries
 // on one stream order the levels), and wait.
+// Device d's refit tables, if it has none yet (no update, rebuild or rpt_set_mesh_shading since the upload): the plan's staging, on
+// d's stream.  What the context's first update does, and rpt_set_mesh_shading before it: shading reads the positions and slot_vertex.
+static int ensure_refit(rpt_ctx* ctx, DevState& d)
+{
+    if (d.refit) return RPT_OK;
+    const rpthost::RefitPlan& plan = ctx->refit;
+    const rpthost::RefitLayout lay(plan.n_vertices(), plan.n_slots, plan.n_nodes);
+    RPT_HIP_CHECK(ctx, hipMalloc(&d.refit, lay.total));
+    unsigned char* base = static_cast<unsigned char*>(d.refit);
+    if (!plan.vertices.empty()) RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_vertices, plan.vertices.data(), sizeof(float) * plan.vertices.size(), hipMemcpyHostToDevice, d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_slot_vertex, plan.slot_vertex.data(), sizeof(uint32_t) * plan.slot_vertex.size(), hipMemcpyHostToDevice, d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_level_nodes, plan.level_nodes.data(), sizeof(uint32_t) * plan.level_nodes.size(), hipMemcpyHostToDevice, d.stream));
+    return RPT_OK;
+}
+
+// The normals of every SMOOTH mesh from the positions device d holds, on d's stream (k_smooth.hip: one launch pair); nothing while
+// every mesh is FLAT.  The last device work of every call that moves a mesh, and of rpt_set_mesh_shading.
+static int smooth_normals_device(rpt_ctx* ctx, DevState& d)
+{
+    if (!d.smooth) return RPT_OK;
+    const rpthost::SmoothPlan& sp = ctx->smooth;
+    const rpthost::SmoothLayout sl(sp.n_vertices, sp.n_tris, sp.n_faces, sp.n_adj);
+    unsigned char* base = static_cast<unsigned char*>(d.smooth);
+    RPT_HIP_CHECK(ctx, rptlaunch::smooth_normals(static_cast<const float*>(d.refit), reinterpret_cast<const uint32_t*>(base + sl.off_face_vertex),
+                                                 reinterpret_cast<float4*>(base + sl.off_face), sp.n_faces, reinterpret_cast<const uint32_t*>(base + sl.off_adj_first),
+                                                 reinterpret_cast<const uint32_t*>(base + sl.off_adj), reinterpret_cast<float4*>(base + sl.off_normals), sp.n_vertices,
+                                                 d.stream));
+    return RPT_OK;
+}
+
 static int update_device(rpt_ctx* ctx, DevState& d, const MeshPositions& pos)
 {
     const rpthost::RefitPlan& plan = ctx->refit;
     const rpthost::RefitLayout lay(plan.n_vertices(), plan.n_slots, plan.n_nodes);
     RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    RPT_CHECK_RC(ensure_refit(ctx, d));
     unsigned char* base = static_cast<unsigned char*>(d.refit);
-    if (!base) {
-        RPT_HIP_CHECK(ctx, hipMalloc(&d.refit, lay.total));
-        base = static_cast<unsigned char*>(d.refit);
-        if (!plan.vertices.empty()) RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_vertices, plan.vertices.data(), sizeof(float) * plan.vertices.size(), hipMemcpyHostToDevice, d.stream));
-        RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_slot_vertex, plan.slot_vertex.data(), sizeof(uint32_t) * plan.slot_vertex.size(), hipMemcpyHostToDevice, d.stream));
-        RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + lay.off_level_nodes, plan.level_nodes.data(), sizeof(uint32_t) * plan.level_nodes.size(), hipMemcpyHostToDevice, d.stream));
-    }
     RPT_CHECK_RC(put_positions(ctx, d, pos, base + lay.off_vertices));
     float4* tris = const_cast<float4*>(d.scene.tris);
     float4* nodes = const_cast<float4*>(d.scene.nodes);
@@ -978,6 +1032,7 @@ static int update_device(rpt_ctx* ctx, DevState& d, const MeshPositions& pos)
                                                   tris, reinterpret_cast<float*>(base + lay.off_slot_box), plan.n_slots, d.stream));
     for (uint32_t level = plan.n_levels(); level-- > 0;)
         RPT_HIP_CHECK(ctx, rptlaunch::refit_nodes(nodes, slot_box, level_nodes + plan.level_first[level], plan.level_first[level + 1u] - plan.level_first[level], d.stream));
+    RPT_CHECK_RC(smooth_normals_device(ctx, d));
     RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
     return RPT_OK;
 }
@@ -1104,6 +1159,7 @@ static int rebuild_device(rpt_ctx* ctx, DevState& d, const MeshPositions& pos, u
     }
     for (uint32_t level = n_levels; level-- > 0;)
         RPT_HIP_CHECK(ctx, rptlaunch::refit_nodes(t.nodes, t.slot_box, t.level_nodes + levels[level], levels[kBuildLevelCount + level], d.stream));
+    RPT_CHECK_RC(smooth_normals_device(ctx, d));
     RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
     d.scene.nodes = t.nodes;
     return RPT_OK;
@@ -1313,6 +1369,127 @@ int rpt_download_mesh_vertices(rpt_ctx* ctx, uint32_t mesh, float* vertices, uin
     RPT_ON_DEVICE(ctx);
     const rpthost::RefitLayout lay(plan.n_vertices(), 0, 0);        // (the vertices come first whatever follows them)
     RPT_HIP_CHECK(ctx, hipMemcpy(vertices, static_cast<const unsigned char*>(d.refit) + lay.off_vertices + 12 * (size_t)first, 12 * (size_t)count, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+// ---- rpt_set_mesh_shading / rpt_download_mesh_normals (include/rpt.h, "smooth mesh shading") ---------------------------------------
+// One device's part: wait for its earlier work (a launch may still read the old tables), make its refit tables if it has none, drop
+// the old smooth tables, copy the new ones in, compute the normals, and wait.  ctx->smooth is already the new plan.
+static int shade_device(rpt_ctx* ctx, DevState& d)
+{
+    const rpthost::SmoothPlan& sp = ctx->smooth;
+    const rpthost::SmoothLayout sl(sp.n_vertices, sp.n_tris, sp.n_faces, sp.n_adj);
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    RPT_CHECK_RC(ensure_refit(ctx, d));
+    if (d.smooth) { (void)hipFree(d.smooth); d.smooth = nullptr; }
+    RPT_HIP_CHECK(ctx, hipMalloc(&d.smooth, sl.total));
+    unsigned char* base = static_cast<unsigned char*>(d.smooth);
+    const auto put = [&](size_t off, const std::vector<uint32_t>& v) {
+        return v.empty() ? hipSuccess : hipMemcpyAsync(base + off, v.data(), sizeof(uint32_t) * v.size(), hipMemcpyHostToDevice, d.stream);
+    };
+    RPT_HIP_CHECK(ctx, put(sl.off_face_vertex, sp.face_vertex));
+    RPT_HIP_CHECK(ctx, put(sl.off_adj_first, sp.adj_first));
+    RPT_HIP_CHECK(ctx, put(sl.off_adj, sp.adj));
+    RPT_HIP_CHECK(ctx, put(sl.off_bits, sp.bits));
+    RPT_CHECK_RC(smooth_normals_device(ctx, d));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    return RPT_OK;
+}
+
+// The flattened triangles' corners, read back from the context's first device (the current one): its refit tables' slot_vertex and
+// the rows' index words say which slot holds which triangle, whatever updates and rebuilds have done since the upload.
+static int read_flat_indices(rpt_ctx* ctx, std::vector<uint32_t>& flat)
+{
+    DevState& d = ctx->devs[0];
+    const rpthost::RefitPlan& plan = ctx->refit;
+    const size_t n = plan.n_slots;
+    const rpthost::RefitLayout rl(plan.n_vertices(), 0, 0);
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    RPT_CHECK_RC(ensure_refit(ctx, d));
+    std::vector<unsigned char> rows(48 * n);
+    std::vector<uint32_t> slot_vertex(3 * n);
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(rows.data(), d.scene.tris, rows.size(), hipMemcpyDeviceToHost, d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(slot_vertex.data(), static_cast<const unsigned char*>(d.refit) + rl.off_slot_vertex, 12 * n, hipMemcpyDeviceToHost, d.stream));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    if (!rpthost::smooth_flat_indices(rows.data(), slot_vertex.data(), n, flat)) {
+        set_err(ctx, "rpt_set_mesh_shading: the triangle table of device %d does not name every triangle once", d.device);
+        return RPT_ERR_HIP;
+    }
+    for (uint32_t x : flat)
+        if (x >= plan.n_vertices()) { set_err(ctx, "rpt_set_mesh_shading: device %d's slot_vertex table names a vertex out of range", d.device); return RPT_ERR_HIP; }
+    return RPT_OK;
+}
+
+int rpt_set_mesh_shading(rpt_ctx* ctx, const rpt_mesh_shading* items, uint32_t n_items)
+{
+    using namespace rpthost;
+    if (!ctx) { set_err(nullptr, "rpt_set_mesh_shading: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    std::vector<uint8_t> mode;
+    std::string why;
+    const int rc = check_mesh_shading(ctx->refit, ctx->scene.kind == SceneKind::mesh, items, n_items, ctx->smooth.mode, mode, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    if (n_items == 0) return RPT_OK;
+    SmoothPlan fresh;
+    fresh.mode = mode;
+    DeviceGuard guard(ctx->devs[0].device);
+    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
+    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_shading: cannot select device %d", ctx->devs[0].device);
+    if (rc_dev == RPT_OK && !fresh.any()) {                         // every mesh FLAT (again): the context is what it was before the first call
+        for (DevState& d : ctx->devs) {
+            if (!d.smooth) continue;
+            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
+                set_err(ctx, "rpt_set_mesh_shading: cannot wait for device %d", d.device);
+                rc_dev = RPT_ERR_HIP;
+                break;
+            }
+            (void)hipFree(d.smooth);
+            d.smooth = nullptr;
+        }
+        if (rc_dev == RPT_OK) { ctx->smooth = SmoothPlan(); return RPT_OK; }
+    }
+    if (rc_dev == RPT_OK) {
+        std::vector<uint32_t> flat;
+        rc_dev = read_flat_indices(ctx, flat);
+        if (rc_dev == RPT_OK) {
+            build_smooth_plan(ctx->refit, flat.data(), mode, fresh);
+            ctx->smooth = std::move(fresh);
+        }
+    }
+    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
+        DevState& d = ctx->devs[i];
+        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_shading: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
+        else rc_dev = shade_device(ctx, d);
+    }
+    if (rc_dev != RPT_OK) {
+        const std::string first = ctx->err;
+        drop_scene(ctx);
+        set_err(ctx, "%s; the context now holds no scene", first.c_str());
+        return rc_dev;
+    }
+    ctx->refit.release_staging();                                   // every device holds the refit tables
+    ctx->smooth.release_staging();
+    return RPT_OK;
+}
+
+int rpt_download_mesh_normals(rpt_ctx* ctx, uint32_t mesh, float* normals, uint32_t n_vertices)
+{
+    if (!ctx) { set_err(nullptr, "rpt_download_mesh_normals: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_mesh_normals: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    const rpthost::RefitPlan& plan = ctx->refit;
+    if (!plan.ok) { set_err(ctx, "rpt_download_mesh_normals: the scene's meshes hold 2^32 vertices or more"); return RPT_ERR_UNSUPPORTED; }
+    if (mesh >= plan.n_meshes()) { set_err(ctx, "rpt_download_mesh_normals: mesh %u out of range (the scene has %u)", mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
+    const uint32_t first = plan.mesh_first[mesh], count = plan.mesh_first[mesh + 1u] - first;
+    if (n_vertices != count) { set_err(ctx, "rpt_download_mesh_normals: mesh %u: n_vertices %u != the uploaded mesh's %u", mesh, n_vertices, count); return RPT_ERR_INVALID_ARG; }
+    const DevState& d = ctx->devs[0];
+    if (!ctx->smooth.smooth(mesh) || !d.smooth) { set_err(ctx, "rpt_download_mesh_normals: mesh %u is FLAT: the context holds no normals for it (rpt_set_mesh_shading)", mesh); return RPT_ERR_INVALID_ARG; }
+    if (count == 0) return RPT_OK;
+    if (!normals) { set_err(ctx, "rpt_download_mesh_normals: normals is NULL"); return RPT_ERR_INVALID_ARG; }
+    RPT_ON_DEVICE(ctx);
+    const rpthost::SmoothPlan& sp = ctx->smooth;
+    const rpthost::SmoothLayout sl(sp.n_vertices, sp.n_tris, sp.n_faces, sp.n_adj);
+    std::vector<float> rows(4 * (size_t)count);
+    RPT_HIP_CHECK(ctx, hipMemcpy(rows.data(), static_cast<const unsigned char*>(d.smooth) + sl.off_normals + 16 * (size_t)first, 16 * (size_t)count, hipMemcpyDeviceToHost));
+    for (size_t v = 0; v < count; ++v) memcpy(normals + 3 * v, &rows[4 * v], 12);
     return RPT_OK;
 }
 
@@ -1881,6 +2058,18 @@ int rpt_debug_mesh_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_query(ctx->devs[0].scene, rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_debug_mesh_normal_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_normal_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_normal_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    if (!rays_dev || !out_dev || (flags & ~(uint32_t)RPT_MESH_QUERY_BRUTE)) { set_err(ctx, "rpt_debug_mesh_normal_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->smooth.any() || !ctx->devs[0].smooth) { set_err(ctx, "rpt_debug_mesh_normal_query: no mesh is SMOOTH"); return RPT_ERR_INVALID_ARG; }
+    if (n == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_normal_query(smooth_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
 }
 

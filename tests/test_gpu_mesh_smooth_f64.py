@@ -1,0 +1,173 @@
+"""Smooth-shaded mesh renders held to tests/pt_f64.py, the float64 restatement of one pixel-sample (include/rpt.h, "smooth mesh
+shading"): SmoothMeshDescScene is test_gpu_mesh_f64.MeshDescScene with a winning triangle's normal restated — float64 vertex normals
+from the f32 positions (area-weighted face vectors, summed, normalised), interpolated with the triangle test's u and v, falling back
+to the flat normal — and records the margin of the `l2 > 0` branch.  One-sample renders with every mesh SMOOTH are compared sample by
+sample with test_path_f64's TAU / REL_CLEAN / NEAR_TIE_MAX over test_gpu_mesh_f64's own draws (needs an MI355X).
+
+The restatement alone, on the CPU, for exactly these draws: 131 of 1 200 samples lie below TAU (10.9 %, under the 12 % cap; the flat
+restatement has 127), no vertex normal is zero, the smallest interpolated l2 is 0.92, and f32 and f64 vertex normals differ by at
+most 1.3e-7.  271 clean samples differ between the flat and the smooth restatement by more than REL_CLEAN: a device that ignored the
+vertex normals would fail."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import pt_f64 as P
+from test_gpu_mesh_f64 import MeshDescScene, _scenes
+from test_gpu_path_f64 import Tally
+from test_path_f64 import NEAR_TIE_MAX, REL_CLEAN, TAU, rel_distance
+
+pytestmark = pytest.mark.gpu
+
+SMOOTH_BIT = 1 << 26
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    return torch
+
+
+def vertex_normals_f64(v, idx):
+    """include/rpt.h's vertex normals of one mesh in float64, from its f32 positions: [n, 3]; (0, 0, 0) where !(l2 > 0)."""
+    v = np.asarray(v, np.float32).astype(np.float64)
+    idx = np.asarray(idx, np.int64)
+    g = np.cross(v[idx[:, 1]] - v[idx[:, 0]], v[idx[:, 2]] - v[idx[:, 0]])
+    s = np.zeros_like(v)
+    for k, (a, b, c) in enumerate(idx):
+        for j in {int(a), int(b), int(c)}:                            # each triangle once per vertex it names
+            s[j] += g[k]
+    l2 = (s * s).sum(1)
+    with np.errstate(all="ignore"):
+        return np.where((l2 > 0.0)[:, None], s / np.sqrt(l2)[:, None], 0.0)
+
+
+class SmoothMeshDescScene(MeshDescScene):
+    """MeshDescScene with every mesh SMOOTH: closest_hit's triangle normal is the interpolated one."""
+
+    def __init__(self, desc, scene):
+        super().__init__(desc, scene)
+        normals, corners, first = [], [], 0
+        for v, t, _ in scene.meshes:
+            normals.append(vertex_normals_f64(v, t))
+            corners.append(np.asarray(t, np.int64) + first)
+            first += len(v)
+        self.vn = np.concatenate(normals)
+        self.corner = np.concatenate(corners)
+        self.l2_min = np.inf
+
+    def triangle_normal(self, k, o, d, M):
+        o, d = np.array(o), np.array(d)
+        p = np.cross(d, self.e2[k])
+        inv = 1.0 / float((self.e1[k] * p).sum())
+        s = o - self.ta[k]
+        u = float((s * p).sum()) * inv
+        v = float((d * np.cross(s, self.e1[k])).sum()) * inv
+        na, nb, nc = (self.vn[j] for j in self.corner[k])
+        m = ((1.0 - u) - v) * na + u * nb + v * nc
+        l2 = float((m * m).sum())
+        M.of(l2, 1.0)                                                 # the `l2 > 0` branch: the corners' normals are unit vectors
+        self.l2_min = min(self.l2_min, l2)
+        if l2 > 0.0 and l2 <= P.F_MAX:
+            return P.normalize(tuple(float(x) for x in m))
+        return P.normalize(tuple(float(x) for x in np.cross(self.e1[k], self.e2[k])))
+
+    def closest_hit(self, o, d, st, ls, mut, M):
+        """MeshDescScene.closest_hit with the winning triangle's normal replaced."""
+        dist = P.F_MAX
+        hit = False
+        first = True
+        for c, r, m in self.spheres:
+            t = P.sphere(o, d, c, r, mut, M)
+            if t is not None:
+                if not first:
+                    M.rel(t, dist)
+                if first or t < dist:
+                    hp = P.add(o, P.scale(t, d))
+                    st.hit_dist, st.normal = t, P.normalize(P.sub(hp, c))
+                    self.patch(m, d, hp, st.material, mut, M)
+                    hit, dist = True, t
+            first = False
+        for n, p, md, m, mt in self.planes:
+            t = P.plane(o, d, n, p, md, mt, M)
+            if t is not None:
+                if not first:
+                    M.rel(t, dist)
+                if first or t < dist:
+                    st.hit_dist, st.normal = t, n
+                    self.patch(m, d, P.add(o, P.scale(t, d)), st.material, mut, M)
+                    hit, dist = True, t
+            first = False
+        th, tt = self._triangles(o, d, M)
+        idx = np.nonzero(th)[0]
+        if idx.size:
+            ts = tt[idx]
+            order = np.argsort(ts, kind="stable")
+            if hit:
+                M.rel(float(ts[order[0]]), dist)
+            if idx.size > 1:
+                M.rel(float(ts[order[0]]), float(ts[order[1]]))
+            k = int(idx[order[0]])                                     # least t, lowest index on ties
+            t = float(tt[k])
+            if t < dist:
+                st.hit_dist, st.normal = t, self.triangle_normal(k, o, d, M)
+                self.patch(int(self.tri_mat[k]), d, P.add(o, P.scale(t, d)), st.material, mut, M)
+                hit, dist = True, t
+        if self.sample_lights(o, d, st, ls, mut, M):
+            hit = True
+        return hit
+
+
+def _one_smooth_sample(rpt, torch, scene, w, h, seed):
+    """A one-sample render with every mesh SMOOTH into a fresh buffer -> (frame, kernel choice)."""
+    t = rpt.Tracer(scene, device=0, seed=seed)
+    try:
+        t.set_mesh_shading({m: "smooth" for m in range(len(scene.meshes))})
+        buf = rpt.DeviceColorBuffer(w, h)
+        t.render_n(buf, 1)
+        torch.cuda.synchronize()
+        choice = C.c_uint32()
+        assert rpt.lib().rpt_debug_kernel_choice(t._h, C.byref(choice)) == 0
+        return buf.pixels.cpu().numpy(), choice.value
+    finally:
+        t.close()
+
+
+def _draws():
+    """test_gpu_mesh_f64's own draws: default_rng(35), seeds 50 + 10k + seed, 200 pixels each, 64 x 48."""
+    w, h = 64, 48
+    rng = np.random.default_rng(35)
+    for k, (what, s) in enumerate(_scenes()):
+        for seed in (1, 2, 3):
+            pixels = list(zip(rng.integers(0, w, 200).tolist(), rng.integers(0, h, 200).tolist()))
+            yield k, what, s, 50 + 10 * k + seed, pixels, w, h
+
+
+def test_smooth_mesh_renders_against_the_restatement(rpt, oracle, torch_cuda):
+    t = Tally(TAU, NEAR_TIE_MAX)
+    differ = 0
+    refs = {}
+    for k, what, s, seed, pixels, w, h in _draws():
+        if k not in refs:
+            refs[k] = (SmoothMeshDescScene(s.describe(), s), MeshDescScene(s.describe(), s))
+            assert refs[k][0].vn.any(axis=1).all(), "no vertex normal is zero"
+        ref, flat = refs[k]
+        frame, choice = _one_smooth_sample(rpt, torch_cuda, s, w, h, seed)
+        assert choice & (1 << 25) and choice & SMOOTH_BIT, "the smooth mesh kernel ran"
+        t.ran.add("meshsmooth_regen_kernel")
+        items = [(c, r, 0) for c, r in pixels]
+        restated, margins, _ = P.sample_many(ref, oracle, seed, items, w, h)
+        print("%s (seed %d): %d of %d samples below TAU" % (what, seed, int((margins <= TAU).sum()), len(margins)))
+        t.add("%s, smooth (seed %d)" % (what, seed), frame, restated, margins, pixels)
+        # teeth: where the flat restatement lands elsewhere, a device that ignored the vertex normals would have failed above
+        flat_restated, flat_margins, _ = P.sample_many(flat, oracle, seed, items, w, h)
+        clean = (margins > TAU) & (flat_margins > TAU)
+        differ += int((rel_distance(np.nan_to_num(flat_restated), np.nan_to_num(restated))[clean] > REL_CLEAN).sum())
+    t.check("smooth mesh scenes")
+    print("smallest interpolated l2 %.3g; %d clean samples differ between the flat and the smooth restatement" % (
+        min(r.l2_min for r, _ in refs.values()), differ))
+    assert t.n == 2 * 3 * 200
+    assert min(r.l2_min for r, _ in refs.values()) > 0.5
+    assert differ > 50

@@ -20,7 +20,12 @@ time of update_meshes and rebuild_meshes from host arrays (unchanged code: the y
 include/rpt.h records for them); of the two device forms without a transform on the same positions held in CUDA tensors; of the two
 device forms moving the torus alone, rigidly, from a rest tensor by a matrix; and each device form's first call apart (it allocates).
 
-    python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild] [--device]
+--smooth: one JSON line more, for smooth mesh shading (include/rpt.h, "smooth mesh shading"), in one process, the two sides of each
+comparison alternating `--reps` times (at least 5): the resident render rate of the scene flat and with both meshes SMOOTH, on two
+contexts; the wall time of update_meshes, rebuild_meshes and their device forms for the medium move and back, on a context whose
+meshes are SMOOTH against one whose meshes are FLAT (one pair of contexts per call); and the time of rpt_set_mesh_shading itself.
+
+    python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild] [--device] [--smooth]
 """
 import argparse
 import ctypes as C
@@ -42,6 +47,7 @@ def main():
     ap.add_argument("--update", action="store_true")
     ap.add_argument("--rebuild", action="store_true")
     ap.add_argument("--device", action="store_true")
+    ap.add_argument("--smooth", action="store_true")
     a = ap.parse_args()
     os.environ.setdefault("RPT_LIB", os.path.join(ROOT, "rust-pathtracer_amd", "librpt_hip_test.so"))     # (the product has no hooks)
     import __graft_entry__
@@ -66,6 +72,7 @@ def main():
     update = measure_updates(pkg, t, s, a) if a.update else None
     rebuild = measure_rebuilds(pkg, s, a) if a.rebuild else None
     device = measure_device_sources(pkg, s, a) if a.device else None
+    smooth = measure_smooth(pkg, s, a) if a.smooth else None
     t.close()
     print(json.dumps({"workload": "mesh_scene %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "triangles": n_tris,
                       "gsamples_per_s_median": sorted(rates)[len(rates) // 2], "gsamples_per_s": rates,
@@ -76,6 +83,8 @@ def main():
         print(json.dumps(rebuild))
     if device:
         print(json.dumps(device))
+    if smooth:
+        print(json.dumps(smooth))
 
 
 def measure_updates(pkg, t, s, a):
@@ -262,6 +271,69 @@ def measure_device_sources(pkg, s, a):
     for name, phase in phases:
         out[name] = {"phase": phase}
         out[name].update({c + "_ms": stats(res[name][c]) for c in columns})
+    return out
+
+
+def measure_smooth(pkg, s, a):
+    """-> the --smooth line.  Two contexts for the frames and two per move call, one FLAT and one with both meshes SMOOTH, so that
+    every context's calls follow calls of its own kind; within a repetition the two sides alternate."""
+    import numpy as np
+    import torch
+    from rust_pathtracer_amd import scenes
+    original = [np.array(v, np.float32, copy=True) for v, _, _ in s.meshes]
+    both = {0: "smooth", 1: "smooth"}
+
+    def stats(xs):
+        xs = sorted(xs)
+        return {"median": xs[len(xs) // 2], "min": xs[0], "max": xs[-1]}
+
+    def timed(call, arg):
+        t0 = time.perf_counter()
+        call(arg)
+        return (time.perf_counter() - t0) * 1e3
+
+    def rate(tr):
+        tr.render_resident(a.width, a.height, a.spp)
+        return a.width * a.height * a.spp / (tr.resident_kernel_ms() * 1e-3) / 1e9
+
+    reps = max(5, a.reps)
+    # frames
+    flat, smooth = pkg.Tracer(scenes.mesh_scene(), device=0, seed=1), pkg.Tracer(scenes.mesh_scene(), device=0, seed=1)
+    first_shading_ms = timed(smooth.set_mesh_shading, both)         # brings the refit tables, reads the corners back, builds the lists
+    again_ms = [timed(smooth.set_mesh_shading, both) for _ in range(reps)]
+    for tr in (flat, smooth):
+        rate(tr)                                                    # warm-up (and the dispatch order's first costs)
+        rate(tr)
+    rates = {"flat": [], "smooth": []}
+    for _ in range(reps):
+        rates["flat"].append(rate(flat))
+        rates["smooth"].append(rate(smooth))
+    flat.close()
+    smooth.close()
+    # moves: the medium move and back, so that every call moves every vertex
+    moved = scenes.mesh_scene_moved(s, 0.5)
+    dev = lambda arrays: {m: torch.from_numpy(np.ascontiguousarray(v, np.float32)).to("cuda:0") for m, v in enumerate(arrays)}   # noqa: E731
+    there, back = {"host": dict(enumerate(moved)), "device": dev(moved)}, {"host": dict(enumerate(original)), "device": dev(original)}
+    torch.cuda.synchronize()
+    calls = (("update_meshes", "host"), ("rebuild_meshes", "host"), ("update_meshes_device", "device"), ("rebuild_meshes_device", "device"))
+    out = {"workload": "mesh_scene smooth shading %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "reps": reps,
+           "first_set_mesh_shading_ms": first_shading_ms, "set_mesh_shading_again_ms": stats(again_ms),
+           "gsamples_per_s_flat": stats(rates["flat"]), "gsamples_per_s_smooth": stats(rates["smooth"]),
+           "smooth_over_flat_rate": stats(rates["smooth"])["median"] / stats(rates["flat"])["median"]}
+    for name, where in calls:
+        pair = {"flat": pkg.Tracer(scenes.mesh_scene(), device=0, seed=1), "smooth": pkg.Tracer(scenes.mesh_scene(), device=0, seed=1)}
+        pair["smooth"].set_mesh_shading(both)
+        for tr in pair.values():
+            getattr(tr, name)(back[where])                          # the context's first call of its kind: allocates
+        ms = {"flat": [], "smooth": []}
+        for _ in range(reps):
+            for arg in (there[where], back[where]):
+                for side in ("flat", "smooth"):
+                    ms[side].append(timed(getattr(pair[side], name), arg))
+        for tr in pair.values():
+            tr.close()
+        fl, sm = stats(ms["flat"]), stats(ms["smooth"])
+        out[name] = {"flat_ms": fl, "smooth_ms": sm, "smooth_adds_ms": sm["median"] - fl["median"]}
     return out
 
 
