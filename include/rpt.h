@@ -276,8 +276,8 @@ enum {                                /* rpt_scene_desc.flags */
  *
  * Materials: a scene with meshes follows the large scenes' rule — every sphere and mesh material must be a full patch
  * ((mask & RPT_MAT_ALL) == RPT_MAT_ALL, proc_kind == RPT_PROC_NONE); planes may carry any patch (at most 4 planes).  A triangle
- * that wins therefore leaves its own material.  A mesh's emission counts when a path hits it, as for spheres; meshes are not
- * lights (next-event estimation does not sample them).
+ * that wins therefore leaves its own material.  A mesh's emission counts when a path hits it, as for spheres; a mesh is a
+ * light for next-event estimation only while rpt_set_mesh_lights has turned it ON (below, "mesh lights").
  *
  * Limits: at most RPT_MESH_MAX_TRIANGLES triangles in all, n_spheres + triangles below 2^28 - 1, and the scene's device tables
  * (spheres, lights, materials, triangles at 48 B, BVH nodes at 64 B: at most one per triangle) below 4 GiB (RPT_ERR_UNSUPPORTED).
@@ -655,6 +655,104 @@ typedef struct rpt_mesh_shading {
 
 int rpt_set_mesh_shading(rpt_ctx* ctx, const rpt_mesh_shading* items, uint32_t n_items);
 int rpt_download_mesh_normals(rpt_ctx* ctx, uint32_t mesh, float* normals /* host, xyz per vertex */, uint32_t n_vertices);
+
+/* ---- mesh lights — PROJECT-DEFINED ------------------------------------------------------------------------------------------------
+ * Per mesh, next-event estimation samples the mesh's surface: an emissive mesh that is ON is a light like an rpt_light, picked by
+ * direct_light's index draw, sampled over its area, and weighed against BSDF sampling by the power heuristic on both sides.  The
+ * library computes the table the sampler reads on the device from the f32 positions the context holds, and computes it again inside
+ * every call that moves a mesh; nothing crosses the host.  Every operation is stated, so that tables, samples and frames stay
+ * checkable bit for bit (tests/test_gpu_mesh_light.py holds them to a numpy restatement).  dot, cross and F::MAX are those of
+ * "triangle meshes"; the square roots and the divides are the library's correctly rounded ones.
+ *
+ * The table of an ON mesh.  Its triangles are k = 0 .. n-1 in the mesh's own order, never in slot order: rpt_rebuild_meshes leaves
+ * the table bit for bit where it was.  (a, b, c) are the f32 corner positions the context holds.
+ *     g = cross(b - a, c - a);  l2 = dot(g, g);  A_k = !(l2 > 0 && l2 <= F::MAX) ? 0 : 0.5f * sqrt(l2)
+ *     A_max = max over k of A_k.  The mesh is DARK if A_max == 0, if it has no triangle, or if A_tot below is not finite; a dark
+ *             mesh has E = 0, every C_k = 0 and A_tot = 0.  Otherwise E is the integer with A_max = f * 2^E, f in [0.5, 1).
+ *     q_k   = floor(A_k * 2^(36 - E)) as a uint64 (A_k is an f32 and the scale a power of two: the product is exact in float64;
+ *             q_k < 2^36)
+ *     C_k   = q_0 + ... + q_k as a uint64 (below 2^62 for 2^26 triangles);  Q = C_(n-1)
+ *     A_tot = f32(Q) * 2^(E - 36): the integer rounded to the nearest f32, ties to even, then an exact scaling; an overflow gives
+ *             +inf, which makes the mesh dark.
+ * The sums are fixed-point integers on purpose: integer addition is associative, so any parallel scan and any maximum give the
+ * same bits, no summation order needs a promise, and the CDF is monotone by construction.
+ *
+ * Pickable lights.  N = n_lights + the number of ON meshes, and N_f = (float)N takes the place of `n_lights as F` everywhere the
+ * integrator uses it: the index draw and the emission factor of every light, the rpt_lights included.  Index i < n_lights is the
+ * i-th rpt_light as before; index n_lights + j is the j-th ON mesh in ascending mesh index.  Next-event estimation is skipped when
+ * N == 0 (not when n_lights == 0).
+ *
+ * Sampling an ON mesh from scatter_pos.  The draws, in this order after the light-index draw: r0a, r0b, r1, r2 — all four are always
+ * taken.  A dark mesh leaves LightSampleRec::new()'s zeros, so the facing test fails.  Otherwise
+ *     J = (uint64)(r0a * 2^24) << 24 | (uint64)(r0b * 2^24)       (draws are multiples of 2^-24: exact)
+ *     T = (J * Q) >> 48, the high part of the 64 x 64 product of (J << 16) and Q;  T < Q
+ *     k = the first index with C_k > T, by binary search (q_k > 0 there)
+ *     e1 = b - a;  e2 = c - a;  su = sqrt(r1);  bu = 1 - su;  bv = r2 * su
+ *     P.i = (a.i + bu * e1.i) + bv * e2.i                           i = x, y, z
+ *     direction = P - scatter_pos;  dist = length(direction);  dist_sq = dist * dist;  direction = direction / dist, per component
+ *     n = normalize(cross(e1, e2));  c = dot(n, direction);  normal = (c > 0) ? -n : n
+ *     emission = N_f * (the mesh material's emission);  pdf = dist_sq / (A_tot * |c|)
+ * The mesh is two-sided like its emission, so the integrator's dot(direction, normal) < 0 passes from either side and fails for
+ * c == 0 or NaN.  The light.area that gates the MIS weight is A_tot (> 0).  The shadow ray, disney_eval, the MIS weight and the
+ * contribution are direct_light's as they stand.
+ *
+ * Hit side.  Where a hit's emission is added (tracer.rs:74) — `radiance += emission * throughput` — a path whose ray won a
+ * triangle of an ON, not dark, mesh adds `(w * emission) * throughput` instead:
+ *     w = 1 at bounce 0;  otherwise c = |dot(ray.d, n_flat)|, n_flat = normalize(cross(e1, e2)) of the winning triangle's row;
+ *     !(c > 0) -> w = 1;  else lp = (hit_dist * hit_dist) / (A_tot * c) and w = power_heuristic(scatter_pdf, lp)
+ * with the previous bounce's scatter_pdf and the state's hit_dist — exactly how the emitter exit weighs an rpt_light.  (Where
+ * Scene::sample_lights found an rpt_light in front of that triangle, hit_dist is the light's distance, as the state holds it.)  The
+ * path goes on as for any surface: a mesh light is not an emitter exit.  A SMOOTH mesh may be ON: sampling and lp use the flat
+ * normal, shading the normal the mesh's mode says.  Triangle test, acceptance order, any_hit, Scene::sample_lights and the materials
+ * are unchanged.
+ *
+ * rpt_set_mesh_lights sets the mode of the named meshes of the uploaded scene, before or after any number of moves, rebuilds or
+ * shading changes; meshes not named keep theirs, and rpt_upload_scene leaves every mesh RPT_MESH_LIGHT_OFF.  On return every ON
+ * mesh's table is current on every device of the context (rpt_create_multi: all of them; one process per GPU: every rank makes the
+ * call itself, as for rpt_update_meshes).  A mesh without triangles may be named (it is dark).  The checks, in this order, all on
+ * the host before any device is touched — a rejected call changes nothing, and rpt_last_error names the item:
+ *   RPT_ERR_INVALID_ARG  ctx is NULL;
+ *   RPT_ERR_NO_SCENE     no scene with meshes is uploaded;
+ *   RPT_ERR_UNSUPPORTED  the scene lacks RPT_SCENE_ANYHIT_USES_MAX_DIST: without it a mesh light's own triangles occlude every
+ *                        shadow ray aimed at them; the scene's meshes hold 2^32 vertices or more;
+ *   RPT_ERR_UNSUPPORTED  n_lights plus the number of ON meshes would reach 2^24 (the index draw has 24 bits).  This comes before the
+ *                        items' own checks, so it counts what the well-formed items would leave ON: an item whose mesh or mode
+ *                        is out of range counts as absent, a mesh named twice with its last mode;
+ *   RPT_ERR_INVALID_ARG  items NULL with a non-zero count; then per item: mesh >= n_meshes, a mesh named twice, a mode that is
+ *                        neither constant;
+ *   RPT_OK               n_items == 0: nothing is done;
+ *   RPT_ERR_HIP          a runtime call failed part-way: the context is left with NO scene, as for rpt_update_meshes.
+ * While some mesh is ON the scene renders through a kernel of its own (the mesh kernel's body with the sampler and the weight
+ * above; it serves FLAT and SMOOTH meshes alike); when the last ON mesh goes OFF the context renders exactly as if the call had
+ * never been made — the same kernel, the same tables.  A scene on which the call was never made is untouched by all of this.
+ *
+ * Moves.  rpt_update_meshes, rpt_rebuild_meshes and both _device forms recompute the table of every ON mesh on the device before
+ * they return RPT_OK (five more kernel launches per device, whatever the number of meshes: reset, areas and maxima, quantise and
+ * scan within 256 triangles, scan of the block sums, CDF and A_tot); a rejected move leaves the tables as they were.
+ *
+ * rpt_download_mesh_light_table copies the table the context holds for one ON mesh to host memory from its first device: C_k for
+ * all its triangles, E and A_tot.  It follows rpt_download_mesh_normals: a mesh out of range, an n_triangles that is not the
+ * uploaded mesh's, a NULL destination or an OFF mesh answer RPT_ERR_INVALID_ARG (the last says so).  It never changes anything.
+ *
+ * Memory.  The call brings the refit's tables to every device as the context's first rpt_update_meshes does (and reads the
+ * triangles' corners back from the first device once per call, like rpt_set_mesh_shading).  While a mesh is ON every device holds,
+ * until the last mesh is OFF again or the next rpt_upload_scene: per ON mesh 32 B; per triangle of the ON meshes 36 B (C_k and the
+ * scan's partial sum, 8 B each, A_k, 4 B, its corners, 12 B, its mesh's ordinal, 4 B) and 8 B per 256 of them; per triangle of the
+ * SCENE 4 B (the hit side's lookup) and one bit.
+ *
+ * Timings: not measured yet — neither what the binary search and the extra tables cost a frame nor what the five launches add to a
+ * move.  tools/mesh_bench.py --lights alternates, in one process, frames of scenes.mesh_scene with its torus emissive and OFF / ON,
+ * and the four move calls with the mesh ON against OFF. */
+enum { RPT_MESH_LIGHT_OFF = 0, RPT_MESH_LIGHT_ON = 1 };
+
+typedef struct rpt_mesh_light {
+    uint32_t mesh;                    /* index into the uploaded scene's rpt_scene_desc.meshes */
+    uint32_t mode;                    /* RPT_MESH_LIGHT_OFF or RPT_MESH_LIGHT_ON */
+} rpt_mesh_light;
+
+int rpt_set_mesh_lights(rpt_ctx* ctx, const rpt_mesh_light* items, uint32_t n_items);
+int rpt_download_mesh_light_table(rpt_ctx* ctx, uint32_t mesh, uint64_t* cdf /* host, one per triangle of the mesh */,
+                                  uint32_t n_triangles, int32_t* exponent, float* area);
 
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)

@@ -235,6 +235,19 @@ public:
         check(rpt_download_mesh_normals(ctx_, mesh, out.data(), n_vertices), ctx_);
         return out;
     }
+    /// Mesh lights (rpt.h, "mesh lights"): next-event estimation samples the surface of every mesh that is RPT_MESH_LIGHT_ON, through
+    /// a table the library computes on the device and keeps current through every call above; sync_scene() leaves every mesh off.
+    void set_mesh_lights(const std::vector<rpt_mesh_light>& items) {
+        check(rpt_set_mesh_lights(ctx_, items.data(), (uint32_t)items.size()), ctx_);
+    }
+    /// The table the context holds for one ON mesh: the running sums C_k (one per triangle), the exponent E and the area A_tot.
+    struct MeshLightTable { std::vector<uint64_t> cdf; int32_t exponent = 0; float area = 0.0f; };
+    MeshLightTable mesh_light_table(uint32_t mesh, uint32_t n_triangles) {
+        MeshLightTable t;
+        t.cdf.resize(n_triangles);
+        check(rpt_download_mesh_light_table(ctx_, mesh, t.cdf.data(), n_triangles, &t.exponent, &t.area), ctx_);
+        return t;
+    }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

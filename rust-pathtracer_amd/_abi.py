@@ -133,6 +133,13 @@ class rpt_mesh_shading(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("mode", C.c_uint32)]
 
 
+RPT_MESH_LIGHT_OFF, RPT_MESH_LIGHT_ON = 0, 1
+
+
+class rpt_mesh_light(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("mode", C.c_uint32)]
+
+
 class rpt_scene_desc(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("flags", C.c_uint32),
@@ -185,6 +192,8 @@ SYMBOLS = {
     "rpt_download_mesh_vertices": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "rpt_set_mesh_shading": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_shading), C.c_uint32]),
     "rpt_download_mesh_normals": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "rpt_set_mesh_lights": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_light), C.c_uint32]),
+    "rpt_download_mesh_light_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "rpt_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -219,6 +228,7 @@ TEST_SYMBOLS = {
     "rpt_probe_math": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "rpt_debug_mesh_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rpt_debug_mesh_normal_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rpt_debug_mesh_light_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "rpt_debug_mesh_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "rpt_debug_mesh_walk": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rpt_debug_mesh_tables": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

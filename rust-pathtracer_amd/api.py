@@ -476,6 +476,28 @@ class Tracer:
         check(lib().rpt_download_mesh_normals(self._h, int(m), out.ctypes.data, n), self._h)
         return out
 
+    def set_mesh_lights(self, modes):
+        """Mesh lights (include/rpt.h, "mesh lights"): `modes` maps a mesh's index in scene().meshes to True — next-event estimation
+        samples the mesh's surface, through a table the library computes on the device and keeps current through every call that
+        moves the mesh — or False.  Meshes not named keep their mode; upload_scene() leaves every mesh off again, as in C.  The scene
+        needs any_hit_uses_max_dist."""
+        items = sorted(modes.items())
+        its = (_abi.rpt_mesh_light * max(1, len(items)))()
+        for it, (m, on) in zip(its, items):
+            if not isinstance(on, (bool, np.bool_)):
+                raise ValueError("mesh %d: the mode must be True or False, not %r" % (m, on))
+            it.mesh, it.mode = int(m), _abi.RPT_MESH_LIGHT_ON if on else _abi.RPT_MESH_LIGHT_OFF
+        self._checked_move(lib().rpt_set_mesh_lights(self._h, its, len(items)))
+
+    def mesh_light_table(self, m):
+        """The table the context holds for the mesh light `m` (rpt_download_mesh_light_table): (cdf, exponent, area) — a new uint64
+        array with one running sum per triangle of the mesh, the integer E and the float32 A_tot; (zeros, 0, 0.0): the mesh is dark."""
+        n = np.asarray(self._scene.meshes[m][1]).reshape(-1, 3).shape[0]
+        cdf = np.zeros(n, np.uint64)
+        e, area = C.c_int32(0), C.c_float(0.0)
+        check(lib().rpt_download_mesh_light_table(self._h, int(m), cdf.ctypes.data, n, C.byref(e), C.byref(area)), self._h)
+        return cdf, int(e.value), np.float32(area.value)
+
     def _refresh_stale_meshes(self):
         """scene().meshes' vertex arrays that a device-source call left stale, read back once (only before an upload)."""
         for m in sorted(self._stale_meshes):

@@ -20,6 +20,7 @@
 
 #include "../../include/rpt.h"
 #include "host_build.h"
+#include "host_light.h"
 #include "host_move.h"
 #include "host_refit.h"
 #include "host_smooth.h"
@@ -27,6 +28,7 @@
 #include "knobs.h"
 #include "launch.h"
 #include "launch_build.h"
+#include "launch_light.h"
 #include "launch_move.h"
 #include "launch_smooth.h"
 #ifdef RPT_TEST_HOOKS
@@ -56,6 +58,7 @@ struct DevState {
                                       // first rpt_update_meshes_device / rpt_rebuild_meshes_device to the next upload
     void* move_stage = nullptr;       // ... and copies of sources that lie on another device (12 B per vertex of the scene), made on demand
     void* smooth = nullptr;           // smooth shading's tables (host_smooth.h, SmoothLayout): while some mesh is SMOOTH (rpt_set_mesh_shading)
+    void* light = nullptr;            // mesh lights' tables (host_light.h, LightLayout): while some mesh is ON (rpt_set_mesh_lights)
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -101,6 +104,7 @@ struct rpt_ctx {
     rpthost::SceneState scene;        // its class, camera, small scenes' kernel argument (host_upload.h); every device's tables: DevState
     rpthost::RefitPlan refit;         // a mesh scene's plan for rpt_update_meshes (host_refit.h)
     rpthost::SmoothPlan smooth;       // its meshes' shading modes and the sizes of every device's smooth tables (host_smooth.h)
+    rpthost::LightPlan light;         // which of its meshes are lights and the sizes of every device's light tables (host_light.h)
     // resident ColorBuffer (buffer.rs:6-14): pixels as per-rank tiles + frames
     uint32_t res_w = 0, res_h = 0, res_tile_rows = 0, res_rows_padded = 0;
     uint64_t res_frames = 0;
@@ -283,6 +287,7 @@ static void free_mesh_work(DevState& d)
     if (d.move) { (void)hipFree(d.move); d.move = nullptr; }
     if (d.move_stage) { (void)hipFree(d.move_stage); d.move_stage = nullptr; }
     if (d.smooth) { (void)hipFree(d.smooth); d.smooth = nullptr; }
+    if (d.light) { (void)hipFree(d.light); d.light = nullptr; }
     d.refit_full = false;
     d.build_temp_bytes = 0;
 }
@@ -448,6 +453,55 @@ static SceneMeshSmooth smooth_scene_of(const rpt_ctx* ctx, const DevState& d)
     return s;
 }
 
+// The table kernels' argument: pointers into device d's light tables (ctx->light says their sizes).
+static LightTables light_tables_of(const rpt_ctx* ctx, const DevState& d)
+{
+    const rpthost::LightPlan& lp = ctx->light;
+    const rpthost::LightLayout ll(lp.n_on(), lp.n_faces, lp.n_tris);
+    unsigned char* base = static_cast<unsigned char*>(d.light);
+    LightTables t{};
+    t.desc = reinterpret_cast<LightMeshDesc*>(base + ll.off_desc);
+    t.cdf = reinterpret_cast<uint64_t*>(base + ll.off_cdf);
+    t.part = reinterpret_cast<uint64_t*>(base + ll.off_part);
+    t.block = reinterpret_cast<uint64_t*>(base + ll.off_block);
+    t.area = reinterpret_cast<float*>(base + ll.off_area);
+    t.face_vertex = reinterpret_cast<const uint32_t*>(base + ll.off_face_vertex);
+    t.face_mesh = reinterpret_cast<const uint32_t*>(base + ll.off_face_mesh);
+    t.n_on = lp.n_on();
+    t.n_faces = lp.n_faces;
+    return t;
+}
+
+// A mesh scene's kernel argument while some mesh is ON: device d's scene, its smooth tables if some mesh is SMOOTH (else the
+// refit's slot_vertex and all-zero smooth bits: every hit takes the flat normal), and pointers into its refit and light tables.
+static SceneMeshLight light_scene_of(const rpt_ctx* ctx, const DevState& d)
+{
+    const rpthost::LightPlan& lp = ctx->light;
+    const rpthost::RefitLayout rl(ctx->refit.n_vertices(), 0, 0);
+    const rpthost::LightLayout ll(lp.n_on(), lp.n_faces, lp.n_tris);
+    const unsigned char* refit = static_cast<const unsigned char*>(d.refit);
+    const unsigned char* base = static_cast<const unsigned char*>(d.light);
+    SceneMeshLight s{};
+    if (d.smooth && ctx->smooth.any()) {
+        static_cast<SceneMeshSmooth&>(s) = smooth_scene_of(ctx, d);
+    } else {
+        static_cast<SceneMesh&>(s) = d.scene;
+        s.slot_vertex = reinterpret_cast<const uint32_t*>(refit + rl.off_slot_vertex);
+        s.vnormals = nullptr;                                       // (not read: no smooth bit is set)
+        s.smooth_bits = reinterpret_cast<const uint32_t*>(base + ll.off_flat_bits);
+    }
+    const LightTables t = light_tables_of(ctx, d);
+    s.vertices = reinterpret_cast<const float*>(refit + rl.off_vertices);
+    s.face_vertex = t.face_vertex;
+    s.light_desc = t.desc;
+    s.light_cdf = t.cdf;
+    s.tri_light = reinterpret_cast<const uint32_t*>(base + ll.off_tri_light);
+    s.n_faces = lp.n_faces;
+    s.n_pick = s.n_lights + lp.n_on();
+    s.n_lights_f = (float)s.n_pick;                                 // include/rpt.h, "pickable lights": N_f
+    return s;
+}
+
 // One render launch sequence on one device.
 static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t width, uint32_t height, uint64_t frames_done, uint32_t spp,
                          uint64_t seed, uint32_t flags, uint32_t tile_rows, uint32_t rank, uint32_t world, hipStream_t stream)
@@ -463,6 +517,7 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     SceneLarge scl = d.scene;
     SceneMesh scm = d.scene;
     const bool smooth = kind == SceneKind::mesh && d.smooth && d.refit && ctx->smooth.any();      // some mesh is SMOOTH: k_smooth.hip's form
+    const bool lights = kind == SceneKind::mesh && d.light && d.refit && ctx->light.any();        // some mesh is ON: k_light.hip's form, for flat and smooth meshes alike
     scs.cam = scl.cam = scm.cam = make_camera(ctx->scene.camera, (float)width, (float)height);
     const bool in_hbm = kind == SceneKind::large || kind == SceneKind::mesh;     // the scene's tables are in device memory
     const bool has_sdf = !in_hbm && scs.sdf.n_prims > 0;
@@ -524,9 +579,15 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
                         (fast ? 1u << 20 : 0u) | (rp.compact && !nested ? 1u << 21 : 0u) |
                         (rp.compact && !nested && nblocks <= kCompactDenseMaxBlocks ? 1u << 22 : 0u) | (nested ? 1u << 23 : 0u) |
                         (media ? 1u << 24 : 0u) | (kind == SceneKind::mesh ? 1u << 25 : 0u) |
-                        (smooth ? 1u << 26 : 0u);
+                        (smooth ? 1u << 26 : 0u) | (lights ? 1u << 27 : 0u);
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
+        if (lights) {
+            SceneMeshLight sml = light_scene_of(ctx, d);
+            sml.cam = scm.cam;
+            sml.flags = scm.flags;
+            return rptlaunch::render_mesh_light(sml, rp, grid, stream);
+        }
         if (smooth) {
             SceneMeshSmooth sms = smooth_scene_of(ctx, d);
             static_cast<SceneMesh&>(sms) = scm;
@@ -909,6 +970,7 @@ static void commit_scene(rpt_ctx* ctx, SceneImage& img, const std::vector<void*>
     ctx->scene = img.state;
     ctx->refit = std::move(img.refit);
     ctx->smooth = rpthost::SmoothPlan();                            // every mesh FLAT
+    ctx->light = rpthost::LightPlan();                              // every mesh OFF
 }
 
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
@@ -938,6 +1000,7 @@ static void drop_scene(rpt_ctx* ctx)
     ctx->scene = rpthost::SceneState();
     ctx->refit = rpthost::RefitPlan();
     ctx->smooth = rpthost::SmoothPlan();
+    ctx->light = rpthost::LightPlan();
 }
 
 // Where the named meshes' new positions come from: host arrays (rpt_update_meshes, rpt_rebuild_meshes) or device arrays through a
@@ -1016,6 +1079,15 @@ static int smooth_normals_device(rpt_ctx* ctx, DevState& d)
     return RPT_OK;
 }
 
+// The tables of every ON mesh from the positions device d holds, on d's stream (k_light.hip: five launches); nothing while every
+// mesh is OFF.  Beside smooth_normals_device in every call that moves a mesh, and the last device work of rpt_set_mesh_lights.
+static int light_tables_device(rpt_ctx* ctx, DevState& d)
+{
+    if (!d.light) return RPT_OK;
+    RPT_HIP_CHECK(ctx, rptlaunch::light_tables(static_cast<const float*>(d.refit), light_tables_of(ctx, d), d.stream));
+    return RPT_OK;
+}
+
 static int update_device(rpt_ctx* ctx, DevState& d, const MeshPositions& pos)
 {
     const rpthost::RefitPlan& plan = ctx->refit;
@@ -1033,6 +1105,7 @@ static int update_device(rpt_ctx* ctx, DevState& d, const MeshPositions& pos)
     for (uint32_t level = plan.n_levels(); level-- > 0;)
         RPT_HIP_CHECK(ctx, rptlaunch::refit_nodes(nodes, slot_box, level_nodes + plan.level_first[level], plan.level_first[level + 1u] - plan.level_first[level], d.stream));
     RPT_CHECK_RC(smooth_normals_device(ctx, d));
+    RPT_CHECK_RC(light_tables_device(ctx, d));
     RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
     return RPT_OK;
 }
@@ -1160,6 +1233,7 @@ static int rebuild_device(rpt_ctx* ctx, DevState& d, const MeshPositions& pos, u
     for (uint32_t level = n_levels; level-- > 0;)
         RPT_HIP_CHECK(ctx, rptlaunch::refit_nodes(t.nodes, t.slot_box, t.level_nodes + levels[level], levels[kBuildLevelCount + level], d.stream));
     RPT_CHECK_RC(smooth_normals_device(ctx, d));
+    RPT_CHECK_RC(light_tables_device(ctx, d));
     RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
     d.scene.nodes = t.nodes;
     return RPT_OK;
@@ -1398,7 +1472,7 @@ static int shade_device(rpt_ctx* ctx, DevState& d)
 
 // The flattened triangles' corners, read back from the context's first device (the current one): its refit tables' slot_vertex and
 // the rows' index words say which slot holds which triangle, whatever updates and rebuilds have done since the upload.
-static int read_flat_indices(rpt_ctx* ctx, std::vector<uint32_t>& flat)
+static int read_flat_indices(rpt_ctx* ctx, std::vector<uint32_t>& flat, const char* who = "rpt_set_mesh_shading")
 {
     DevState& d = ctx->devs[0];
     const rpthost::RefitPlan& plan = ctx->refit;
@@ -1412,11 +1486,11 @@ static int read_flat_indices(rpt_ctx* ctx, std::vector<uint32_t>& flat)
     RPT_HIP_CHECK(ctx, hipMemcpyAsync(slot_vertex.data(), static_cast<const unsigned char*>(d.refit) + rl.off_slot_vertex, 12 * n, hipMemcpyDeviceToHost, d.stream));
     RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
     if (!rpthost::smooth_flat_indices(rows.data(), slot_vertex.data(), n, flat)) {
-        set_err(ctx, "rpt_set_mesh_shading: the triangle table of device %d does not name every triangle once", d.device);
+        set_err(ctx, "%s: the triangle table of device %d does not name every triangle once", who, d.device);
         return RPT_ERR_HIP;
     }
     for (uint32_t x : flat)
-        if (x >= plan.n_vertices()) { set_err(ctx, "rpt_set_mesh_shading: device %d's slot_vertex table names a vertex out of range", d.device); return RPT_ERR_HIP; }
+        if (x >= plan.n_vertices()) { set_err(ctx, "%s: device %d's slot_vertex table names a vertex out of range", who, d.device); return RPT_ERR_HIP; }
     return RPT_OK;
 }
 
@@ -1490,6 +1564,109 @@ int rpt_download_mesh_normals(rpt_ctx* ctx, uint32_t mesh, float* normals, uint3
     std::vector<float> rows(4 * (size_t)count);
     RPT_HIP_CHECK(ctx, hipMemcpy(rows.data(), static_cast<const unsigned char*>(d.smooth) + sl.off_normals + 16 * (size_t)first, 16 * (size_t)count, hipMemcpyDeviceToHost));
     for (size_t v = 0; v < count; ++v) memcpy(normals + 3 * v, &rows[4 * v], 12);
+    return RPT_OK;
+}
+
+// ---- rpt_set_mesh_lights / rpt_download_mesh_light_table (include/rpt.h, "mesh lights") --------------------------------------------
+// One device's part: wait for its earlier work (a launch may still read the old tables), make its refit tables if it has none, drop
+// the old light tables, copy the new ones in, compute the ON meshes' tables, and wait.  ctx->light is already the new plan.
+static int light_device(rpt_ctx* ctx, DevState& d)
+{
+    const rpthost::LightPlan& lp = ctx->light;
+    const rpthost::LightLayout ll(lp.n_on(), lp.n_faces, lp.n_tris);
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    RPT_CHECK_RC(ensure_refit(ctx, d));
+    if (d.light) { (void)hipFree(d.light); d.light = nullptr; }
+    RPT_HIP_CHECK(ctx, hipMalloc(&d.light, ll.total));
+    unsigned char* base = static_cast<unsigned char*>(d.light);
+    const auto put = [&](size_t off, const std::vector<uint32_t>& v) {
+        return v.empty() ? hipSuccess : hipMemcpyAsync(base + off, v.data(), sizeof(uint32_t) * v.size(), hipMemcpyHostToDevice, d.stream);
+    };
+    RPT_HIP_CHECK(ctx, put(ll.off_desc, lp.desc));
+    RPT_HIP_CHECK(ctx, put(ll.off_face_vertex, lp.face_vertex));
+    RPT_HIP_CHECK(ctx, put(ll.off_face_mesh, lp.face_mesh));
+    RPT_HIP_CHECK(ctx, put(ll.off_tri_light, lp.tri_light));
+    if (ll.total > ll.off_flat_bits) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + ll.off_flat_bits, 0, ll.total - ll.off_flat_bits, d.stream));
+    RPT_CHECK_RC(light_tables_device(ctx, d));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    return RPT_OK;
+}
+
+int rpt_set_mesh_lights(rpt_ctx* ctx, const rpt_mesh_light* items, uint32_t n_items)
+{
+    using namespace rpthost;
+    if (!ctx) { set_err(nullptr, "rpt_set_mesh_lights: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    std::vector<uint8_t> mode;
+    std::string why;
+    const bool mesh_scene = ctx->scene.kind == SceneKind::mesh;
+    const SceneMesh& sc0 = ctx->devs[0].scene;
+    const int rc = check_mesh_lights(ctx->refit, mesh_scene, mesh_scene ? sc0.flags : 0u, mesh_scene ? sc0.n_lights : 0u, items, n_items, ctx->light.mode, mode, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    if (n_items == 0) return RPT_OK;
+    LightPlan fresh;
+    fresh.mode = mode;
+    DeviceGuard guard(ctx->devs[0].device);
+    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
+    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_lights: cannot select device %d", ctx->devs[0].device);
+    if (rc_dev == RPT_OK && !fresh.any()) {                         // every mesh OFF (again): the context is what it was before the first call
+        for (DevState& d : ctx->devs) {
+            if (!d.light) continue;
+            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
+                set_err(ctx, "rpt_set_mesh_lights: cannot wait for device %d", d.device);
+                rc_dev = RPT_ERR_HIP;
+                break;
+            }
+            (void)hipFree(d.light);
+            d.light = nullptr;
+        }
+        if (rc_dev == RPT_OK) { ctx->light = LightPlan(); return RPT_OK; }
+    }
+    if (rc_dev == RPT_OK) {
+        std::vector<uint32_t> flat;
+        rc_dev = read_flat_indices(ctx, flat, "rpt_set_mesh_lights");
+        if (rc_dev == RPT_OK) {
+            build_light_plan(ctx->refit, flat.data(), mode, fresh);
+            ctx->light = std::move(fresh);
+        }
+    }
+    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
+        DevState& d = ctx->devs[i];
+        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_lights: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
+        else rc_dev = light_device(ctx, d);
+    }
+    if (rc_dev != RPT_OK) {
+        const std::string first = ctx->err;
+        drop_scene(ctx);
+        set_err(ctx, "%s; the context now holds no scene", first.c_str());
+        return rc_dev;
+    }
+    ctx->refit.release_staging();                                   // every device holds the refit tables
+    ctx->light.release_staging();
+    return RPT_OK;
+}
+
+int rpt_download_mesh_light_table(rpt_ctx* ctx, uint32_t mesh, uint64_t* cdf, uint32_t n_triangles, int32_t* exponent, float* area)
+{
+    if (!ctx) { set_err(nullptr, "rpt_download_mesh_light_table: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_mesh_light_table: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    const rpthost::RefitPlan& plan = ctx->refit;
+    if (!plan.ok) { set_err(ctx, "rpt_download_mesh_light_table: the scene's meshes hold 2^32 vertices or more"); return RPT_ERR_UNSUPPORTED; }
+    if (mesh >= plan.n_meshes()) { set_err(ctx, "rpt_download_mesh_light_table: mesh %u out of range (the scene has %u)", mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
+    const uint32_t count = plan.tri_first[mesh + 1u] - plan.tri_first[mesh];
+    if (n_triangles != count) { set_err(ctx, "rpt_download_mesh_light_table: mesh %u: n_triangles %u != the uploaded mesh's %u", mesh, n_triangles, count); return RPT_ERR_INVALID_ARG; }
+    const DevState& d = ctx->devs[0];
+    const rpthost::LightPlan& lp = ctx->light;
+    const uint32_t ord = lp.ordinal(mesh);
+    if (ord == rpthost::kLightNone || !d.light) { set_err(ctx, "rpt_download_mesh_light_table: mesh %u is OFF: the context holds no table for it (rpt_set_mesh_lights)", mesh); return RPT_ERR_INVALID_ARG; }
+    if (!exponent || !area || (count && !cdf)) { set_err(ctx, "rpt_download_mesh_light_table: cdf, exponent or area is NULL"); return RPT_ERR_INVALID_ARG; }
+    RPT_ON_DEVICE(ctx);
+    const rpthost::LightLayout ll(lp.n_on(), lp.n_faces, lp.n_tris);
+    const unsigned char* base = static_cast<const unsigned char*>(d.light);
+    LightMeshDesc desc;
+    RPT_HIP_CHECK(ctx, hipMemcpy(&desc, base + ll.off_desc + sizeof(LightMeshDesc) * (size_t)ord, sizeof(desc), hipMemcpyDeviceToHost));
+    if (count) RPT_HIP_CHECK(ctx, hipMemcpy(cdf, base + ll.off_cdf + 8 * (size_t)lp.on_first[ord], 8 * (size_t)count, hipMemcpyDeviceToHost));
+    *exponent = desc.exponent;
+    *area = desc.area;
     return RPT_OK;
 }
 
@@ -2070,6 +2247,18 @@ int rpt_debug_mesh_normal_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n,
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_normal_query(smooth_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_debug_mesh_light_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, uint32_t* out_dev, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_light_sample: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_light_sample: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    if (!in_dev || !out_dev) { set_err(ctx, "rpt_debug_mesh_light_sample: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->light.any() || !ctx->devs[0].light) { set_err(ctx, "rpt_debug_mesh_light_sample: no mesh is ON"); return RPT_ERR_INVALID_ARG; }
+    if (n == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_light_sample(light_scene_of(ctx, ctx->devs[0]), in_dev, out_dev, n, (hipStream_t)stream));
     return RPT_OK;
 }
 

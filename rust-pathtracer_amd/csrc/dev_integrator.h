@@ -812,6 +812,11 @@ struct MaterialTableMapped {
     }
 };
 
+// Mesh lights (include/rpt.h, "mesh lights"; project-defined) are a COMPILE-TIME property of the scene type, like media: the scene
+// type that has them specialises this (dev_mesh_light.h) and provides mesh_light_nee and mesh_light_hit_weight; every other scene
+// type's kernels contain none of that code.
+template <class S> struct MeshLights { static constexpr bool value = false; };
+
 // Head of direct_light (tracer.rs:130-145): pick a light, sample it.  Returns the facing test of tracer.rs:147.
 // OFFSET false: the estimate is taken at a point inside a medium (media, dev_media.h): scatter_pos is `fhp` itself.
 template <bool OFFSET = true, class S>
@@ -823,7 +828,17 @@ RPT_DEV bool nee_sample(const S& sc, v3 fhp, v3 ffnormal, Rng& rng, v3& scatter_
     random = random * sc.n_lights_f;
     uint32_t index = (uint32_t)random;                              // `as usize`
     const uint32_t n_lights = uniform_here(sc.n_lights);
-    index = (index >= n_lights) ? n_lights - 1u : index;            // the reference would panic; unreachable for n < 2^24
+    if constexpr (MeshLights<S>::value) {
+        // index n_lights + j is the j-th ON mesh; n_lights_f is (float)n_pick
+        const uint32_t n_pick = uniform_here(sc.n_pick);
+        index = (index >= n_pick) ? n_pick - 1u : index;
+        if (index >= n_lights) {
+            light_area = mesh_light_nee(sc, index - n_lights, scatter_pos, ls, rng);
+            return dot3(ls.direction, ls.normal) < 0.0f;
+        }
+    } else {
+        index = (index >= n_lights) ? n_lights - 1u : index;        // the reference would panic; unreachable for n < 2^24
+    }
 
     const DevLight L = light_at(sc, index);                         // Scene::light_at for a per-lane index
     light_area = L.area;
@@ -852,7 +867,11 @@ RPT_DEV NeeQuery nee_query(const S& sc, const Q& q, v3 fhp, v3 ffnormal, Rng& rn
     n.light_area = 0.0f;
     n.ls.normal = mk3(0.0f, 0.0f, 0.0f); n.ls.emission = mk3(0.0f, 0.0f, 0.0f); n.ls.direction = mk3(0.0f, 0.0f, 0.0f);
     n.ls.dist = 0.0f; n.ls.pdf = 0.0f;
-    if (sc.n_lights == 0) return n;
+    if constexpr (MeshLights<S>::value) {
+        if (sc.n_pick == 0) return n;
+    } else {
+        if (sc.n_lights == 0) return n;
+    }
     v3 scatter_pos;
     bool facing;
     { RPT_PROF(PB_NEE_SAMPLE); facing = nee_sample<OFFSET>(sc, fhp, ffnormal, rng, scatter_pos, n.light_area, n.ls); }
@@ -973,7 +992,8 @@ RPT_DEV uint32_t path_trace_geom_split(const S& sc, const Q& q, PathRegs& p, Geo
     }
     if (e.is_emitter) {
         RPT_PROF(PB_FINALIZE);
-        p.radiance = p.radiance + hit_emission(sc, g) * p.throughput;                      // tracer.rs:74
+        if constexpr (MeshLights<S>::value) p.radiance = p.radiance + (mesh_light_hit_weight(sc, p.ray, p.ps, p.bounce, g) * hit_emission(sc, g)) * p.throughput;
+        else p.radiance = p.radiance + hit_emission(sc, g) * p.throughput;                 // tracer.rs:74
         // state.depth > 0 always holds (tracer.rs:57,80): the MIS weight is always applied
         float mis_weight = power_heuristic(p.ps.scatter_pdf, e.light_pdf);
         p.radiance = p.radiance + (mis_weight * e.light_emission) * p.throughput;
@@ -1067,13 +1087,15 @@ RPT_DEV bool path_shade_full(const S& sc, const Q& q, PathRegs& p, const GeomHit
         v3 emission;
         materials.fetch(sc, p.ray, g.code, ndd < 0.0f, mat, eta, emission);
         fr.spec_col = fr.sheen_col = mk3(0.0f, 0.0f, 0.0f);          // (not read: mat_spec_col)
+        static_assert(!MeshLights<S>::value, "a scene type with mesh lights reads its materials per hit");
         p.radiance = p.radiance + emission * p.throughput;
     } else {
         RPT_PROF(PB_FINALIZE);
         hit_material(sc, p.ray, g, mat);
         mat_finalize(mat);
         eta = (ndd < 0.0f) ? fdiv(1.0f, mat.ior) : mat.ior;
-        p.radiance = p.radiance + mat.emission * p.throughput;
+        if constexpr (MeshLights<S>::value) p.radiance = p.radiance + (mesh_light_hit_weight(sc, p.ray, p.ps, p.bounce, g) * mat.emission) * p.throughput;
+        else p.radiance = p.radiance + mat.emission * p.throughput;
     }
     const v3 fhp = cold ? mk3(cold->x, cold->y, cold->z) : (p.ray.o + p.ps.hit_dist * p.ray.d);
     if constexpr (M::kTable) {

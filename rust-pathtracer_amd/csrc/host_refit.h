@@ -34,6 +34,7 @@ struct RefitPlan {
     // kept for the life of the scene
     std::vector<uint32_t> mesh_first;          // mesh -> its first vertex in the concatenated vertex array; n_meshes + 1 entries
     std::vector<uint32_t> tri_first;           // mesh -> its first triangle in the flattened list; n_meshes + 1 entries (host_smooth.h)
+    std::vector<uint32_t> mesh_material;       // mesh -> rpt_mesh.material (host_light.h: a mesh light's emission)
     std::vector<uint8_t> referenced;           // concatenated vertex -> some triangle uses it (upload's 2^60 rule looks at those only)
     std::vector<float> mesh_max_abs;           // mesh -> the largest |coordinate| of its referenced vertices (0: none)
     std::vector<uint32_t> level_first;         // depth -> offset into level_nodes; n_levels + 1 entries
@@ -98,6 +99,7 @@ inline void build_refit_plan(const rpt_scene_desc* s, const HostBvh& bvh, RefitP
     plan.n_nodes = (uint32_t)bvh.nodes.size();
     plan.mesh_first.assign(s->n_meshes + 1u, 0u);
     plan.tri_first.assign(s->n_meshes + 1u, 0u);
+    plan.mesh_material.assign(s->n_meshes, 0u);
     plan.vertices.resize(3 * (size_t)n_vertices);
     plan.referenced.assign((size_t)n_vertices, 0);
     plan.mesh_max_abs.assign(s->n_meshes, 0.0f);
@@ -108,6 +110,7 @@ inline void build_refit_plan(const rpt_scene_desc* s, const HostBvh& bvh, RefitP
         const uint32_t first = plan.mesh_first[m];
         plan.mesh_first[m + 1u] = first + me.n_vertices;
         plan.tri_first[m + 1u] = plan.tri_first[m] + me.n_triangles;
+        plan.mesh_material[m] = me.material;
         if (me.n_vertices) memcpy(&plan.vertices[3 * (size_t)first], me.vertices, 12 * (size_t)me.n_vertices);
         for (size_t i = 0; i < 3 * (size_t)me.n_triangles; ++i, ++k) {
             flat[k] = first + me.indices[i];

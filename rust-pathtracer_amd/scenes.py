@@ -198,6 +198,35 @@ def mesh_scene(subdivisions=7, n_major=256, n_minor=128):
     return s
 
 
+def mesh_light_scene(sphere_light=False, lamp_emission=(40.0, 36.0, 30.0)):
+    """A small scene for mesh lights (include/rpt.h, "mesh lights"): a diffuse floor plane, a low-poly diffuse icosphere (mesh 0,
+    80 triangles) and above them a small emissive quad, the "lamp" (mesh 1, two triangles, 0.3 x 0.3 around y = 1.4, tilted a
+    little so that its triangles' boxes are not flat: a hit on a flat box passes include/rpt.h's point check by rounding alone) — the only light
+    unless `sphere_light` adds one spherical rpt_light to the side (then two lights are pickable once the lamp is ON).  A black
+    background, so every bit of radiance comes from the lamp (or the light); any_hit_uses_max_dist is set, as mesh lights need."""
+    import numpy as np
+    s = Scene()
+    s.camera = Pinhole((0.0, 0.5, 3.2), (0.0, 0.0, 0.0), 60.0)
+    s.any_hit_uses_max_dist = True                                  # (the background stays Scene()'s: constant black)
+    # Twelve bounces, not the reference's four: direct_light at a path's LAST bounce sees the lamp over one more segment than any hit
+    # of that path can, so with the lamp ON a frame holds one path length more than with it OFF.  Here that tail is far below what
+    # the tests that compare the two can resolve (the floor reflects 0.7 and most directions leave into the black background).
+    s.max_depth = 12
+    s.lights = [AnalyticalLight.spherical((-2.5, 1.5, 1.0), 0.25, (6.0, 6.0, 6.0))] if sphere_light else []
+    s.materials = [
+        full_material(rgb=(0.8, 0.3, 0.25), roughness=0.9),                                      # the object
+        full_material(rgb=(0.6, 0.6, 0.6), roughness=1.0, emission=tuple(lamp_emission)),        # the lamp
+        Material(rgb=(0.7, 0.7, 0.7), roughness=1.0),                                            # floor
+    ]
+    s.planes = [((0.0, 1.0, 0.0), (0.0, -0.6, 0.0), 0.0001, 2)]
+    v, t = icosphere(1, (0.0, 0.0, 0.0), 0.6)
+    s.meshes.append((v, t, 0))
+    h = 0.15
+    quad = np.array([[-h, 1.37, -h], [h, 1.43, -h], [h, 1.43, h], [-h, 1.37, h]], dtype=np.float32)
+    s.meshes.append((quad, np.array([[0, 1, 2], [0, 2, 3]], dtype=np.uint32), 1))
+    return s
+
+
 def mesh_scene_moved(scene, phase, seed=0x5EED0006):
     """-> new vertex arrays for `scene` (a mesh_scene(): the icosphere, then the torus), one per mesh, for Tracer.update_meshes: a
     radial ripple travelling over the icosphere — amplitude 0.25 * min(phase, 1) of its radius, six waves from pole to pole, a seeded
