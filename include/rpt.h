@@ -754,6 +754,100 @@ int rpt_set_mesh_lights(rpt_ctx* ctx, const rpt_mesh_light* items, uint32_t n_it
 int rpt_download_mesh_light_table(rpt_ctx* ctx, uint32_t mesh, uint64_t* cdf /* host, one per triangle of the mesh */,
                                   uint32_t n_triangles, int32_t* exponent, float* area);
 
+/* ---- mesh textures — PROJECT-DEFINED ----------------------------------------------------------------------------------------------
+ * Per mesh, a UV-mapped base colour: one RGBA8 image and one UV per vertex, sampled at the winning triangle and multiplied into the
+ * mesh material's rgb.  Every operation is stated, so that texels, lookups and frames stay checkable bit for bit
+ * (tests/test_gpu_mesh_texture.py holds them to a numpy restatement).  All arithmetic is f32, one rounding per operation, nothing
+ * contracted; the divide is the library's correctly rounded one, the power is rpt_powf of include/rpt_strict_math.h.
+ *
+ * Scope.  A textured mesh keeps its full-patch material.  At a winning triangle of that mesh only mat.rgb changes:
+ *     rgb.c = m.rgb[c] * tex.c                                       c = r, g, b; one product each
+ * Emission is never textured.  hit_emission, the sampler of mesh lights and its hit weight, the triangle test, the acceptance
+ * order, any_hit and the normals are unchanged.  One texture per mesh, one UV per vertex: a UV seam needs duplicated vertices, as
+ * any OBJ loader produces them.
+ *
+ * Decode, once per rpt_set_mesh_textures, on the device.  The input is RGBA8, alpha ignored, width * height * 4 bytes, row 0 first.
+ * The linear value L[k] of byte value k:
+ *     gamma == 1.0f:  L[k] = (float)k / 255.0f
+ *     otherwise:      L[0] = 0;  L[255] = 1;  L[k] = rpt_powf((float)k / 255.0f, gamma) for every other k
+ * The end points are by definition: nothing rests on pow(1, g).  A decoded texel is {L[R], L[G], L[B], 0}, four f32, 16 B: a filter
+ * tap is one gather.
+ *
+ * Lookup at the hit.  u and v are recomputed from the ray and the winning triangle's row exactly as "smooth mesh shading" does — the
+ * same operations, the same bits.  (sa, ta), (sb, tb), (sc, tc) are the UVs of the corners a, b, c.
+ *     w = (1 - u) - v
+ *     s = (w*sa + u*sb) + v*sc
+ *     t = (w*ta + u*tb) + v*tc
+ * Per axis — x from s with W = width, y from t with H = height — and W_f = (float)W:
+ *     REPEAT:   x = s - floorf(s)              (in [0, 1]; 1.0 is reached by rounding for a tiny negative s, and is legal)
+ *     CLAMP:    x = s < 0 ? 0 : (s > 1 ? 1 : s)
+ *     NEAREST:  i = (int32)floorf(x * W_f);    REPEAT: i == W -> 0;    CLAMP: i = min(i, W - 1)
+ *     BILINEAR: p = x * W_f - 0.5f  (two operations);  f0 = floorf(p);  fx = p - f0;  i0 = (int32)f0;  i1 = i0 + 1
+ *               REPEAT: i0 < 0 -> i0 + W;  i1 >= W -> i1 - W;          CLAMP: i0 = max(i0, 0);  i1 = min(i1, W - 1)
+ * Texel (i, j) is entry j * W + i; row j = 0 is t = 0: there is no flip.
+ *     NEAREST:  tex = texel(i, j)
+ *     BILINEAR: gx = 1 - fx;  gy = 1 - fy;  top = gx*c00 + fx*c10;  bot = gx*c01 + fx*c11;  tex = gy*top + fy*bot
+ * with c00 = texel(i0, j0), c10 = texel(i1, j0), c01 = texel(i0, j1), c11 = texel(i1, j1); every a*b + c*d is two products and one
+ * add, per component.  The statement is written once, in csrc/host_tex.h, which the kernels and the host reference both compile.
+ *
+ * rpt_set_mesh_textures sets or removes the texture of the named meshes of the uploaded scene, before or after any number of moves,
+ * rebuilds, shading or light changes; meshes not named keep theirs, and rpt_upload_scene leaves every mesh untextured and drops
+ * every texture table.  An item with width == height == 0 and texels == NULL removes its mesh's texture (its uvs are not read).
+ * Both arrays of an item are copied inside the call.  On return every texture is decoded on every device of the context
+ * (rpt_create_multi: all of them; one process per GPU: every rank makes the call itself, as for rpt_set_mesh_lights).  The checks,
+ * in this order, all on the host before any device is touched — a rejected call changes nothing, and rpt_last_error names the item:
+ *   RPT_ERR_INVALID_ARG  ctx is NULL;
+ *   RPT_ERR_NO_SCENE     no scene with meshes is uploaded;
+ *   RPT_ERR_UNSUPPORTED  the scene's meshes hold 2^32 vertices or more;
+ *   RPT_ERR_INVALID_ARG  items NULL with a non-zero count; then per item, in order: mesh >= n_meshes; a mesh named twice; and when
+ *                        setting: n_vertices differs from the mesh's; uvs NULL with a non-zero count; width or height 0 or above
+ *                        16384; texels NULL; wrap or filter neither constant; gamma not finite, <= 0 or > 16; a UV that is not
+ *                        finite or beyond 2^20 in magnitude (the message names the mesh and the vertex; the bound keeps floorf and
+ *                        the casts exact);
+ *   RPT_ERR_UNSUPPORTED  the scene's textures would hold more than 2^26 texels in all;
+ *   RPT_OK               n_items == 0: nothing is done;
+ *   RPT_ERR_HIP          a runtime call failed part-way: the context is left with NO scene, as for rpt_update_meshes.
+ * While some mesh is textured the scene renders through a kernel of its own — the mesh kernel's body with the lookup above, one
+ * form over the smooth scenes' tables (FLAT meshes through all-zero smooth bits) and one over the mesh lights' while some mesh is ON:
+ * textures compose with FLAT / SMOOTH and OFF / ON in every combination.  When the last texture is removed the context renders
+ * exactly as if the call had never been made — the same kernel, the same tables.  A scene on which the call was never made is
+ * untouched by all of this.
+ *
+ * Moves.  rpt_update_meshes, rpt_rebuild_meshes and both _device forms leave UVs and texels alone: no new launch inside a move.
+ * rpt_rebuild_meshes reorders slots and changes no textured frame: the lookup goes through the refit's slot -> vertex table and the
+ * flattened triangle index, never through slot order.
+ *
+ * rpt_download_mesh_texture copies the decoded texels the context holds for one textured mesh to host memory from its first device:
+ * width * height * 4 f32, row 0 first.  It follows rpt_download_mesh_normals: a mesh out of range, an untextured mesh (it says so), a
+ * size that is not the texture's or a NULL destination answer RPT_ERR_INVALID_ARG.  It never changes anything.
+ *
+ * Memory.  The call brings the refit's tables to every device as rpt_set_mesh_shading does.  While a mesh is textured every device
+ * holds, until the last texture is removed or the next rpt_upload_scene: 16 B per texel; 32 B per textured mesh; per triangle of the
+ * SCENE 4 B (which texture) and one bit; per vertex of the SCENE 8 B (its UV).  During a call, per device, the new tables beside the
+ * old ones, and 4 B per texel plus 1 KiB per image being set.  The host keeps 8 B per vertex of the scene.
+ *
+ * Timings (one MI355X, tools/mesh_bench.py --textures: scenes.mesh_scene, 393 216 triangles, 1920 x 1080 x 16 spp resident, untextured
+ * against a 1024 x 1024 BILINEAR / REPEAT texture on both meshes, alternating in one process, medians of 5): 0.824 Gsamples/s
+ * untextured, 0.797 textured (0.967); the textured kernels have the mesh kernel's VGPR count, so its occupancy.  The set call for both
+ * images (2 x 2^20 texels): 2.49 ms the first time, 1.09 ms again.  The four move calls take the same time textured and untextured
+ * (within 0.01 ms). */
+enum { RPT_TEX_WRAP_REPEAT = 0, RPT_TEX_WRAP_CLAMP = 1 };
+enum { RPT_TEX_FILTER_NEAREST = 0, RPT_TEX_FILTER_BILINEAR = 1 };
+
+typedef struct rpt_mesh_texture {
+    uint32_t mesh;                    /* index into the uploaded scene's rpt_scene_desc.meshes */
+    uint32_t n_vertices;              /* of `uvs`: the uploaded mesh's n_vertices */
+    const float* uvs;                 /* HOST, 2 floats per vertex, all of the mesh's vertices */
+    uint32_t width, height;
+    const uint8_t* texels;            /* HOST, RGBA8; width == height == 0 and texels == NULL: remove this mesh's texture */
+    uint32_t wrap, filter;            /* RPT_TEX_WRAP_*, RPT_TEX_FILTER_* */
+    float gamma;                      /* 1.0f: the bytes are linear; 2.2f: the usual decode of an sRGB-like image */
+} rpt_mesh_texture;
+
+int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t n_items);
+int rpt_download_mesh_texture(rpt_ctx* ctx, uint32_t mesh, float* texels /* host, width*height*4 f32, decoded */, uint32_t width,
+                              uint32_t height);
+
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)
  *   frames_done ColorBuffer.frames before the call; the caller adds `spp` afterwards

@@ -248,6 +248,17 @@ public:
         check(rpt_download_mesh_light_table(ctx_, mesh, t.cdf.data(), n_triangles, &t.exponent, &t.area), ctx_);
         return t;
     }
+    /// Mesh textures (rpt.h, "mesh textures"): a UV-mapped RGBA8 base colour per mesh, decoded on the device and multiplied into the
+    /// mesh material's rgb at every hit; an item without an image removes its mesh's texture; sync_scene() leaves every mesh untextured.
+    void set_mesh_textures(const std::vector<rpt_mesh_texture>& items) {
+        check(rpt_set_mesh_textures(ctx_, items.data(), (uint32_t)items.size()), ctx_);
+    }
+    /// The decoded texels the context holds for one textured mesh: width * height * 4 floats, row 0 first.
+    std::vector<float> mesh_texture(uint32_t mesh, uint32_t width, uint32_t height) {
+        std::vector<float> out(4 * (size_t)width * height);
+        check(rpt_download_mesh_texture(ctx_, mesh, out.data(), width, height), ctx_);
+        return out;
+    }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

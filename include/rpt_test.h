@@ -73,6 +73,12 @@ int rpt_debug_mesh_normal_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n,
  * no mesh is ON (that kernel does not run then). */
 int rpt_debug_mesh_light_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, uint32_t* out_dev, void* stream);
 
+/* The base colour a winning triangle is shaded with (include/rpt.h, "mesh textures"), through the hit_material the textured scenes'
+ * render kernels call: rays_dev as for rpt_debug_mesh_query (max_dist is not read); out_dev = n x 4 dwords {the nearest triangle's
+ * flattened index or 0xFFFFFFFF, the three words of mat.rgb (zeros when nothing is hit)}.  `flags`: RPT_MESH_QUERY_BRUTE or 0.
+ * RPT_ERR_NO_SCENE unless the uploaded scene has meshes; RPT_ERR_INVALID_ARG while no mesh is textured (those kernels do not run then). */
+int rpt_debug_mesh_texture_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
+
 /* The uploaded mesh scene's hierarchy (csrc/host_bvh.h): its interior nodes, the depth of its deepest leaf, and the host time its build
  * took in rpt_upload_scene — after rpt_rebuild_meshes the rebuilt hierarchy's, and the wall time of that call's device part.
  * RPT_ERR_NO_SCENE unless the uploaded scene has meshes.  (tools/mesh_bench.py) */
@@ -107,7 +113,9 @@ int rpt_debug_sched_read(rpt_ctx* ctx, uint32_t* out, uint32_t capacity_tiles, u
  * bit 3 the table by class of accepted set (5-12 primitives), bits 8-15 the number of classes then, bits 16-19 the SDF object's
  * compile-time primitive count, bit 20 the relaxed-arithmetic build (RPT_RENDER_FAST_MATH), bit 21 small scenes' compacting kernel
  * (else the class's megakernel), bit 22 its dense form (at most 3 072 workgroups), bit 23 the nested-loop kernel, bit 24 the class's
- * participating-media form (the scene has media: RPT_SCENE_MEDIA), bit 25 the mesh scene class's kernel (k_mesh.hip), bit 26 beside it its smooth-shading form (k_smooth.hip: some mesh is SMOOTH), bit 27 some mesh is ON (include/rpt.h, "mesh lights"): the kernel that ran is k_light.hip's, which serves flat and smooth meshes alike — with bit 26 set as well it is still that one kernel, shading the SMOOTH meshes through their per-triangle bit.  For tests that must know that the kernel they aim at is the one
+ * participating-media form (the scene has media: RPT_SCENE_MEDIA), bit 25 the mesh scene class's kernel (k_mesh.hip), bit 26 beside it its smooth-shading form (k_smooth.hip: some mesh is SMOOTH), bit 27 some mesh is ON (include/rpt.h, "mesh lights"): the kernel that ran is k_light.hip's, which serves flat and smooth meshes alike — with bit 26 set as well it is still that one kernel, shading the SMOOTH meshes through their per-triangle bit;
+ * bit 28 some mesh is textured (include/rpt.h, "mesh textures"): the kernel that ran is one of k_tex.hip's two, the one over the mesh
+ * lights' tables while bit 27 is set as well, else the one over the smooth scenes' tables.  For tests that must know that the kernel they aim at is the one
  * that ran. */
 int rpt_debug_kernel_choice(rpt_ctx* ctx, uint32_t* out);
 

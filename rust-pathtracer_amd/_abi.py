@@ -140,6 +140,16 @@ class rpt_mesh_light(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("mode", C.c_uint32)]
 
 
+RPT_TEX_WRAP_REPEAT, RPT_TEX_WRAP_CLAMP = 0, 1
+RPT_TEX_FILTER_NEAREST, RPT_TEX_FILTER_BILINEAR = 0, 1
+
+
+class rpt_mesh_texture(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("n_vertices", C.c_uint32), ("uvs", C.POINTER(C.c_float)),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("texels", C.POINTER(C.c_uint8)),
+                ("wrap", C.c_uint32), ("filter", C.c_uint32), ("gamma", C.c_float)]
+
+
 class rpt_scene_desc(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("flags", C.c_uint32),
@@ -194,6 +204,8 @@ SYMBOLS = {
     "rpt_download_mesh_normals": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "rpt_set_mesh_lights": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_light), C.c_uint32]),
     "rpt_download_mesh_light_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "rpt_set_mesh_textures": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_texture), C.c_uint32]),
+    "rpt_download_mesh_texture": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
     "rpt_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -229,6 +241,7 @@ TEST_SYMBOLS = {
     "rpt_debug_mesh_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rpt_debug_mesh_normal_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rpt_debug_mesh_light_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "rpt_debug_mesh_texture_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rpt_debug_mesh_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "rpt_debug_mesh_walk": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rpt_debug_mesh_tables": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -498,6 +498,46 @@ class Tracer:
         check(lib().rpt_download_mesh_light_table(self._h, int(m), cdf.ctypes.data, n, C.byref(e), C.byref(area)), self._h)
         return cdf, int(e.value), np.float32(area.value)
 
+    def set_mesh_textures(self, items):
+        """Mesh textures (include/rpt.h, "mesh textures"): `items` maps a mesh's index in scene().meshes to None — the mesh loses its
+        texture — or to a dict with "uvs" (n_vertices, 2) float32, "texels" (height, width, 4) uint8 RGBA with row 0 at t = 0, and
+        optionally "wrap" ("repeat" / "clamp"), "filter" ("bilinear" / "nearest") and "gamma" (1.0: the bytes are linear).  The
+        library decodes the image on the device and multiplies it into the mesh material's rgb at every hit.  Meshes not named
+        keep their texture; upload_scene() leaves every mesh untextured again, as in C."""
+        wraps = {"repeat": _abi.RPT_TEX_WRAP_REPEAT, "clamp": _abi.RPT_TEX_WRAP_CLAMP}
+        filters = {"nearest": _abi.RPT_TEX_FILTER_NEAREST, "bilinear": _abi.RPT_TEX_FILTER_BILINEAR}
+        items = sorted(items.items())
+        its = (_abi.rpt_mesh_texture * max(1, len(items)))()
+        keep = []
+        for it, (m, tex) in zip(its, items):
+            it.mesh = int(m)
+            if tex is None:
+                continue
+            wrap, filt = tex.get("wrap", "repeat"), tex.get("filter", "bilinear")
+            if wrap not in wraps or filt not in filters:
+                raise ValueError("mesh %d: wrap must be \"repeat\" or \"clamp\" and filter \"nearest\" or \"bilinear\", not %r / %r" % (m, wrap, filt))
+            texels = np.ascontiguousarray(tex["texels"], dtype=np.uint8)
+            if texels.ndim != 3 or texels.shape[2] != 4:
+                raise ValueError("mesh %d: texels must have the shape (height, width, 4)" % m)
+            uvs = np.ascontiguousarray(tex["uvs"], dtype=np.float32).reshape(-1, 2)
+            keep.append((texels, uvs))
+            it.n_vertices, it.uvs = uvs.shape[0], uvs.ctypes.data_as(C.POINTER(C.c_float))
+            it.height, it.width, it.texels = texels.shape[0], texels.shape[1], texels.ctypes.data_as(C.POINTER(C.c_uint8))
+            it.wrap, it.filter, it.gamma = wraps[wrap], filters[filt], float(tex.get("gamma", 1.0))
+        self._checked_move(lib().rpt_set_mesh_textures(self._h, its, len(items)))
+        sizes = self.__dict__.setdefault("_texture_sizes", {})
+        for it, (m, tex) in zip(its, items):
+            sizes[int(m)] = (it.width, it.height)
+
+    def mesh_texture(self, m, width=None, height=None):
+        """The decoded texels the context holds for the textured mesh `m` (rpt_download_mesh_texture): a new float32 array of shape
+        (height, width, 4), linear values, the fourth 0.  Without a size: the one set_mesh_textures last gave the mesh."""
+        if width is None or height is None:
+            width, height = self.__dict__.get("_texture_sizes", {}).get(int(m), (0, 0))
+        out = np.empty((int(height), int(width), 4), np.float32)
+        check(lib().rpt_download_mesh_texture(self._h, int(m), out.ctypes.data, int(width), int(height)), self._h)
+        return out
+
     def _refresh_stale_meshes(self):
         """scene().meshes' vertex arrays that a device-source call left stale, read back once (only before an upload)."""
         for m in sorted(self._stale_meshes):

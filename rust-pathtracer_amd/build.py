@@ -71,6 +71,15 @@ def light_lib_of(lib):
 
 LIGHT_LIB = light_lib_of(LIB)
 
+
+# The kernels of mesh textures (k_tex.hip: meshtex_*) are an eighth, again named, linked and found the same way:
+# tests/test_mesh_texture_host.py keeps its census.
+def tex_lib_of(lib):
+    return os.path.splitext(os.path.abspath(lib))[0] + "_tex.so"
+
+
+TEX_LIB = tex_lib_of(LIB)
+
 # One translation unit per kernel class (csrc/kernel_common.h says what each build of them is):
 #   strict    k_small tracks the range tests of the short divide / sqrt; k_compact, k_sdf, k_large, k_mesh test next to every operation
 #   relaxed   the four render TUs once more with hipcc's fast divide / sqrt and FMA contraction: what RPT_RENDER_FAST_MATH selects
@@ -88,6 +97,7 @@ OBJECTS = [
     ("k_move", "k_move.hip", [], "move"),                          # the device-source calls' check and apply of new positions; MOVE_LIB
     ("k_smooth", "k_smooth.hip", PEROP, "smooth"),                 # smooth mesh shading: the normals' two passes and the mesh kernel's smooth form; SMOOTH_LIB
     ("k_light", "k_light.hip", PEROP, "light"),                    # mesh lights: the ON meshes' tables and the mesh kernel's form that samples them; LIGHT_LIB
+    ("k_tex", "k_tex.hip", PEROP, "tex"),                          # mesh textures: the decode and the mesh kernel's two textured forms; TEX_LIB
     ("k_small_fast", "k_small.hip", RELAXED, "both"),
     ("k_compact_fast", "k_compact.hip", RELAXED, "both"),
     ("k_sdf_fast", "k_sdf.hip", RELAXED, "both"),
@@ -149,12 +159,12 @@ def _deps():
             [os.path.abspath(__file__)])
 
 
-def needs_build(lib=LIB, mesh_lib=None, refit_lib=None, build_lib=None, move_lib=None, smooth_lib=None, light_lib=None):
-    """`mesh_lib`, `refit_lib`, `build_lib`, `move_lib`, `smooth_lib`, `light_lib`: the code object libraries `lib` loads (default
-    mesh_lib_of(lib), refit_lib_of(lib), build_lib_of(lib), move_lib_of(lib), smooth_lib_of(lib), light_lib_of(lib); the test build
-    loads the product's)."""
+def needs_build(lib=LIB, mesh_lib=None, refit_lib=None, build_lib=None, move_lib=None, smooth_lib=None, light_lib=None, tex_lib=None):
+    """`mesh_lib`, `refit_lib`, `build_lib`, `move_lib`, `smooth_lib`, `light_lib`, `tex_lib`: the code object libraries `lib` loads
+    (default mesh_lib_of(lib), refit_lib_of(lib), build_lib_of(lib), move_lib_of(lib), smooth_lib_of(lib), light_lib_of(lib),
+    tex_lib_of(lib); the test build loads the product's)."""
     parts = [lib, mesh_lib or mesh_lib_of(lib), refit_lib or refit_lib_of(lib), build_lib or build_lib_of(lib), move_lib or move_lib_of(lib),
-             smooth_lib or smooth_lib_of(lib), light_lib or light_lib_of(lib)]
+             smooth_lib or smooth_lib_of(lib), light_lib or light_lib_of(lib), tex_lib or tex_lib_of(lib)]
     if not all(os.path.exists(p) for p in parts):
         return True
     t = min(os.path.getmtime(p) for p in parts)
@@ -166,7 +176,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
     `extra_flags` / `lib` / `objdir_name`: experiment builds next to the product library (tools/); `only`: recompile just these
     objects (the others are taken from `objdir_name`/ as they are — or, if missing there, from the product's build/)."""
     if not force and not needs_build(lib) and (test_lib is None or not needs_build(test_lib, mesh_lib_of(lib), refit_lib_of(lib), build_lib_of(lib), move_lib_of(lib),
-                                                                         smooth_lib_of(lib), light_lib_of(lib))):
+                                                                         smooth_lib_of(lib), light_lib_of(lib), tex_lib_of(lib))):
         return lib
     objdir = os.path.join(HERE, objdir_name)
     os.makedirs(objdir, exist_ok=True)
@@ -196,8 +206,9 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
     if failed:
         raise RuntimeError("build.py: compilation failed:\n" + "\n".join(failed))
     mesh_lib, refit_lib, build_lib, move_lib, smooth_lib = mesh_lib_of(lib), refit_lib_of(lib), build_lib_of(lib), move_lib_of(lib), smooth_lib_of(lib)
-    light_lib = light_lib_of(lib)
-    for part, kind in ((mesh_lib, "mesh"), (refit_lib, "refit"), (build_lib, "bvhbuild"), (move_lib, "move"), (smooth_lib, "smooth"), (light_lib, "light")):
+    light_lib, tex_lib = light_lib_of(lib), tex_lib_of(lib)
+    for part, kind in ((mesh_lib, "mesh"), (refit_lib, "refit"), (build_lib, "bvhbuild"), (move_lib, "move"), (smooth_lib, "smooth"), (light_lib, "light"),
+                       (tex_lib, "tex")):
         link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w == kind] + [
             "-Wl,-soname," + os.path.basename(part), "-o", part]
         if verbose:
@@ -208,7 +219,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
             continue
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w in kinds] + [
-            mesh_lib, refit_lib, build_lib, move_lib, smooth_lib, light_lib, "-Wl,-rpath,$ORIGIN", "-ldl", "-o", out]
+            mesh_lib, refit_lib, build_lib, move_lib, smooth_lib, light_lib, tex_lib, "-Wl,-rpath,$ORIGIN", "-ldl", "-o", out]
         if verbose:
             print(" ".join(link))
         subprocess.run(link, check=True, cwd=CSRC)

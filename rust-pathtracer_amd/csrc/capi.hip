@@ -24,6 +24,7 @@
 #include "host_move.h"
 #include "host_refit.h"
 #include "host_smooth.h"
+#include "host_tex.h"
 #include "host_upload.h"
 #include "knobs.h"
 #include "launch.h"
@@ -31,6 +32,7 @@
 #include "launch_light.h"
 #include "launch_move.h"
 #include "launch_smooth.h"
+#include "launch_tex.h"
 #ifdef RPT_TEST_HOOKS
 #include "../../include/rpt_test.h"
 #endif
@@ -59,6 +61,7 @@ struct DevState {
     void* move_stage = nullptr;       // ... and copies of sources that lie on another device (12 B per vertex of the scene), made on demand
     void* smooth = nullptr;           // smooth shading's tables (host_smooth.h, SmoothLayout): while some mesh is SMOOTH (rpt_set_mesh_shading)
     void* light = nullptr;            // mesh lights' tables (host_light.h, LightLayout): while some mesh is ON (rpt_set_mesh_lights)
+    void* tex = nullptr;              // mesh textures' tables (host_tex.h, TexLayout): while some mesh is textured (rpt_set_mesh_textures)
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -105,6 +108,7 @@ struct rpt_ctx {
     rpthost::RefitPlan refit;         // a mesh scene's plan for rpt_update_meshes (host_refit.h)
     rpthost::SmoothPlan smooth;       // its meshes' shading modes and the sizes of every device's smooth tables (host_smooth.h)
     rpthost::LightPlan light;         // which of its meshes are lights and the sizes of every device's light tables (host_light.h)
+    rpthost::TexPlan tex;             // which of its meshes are textured, their UVs and the sizes of every device's texture tables (host_tex.h)
     // resident ColorBuffer (buffer.rs:6-14): pixels as per-rank tiles + frames
     uint32_t res_w = 0, res_h = 0, res_tile_rows = 0, res_rows_padded = 0;
     uint64_t res_frames = 0;
@@ -288,6 +292,7 @@ static void free_mesh_work(DevState& d)
     if (d.move_stage) { (void)hipFree(d.move_stage); d.move_stage = nullptr; }
     if (d.smooth) { (void)hipFree(d.smooth); d.smooth = nullptr; }
     if (d.light) { (void)hipFree(d.light); d.light = nullptr; }
+    if (d.tex) { (void)hipFree(d.tex); d.tex = nullptr; }
     d.refit_full = false;
     d.build_temp_bytes = 0;
 }
@@ -502,6 +507,47 @@ static SceneMeshLight light_scene_of(const rpt_ctx* ctx, const DevState& d)
     return s;
 }
 
+// What the textured forms add to their base: pointers into device d's texture tables (ctx->tex says their sizes).
+template <class Base> static void bind_tex(const rpt_ctx* ctx, const DevState& d, SceneMeshTexT<Base>& s)
+{
+    const rpthost::TexPlan& tp = ctx->tex;
+    const rpthost::TexLayout tl(tp.n_tex(), tp.n_tris, tp.n_vertices, tp.n_texels);
+    const unsigned char* base = static_cast<const unsigned char*>(d.tex);
+    s.tex_desc = reinterpret_cast<const rpthost::TexDesc*>(base + tl.off_desc);
+    s.tri_tex = reinterpret_cast<const uint32_t*>(base + tl.off_tri_tex);
+    s.uvs = reinterpret_cast<const float*>(base + tl.off_uvs);
+    s.texels = reinterpret_cast<const rpthost::TexTexel*>(base + tl.off_texels);
+}
+
+// A mesh scene's kernel argument while some mesh is textured and none is ON: device d's scene, its smooth tables if some mesh is
+// SMOOTH (else the refit's slot_vertex and all-zero smooth bits: every hit takes the flat normal), and its texture tables.
+static SceneMeshTex tex_scene_of(const rpt_ctx* ctx, const DevState& d)
+{
+    const rpthost::TexPlan& tp = ctx->tex;
+    const rpthost::RefitLayout rl(ctx->refit.n_vertices(), 0, 0);
+    const rpthost::TexLayout tl(tp.n_tex(), tp.n_tris, tp.n_vertices, tp.n_texels);
+    SceneMeshTex s{};
+    if (d.smooth && ctx->smooth.any()) {
+        static_cast<SceneMeshSmooth&>(s) = smooth_scene_of(ctx, d);
+    } else {
+        static_cast<SceneMesh&>(s) = d.scene;
+        s.slot_vertex = reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(d.refit) + rl.off_slot_vertex);
+        s.vnormals = nullptr;                                       // (not read: no smooth bit is set)
+        s.smooth_bits = reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(d.tex) + tl.off_flat_bits);
+    }
+    bind_tex(ctx, d, s);
+    return s;
+}
+
+// ... and while some mesh is ON as well: light_scene_of's argument plus the texture tables.
+static SceneMeshLightTex light_tex_scene_of(const rpt_ctx* ctx, const DevState& d)
+{
+    SceneMeshLightTex s{};
+    static_cast<SceneMeshLight&>(s) = light_scene_of(ctx, d);
+    bind_tex(ctx, d, s);
+    return s;
+}
+
 // One render launch sequence on one device.
 static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t width, uint32_t height, uint64_t frames_done, uint32_t spp,
                          uint64_t seed, uint32_t flags, uint32_t tile_rows, uint32_t rank, uint32_t world, hipStream_t stream)
@@ -518,6 +564,7 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     SceneMesh scm = d.scene;
     const bool smooth = kind == SceneKind::mesh && d.smooth && d.refit && ctx->smooth.any();      // some mesh is SMOOTH: k_smooth.hip's form
     const bool lights = kind == SceneKind::mesh && d.light && d.refit && ctx->light.any();        // some mesh is ON: k_light.hip's form, for flat and smooth meshes alike
+    const bool textured = kind == SceneKind::mesh && d.tex && d.refit && ctx->tex.any();          // some mesh is textured: k_tex.hip's forms, over either of the two above
     scs.cam = scl.cam = scm.cam = make_camera(ctx->scene.camera, (float)width, (float)height);
     const bool in_hbm = kind == SceneKind::large || kind == SceneKind::mesh;     // the scene's tables are in device memory
     const bool has_sdf = !in_hbm && scs.sdf.n_prims > 0;
@@ -579,9 +626,21 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
                         (fast ? 1u << 20 : 0u) | (rp.compact && !nested ? 1u << 21 : 0u) |
                         (rp.compact && !nested && nblocks <= kCompactDenseMaxBlocks ? 1u << 22 : 0u) | (nested ? 1u << 23 : 0u) |
                         (media ? 1u << 24 : 0u) | (kind == SceneKind::mesh ? 1u << 25 : 0u) |
-                        (smooth ? 1u << 26 : 0u) | (lights ? 1u << 27 : 0u);
+                        (smooth ? 1u << 26 : 0u) | (lights ? 1u << 27 : 0u) | (textured ? 1u << 28 : 0u);
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
+        if (textured && lights) {
+            SceneMeshLightTex smt = light_tex_scene_of(ctx, d);
+            smt.cam = scm.cam;
+            smt.flags = scm.flags;
+            return rptlaunch::render_mesh_light_tex(smt, rp, grid, stream);
+        }
+        if (textured) {
+            SceneMeshTex smt = tex_scene_of(ctx, d);
+            smt.cam = scm.cam;
+            smt.flags = scm.flags;
+            return rptlaunch::render_mesh_tex(smt, rp, grid, stream);
+        }
         if (lights) {
             SceneMeshLight sml = light_scene_of(ctx, d);
             sml.cam = scm.cam;
@@ -971,6 +1030,7 @@ static void commit_scene(rpt_ctx* ctx, SceneImage& img, const std::vector<void*>
     ctx->refit = std::move(img.refit);
     ctx->smooth = rpthost::SmoothPlan();                            // every mesh FLAT
     ctx->light = rpthost::LightPlan();                              // every mesh OFF
+    ctx->tex = rpthost::TexPlan();                                  // every mesh untextured
 }
 
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
@@ -1001,6 +1061,7 @@ static void drop_scene(rpt_ctx* ctx)
     ctx->refit = rpthost::RefitPlan();
     ctx->smooth = rpthost::SmoothPlan();
     ctx->light = rpthost::LightPlan();
+    ctx->tex = rpthost::TexPlan();
 }
 
 // Where the named meshes' new positions come from: host arrays (rpt_update_meshes, rpt_rebuild_meshes) or device arrays through a
@@ -1670,6 +1731,137 @@ int rpt_download_mesh_light_table(rpt_ctx* ctx, uint32_t mesh, uint64_t* cdf, ui
     return RPT_OK;
 }
 
+// ---- rpt_set_mesh_textures / rpt_download_mesh_texture (include/rpt.h, "mesh textures") -------------------------------------------
+// One device's part: wait for its earlier work (a launch may still read the old tables), make its refit tables if it has none, make
+// the new tables, copy the kept meshes' texels over from the old ones on the device, decode the named meshes' images, drop the old
+// tables, and wait.  ctx->tex is already the new plan; `old` is the plan the old tables were made by.
+static int tex_device(rpt_ctx* ctx, DevState& d, const rpthost::TexPlan& old, const rpt_mesh_texture* items, uint32_t n_items)
+{
+    const rpthost::TexPlan& tp = ctx->tex;
+    const rpthost::TexLayout tl(tp.n_tex(), tp.n_tris, tp.n_vertices, tp.n_texels);
+    const rpthost::TexLayout ol(old.n_tex(), old.n_tris, old.n_vertices, old.n_texels);
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    RPT_CHECK_RC(ensure_refit(ctx, d));
+    void* fresh = nullptr;
+    void* stage = nullptr;
+    RPT_HIP_CHECK(ctx, hipMalloc(&fresh, tl.total));
+    // the named images' bytes and one L table each, in one allocation that lives until the decodes have run
+    size_t stage_bytes = 0;
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (items[i].width) stage_bytes += 1024 + (((size_t)items[i].width * items[i].height * 4 + 15) & ~(size_t)15);
+    const auto fail = [&](int rc) { (void)hipFree(fresh); if (stage) (void)hipFree(stage); return rc; };
+    const auto work = [&]() -> int {
+        if (stage_bytes) RPT_HIP_CHECK(ctx, hipMalloc(&stage, stage_bytes));
+        unsigned char* base = static_cast<unsigned char*>(fresh);
+        const auto put = [&](size_t off, const void* p, size_t bytes) {
+            return bytes == 0 ? hipSuccess : hipMemcpyAsync(base + off, p, bytes, hipMemcpyHostToDevice, d.stream);
+        };
+        RPT_HIP_CHECK(ctx, put(tl.off_desc, tp.desc.data(), 4 * tp.desc.size()));
+        RPT_HIP_CHECK(ctx, put(tl.off_tri_tex, tp.tri_tex.data(), 4 * tp.tri_tex.size()));
+        RPT_HIP_CHECK(ctx, put(tl.off_uvs, tp.uvs.data(), 4 * tp.uvs.size()));
+        if (tl.off_texels > tl.off_flat_bits) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + tl.off_flat_bits, 0, tl.off_texels - tl.off_flat_bits, d.stream));
+        std::vector<uint8_t> named(tp.image.size(), 0);
+        size_t at = 0;
+        for (uint32_t i = 0; i < n_items; ++i) {
+            const rpt_mesh_texture& it = items[i];
+            named[it.mesh] = 1;
+            if (!it.width) continue;
+            const rpthost::TexImage& im = tp.image[it.mesh];
+            const size_t n = (size_t)im.width * im.height;
+            unsigned char* at_dev = static_cast<unsigned char*>(stage) + at;
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(at_dev + 1024, it.texels, 4 * n, hipMemcpyHostToDevice, d.stream));
+            RPT_HIP_CHECK(ctx, rptlaunch::tex_decode(at_dev + 1024, reinterpret_cast<float*>(at_dev),
+                                                     reinterpret_cast<rpthost::TexTexel*>(base + tl.off_texels) + im.first, (uint32_t)n, im.gamma, d.stream));
+            at += 1024 + ((4 * n + 15) & ~(size_t)15);
+        }
+        for (uint32_t m = 0; m < tp.image.size(); ++m) {
+            if (named[m] || !tp.image[m].width) continue;           // a mesh not named keeps its texture: the decoded texels move on the device
+            if (!d.tex || !old.textured(m)) { set_err(ctx, "rpt_set_mesh_textures: device %d holds no texels for mesh %u", d.device, m); return RPT_ERR_HIP; }
+            const size_t n = (size_t)tp.image[m].width * tp.image[m].height;
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + tl.off_texels + 16 * (size_t)tp.image[m].first,
+                                              static_cast<const unsigned char*>(d.tex) + ol.off_texels + 16 * (size_t)old.image[m].first, 16 * n,
+                                              hipMemcpyDeviceToDevice, d.stream));
+        }
+        RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+        return RPT_OK;
+    };
+    const int rc = work();
+    if (rc != RPT_OK) return fail(rc);
+    if (stage) (void)hipFree(stage);
+    if (d.tex) (void)hipFree(d.tex);
+    d.tex = fresh;
+    return RPT_OK;
+}
+
+int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t n_items)
+{
+    using namespace rpthost;
+    if (!ctx) { set_err(nullptr, "rpt_set_mesh_textures: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    std::vector<TexImage> image;
+    std::string why;
+    const int rc = check_mesh_textures(ctx->refit, ctx->scene.kind == SceneKind::mesh, items, n_items, ctx->tex.image, image, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    if (n_items == 0) return RPT_OK;
+    bool any = false;
+    for (const TexImage& im : image) any = any || im.width != 0u;
+    DeviceGuard guard(ctx->devs[0].device);
+    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
+    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_textures: cannot select device %d", ctx->devs[0].device);
+    if (rc_dev == RPT_OK && !any) {                                 // no mesh textured (again): the context is what it was before the first call
+        for (DevState& d : ctx->devs) {
+            if (!d.tex) continue;
+            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
+                set_err(ctx, "rpt_set_mesh_textures: cannot wait for device %d", d.device);
+                rc_dev = RPT_ERR_HIP;
+                break;
+            }
+            (void)hipFree(d.tex);
+            d.tex = nullptr;
+        }
+        if (rc_dev == RPT_OK) { ctx->tex = TexPlan(); return RPT_OK; }
+    }
+    TexPlan old;
+    if (rc_dev == RPT_OK) {
+        std::vector<float> uvs = ctx->tex.uvs;
+        tex_merge_uvs(ctx->refit, items, n_items, uvs);
+        old = std::move(ctx->tex);
+        build_tex_plan(ctx->refit, std::move(image), std::move(uvs), ctx->tex);
+    }
+    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
+        DevState& d = ctx->devs[i];
+        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_textures: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
+        else rc_dev = tex_device(ctx, d, old, items, n_items);
+    }
+    if (rc_dev != RPT_OK) {
+        const std::string first = ctx->err;
+        drop_scene(ctx);
+        set_err(ctx, "%s; the context now holds no scene", first.c_str());
+        return rc_dev;
+    }
+    ctx->refit.release_staging();                                   // every device holds the refit tables
+    ctx->tex.release_staging();
+    return RPT_OK;
+}
+
+int rpt_download_mesh_texture(rpt_ctx* ctx, uint32_t mesh, float* texels, uint32_t width, uint32_t height)
+{
+    if (!ctx) { set_err(nullptr, "rpt_download_mesh_texture: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_mesh_texture: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    const rpthost::RefitPlan& plan = ctx->refit;
+    if (!plan.ok) { set_err(ctx, "rpt_download_mesh_texture: the scene's meshes hold 2^32 vertices or more"); return RPT_ERR_UNSUPPORTED; }
+    if (mesh >= plan.n_meshes()) { set_err(ctx, "rpt_download_mesh_texture: mesh %u out of range (the scene has %u)", mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
+    const DevState& d = ctx->devs[0];
+    const rpthost::TexPlan& tp = ctx->tex;
+    if (!tp.textured(mesh) || !d.tex) { set_err(ctx, "rpt_download_mesh_texture: mesh %u is untextured: the context holds no texels for it (rpt_set_mesh_textures)", mesh); return RPT_ERR_INVALID_ARG; }
+    const rpthost::TexImage& im = tp.image[mesh];
+    if (width != im.width || height != im.height) { set_err(ctx, "rpt_download_mesh_texture: mesh %u: %u x %u is not its texture's %u x %u", mesh, width, height, im.width, im.height); return RPT_ERR_INVALID_ARG; }
+    if (!texels) { set_err(ctx, "rpt_download_mesh_texture: texels is NULL"); return RPT_ERR_INVALID_ARG; }
+    RPT_ON_DEVICE(ctx);
+    const rpthost::TexLayout tl(tp.n_tex(), tp.n_tris, tp.n_vertices, tp.n_texels);
+    RPT_HIP_CHECK(ctx, hipMemcpy(texels, static_cast<const unsigned char*>(d.tex) + tl.off_texels + 16 * (size_t)im.first, 16 * (size_t)im.width * im.height, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
 uint32_t rpt_tile_row_count(uint32_t height, uint32_t tile_rows, uint32_t rank, uint32_t world)
 {
     return tile_row_count(height, tile_rows, rank, world);
@@ -2259,6 +2451,18 @@ int rpt_debug_mesh_light_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, u
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_light_sample(light_scene_of(ctx, ctx->devs[0]), in_dev, out_dev, n, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_debug_mesh_texture_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_texture_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_texture_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    if (!rays_dev || !out_dev || (flags & ~(uint32_t)RPT_MESH_QUERY_BRUTE)) { set_err(ctx, "rpt_debug_mesh_texture_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->tex.any() || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_texture_query: no mesh is textured"); return RPT_ERR_INVALID_ARG; }
+    if (n == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_texture_query(tex_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
 }
 

@@ -227,6 +227,73 @@ def mesh_light_scene(sphere_light=False, lamp_emission=(40.0, 36.0, 30.0)):
     return s
 
 
+def checker_texture(w, h, colour_a=(255, 255, 255), colour_b=(40, 40, 40), cells=8):
+    """-> [h, w, 4] uint8 RGBA: a checker of `cells` x `cells` fields over the whole image in two colours, alpha 255; texel (0, 0)
+    has colour_a."""
+    import numpy as np
+    j, i = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    odd = ((i * cells // max(w, 1)) + (j * cells // max(h, 1))) % 2 == 1
+    out = np.empty((h, w, 4), np.uint8)
+    out[..., :3] = np.where(odd[..., None], np.asarray(colour_b, np.uint8), np.asarray(colour_a, np.uint8))
+    out[..., 3] = 255
+    return out
+
+
+def spherical_uvs(vertices, center):
+    """-> [N, 2] f32: longitude / latitude UVs of `vertices` about `center`: s = atan2(z, x) / 2 pi + 0.5, t = acos(y / r) / pi.  (A
+    triangle that crosses the s = 0 / 1 meridian interpolates the long way round: a seam needs duplicated vertices.)"""
+    import numpy as np
+    q = np.asarray(vertices, np.float64).reshape(-1, 3) - np.asarray(center, np.float64)
+    r = np.sqrt((q * q).sum(1))
+    r = np.where(r > 0.0, r, 1.0)
+    s = np.arctan2(q[:, 2], q[:, 0]) / (2.0 * np.pi) + 0.5
+    t = np.arccos(np.clip(q[:, 1] / r, -1.0, 1.0)) / np.pi
+    return np.stack([s, t], 1).astype(np.float32)
+
+
+def torus_uv(major=0.7, minor=0.3, n_major=128, n_minor=64, center=(0.0, 0.0, 0.0)):
+    """-> (vertices, indices, uvs): torus() with its seam rows duplicated — (n_major + 1) x (n_minor + 1) vertices, the last row and
+    column repeating the first one's positions — so that s = i / n_major and t = j / n_minor are continuous across every triangle."""
+    import numpy as np
+    u = np.arange(n_major + 1) * (2.0 * np.pi / n_major)
+    w = np.arange(n_minor + 1) * (2.0 * np.pi / n_minor)
+    u[-1], w[-1] = 0.0, 0.0                                           # the seam's positions are the first row's, bit for bit
+    uu, ww = np.meshgrid(u, w, indexing="ij")
+    ring = major + minor * np.cos(ww)
+    pts = np.stack([ring * np.cos(uu), ring * np.sin(uu), minor * np.sin(ww)], -1).reshape(-1, 3) + np.asarray(center)
+    i, j = np.meshgrid(np.arange(n_major), np.arange(n_minor), indexing="ij")
+    row = n_minor + 1
+    a, b, c, d = i * row + j, (i + 1) * row + j, (i + 1) * row + j + 1, i * row + j + 1
+    idx = np.concatenate([np.stack([a, b, c], -1).reshape(-1, 3), np.stack([a, c, d], -1).reshape(-1, 3)])
+    si, tj = np.meshgrid(np.arange(n_major + 1) / n_major, np.arange(n_minor + 1) / n_minor, indexing="ij")
+    return pts.astype(np.float32), idx.astype(np.uint32), np.stack([si, tj], -1).reshape(-1, 2).astype(np.float32)
+
+
+def mesh_texture_scene():
+    """-> (scene, uvs): a small scene for mesh textures (include/rpt.h, "mesh textures"): mesh_light_scene()'s floor and icosphere
+    (mesh 0, 80 triangles, spherical_uvs) and a two-triangle quad (mesh 1, 1.2 x 1.2, standing behind and beside the icosphere,
+    tilted a little) whose UVs run from -1.5 to 2.5, so that both wraps show; one spherical light and a grey constant
+    background.  `uvs`: one [n_vertices, 2] f32 array per mesh."""
+    import numpy as np
+    s = Scene()
+    s.camera = Pinhole((0.0, 0.5, 3.2), (0.0, 0.0, 0.0), 60.0)
+    s.any_hit_uses_max_dist = True
+    s.background = dict(kind=_abi.RPT_BG_CONSTANT, colour_a=(0.6, 0.6, 0.6), colour_b=(0.0, 0.0, 0.0), gamma=2.2, scale=1.0)
+    s.lights = [AnalyticalLight.spherical((-2.5, 1.5, 1.0), 0.25, (6.0, 6.0, 6.0))]
+    s.materials = [
+        full_material(rgb=(0.8, 0.7, 0.6), roughness=0.9),                                       # the object
+        full_material(rgb=(0.9, 0.9, 0.9), roughness=0.7),                                       # the quad
+        Material(rgb=(0.7, 0.7, 0.7), roughness=1.0),                                            # floor
+    ]
+    s.planes = [((0.0, 1.0, 0.0), (0.0, -0.6, 0.0), 0.0001, 2)]
+    v, t = icosphere(1, (0.0, 0.0, 0.0), 0.6)
+    s.meshes.append((v, t, 0))
+    quad = np.array([[0.5, -0.5, -0.9], [1.7, -0.5, -0.6], [1.7, 0.7, -0.55], [0.5, 0.7, -0.85]], dtype=np.float32)
+    s.meshes.append((quad, np.array([[0, 1, 2], [0, 2, 3]], dtype=np.uint32), 1))
+    quad_uv = np.array([[-1.5, -1.5], [2.5, -1.5], [2.5, 2.5], [-1.5, 2.5]], dtype=np.float32)
+    return s, [spherical_uvs(v, (0.0, 0.0, 0.0)), quad_uv]
+
+
 def mesh_scene_moved(scene, phase, seed=0x5EED0006):
     """-> new vertex arrays for `scene` (a mesh_scene(): the icosphere, then the torus), one per mesh, for Tracer.update_meshes: a
     radial ripple travelling over the icosphere — amplitude 0.25 * min(phase, 1) of its radius, six waves from pole to pole, a seeded

@@ -1,0 +1,182 @@
+"""Textured mesh renders held to tests/pt_f64.py, the float64 restatement of one pixel-sample (include/rpt.h, "mesh textures"):
+TexMeshDescScene is test_gpu_mesh_smooth_f64.SmoothMeshDescScene — shading flat, as the scenes here are — with the winning
+triangle's rgb restated in float64: the decode by P.powf with the end-point rule, the UV interpolation with the triangle test's u
+and v, the wrap and the filter.  One-sample renders are compared sample by sample with test_path_f64's TAU / REL_CLEAN /
+NEAR_TIE_MAX over test_gpu_mesh_f64's own draws, 200 pixels x 3 seeds x 2 scenes (needs an MI355X).  Every mesh carries a 5 x 3
+two-colour texture over spherical UVs; the first scene is BILINEAR / REPEAT, the second NEAREST / CLAMP.
+
+Margins.  BILINEAR adds none: the filter is continuous across texels and across the wrap, so floorf's choice moves no value.
+NEAREST records the distance of x*W (and y*H) to the next integer through M.of(., 1.0), where the coordinate is not clamped.
+
+The restatement alone, on the CPU, for exactly these draws (test_the_near_tie_count_of_the_restatement counts it again):
+128 of 1 200 samples lie below TAU (10.7 %), under the 12 % cap of 144; the flat untextured restatement has 127.
+Mutation (test_the_restatement_sees_the_texture, the first scene's first 200 draws): a restatement that ignores the texture moves
+69 clean samples beyond REL_CLEAN, one that swaps s and t 57."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import pt_f64 as P
+from test_gpu_mesh_smooth_f64 import SmoothMeshDescScene, _draws
+from test_gpu_path_f64 import Tally
+from test_path_f64 import NEAR_TIE_MAX, REL_CLEAN, TAU, rel_distance
+
+REPEAT, CLAMP, NEAREST, BILINEAR = 0, 1, 0, 1
+TEX_BIT = 1 << 28
+GAMMA = 2.2
+MODES = ((REPEAT, BILINEAR), (CLAMP, NEAREST))                      # per scene of test_gpu_mesh_f64._scenes()
+NEAR_TIE_COUNT = 128                                                # of 1 200, counted on the CPU
+MUT_IGNORE, MUT_SWAP = 69, 57                                       # of the 200 draws of the mutation case
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    return torch
+
+
+def scene_textures(scene):
+    """-> {mesh: (uvs [n, 2] f32, RGBA8 [3, 5, 4])}: spherical UVs about each mesh's centre — the second mesh's stretched to
+    [-1, 2], so that the wrap matters — and a two-colour 5 x 3 checker each."""
+    from rust_pathtracer_amd import scenes
+    out = {}
+    for m, (v, _, _) in enumerate(scene.meshes):
+        v = np.asarray(v, np.float32)
+        uv = scenes.spherical_uvs(v, 0.5 * (v.min(0).astype(np.float64) + v.max(0)))
+        if m % 2:
+            uv = (uv * np.float32(3.0) - np.float32(1.0)).astype(np.float32)
+        colours = ((250, 240, 230), (40, 90, 160)) if m % 2 == 0 else ((255, 200, 60), (70, 30, 120))
+        out[m] = (uv, scenes.checker_texture(5, 3, colours[0], colours[1], cells=5))
+    return out
+
+
+def decode_f64(rgba, gamma):
+    """include/rpt.h's decode in float64: [h, w, 3]."""
+    table = np.array([0.0 if k == 0 else 1.0 if k == 255 else P.powf(k / 255.0, gamma) for k in range(256)])
+    if gamma == 1.0:
+        table = np.arange(256) / 255.0
+    return table[np.asarray(rgba, np.uint8)[..., :3]]
+
+
+class TexMeshDescScene(SmoothMeshDescScene):
+    """Every mesh FLAT and textured.  fault: None, "ignore" (the texture is not applied) or "swap" (s and t change places)."""
+
+    def __init__(self, desc, scene, wrap, filt, fault=None):
+        super().__init__(desc, scene)
+        self.wrap, self.filt, self.fault = wrap, filt, fault
+        tex = scene_textures(scene)
+        self.uv = np.concatenate([tex[m][0] for m in range(len(scene.meshes))]).astype(np.float64)
+        self.texels = [decode_f64(tex[m][1], GAMMA) for m in range(len(scene.meshes))]
+        self.tri_mesh = np.concatenate([np.full(len(t), m) for m, (_, t, _) in enumerate(scene.meshes)])
+        self._won = None
+
+    def triangle_normal(self, k, o, d, M):
+        self._won = (k, np.array(o), np.array(d))
+        return P.normalize(tuple(float(x) for x in np.cross(self.e1[k], self.e2[k])))
+
+    def patch(self, m, d, hp, mat, mut, M):
+        super().patch(m, d, hp, mat, mut, M)
+        won, self._won = self._won, None                             # (set by the triangle that has just won, and by nothing else)
+        if won is not None and self.fault != "ignore":
+            tex = self.lookup(*won, M)
+            mat.rgb = tuple(float(c) * float(x) for c, x in zip(mat.rgb, tex))
+
+    def _axis(self, s, n, M):
+        x = min(max(s, 0.0), 1.0) if self.wrap == CLAMP else s - np.floor(s)
+        p = x * n
+        if self.filt == NEAREST:
+            if self.wrap == REPEAT or 0.0 < s < 1.0:
+                M.of(p - np.round(p), 1.0)
+            i = int(np.floor(p))
+            return (min(i, n - 1) if self.wrap == CLAMP else i % n), None, None
+        p -= 0.5
+        f0 = np.floor(p)
+        i0, i1 = int(f0), int(f0) + 1
+        if self.wrap == CLAMP:
+            return min(max(i0, 0), n - 1), min(max(i1, 0), n - 1), p - f0
+        return i0 % n, i1 % n, p - f0
+
+    def lookup(self, k, o, d, M):
+        p = np.cross(d, self.e2[k])
+        inv = 1.0 / float((self.e1[k] * p).sum())
+        sv = o - self.ta[k]
+        u = float((sv * p).sum()) * inv
+        v = float((d * np.cross(sv, self.e1[k])).sum()) * inv
+        ua, ub, uc = (self.uv[j] for j in self.corner[k])
+        s, t = ((1.0 - u) - v) * ua + u * ub + v * uc
+        if self.fault == "swap":
+            s, t = t, s
+        texels = self.texels[int(self.tri_mesh[k])]
+        h, w = texels.shape[:2]
+        i0, i1, fx = self._axis(float(s), w, M)
+        j0, j1, fy = self._axis(float(t), h, M)
+        if self.filt == NEAREST:
+            return texels[j0, i0]
+        top = (1.0 - fx) * texels[j0, i0] + fx * texels[j0, i1]
+        bot = (1.0 - fx) * texels[j1, i0] + fx * texels[j1, i1]
+        return (1.0 - fy) * top + fy * bot
+
+
+def _one_textured_sample(rpt, torch, scene, wrap, filt, w, h, seed):
+    """A one-sample render with every mesh textured into a fresh buffer -> (frame, kernel choice)."""
+    t = rpt.Tracer(scene, device=0, seed=seed)
+    try:
+        t.set_mesh_textures({m: dict(uvs=uv, texels=img, wrap=("repeat", "clamp")[wrap], filter=("nearest", "bilinear")[filt], gamma=GAMMA)
+                             for m, (uv, img) in scene_textures(scene).items()})
+        buf = rpt.DeviceColorBuffer(w, h)
+        t.render_n(buf, 1)
+        torch.cuda.synchronize()
+        choice = C.c_uint32()
+        assert rpt.lib().rpt_debug_kernel_choice(t._h, C.byref(choice)) == 0
+        return buf.pixels.cpu().numpy(), choice.value
+    finally:
+        t.close()
+
+
+@pytest.mark.gpu
+def test_textured_mesh_renders_against_the_restatement(rpt, oracle, torch_cuda):
+    t = Tally(TAU, NEAR_TIE_MAX)
+    refs = {}
+    for k, what, s, seed, pixels, w, h in _draws():
+        wrap, filt = MODES[k]
+        if k not in refs:
+            refs[k] = TexMeshDescScene(s.describe(), s, wrap, filt)
+        frame, choice = _one_textured_sample(rpt, torch_cuda, s, wrap, filt, w, h, seed)
+        assert choice & (1 << 25) and choice & TEX_BIT, "the textured mesh kernel ran"
+        t.ran.add("meshtex_regen_kernel")
+        restated, margins, _ = P.sample_many(refs[k], oracle, seed, [(c, r, 0) for c, r in pixels], w, h)
+        print("%s (seed %d): %d of %d samples below TAU" % (what, seed, int((margins <= TAU).sum()), len(margins)))
+        t.add("%s, textured (seed %d)" % (what, seed), frame, restated, margins, pixels)
+    t.check("textured mesh scenes")
+    assert t.n == 2 * 3 * 200
+
+
+def test_the_near_tie_count_of_the_restatement(rpt, oracle):
+    """The restatement alone, for exactly the draws of the GPU comparison: the count in this file's docstring, under the cap."""
+    near = n = 0
+    refs = {}
+    for k, what, s, seed, pixels, w, h in _draws():
+        if k not in refs:
+            refs[k] = TexMeshDescScene(s.describe(), s, *MODES[k])
+        _, margins, _ = P.sample_many(refs[k], oracle, seed, [(c, r, 0) for c, r in pixels], w, h)
+        near += int((margins <= TAU).sum())
+        n += len(margins)
+    print("%d of %d samples below TAU" % (near, n))
+    assert n == 1200 and near == NEAR_TIE_COUNT and near <= NEAR_TIE_MAX * n
+
+
+def test_the_restatement_sees_the_texture(rpt, oracle):
+    """Two planted faults, each of which a device could have: the texture ignored, s and t swapped.  Each moves clean samples beyond
+    REL_CLEAN, so the comparison above would catch it."""
+    k, what, s, seed, pixels, w, h = next(iter(_draws()))
+    items = [(c, r, 0) for c, r in pixels]
+    base, marg, _ = P.sample_many(TexMeshDescScene(s.describe(), s, *MODES[k]), oracle, seed, items, w, h)
+    moved = {}
+    for fault in ("ignore", "swap"):
+        other, marg2, _ = P.sample_many(TexMeshDescScene(s.describe(), s, *MODES[k], fault=fault), oracle, seed, items, w, h)
+        clean = (marg > TAU) & (marg2 > TAU)
+        moved[fault] = int((rel_distance(np.nan_to_num(other), np.nan_to_num(base))[clean] > REL_CLEAN).sum())
+    print("clean samples moved beyond REL_CLEAN:", moved)
+    assert moved == {"ignore": MUT_IGNORE, "swap": MUT_SWAP} and min(moved.values()) > 10

@@ -29,7 +29,11 @@ meshes are SMOOTH against one whose meshes are FLAT (one pair of contexts per ca
 scene with its torus emissive, every mesh OFF against the torus ON, on two contexts; the wall time of the four move calls on a
 context whose torus is ON against one whose meshes are OFF; and the time of rpt_set_mesh_lights itself.
 
-    python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild] [--device] [--smooth] [--lights]
+--textures: one JSON line more, for mesh textures (include/rpt.h, "mesh textures"), in the same manner: the resident render rate of
+the scene untextured against both meshes under a 1024 x 1024 BILINEAR / REPEAT texture, on two contexts; the wall time of the four
+move calls on a textured context against an untextured one; and the time of rpt_set_mesh_textures itself.
+
+    python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild] [--device] [--smooth] [--lights] [--textures]
 """
 import argparse
 import ctypes as C
@@ -53,6 +57,7 @@ def main():
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--smooth", action="store_true")
     ap.add_argument("--lights", action="store_true")
+    ap.add_argument("--textures", action="store_true")
     a = ap.parse_args()
     os.environ.setdefault("RPT_LIB", os.path.join(ROOT, "rust-pathtracer_amd", "librpt_hip_test.so"))     # (the product has no hooks)
     import __graft_entry__
@@ -79,6 +84,7 @@ def main():
     device = measure_device_sources(pkg, s, a) if a.device else None
     smooth = measure_smooth(pkg, s, a) if a.smooth else None
     lights = measure_lights(pkg, s, a) if a.lights else None
+    textures = measure_textures(pkg, s, a) if a.textures else None
     t.close()
     print(json.dumps({"workload": "mesh_scene %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "triangles": n_tris,
                       "gsamples_per_s_median": sorted(rates)[len(rates) // 2], "gsamples_per_s": rates,
@@ -93,6 +99,8 @@ def main():
         print(json.dumps(smooth))
     if lights:
         print(json.dumps(lights))
+    if textures:
+        print(json.dumps(textures))
 
 
 def measure_updates(pkg, t, s, a):
@@ -402,6 +410,74 @@ def measure_lights(pkg, s, a):
     for name, where in calls:
         pair = {"off": pkg.Tracer(make(), device=0, seed=1), "on": pkg.Tracer(make(), device=0, seed=1)}
         pair["on"].set_mesh_lights(torus_on)
+        for tr in pair.values():
+            getattr(tr, name)(back[where])                          # the context's first call of its kind: allocates
+        ms = {"off": [], "on": []}
+        for _ in range(reps):
+            for arg in (there[where], back[where]):
+                for side in ("off", "on"):
+                    ms[side].append(timed(getattr(pair[side], name), arg))
+        for tr in pair.values():
+            tr.close()
+        fo, fn = stats(ms["off"]), stats(ms["on"])
+        out[name] = {"off_ms": fo, "on_ms": fn, "on_adds_ms": fn["median"] - fo["median"]}
+    return out
+
+
+def measure_textures(pkg, s, a):
+    """-> the --textures line.  scenes.mesh_scene() untextured ("off") against both meshes under a 1024 x 1024 checker, BILINEAR /
+    REPEAT, gamma 2.2, over spherical UVs ("on").  Two contexts for the frames and two per move call, so that every context's calls
+    follow calls of its own kind; within a repetition the two sides alternate."""
+    import numpy as np
+    import torch
+    from rust_pathtracer_amd import scenes
+
+    original = [np.array(v, np.float32, copy=True) for v, _, _ in s.meshes]
+    image = scenes.checker_texture(1024, 1024, (255, 255, 255), (60, 60, 60), cells=32)
+    both = {m: dict(uvs=scenes.spherical_uvs(v, 0.5 * (v.min(0).astype(np.float64) + v.max(0))) * np.float32(4.0), texels=image,
+                    wrap="repeat", filter="bilinear", gamma=2.2) for m, v in enumerate(original)}
+
+    def stats(xs):
+        xs = sorted(xs)
+        return {"median": xs[len(xs) // 2], "min": xs[0], "max": xs[-1]}
+
+    def timed(call, arg):
+        t0 = time.perf_counter()
+        call(arg)
+        return (time.perf_counter() - t0) * 1e3
+
+    def rate(tr):
+        tr.render_resident(a.width, a.height, a.spp)
+        return a.width * a.height * a.spp / (tr.resident_kernel_ms() * 1e-3) / 1e9
+
+    reps = max(5, a.reps)
+    # frames
+    off, on = pkg.Tracer(scenes.mesh_scene(), device=0, seed=1), pkg.Tracer(scenes.mesh_scene(), device=0, seed=1)
+    first_ms = timed(on.set_mesh_textures, both)                    # brings the refit tables, uploads and decodes 2 x 2^20 texels
+    again_ms = [timed(on.set_mesh_textures, both) for _ in range(reps)]
+    for tr in (off, on):
+        rate(tr)                                                    # warm-up (and the dispatch order's first costs)
+        rate(tr)
+    rates = {"off": [], "on": []}
+    for _ in range(reps):
+        rates["off"].append(rate(off))
+        rates["on"].append(rate(on))
+    off.close()
+    on.close()
+    # moves: the medium move and back, so that every call moves every vertex
+    moved = scenes.mesh_scene_moved(s, 0.5)
+    dev = lambda arrays: {m: torch.from_numpy(np.ascontiguousarray(v, np.float32)).to("cuda:0") for m, v in enumerate(arrays)}   # noqa: E731
+    there, back = {"host": dict(enumerate(moved)), "device": dev(moved)}, {"host": dict(enumerate(original)), "device": dev(original)}
+    torch.cuda.synchronize()
+    calls = (("update_meshes", "host"), ("rebuild_meshes", "host"), ("update_meshes_device", "device"), ("rebuild_meshes_device", "device"))
+    out = {"workload": "mesh_scene mesh textures %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "reps": reps,
+           "texture": "2 x 1024x1024 RGBA8, bilinear, repeat",
+           "first_set_mesh_textures_ms": first_ms, "set_mesh_textures_again_ms": stats(again_ms),
+           "gsamples_per_s_off": stats(rates["off"]), "gsamples_per_s_on": stats(rates["on"]),
+           "on_over_off_rate": stats(rates["on"])["median"] / stats(rates["off"])["median"]}
+    for name, where in calls:
+        pair = {"off": pkg.Tracer(scenes.mesh_scene(), device=0, seed=1), "on": pkg.Tracer(scenes.mesh_scene(), device=0, seed=1)}
+        pair["on"].set_mesh_textures(both)
         for tr in pair.values():
             getattr(tr, name)(back[where])                          # the context's first call of its kind: allocates
         ms = {"off": [], "on": []}
