@@ -848,6 +848,102 @@ int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t 
 int rpt_download_mesh_texture(rpt_ctx* ctx, uint32_t mesh, float* texels /* host, width*height*4 f32, decoded */, uint32_t width,
                               uint32_t height);
 
+/* ---- environment lighting — PROJECT-DEFINED ----------------------------------------------------------------------------------------
+ * One image-based sky for the uploaded MESH scene: a square f32 RGB image in an OCTAHEDRAL layout replaces rpt_background at a miss
+ * and, with RPT_ENV_SAMPLED, is one more pickable light of direct_light, importance-sampled by texel and weighed against BSDF
+ * sampling by the power heuristic at the miss, so nothing is counted twice.  Every operation is stated, so that tables, lookups,
+ * samples and frames stay checkable bit for bit (tests/test_gpu_mesh_env.py holds them to a numpy restatement).  All arithmetic is
+ * f32, one rounding per operation, nothing contracted; the divide and the root are the library's correctly rounded ones; dot and
+ * F::MAX are those of "triangle meshes".  The layout needs no atan2 or acos: direction to texel and back is fabs, compares,
+ * products, divides and one root.  The statement is written once, in csrc/host_env.h, which the kernels and the host reference
+ * both compile.
+ *
+ * Lookup of a direction d.  S = size, S_f = (float)S, sgn(x) = x >= 0 ? 1 : -1 (so sgn(-0) = 1).
+ *     l1 = (|d.x| + |d.y|) + |d.z|;   !(l1 > 0 && l1 <= F::MAX)  ->  radiance (0,0,0), k = none     (also a NaN d)
+ *     px = d.x / l1;  pz = d.z / l1
+ *     d.y < 0:  (px, pz) = ((1 - |pz|) * sgn(px), (1 - |px|) * sgn(pz))       both from the OLD px, pz   (d.y = -0 does not fold)
+ *     s = px * 0.5f + 0.5f;  t = pz * 0.5f + 0.5f                              (two operations each; in [0, 1])
+ *     i = min((int32)floorf(s * S_f), S - 1);  j likewise from t;  k = j * S + i
+ *     radiance.c = texel_k.c * scale                                           one product per channel
+ * The lookup is NEAREST only, so the sampler's density is exactly proportional to what the lookup returns.  +y is the centre of the
+ * image, -y its four corners: the lower hemisphere folds into them.  +x is the middle of the right edge (i = S - 1), +z the middle of
+ * the last row.
+ *
+ * Table (RPT_ENV_SAMPLED only): the "mesh lights" table with texels for triangles.
+ *     w_k = (r + g) + b;   W_max = max over k of w_k;   the table is DARK if W_max == 0
+ *     E: the integer with W_max = f * 2^E, f in [0.5, 1)   (a subnormal W_max included)
+ *     q_k = floor(w_k * 2^(36 - E)) as a uint64;   C_k = q_0 + ... + q_k;   Q = C_(S*S-1)  (below 2^60 at 4096 x 4096)
+ * It is computed on the device, in integers: no summation order needs a promise.
+ *
+ * Sampling from scatter_pos.  The draws come after the light-index draw and are r0a, r0b, r1, r2; all four are always taken.  A dark
+ * table leaves LightSampleRec::new()'s zeros.  J, T and the binary search for k are exactly as "mesh lights" states them.  Then
+ *     i = k % S;  j = k / S
+ *     s = ((float)i + r1) / S_f;  t = ((float)j + r2) / S_f
+ *     px = s * 2 - 1;  pz = t * 2 - 1;  py = (1 - |px|) - |pz|
+ *     py < 0:  (px, pz) = ((1 - |pz|) * sgn(px), (1 - |px|) * sgn(pz))        old values; py stays as it is
+ *     l2 = dot(p, p);  len = sqrt(l2);  direction = p / len  (per component)
+ *     sel = (float)q_k / (float)Q                                  each integer rounded to nearest f32, ties to even; one divide
+ *     pdf = (sel * ((S_f * S_f) * 0.25f)) * (l2 * len)
+ *     dist = +inf (as RPT_LIGHT_DISTANT);  normal = -direction;  emission = N_f * (texel_k * scale);  light.area = 1 (the MIS weight
+ *     of direct_light applies)
+ * l2 * len = |p|^3 is the octahedral map's Jacobian: d omega = dp_x dp_z / |p|^3 on the square of area 4.  The emission is that of
+ * the PICKED texel k, not a second lookup of the rounded direction (which, within an ulp of a texel border, may be a neighbour).
+ * scatter_pos does not enter: the light is at infinity.
+ *
+ * Pickable lights.  N = n_lights + ON meshes + (1 if an environment is set and SAMPLED); the environment takes the LAST index, and
+ * N_f replaces `n_lights as F` everywhere, as "mesh lights" arranges.  A BACKGROUND_ONLY environment does not count in N.
+ *
+ * Miss side.  Where the path adds background * throughput it adds (w * radiance(d)) * throughput, in this order: the lookup of
+ * ray.d gives k, p = (px, d.y / l1, pz) BEFORE the fold, and the texel {r, g, b, (float)q_k} by one 16 B gather; radiance as above;
+ *     w = 1   at bounce 0; for BACKGROUND_ONLY; for a dark table; when k = none; when q_k == 0;
+ *     else lp = pdf above for this k and this p  (the same function the sampler calls: csrc/host_env.h, env_pdf);  lp == 0: w = 1;
+ *     else w = power_heuristic(scatter_pdf, lp)
+ * then w * radiance per channel, then the product with the throughput.
+ *
+ * Stated costs.  The weights carry no solid-angle factor: per solid angle, texels near the octahedron's corners (the six axis
+ * directions, |p|^3 = 1) are sampled up to about 5 times denser than those at its face centres (|p|^3 = 3^-1.5), where an ideal
+ * sampler of a uniform sky would treat both alike — unbiased, since the pdf says so.  A texel
+ * more than 2^36 below the brightest has q_k == 0 and is never picked by next-event estimation; BSDF sampling still finds it at
+ * full weight.
+ *
+ * rpt_set_environment sets (env != NULL) or removes (env == NULL) the environment of the uploaded scene, before or after any number
+ * of moves, shading, light or texture changes.  The image is copied inside the call; on return the tables are current on every
+ * device of the context.  The checks, in this order, all on the host before any device is touched — a rejected call changes nothing,
+ * and rpt_last_error names the fault:
+ *   RPT_ERR_INVALID_ARG  ctx is NULL;
+ *   RPT_ERR_NO_SCENE     no scene with meshes is uploaded;
+ *   RPT_ERR_INVALID_ARG  size is 0 or above 4096; texels is NULL; mode is neither constant; scale is not finite or is negative; a
+ *                        texel component is not finite, is negative or is above 2^100 (the message names the texel);
+ *   RPT_ERR_UNSUPPORTED  SAMPLED would bring N to 2^24 (rpt_set_mesh_lights counts a SAMPLED environment in its own rule);
+ *   RPT_ERR_HIP          a runtime call failed part-way: the context is left with NO scene, as for the other mesh calls.
+ * Removing the environment leaves the context rendering exactly as if the call had never been made — the same kernel, the same
+ * tables.  rpt_upload_scene drops the environment.  While an environment is set the scene renders through ONE kernel of its own,
+ * the mesh kernel's body over the textured mesh-light form; a feature the scene does not use goes through empty tables, so the
+ * environment composes with FLAT / SMOOTH, OFF / ON and textures in every combination.
+ *
+ * Moves.  rpt_update_meshes, rpt_rebuild_meshes and both _device forms do not touch the environment: no launch is added to a move.
+ *
+ * rpt_download_environment_table copies C_k (size * size uint64) and E from the context's first device.  RPT_ERR_INVALID_ARG: no
+ * SAMPLED environment is set (it says so), n_texels is not size * size, or a NULL destination.  A dark table is all zeros, E = 0.
+ *
+ * Memory.  The call brings the refit's tables to every device as rpt_set_mesh_shading does.  While an environment is set every
+ * device holds 16 B per texel, SAMPLED 8 B more and 8 B per 256 texels, and per triangle of the SCENE 4 B and one bit (the empty
+ * tables); during the call 12 B per texel more.
+ *
+ * Timings: not measured yet.  tools/mesh_bench.py --environment alternates, in one process, frames of scenes.mesh_scene without an
+ * environment, with a BACKGROUND_ONLY one and with a SAMPLED one (1024 x 1024), and times the set call. */
+enum { RPT_ENV_BACKGROUND_ONLY = 0, RPT_ENV_SAMPLED = 1 };
+
+typedef struct rpt_environment {
+    uint32_t size;                    /* the image is size x size texels, 1 .. 4096 */
+    const float* texels;              /* HOST, linear RGB, size*size*3 f32, row 0 first; copied inside the call */
+    float scale;                      /* finite, >= 0 */
+    uint32_t mode;                    /* RPT_ENV_BACKGROUND_ONLY or RPT_ENV_SAMPLED */
+} rpt_environment;
+
+int rpt_set_environment(rpt_ctx* ctx, const rpt_environment* env /* NULL: remove */);
+int rpt_download_environment_table(rpt_ctx* ctx, uint64_t* cdf /* host, size*size */, uint32_t n_texels, int32_t* exponent);
+
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)
  *   frames_done ColorBuffer.frames before the call; the caller adds `spp` afterwards

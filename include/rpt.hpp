@@ -259,6 +259,16 @@ public:
         check(rpt_download_mesh_texture(ctx_, mesh, out.data(), width, height), ctx_);
         return out;
     }
+    /// Environment lighting (rpt.h, "environment lighting"): a square f32 RGB image in the octahedral layout replaces the background
+    /// of the uploaded mesh scene and, with RPT_ENV_SAMPLED, is importance-sampled by direct_light; sync_scene() drops it.
+    void set_environment(const rpt_environment& env) { check(rpt_set_environment(ctx_, &env), ctx_); }
+    void remove_environment() { check(rpt_set_environment(ctx_, nullptr), ctx_); }
+    /// The running sums C_k of a SAMPLED environment's table (size * size of them) and its exponent E.
+    std::vector<uint64_t> environment_table(uint32_t size, int32_t* exponent) {
+        std::vector<uint64_t> out((size_t)size * size);
+        check(rpt_download_environment_table(ctx_, out.data(), size * size, exponent), ctx_);
+        return out;
+    }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

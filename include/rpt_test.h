@@ -79,6 +79,18 @@ int rpt_debug_mesh_light_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, u
  * RPT_ERR_NO_SCENE unless the uploaded scene has meshes; RPT_ERR_INVALID_ARG while no mesh is textured (those kernels do not run then). */
 int rpt_debug_mesh_texture_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
 
+/* The lookup of the environment (include/rpt.h, "environment lighting"), through the device function the miss exit of the environment
+ * scenes' render kernel calls: dirs_dev = n x 3 floats, one direction each (taken as given: not normalised); out_dev = n x 5 dwords
+ * {the texel k or 0xFFFFFFFF, the radiance's three words, lp as bits: the pdf the sampler has for that direction, 0 where the miss
+ * weight is 1 whatever the bounce (BACKGROUND_ONLY, a dark table, q_k == 0, no texel)}.  RPT_ERR_NO_SCENE unless the uploaded scene has
+ * meshes; RPT_ERR_INVALID_ARG while no environment is set (that kernel does not run then). */
+int rpt_debug_env_query(rpt_ctx* ctx, const float* dirs_dev, uint64_t n, uint32_t* out_dev, void* stream);
+
+/* The sampler of the environment, through the device function that kernel's direct_light calls: in_dev = n x 7 floats {scatter_pos[3]
+ * (not read: the light is at infinity), r0a, r0b, r1, r2}; out_dev = n x 8 dwords {the picked texel k or 0xFFFFFFFF (not SAMPLED, or a
+ * dark table: the rest are LightSampleRec::new()'s zeros), direction[3], pdf, emission[3], as bits}.  Errors as rpt_debug_env_query. */
+int rpt_debug_env_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, uint32_t* out_dev, void* stream);
+
 /* The uploaded mesh scene's hierarchy (csrc/host_bvh.h): its interior nodes, the depth of its deepest leaf, and the host time its build
  * took in rpt_upload_scene — after rpt_rebuild_meshes the rebuilt hierarchy's, and the wall time of that call's device part.
  * RPT_ERR_NO_SCENE unless the uploaded scene has meshes.  (tools/mesh_bench.py) */
@@ -115,7 +127,8 @@ int rpt_debug_sched_read(rpt_ctx* ctx, uint32_t* out, uint32_t capacity_tiles, u
  * (else the class's megakernel), bit 22 its dense form (at most 3 072 workgroups), bit 23 the nested-loop kernel, bit 24 the class's
  * participating-media form (the scene has media: RPT_SCENE_MEDIA), bit 25 the mesh scene class's kernel (k_mesh.hip), bit 26 beside it its smooth-shading form (k_smooth.hip: some mesh is SMOOTH), bit 27 some mesh is ON (include/rpt.h, "mesh lights"): the kernel that ran is k_light.hip's, which serves flat and smooth meshes alike — with bit 26 set as well it is still that one kernel, shading the SMOOTH meshes through their per-triangle bit;
  * bit 28 some mesh is textured (include/rpt.h, "mesh textures"): the kernel that ran is one of k_tex.hip's two, the one over the mesh
- * lights' tables while bit 27 is set as well, else the one over the smooth scenes' tables.  For tests that must know that the kernel they aim at is the one
+ * lights' tables while bit 27 is set as well, else the one over the smooth scenes' tables; bit 29 an environment is set
+ * (include/rpt.h, "environment lighting"): the kernel that ran is k_env.hip's one form, whatever bits 26-28 say.  For tests that must know that the kernel they aim at is the one
  * that ran. */
 int rpt_debug_kernel_choice(rpt_ctx* ctx, uint32_t* out);
 

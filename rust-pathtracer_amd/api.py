@@ -538,6 +538,35 @@ class Tracer:
         check(lib().rpt_download_mesh_texture(self._h, int(m), out.ctypes.data, int(width), int(height)), self._h)
         return out
 
+    def set_environment(self, image, scale=1.0, sampled=True):
+        """Environment lighting (include/rpt.h, "environment lighting"): `image` is a (size, size, 3) float32 linear RGB image in the
+        octahedral layout (scenes.octahedral_from_equirect makes one from a latitude-longitude image) that replaces the background of
+        the uploaded mesh scene, times `scale`; with `sampled` it is also one more light of next-event estimation, importance-sampled
+        by texel.  None removes it; upload_scene() drops it, as in C."""
+        if image is None:
+            self._checked_move(lib().rpt_set_environment(self._h, None))
+            self.__dict__["_environment_size"] = 0
+            return
+        texels = np.ascontiguousarray(image, dtype=np.float32)
+        if texels.ndim != 3 or texels.shape[2] != 3 or texels.shape[0] != texels.shape[1]:
+            raise ValueError("the environment must have the shape (size, size, 3)")
+        env = _abi.rpt_environment()
+        env.size, env.texels = texels.shape[0], texels.ctypes.data_as(C.POINTER(C.c_float))
+        env.scale, env.mode = float(scale), _abi.RPT_ENV_SAMPLED if sampled else _abi.RPT_ENV_BACKGROUND_ONLY
+        self._checked_move(lib().rpt_set_environment(self._h, C.byref(env)))
+        self.__dict__["_environment_size"] = int(texels.shape[0])
+
+    def download_environment_table(self, size=None):
+        """The table the context holds for its sampled environment (rpt_download_environment_table): (cdf, exponent) — a new uint64
+        array with one running sum per texel, row 0 first, and the integer E; (zeros, 0): the table is dark.  Without a size: the
+        one set_environment last gave."""
+        if size is None:
+            size = self.__dict__.get("_environment_size", 0)
+        cdf = np.zeros(int(size) * int(size), np.uint64)
+        e = C.c_int32(0)
+        check(lib().rpt_download_environment_table(self._h, cdf.ctypes.data, cdf.size, C.byref(e)), self._h)
+        return cdf, int(e.value)
+
     def _refresh_stale_meshes(self):
         """scene().meshes' vertex arrays that a device-source call left stale, read back once (only before an upload)."""
         for m in sorted(self._stale_meshes):

@@ -20,6 +20,7 @@
 
 #include "../../include/rpt.h"
 #include "host_build.h"
+#include "host_env.h"
 #include "host_light.h"
 #include "host_move.h"
 #include "host_refit.h"
@@ -29,6 +30,7 @@
 #include "knobs.h"
 #include "launch.h"
 #include "launch_build.h"
+#include "launch_env.h"
 #include "launch_light.h"
 #include "launch_move.h"
 #include "launch_smooth.h"
@@ -62,6 +64,7 @@ struct DevState {
     void* smooth = nullptr;           // smooth shading's tables (host_smooth.h, SmoothLayout): while some mesh is SMOOTH (rpt_set_mesh_shading)
     void* light = nullptr;            // mesh lights' tables (host_light.h, LightLayout): while some mesh is ON (rpt_set_mesh_lights)
     void* tex = nullptr;              // mesh textures' tables (host_tex.h, TexLayout): while some mesh is textured (rpt_set_mesh_textures)
+    void* env = nullptr;              // the environment's tables (host_env.h, EnvLayout): while one is set (rpt_set_environment)
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -109,6 +112,7 @@ struct rpt_ctx {
     rpthost::SmoothPlan smooth;       // its meshes' shading modes and the sizes of every device's smooth tables (host_smooth.h)
     rpthost::LightPlan light;         // which of its meshes are lights and the sizes of every device's light tables (host_light.h)
     rpthost::TexPlan tex;             // which of its meshes are textured, their UVs and the sizes of every device's texture tables (host_tex.h)
+    rpthost::EnvPlan env;             // its environment's size, mode and scale, and Q as the devices computed it (host_env.h)
     // resident ColorBuffer (buffer.rs:6-14): pixels as per-rank tiles + frames
     uint32_t res_w = 0, res_h = 0, res_tile_rows = 0, res_rows_padded = 0;
     uint64_t res_frames = 0;
@@ -293,6 +297,7 @@ static void free_mesh_work(DevState& d)
     if (d.smooth) { (void)hipFree(d.smooth); d.smooth = nullptr; }
     if (d.light) { (void)hipFree(d.light); d.light = nullptr; }
     if (d.tex) { (void)hipFree(d.tex); d.tex = nullptr; }
+    if (d.env) { (void)hipFree(d.env); d.env = nullptr; }
     d.refit_full = false;
     d.build_temp_bytes = 0;
 }
@@ -548,6 +553,60 @@ static SceneMeshLightTex light_tex_scene_of(const rpt_ctx* ctx, const DevState& 
     return s;
 }
 
+// A mesh scene's kernel argument while an environment is set: whatever of the smooth, light and texture tables device d holds, a
+// feature the scene does not use through the empty tables of its environment allocation (all-zero smooth bits; tri_light and tri_tex
+// all 0xFFFFFFFF, no ON mesh), and pointers into its environment tables.
+static SceneMeshEnv env_scene_of(const rpt_ctx* ctx, const DevState& d)
+{
+    const rpthost::EnvPlan& ep = ctx->env;
+    const rpthost::RefitLayout rl(ctx->refit.n_vertices(), 0, 0);
+    const rpthost::EnvLayout el(ep.size, ep.sampled(), ep.n_tris);
+    const unsigned char* refit = static_cast<const unsigned char*>(d.refit);
+    const unsigned char* base = static_cast<const unsigned char*>(d.env);
+    const uint32_t* none = reinterpret_cast<const uint32_t*>(base + el.off_none);
+    SceneMeshEnv s{};
+    if (d.light && ctx->light.any()) {
+        static_cast<SceneMeshLight&>(s) = light_scene_of(ctx, d);
+    } else {
+        if (d.smooth && ctx->smooth.any()) {
+            static_cast<SceneMeshSmooth&>(s) = smooth_scene_of(ctx, d);
+        } else {
+            static_cast<SceneMesh&>(s) = d.scene;
+            s.slot_vertex = reinterpret_cast<const uint32_t*>(refit + rl.off_slot_vertex);
+            s.vnormals = nullptr;                                   // (not read: no smooth bit is set)
+            s.smooth_bits = reinterpret_cast<const uint32_t*>(base + el.off_flat_bits);
+        }
+        s.vertices = reinterpret_cast<const float*>(refit + rl.off_vertices);
+        s.face_vertex = nullptr;                                    // (not read: no mesh is ON)
+        s.light_desc = nullptr;
+        s.light_cdf = nullptr;
+        s.tri_light = none;
+        s.n_faces = 0u;
+        s.n_pick = s.n_lights;
+    }
+    if (d.tex && ctx->tex.any()) {
+        bind_tex(ctx, d, s);
+    } else {
+        s.tex_desc = nullptr;                                       // (not read: no triangle names a texture)
+        s.tri_tex = none;
+        s.uvs = nullptr;
+        s.texels = nullptr;
+    }
+    s.env_texels = reinterpret_cast<const rpthost::EnvTexel*>(base + el.off_texels);
+    s.env_cdf = ep.sampled() ? reinterpret_cast<const uint64_t*>(base + el.off_cdf) : nullptr;
+    s.env_q = ep.q_total;
+    s.env_q_f = (float)ep.q_total;
+    s.env_scale = ep.scale;
+    s.env_size = ep.size;
+    s.env_pick = rpthost::kEnvNone;
+    if (ep.sampled()) {
+        s.env_pick = s.n_pick;                                      // include/rpt.h, "pickable lights": the environment is the last one
+        s.n_pick += 1u;
+        s.n_lights_f = (float)s.n_pick;
+    }
+    return s;
+}
+
 // One render launch sequence on one device.
 static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t width, uint32_t height, uint64_t frames_done, uint32_t spp,
                          uint64_t seed, uint32_t flags, uint32_t tile_rows, uint32_t rank, uint32_t world, hipStream_t stream)
@@ -565,6 +624,7 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     const bool smooth = kind == SceneKind::mesh && d.smooth && d.refit && ctx->smooth.any();      // some mesh is SMOOTH: k_smooth.hip's form
     const bool lights = kind == SceneKind::mesh && d.light && d.refit && ctx->light.any();        // some mesh is ON: k_light.hip's form, for flat and smooth meshes alike
     const bool textured = kind == SceneKind::mesh && d.tex && d.refit && ctx->tex.any();          // some mesh is textured: k_tex.hip's forms, over either of the two above
+    const bool environment = kind == SceneKind::mesh && d.env && d.refit && ctx->env.any();       // an environment is set: k_env.hip's one form, over all of the above
     scs.cam = scl.cam = scm.cam = make_camera(ctx->scene.camera, (float)width, (float)height);
     const bool in_hbm = kind == SceneKind::large || kind == SceneKind::mesh;     // the scene's tables are in device memory
     const bool has_sdf = !in_hbm && scs.sdf.n_prims > 0;
@@ -626,9 +686,16 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
                         (fast ? 1u << 20 : 0u) | (rp.compact && !nested ? 1u << 21 : 0u) |
                         (rp.compact && !nested && nblocks <= kCompactDenseMaxBlocks ? 1u << 22 : 0u) | (nested ? 1u << 23 : 0u) |
                         (media ? 1u << 24 : 0u) | (kind == SceneKind::mesh ? 1u << 25 : 0u) |
-                        (smooth ? 1u << 26 : 0u) | (lights ? 1u << 27 : 0u) | (textured ? 1u << 28 : 0u);
+                        (smooth ? 1u << 26 : 0u) | (lights ? 1u << 27 : 0u) | (textured ? 1u << 28 : 0u) |
+                        (environment ? 1u << 29 : 0u);
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
+        if (environment) {
+            SceneMeshEnv sme = env_scene_of(ctx, d);
+            sme.cam = scm.cam;
+            sme.flags = scm.flags;
+            return rptlaunch::render_mesh_env(sme, rp, grid, stream);
+        }
         if (textured && lights) {
             SceneMeshLightTex smt = light_tex_scene_of(ctx, d);
             smt.cam = scm.cam;
@@ -1031,6 +1098,7 @@ static void commit_scene(rpt_ctx* ctx, SceneImage& img, const std::vector<void*>
     ctx->smooth = rpthost::SmoothPlan();                            // every mesh FLAT
     ctx->light = rpthost::LightPlan();                              // every mesh OFF
     ctx->tex = rpthost::TexPlan();                                  // every mesh untextured
+    ctx->env = rpthost::EnvPlan();                                  // no environment
 }
 
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
@@ -1062,6 +1130,7 @@ static void drop_scene(rpt_ctx* ctx)
     ctx->smooth = rpthost::SmoothPlan();
     ctx->light = rpthost::LightPlan();
     ctx->tex = rpthost::TexPlan();
+    ctx->env = rpthost::EnvPlan();
 }
 
 // Where the named meshes' new positions come from: host arrays (rpt_update_meshes, rpt_rebuild_meshes) or device arrays through a
@@ -1661,7 +1730,7 @@ int rpt_set_mesh_lights(rpt_ctx* ctx, const rpt_mesh_light* items, uint32_t n_it
     std::string why;
     const bool mesh_scene = ctx->scene.kind == SceneKind::mesh;
     const SceneMesh& sc0 = ctx->devs[0].scene;
-    const int rc = check_mesh_lights(ctx->refit, mesh_scene, mesh_scene ? sc0.flags : 0u, mesh_scene ? sc0.n_lights : 0u, items, n_items, ctx->light.mode, mode, why);
+    const int rc = check_mesh_lights(ctx->refit, mesh_scene, mesh_scene ? sc0.flags : 0u, (mesh_scene ? sc0.n_lights : 0u) + (ctx->env.sampled() ? 1u : 0u), items, n_items, ctx->light.mode, mode, why);
     if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
     if (n_items == 0) return RPT_OK;
     LightPlan fresh;
@@ -1859,6 +1928,131 @@ int rpt_download_mesh_texture(rpt_ctx* ctx, uint32_t mesh, float* texels, uint32
     RPT_ON_DEVICE(ctx);
     const rpthost::TexLayout tl(tp.n_tex(), tp.n_tris, tp.n_vertices, tp.n_texels);
     RPT_HIP_CHECK(ctx, hipMemcpy(texels, static_cast<const unsigned char*>(d.tex) + tl.off_texels + 16 * (size_t)im.first, 16 * (size_t)im.width * im.height, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+// ---- rpt_set_environment / rpt_download_environment_table (include/rpt.h, "environment lighting") ---------------------------------
+// One device's part: wait for its earlier work (a launch may still read the old tables), make its refit tables if it has none, make
+// the new tables and the empty ones, copy the image in, run the table kernels, read Q and W_max back, drop the old tables.  `ep` is
+// the new plan (ctx->env still the old one); *q and *w_max: what this device computed.
+static int env_device(rpt_ctx* ctx, DevState& d, const rpthost::EnvPlan& ep, const float* texels, uint64_t* q, uint32_t* w_max)
+{
+    const rpthost::EnvLayout el(ep.size, ep.sampled(), ep.n_tris);
+    const size_t n = ep.n_texels();
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    RPT_CHECK_RC(ensure_refit(ctx, d));
+    void* fresh = nullptr;
+    void* stage = nullptr;
+    const auto fail = [&](int rc) { if (fresh) (void)hipFree(fresh); if (stage) (void)hipFree(stage); return rc; };
+    const auto work = [&]() -> int {
+        RPT_HIP_CHECK(ctx, hipMalloc(&fresh, el.total));
+        RPT_HIP_CHECK(ctx, hipMalloc(&stage, 12 * n));
+        unsigned char* base = static_cast<unsigned char*>(fresh);
+        RPT_HIP_CHECK(ctx, hipMemcpyAsync(stage, texels, 12 * n, hipMemcpyHostToDevice, d.stream));
+        RPT_HIP_CHECK(ctx, hipMemsetAsync(base + el.off_head, 0, 16, d.stream));
+        if (el.off_flat_bits > el.off_none) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + el.off_none, 0xFF, el.off_flat_bits - el.off_none, d.stream));
+        if (el.total > el.off_flat_bits) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + el.off_flat_bits, 0, el.total - el.off_flat_bits, d.stream));
+        EnvTables t{};
+        t.raw = static_cast<const float*>(stage);
+        t.texels = reinterpret_cast<rpthost::EnvTexel*>(base + el.off_texels);
+        t.cdf = reinterpret_cast<uint64_t*>(base + el.off_cdf);
+        t.block = reinterpret_cast<uint64_t*>(base + el.off_block);
+        t.w_max = reinterpret_cast<uint32_t*>(base + el.off_head);
+        t.n_texels = (uint32_t)n;
+        t.sampled = ep.sampled() ? 1u : 0u;
+        RPT_HIP_CHECK(ctx, rptlaunch::env_tables(t, d.stream));
+        *q = 0;
+        *w_max = 0u;
+        if (ep.sampled()) {
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(q, base + el.off_cdf + 8 * (n - 1), 8, hipMemcpyDeviceToHost, d.stream));
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(w_max, base + el.off_head, 4, hipMemcpyDeviceToHost, d.stream));
+        }
+        RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+        return RPT_OK;
+    };
+    const int rc = work();
+    if (rc != RPT_OK) return fail(rc);
+    (void)hipFree(stage);
+    if (d.env) (void)hipFree(d.env);
+    d.env = fresh;
+    return RPT_OK;
+}
+
+int rpt_set_environment(rpt_ctx* ctx, const rpt_environment* env)
+{
+    using namespace rpthost;
+    if (!ctx) { set_err(nullptr, "rpt_set_environment: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    std::string why;
+    const bool mesh_scene = ctx->scene.kind == SceneKind::mesh;
+    const uint64_t n_other = mesh_scene ? (uint64_t)ctx->devs[0].scene.n_lights + ctx->light.n_on() : 0u;
+    const int rc = check_environment(mesh_scene, n_other, env, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    if (!ctx->refit.ok) { set_err(ctx, "rpt_set_environment: the scene's meshes hold 2^32 vertices or more"); return RPT_ERR_UNSUPPORTED; }
+    if (!env && !ctx->env.any()) return RPT_OK;
+    DeviceGuard guard(ctx->devs[0].device);
+    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
+    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_environment: cannot select device %d", ctx->devs[0].device);
+    if (rc_dev == RPT_OK && !env) {                                 // removed: the context is what it was before the first call
+        for (DevState& d : ctx->devs) {
+            if (!d.env) continue;
+            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
+                set_err(ctx, "rpt_set_environment: cannot wait for device %d", d.device);
+                rc_dev = RPT_ERR_HIP;
+                break;
+            }
+            (void)hipFree(d.env);
+            d.env = nullptr;
+        }
+        if (rc_dev == RPT_OK) { ctx->env = EnvPlan(); return RPT_OK; }
+    }
+    EnvPlan fresh;
+    if (rc_dev == RPT_OK) {
+        fresh.size = env->size;
+        fresh.mode = env->mode;
+        fresh.scale = env->scale;
+        fresh.n_tris = ctx->refit.n_slots;
+    }
+    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
+        DevState& d = ctx->devs[i];
+        uint64_t q = 0;
+        uint32_t w_max = 0;
+        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_environment: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
+        else rc_dev = env_device(ctx, d, fresh, env->texels, &q, &w_max);
+        if (rc_dev != RPT_OK) break;
+        float wm;
+        memcpy(&wm, &w_max, 4);
+        if (i == 0) {
+            fresh.q_total = q;
+            fresh.exponent = q ? env_exponent(wm) : 0;
+        } else if (q != fresh.q_total) {                            // integer sums: every device has the same bits
+            set_err(ctx, "rpt_set_environment: device %d computed another table than device %d", d.device, ctx->devs[0].device);
+            rc_dev = RPT_ERR_HIP;
+        }
+    }
+    if (rc_dev != RPT_OK) {
+        const std::string first = ctx->err;
+        drop_scene(ctx);
+        set_err(ctx, "%s; the context now holds no scene", first.c_str());
+        return rc_dev;
+    }
+    ctx->env = fresh;
+    ctx->refit.release_staging();                                   // every device holds the refit tables
+    return RPT_OK;
+}
+
+int rpt_download_environment_table(rpt_ctx* ctx, uint64_t* cdf, uint32_t n_texels, int32_t* exponent)
+{
+    if (!ctx) { set_err(nullptr, "rpt_download_environment_table: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_environment_table: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    const rpthost::EnvPlan& ep = ctx->env;
+    const DevState& d = ctx->devs[0];
+    if (!ep.sampled() || !d.env) { set_err(ctx, "rpt_download_environment_table: no RPT_ENV_SAMPLED environment is set: the context holds no table (rpt_set_environment)"); return RPT_ERR_INVALID_ARG; }
+    if (n_texels != ep.n_texels()) { set_err(ctx, "rpt_download_environment_table: n_texels %u != the environment's %u x %u", n_texels, ep.size, ep.size); return RPT_ERR_INVALID_ARG; }
+    if (!cdf || !exponent) { set_err(ctx, "rpt_download_environment_table: cdf or exponent is NULL"); return RPT_ERR_INVALID_ARG; }
+    RPT_ON_DEVICE(ctx);
+    const rpthost::EnvLayout el(ep.size, true, ep.n_tris);
+    RPT_HIP_CHECK(ctx, hipMemcpy(cdf, static_cast<const unsigned char*>(d.env) + el.off_cdf, 8 * (size_t)n_texels, hipMemcpyDeviceToHost));
+    *exponent = ep.exponent;
     return RPT_OK;
 }
 
@@ -2463,6 +2657,30 @@ int rpt_debug_mesh_texture_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_texture_query(tex_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_debug_env_query(rpt_ctx* ctx, const float* dirs_dev, uint64_t n, uint32_t* out_dev, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_debug_env_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_env_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    if (!dirs_dev || !out_dev) { set_err(ctx, "rpt_debug_env_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->env.any() || !ctx->devs[0].env) { set_err(ctx, "rpt_debug_env_query: no environment is set"); return RPT_ERR_INVALID_ARG; }
+    if (n == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::env_query(env_scene_of(ctx, ctx->devs[0]), dirs_dev, out_dev, n, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_debug_env_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, uint32_t* out_dev, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_debug_env_sample: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_env_sample: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    if (!in_dev || !out_dev) { set_err(ctx, "rpt_debug_env_sample: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->env.any() || !ctx->devs[0].env) { set_err(ctx, "rpt_debug_env_sample: no environment is set"); return RPT_ERR_INVALID_ARG; }
+    if (n == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::env_sample(env_scene_of(ctx, ctx->devs[0]), in_dev, out_dev, n, (hipStream_t)stream));
     return RPT_OK;
 }
 

@@ -816,6 +816,9 @@ struct MaterialTableMapped {
 // type that has them specialises this (dev_mesh_light.h) and provides mesh_light_nee and mesh_light_hit_weight; every other scene
 // type's kernels contain none of that code.
 template <class S> struct MeshLights { static constexpr bool value = false; };
+// Environment lighting (include/rpt.h, "environment lighting"; project-defined) likewise: the scene type that has it specialises this
+// (dev_mesh_env.h) and provides mesh_env_nee and mesh_env_miss.  False for every other scene type.
+template <class S> struct MeshEnv { static constexpr bool value = false; };
 
 // Head of direct_light (tracer.rs:130-145): pick a light, sample it.  Returns the facing test of tracer.rs:147.
 // OFFSET false: the estimate is taken at a point inside a medium (media, dev_media.h): scatter_pos is `fhp` itself.
@@ -832,6 +835,13 @@ RPT_DEV bool nee_sample(const S& sc, v3 fhp, v3 ffnormal, Rng& rng, v3& scatter_
         // index n_lights + j is the j-th ON mesh; n_lights_f is (float)n_pick
         const uint32_t n_pick = uniform_here(sc.n_pick);
         index = (index >= n_pick) ? n_pick - 1u : index;
+        if constexpr (MeshEnv<S>::value) {
+            // the environment, while it is sampled, is the last pickable light
+            if (index == sc.env_pick) {
+                light_area = mesh_env_nee(sc, ls, rng);
+                return dot3(ls.direction, ls.normal) < 0.0f;
+            }
+        }
         if (index >= n_lights) {
             light_area = mesh_light_nee(sc, index - n_lights, scatter_pos, ls, rng);
             return dot3(ls.direction, ls.normal) < 0.0f;
@@ -1008,7 +1018,8 @@ RPT_DEV bool path_trace_geom(const S& sc, const Q& q, PathRegs& p, GeomHit& g)
     const uint32_t what = path_trace_geom_split(sc, q, p, g);
     if (what == 0u) {
         RPT_PROF(PB_BACKGROUND);
-        p.radiance = p.radiance + background(sc, p.ray) * p.throughput;
+        if constexpr (MeshEnv<S>::value) p.radiance = p.radiance + mesh_env_miss(sc, p.ray, p.ps, p.bounce) * p.throughput;
+        else p.radiance = p.radiance + background(sc, p.ray) * p.throughput;
     }
     return what == 2u;
 }

@@ -294,6 +294,51 @@ def mesh_texture_scene():
     return s, [spherical_uvs(v, (0.0, 0.0, 0.0)), quad_uv]
 
 
+def octahedral_directions(size):
+    """-> [size, size, 3] f64: the unit direction of every texel centre of a size x size octahedral image (include/rpt.h,
+    "environment lighting"): texel (i, j) is row j, column i; +y is the centre, -y the four corners, +x the middle of the right
+    edge, +z the middle of the last row."""
+    import numpy as np
+    c = (np.arange(size) + 0.5) / size * 2.0 - 1.0
+    px, pz = np.meshgrid(c, c, indexing="xy")                       # [j, i]
+    py = 1.0 - np.abs(px) - np.abs(pz)
+    sx, sz = np.where(px >= 0.0, 1.0, -1.0), np.where(pz >= 0.0, 1.0, -1.0)
+    fx, fz = (1.0 - np.abs(pz)) * sx, (1.0 - np.abs(px)) * sz
+    low = py < 0.0
+    p = np.stack([np.where(low, fx, px), py, np.where(low, fz, pz)], -1)
+    return p / np.linalg.norm(p, axis=-1, keepdims=True)
+
+
+def octahedral_from_equirect(image, size):
+    """-> [size, size, 3] f32: a latitude-longitude image ([h, w, 3], row 0 at +y, column s = atan2(z, x) / 2 pi + 0.5 as
+    spherical_uvs has it) resampled into the octahedral layout Tracer.set_environment takes: the nearest source texel at every texel
+    centre's direction.  A convenience in plain numpy with no bit promise; rotate or filter the source first if need be."""
+    import numpy as np
+    src = np.asarray(image, np.float32)
+    h, w = src.shape[0], src.shape[1]
+    d = octahedral_directions(size)
+    u = np.arctan2(d[..., 2], d[..., 0]) / (2.0 * np.pi) + 0.5
+    v = np.arccos(np.clip(d[..., 1], -1.0, 1.0)) / np.pi
+    col = np.clip(np.floor(u * w).astype(np.int64), 0, w - 1)
+    row = np.clip(np.floor(v * h).astype(np.int64), 0, h - 1)
+    return np.ascontiguousarray(src[row, col, :3])
+
+
+def mesh_env_scene(size=64, sun=(0.35, 0.8, 0.5), sun_radiance=(900.0, 800.0, 650.0), sun_texels=3.0):
+    """-> (scene, image): a small scene for environment lighting (include/rpt.h, "environment lighting"): mesh_light_scene()'s
+    icosphere on its floor, no lamp and no rpt_light, and a size x size octahedral sky for Tracer.set_environment: dim blue above
+    the horizon, dimmer grey below, and a sun `sun_texels` texels wide towards `sun` — nearly all of the image's power in a few
+    texels, which is what BSDF sampling alone renders as noise."""
+    import numpy as np
+    s = mesh_light_scene(lamp_emission=(0.0, 0.0, 0.0))
+    s.meshes = s.meshes[:1]                                         # the object; the lamp is gone (its material stays unused)
+    d = octahedral_directions(size)
+    img = np.where(d[..., 1:2] >= 0.0, np.array([0.10, 0.14, 0.20]), np.array([0.03, 0.03, 0.03]))
+    to_sun = np.asarray(sun, np.float64) / np.linalg.norm(np.asarray(sun, np.float64))
+    img = np.where((d @ to_sun)[..., None] > np.cos(2.0 * sun_texels / size), np.asarray(sun_radiance, np.float64), img)
+    return s, np.ascontiguousarray(img, dtype=np.float32)
+
+
 def mesh_scene_moved(scene, phase, seed=0x5EED0006):
     """-> new vertex arrays for `scene` (a mesh_scene(): the icosphere, then the torus), one per mesh, for Tracer.update_meshes: a
     radial ripple travelling over the icosphere — amplitude 0.25 * min(phase, 1) of its radius, six waves from pole to pole, a seeded

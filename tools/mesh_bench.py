@@ -33,7 +33,11 @@ context whose torus is ON against one whose meshes are OFF; and the time of rpt_
 the scene untextured against both meshes under a 1024 x 1024 BILINEAR / REPEAT texture, on two contexts; the wall time of the four
 move calls on a textured context against an untextured one; and the time of rpt_set_mesh_textures itself.
 
-    python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild] [--device] [--smooth] [--lights] [--textures]
+--environment: one JSON line more, for environment lighting (include/rpt.h, "environment lighting"): the resident render rate of
+the scene without an environment, with a BACKGROUND_ONLY one and with a SAMPLED one (1024 x 1024, a dim sky with a small sun), on
+three contexts, alternating; and the time of rpt_set_environment itself, for either mode.
+
+    python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild] [--device] [--smooth] [--lights] [--textures] [--environment]
 """
 import argparse
 import ctypes as C
@@ -58,6 +62,7 @@ def main():
     ap.add_argument("--smooth", action="store_true")
     ap.add_argument("--lights", action="store_true")
     ap.add_argument("--textures", action="store_true")
+    ap.add_argument("--environment", action="store_true")
     a = ap.parse_args()
     os.environ.setdefault("RPT_LIB", os.path.join(ROOT, "rust-pathtracer_amd", "librpt_hip_test.so"))     # (the product has no hooks)
     import __graft_entry__
@@ -85,6 +90,7 @@ def main():
     smooth = measure_smooth(pkg, s, a) if a.smooth else None
     lights = measure_lights(pkg, s, a) if a.lights else None
     textures = measure_textures(pkg, s, a) if a.textures else None
+    environment = measure_environment(pkg, a) if a.environment else None
     t.close()
     print(json.dumps({"workload": "mesh_scene %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "triangles": n_tris,
                       "gsamples_per_s_median": sorted(rates)[len(rates) // 2], "gsamples_per_s": rates,
@@ -101,6 +107,8 @@ def main():
         print(json.dumps(lights))
     if textures:
         print(json.dumps(textures))
+    if environment:
+        print(json.dumps(environment))
 
 
 def measure_updates(pkg, t, s, a):
@@ -490,6 +498,53 @@ def measure_textures(pkg, s, a):
         fo, fn = stats(ms["off"]), stats(ms["on"])
         out[name] = {"off_ms": fo, "on_ms": fn, "on_adds_ms": fn["median"] - fo["median"]}
     return out
+
+
+def measure_environment(pkg, a):
+    """-> the --environment line.  scenes.mesh_scene() without an environment ("none"), under a 1024 x 1024 sky BACKGROUND_ONLY
+    ("background") and SAMPLED ("sampled"): three contexts, alternating within a repetition, medians of `reps`; and the set call."""
+    import numpy as np
+    from rust_pathtracer_amd import scenes
+
+    size = 1024
+    d = scenes.octahedral_directions(size)
+    image = np.where(d[..., 1:2] >= 0.0, np.array([0.25, 0.35, 0.5]), np.array([0.05, 0.05, 0.05]))
+    sun = np.array([0.35, 0.8, 0.5]) / np.linalg.norm([0.35, 0.8, 0.5])
+    image = np.ascontiguousarray(np.where((d @ sun)[..., None] > np.cos(0.02), np.array([2000.0, 1800.0, 1500.0]), image), dtype=np.float32)
+
+    def stats(xs):
+        xs = sorted(xs)
+        return {"median": xs[len(xs) // 2], "min": xs[0], "max": xs[-1]}
+
+    def timed(call, *args, **kw):
+        t0 = time.perf_counter()
+        call(*args, **kw)
+        return (time.perf_counter() - t0) * 1e3
+
+    def rate(tr):
+        tr.render_resident(a.width, a.height, a.spp)
+        return a.width * a.height * a.spp / (tr.resident_kernel_ms() * 1e-3) / 1e9
+
+    reps = max(5, a.reps)
+    sides = ("none", "background", "sampled")
+    tr = {k: pkg.Tracer(scenes.mesh_scene(), device=0, seed=1) for k in sides}
+    first = {k: timed(tr[k].set_environment, image, sampled=(k == "sampled")) for k in sides[1:]}      # brings the refit tables too
+    again = {k: [timed(tr[k].set_environment, image, sampled=(k == "sampled")) for _ in range(reps)] for k in sides[1:]}
+    for t in tr.values():
+        rate(t)                                                     # warm-up (and the dispatch order's first costs)
+        rate(t)
+    rates = {k: [] for k in sides}
+    for _ in range(reps):
+        for k in sides:
+            rates[k].append(rate(tr[k]))
+    for t in tr.values():
+        t.close()
+    med = {k: stats(rates[k])["median"] for k in sides}
+    return {"workload": "mesh_scene environment %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "reps": reps,
+            "environment": "%d x %d f32 RGB" % (size, size),
+            "first_set_environment_ms": first, "set_environment_again_ms": {k: stats(v) for k, v in again.items()},
+            "gsamples_per_s": {k: stats(rates[k]) for k in sides},
+            "background_over_none_rate": med["background"] / med["none"], "sampled_over_none_rate": med["sampled"] / med["none"]}
 
 
 if __name__ == "__main__":
