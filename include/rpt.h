@@ -944,6 +944,93 @@ typedef struct rpt_environment {
 int rpt_set_environment(rpt_ctx* ctx, const rpt_environment* env /* NULL: remove */);
 int rpt_download_environment_table(rpt_ctx* ctx, uint64_t* cdf /* host, size*size */, uint32_t n_texels, int32_t* exponent);
 
+/* ---- mesh cutouts — PROJECT-DEFINED ------------------------------------------------------------------------------------------------
+ * Per mesh, geometry cut out by a mask: one A8 image, looked up through the mesh's texture UVs INSIDE the triangle test, so that a
+ * ray through a hole goes on to whatever lies behind it and a shadow ray through a hole is not occluded: leaves, fences, grilles,
+ * decals.  Every operation is stated, so that masks, walks and frames stay checkable bit for bit (tests/test_gpu_mesh_cutout.py holds
+ * them to a numpy restatement).  The mask is given on its own, as A8: the library does not keep a texture's bytes, rpt_mesh_texture
+ * and the decoded texels (rpt_download_mesh_texture) are what they were.  The statement is written once, in csrc/host_cut.h, which
+ * the kernels and the host reference both compile.
+ *
+ * Mask bits.  Bit k = j * width + i of a mesh's mask is
+ *     alpha[k] >= threshold                                          an integer compare; 1: the texel is OPAQUE
+ * stored as bit k % 32 of word k / 32.  Each mask starts at a 16 B boundary (it is padded with zero bits to a multiple of 128
+ * texels).  The bits are made on the device, one lane per texel and one ballot per wave; nothing in them depends on the launch.
+ *
+ * Cut test.  The triangle test of "triangle meshes" gains one last line, after the point check, for a triangle whose mesh has a
+ * cutout ON.  It uses that test's own u and v — the same operations on the same words — and tex_interp, tex_wrap and the NEAREST
+ * index of "mesh textures" (csrc/host_tex.h), reused and not restated.  The mesh's TEXTURE supplies the UVs (sa, ta), (sb, tb),
+ * (sc, tc) of the corners a, b, c and the wrap; W and H are the MASK's width and height, which need not be the texture's:
+ *     w = (1 - u) - v
+ *     s = (w*sa + u*sb) + v*sc;   t = (w*ta + u*tb) + v*tc
+ *     x = wrap(s);  y = wrap(t)                                      REPEAT or CLAMP, as "mesh textures" states them
+ *     i = nearest(x, W);  j = nearest(y, H)                          i = (int32)floorf(x * W_f); REPEAT: i == W -> 0; CLAMP: min(i, W - 1)
+ *     !bit(j * W + i)  ->  miss
+ * The mask is always looked up NEAREST, whatever the colour filter.  Stated cost: with a BILINEAR colour texture, a texel next to a
+ * hole bleeds the hole's RGB into the opaque side; paint the holes' RGB like their neighbours'.
+ *
+ * closest_hit and any_hit are unchanged in wording: they use "the triangle test".  The library applies the cut test only to a
+ * candidate that would otherwise be accepted — in the closest walk after t < best (or the tie rule), in the any-hit walk after
+ * t < max_dist: rejecting a candidate that would not have been accepted changes nothing, and it is what keeps rejected candidates
+ * from paying for the lookup.  The hierarchy returns the ordered loop's answer as before: the test is a function of
+ * (ray, triangle) alone, and rejecting more candidates never moves a hit outside its triangle's box.
+ *
+ * Composition.  Cutouts compose with FLAT / SMOOTH, textures of any wrap and filter, and an environment in either mode.  A path
+ * that hits an emissive cutout mesh sees its emission only where the mesh is opaque.  A cutout mesh cannot be a mesh light (next-
+ * event estimation would sample points inside holes): rpt_set_mesh_cutouts answers RPT_ERR_UNSUPPORTED for a mesh that is ON, and
+ * rpt_set_mesh_lights answers the same for turning ON a mesh with a cutout.  A cutout needs the mesh's UVs: an untextured mesh is
+ * RPT_ERR_INVALID_ARG (a 1 x 1 white texture is enough).  rpt_set_mesh_textures that would remove the texture of a mesh whose cutout
+ * is ON is RPT_ERR_INVALID_ARG ("remove the cutout first"); replacing the texture keeps the cutout, which then reads the new UVs and
+ * wrap.  rpt_upload_scene drops all cutouts.
+ *
+ * rpt_set_mesh_cutouts sets (ON) or removes (OFF) the cutout of the named meshes of the uploaded scene; meshes not named keep
+ * theirs.  `alpha` is copied inside the call; on return every mask is current on every device of the context.  The checks, in this
+ * order, all on the host before any device is touched — a rejected call changes nothing, and rpt_last_error starts with
+ * "rpt_set_mesh_cutouts: " and names the item:
+ *   RPT_ERR_INVALID_ARG  ctx is NULL;
+ *   RPT_ERR_NO_SCENE     no scene with meshes is uploaded;
+ *   RPT_ERR_INVALID_ARG  items NULL with a non-zero count; then per item, in order: mesh >= n_meshes, or a mesh named twice; mode
+ *                        neither constant; ON with width or height 0 or above 16384; ON with alpha NULL; ON with threshold outside
+ *                        1 .. 255; OFF with a non-zero size or a non-NULL alpha; ON on an untextured mesh;
+ *   RPT_ERR_UNSUPPORTED  ON on a mesh light;
+ *   RPT_ERR_UNSUPPORTED  all masks together would hold more than 2^26 texels;
+ *   RPT_OK               n_items == 0: nothing is done;
+ *   RPT_ERR_HIP          a runtime call failed part-way: the context is left with NO scene, as for the other mesh calls.
+ * While some cutout is ON the scene renders through a kernel of its own — the mesh kernel's body with the two walks above, one form
+ * over the textured mesh-light tables (absent lights through empty tables, as the environment form does it) and one over the
+ * environment form.  Turning every cutout OFF leaves the context rendering through exactly the kernels and tables it had before
+ * the first call.
+ *
+ * Moves.  rpt_update_meshes, rpt_rebuild_meshes and both _device forms leave masks alone and add no launch: the cut test goes
+ * through the refit's slot -> vertex table and the flattened triangle index, never through slot order.
+ *
+ * rpt_download_mesh_cutout copies one mesh's mask bits from the context's first device: n_words = ceil(width * height / 32) words.
+ * A mesh out of range, a mesh without a cutout (it says so), another n_words or a NULL destination answer RPT_ERR_INVALID_ARG.
+ *
+ * Memory.  While a cutout is ON every device holds one bit per mask texel (each mask padded to 128 texels), 16 B per mesh of the
+ * scene (the descriptors are indexed by texture ordinal; the table is sized for every mesh being textured), and 4 B per triangle of
+ * the SCENE (the empty light table); during the call, per device, the new tables beside the old ones and one byte per texel of the
+ * masks being set.  Per candidate of a cutout mesh that passes the distance compare the walk gathers 4 B (which texture), the 16 B
+ * descriptor, three slot -> vertex words, three UVs and one mask word; a candidate of another mesh the first 4 B only.
+ *
+ * Timings: not measured yet.  tools/mesh_bench.py --cutouts alternates, in one process, frames of scenes.mesh_scene textured as
+ * --textures does with no mask, under a 1024 x 1024 checker mask on both meshes (rays pass through holes: faster or slower, both are
+ * legitimate) and under an all-opaque mask (the pure cost of the test), and times the set call and the four move calls.  Registers:
+ * meshcut_regen_kernel 110 VGPRs and meshcut_env_regen_kernel 112, next to meshtex_light_regen_kernel's 111 and
+ * meshenv_regen_kernel's 113; neither uses scratch. */
+enum { RPT_MESH_CUTOUT_OFF = 0, RPT_MESH_CUTOUT_ON = 1 };
+
+typedef struct rpt_mesh_cutout {
+    uint32_t mesh;                    /* index into the uploaded scene's rpt_scene_desc.meshes */
+    uint32_t mode;                    /* RPT_MESH_CUTOUT_* ; OFF: width == height == 0, alpha == NULL */
+    uint32_t width, height;           /* of the mask: its own size, need not be the texture's */
+    const uint8_t* alpha;             /* HOST, one byte per texel, row 0 first; copied inside the call */
+    uint32_t threshold;               /* 1 .. 255: a texel is OPAQUE when alpha >= threshold */
+} rpt_mesh_cutout;
+
+int rpt_set_mesh_cutouts(rpt_ctx* ctx, const rpt_mesh_cutout* items, uint32_t n_items);
+int rpt_download_mesh_cutout(rpt_ctx* ctx, uint32_t mesh, uint32_t* bits /* host */, uint32_t n_words);
+
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)
  *   frames_done ColorBuffer.frames before the call; the caller adds `spp` afterwards

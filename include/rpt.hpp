@@ -269,6 +269,15 @@ public:
         check(rpt_download_environment_table(ctx_, out.data(), size * size, exponent), ctx_);
         return out;
     }
+    /// Mesh cutouts (rpt.h, "mesh cutouts"): an A8 mask per named mesh, tested inside the walks through the mesh's texture UVs; an item
+    /// with RPT_MESH_CUTOUT_OFF removes its mesh's.  sync_scene() drops them all.
+    void set_mesh_cutouts(const std::vector<rpt_mesh_cutout>& items) { check(rpt_set_mesh_cutouts(ctx_, items.data(), (uint32_t)items.size()), ctx_); }
+    /// The mask bits the context holds for one cutout mesh: ceil(width * height / 32) words, texel k in bit k % 32 of word k / 32.
+    std::vector<uint32_t> mesh_cutout(uint32_t mesh, uint32_t width, uint32_t height) {
+        std::vector<uint32_t> out(((size_t)width * height + 31) / 32);
+        check(rpt_download_mesh_cutout(ctx_, mesh, out.data(), (uint32_t)out.size()), ctx_);
+        return out;
+    }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

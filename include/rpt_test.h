@@ -79,6 +79,13 @@ int rpt_debug_mesh_light_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, u
  * RPT_ERR_NO_SCENE unless the uploaded scene has meshes; RPT_ERR_INVALID_ARG while no mesh is textured (those kernels do not run then). */
 int rpt_debug_mesh_texture_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
 
+/* The walks of a scene some mesh of which has a cutout ON (include/rpt.h, "mesh cutouts"), through the device functions the cutout
+ * scenes' render kernels call: rays_dev, out_dev and `flags` exactly as for rpt_debug_mesh_query — per ray {t's bits or +inf's, the
+ * winning triangle's flattened index or 0xFFFFFFFF, any_hit}, over the triangles that pass the cut test, through the hierarchy or
+ * (RPT_MESH_QUERY_BRUTE) the ordered loop.  RPT_ERR_NO_SCENE unless the uploaded scene has meshes; RPT_ERR_INVALID_ARG while no
+ * cutout is ON (those kernels do not run then). */
+int rpt_debug_mesh_cutout_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
+
 /* The lookup of the environment (include/rpt.h, "environment lighting"), through the device function the miss exit of the environment
  * scenes' render kernel calls: dirs_dev = n x 3 floats, one direction each (taken as given: not normalised); out_dev = n x 5 dwords
  * {the texel k or 0xFFFFFFFF, the radiance's three words, lp as bits: the pdf the sampler has for that direction, 0 where the miss
@@ -128,7 +135,9 @@ int rpt_debug_sched_read(rpt_ctx* ctx, uint32_t* out, uint32_t capacity_tiles, u
  * participating-media form (the scene has media: RPT_SCENE_MEDIA), bit 25 the mesh scene class's kernel (k_mesh.hip), bit 26 beside it its smooth-shading form (k_smooth.hip: some mesh is SMOOTH), bit 27 some mesh is ON (include/rpt.h, "mesh lights"): the kernel that ran is k_light.hip's, which serves flat and smooth meshes alike — with bit 26 set as well it is still that one kernel, shading the SMOOTH meshes through their per-triangle bit;
  * bit 28 some mesh is textured (include/rpt.h, "mesh textures"): the kernel that ran is one of k_tex.hip's two, the one over the mesh
  * lights' tables while bit 27 is set as well, else the one over the smooth scenes' tables; bit 29 an environment is set
- * (include/rpt.h, "environment lighting"): the kernel that ran is k_env.hip's one form, whatever bits 26-28 say.  For tests that must know that the kernel they aim at is the one
+ * (include/rpt.h, "environment lighting"): the kernel that ran is k_env.hip's one form, whatever bits 26-28 say.; bit 30 some mesh's
+ * cutout is ON (include/rpt.h, "mesh cutouts"): the kernel that ran is one of k_cut.hip's two, the one over the environment form while
+ * bit 29 is set as well, else the one over the textured mesh-light form.  For tests that must know that the kernel they aim at is the one
  * that ran. */
 int rpt_debug_kernel_choice(rpt_ctx* ctx, uint32_t* out);
 

@@ -567,6 +567,45 @@ class Tracer:
         check(lib().rpt_download_environment_table(self._h, cdf.ctypes.data, cdf.size, C.byref(e)), self._h)
         return cdf, int(e.value)
 
+    def set_mesh_cutouts(self, items):
+        """Mesh cutouts (include/rpt.h, "mesh cutouts"): `items` maps a mesh's index in scene().meshes to None — the mesh loses its
+        cutout — or to a 2-D (height, width) uint8 mask with row 0 at t = 0 (`rgba[..., 3]` of the texture works), or to a dict with
+        "alpha" (that array) and optionally "threshold" (1 .. 255, default 128: a texel is opaque when alpha >= threshold).  The mask
+        is tested inside the hierarchy walks through the mesh's texture UVs and wrap, so the mesh must be textured.  Meshes not
+        named keep their cutout; upload_scene() drops every cutout, as in C."""
+        items = sorted(items.items())
+        its = (_abi.rpt_mesh_cutout * max(1, len(items)))()
+        keep = []
+        for it, (m, cut) in zip(its, items):
+            it.mesh, it.mode = int(m), _abi.RPT_MESH_CUTOUT_OFF
+            if cut is None:
+                continue
+            threshold = 128
+            if isinstance(cut, dict):
+                cut, threshold = cut["alpha"], cut.get("threshold", 128)
+            alpha = np.asarray(cut)
+            if alpha.ndim != 2 or alpha.dtype != np.uint8:
+                raise ValueError("mesh %d: the mask must be a 2-D uint8 array (height, width)" % m)
+            alpha = np.ascontiguousarray(alpha)
+            keep.append(alpha)
+            it.mode, it.threshold = _abi.RPT_MESH_CUTOUT_ON, int(threshold)
+            it.height, it.width, it.alpha = alpha.shape[0], alpha.shape[1], alpha.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._checked_move(lib().rpt_set_mesh_cutouts(self._h, its, len(items)))
+        sizes = self.__dict__.setdefault("_cutout_sizes", {})
+        for it, (m, cut) in zip(its, items):
+            sizes[int(m)] = (it.width, it.height)
+
+    def mesh_cutout(self, m, width=None, height=None):
+        """The mask the context holds for the cutout mesh `m` (rpt_download_mesh_cutout): a new bool array of shape (height, width),
+        True where the mesh is opaque.  Without a size: the one set_mesh_cutouts last gave the mesh."""
+        if width is None or height is None:
+            width, height = self.__dict__.get("_cutout_sizes", {}).get(int(m), (0, 0))
+        n = int(width) * int(height)
+        words = np.zeros((n + 31) // 32, np.uint32)
+        check(lib().rpt_download_mesh_cutout(self._h, int(m), words.ctypes.data, words.size), self._h)
+        bits = (words[:, None] >> np.arange(32, dtype=np.uint32)[None, :]) & 1
+        return bits.reshape(-1)[:n].astype(bool).reshape(int(height), int(width))
+
     def _refresh_stale_meshes(self):
         """scene().meshes' vertex arrays that a device-source call left stale, read back once (only before an upload)."""
         for m in sorted(self._stale_meshes):

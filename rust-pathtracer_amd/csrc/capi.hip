@@ -20,6 +20,7 @@
 
 #include "../../include/rpt.h"
 #include "host_build.h"
+#include "host_cut.h"
 #include "host_env.h"
 #include "host_light.h"
 #include "host_move.h"
@@ -30,6 +31,7 @@
 #include "knobs.h"
 #include "launch.h"
 #include "launch_build.h"
+#include "launch_cut.h"
 #include "launch_env.h"
 #include "launch_light.h"
 #include "launch_move.h"
@@ -65,6 +67,7 @@ struct DevState {
     void* light = nullptr;            // mesh lights' tables (host_light.h, LightLayout): while some mesh is ON (rpt_set_mesh_lights)
     void* tex = nullptr;              // mesh textures' tables (host_tex.h, TexLayout): while some mesh is textured (rpt_set_mesh_textures)
     void* env = nullptr;              // the environment's tables (host_env.h, EnvLayout): while one is set (rpt_set_environment)
+    void* cut = nullptr;              // mesh cutouts' tables (host_cut.h, CutLayout): while some mesh's cutout is ON (rpt_set_mesh_cutouts)
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -113,6 +116,7 @@ struct rpt_ctx {
     rpthost::LightPlan light;         // which of its meshes are lights and the sizes of every device's light tables (host_light.h)
     rpthost::TexPlan tex;             // which of its meshes are textured, their UVs and the sizes of every device's texture tables (host_tex.h)
     rpthost::EnvPlan env;             // its environment's size, mode and scale, and Q as the devices computed it (host_env.h)
+    rpthost::CutPlan cut;             // which of its meshes have a cutout and where each one's mask lies on every device (host_cut.h)
     // resident ColorBuffer (buffer.rs:6-14): pixels as per-rank tiles + frames
     uint32_t res_w = 0, res_h = 0, res_tile_rows = 0, res_rows_padded = 0;
     uint64_t res_frames = 0;
@@ -298,6 +302,7 @@ static void free_mesh_work(DevState& d)
     if (d.light) { (void)hipFree(d.light); d.light = nullptr; }
     if (d.tex) { (void)hipFree(d.tex); d.tex = nullptr; }
     if (d.env) { (void)hipFree(d.env); d.env = nullptr; }
+    if (d.cut) { (void)hipFree(d.cut); d.cut = nullptr; }
     d.refit_full = false;
     d.build_temp_bytes = 0;
 }
@@ -607,6 +612,51 @@ static SceneMeshEnv env_scene_of(const rpt_ctx* ctx, const DevState& d)
     return s;
 }
 
+// What the cutout forms add to their base: pointers into device d's cutout tables (ctx->cut says their sizes).
+template <class Base> static void bind_cut(const rpt_ctx* ctx, const DevState& d, SceneMeshCutT<Base>& s)
+{
+    const rpthost::CutPlan& cp = ctx->cut;
+    const rpthost::CutLayout cl(cp.n_meshes, cp.n_tris, cp.n_words);
+    const unsigned char* base = static_cast<const unsigned char*>(d.cut);
+    s.cut_desc = reinterpret_cast<const rpthost::CutDesc*>(base + cl.off_desc);
+    s.cut_bits = reinterpret_cast<const uint32_t*>(base + cl.off_bits);
+}
+
+// A mesh scene's kernel argument while some mesh's cutout is ON and no environment is set: the textured mesh-light form's argument —
+// no mesh ON: the smooth or flat tables as tex_scene_of binds them, tri_light all 0xFFFFFFFF from the cutout allocation — plus the
+// cutout tables.  (A cutout mesh is textured: device d holds texture tables.)
+static SceneMeshCut cut_scene_of(const rpt_ctx* ctx, const DevState& d)
+{
+    SceneMeshCut s{};
+    if (d.light && ctx->light.any()) {
+        static_cast<SceneMeshLightTex&>(s) = light_tex_scene_of(ctx, d);
+    } else {
+        const rpthost::CutPlan& cp = ctx->cut;
+        const rpthost::RefitLayout rl(ctx->refit.n_vertices(), 0, 0);
+        const rpthost::CutLayout cl(cp.n_meshes, cp.n_tris, cp.n_words);
+        static_cast<SceneMeshSmooth&>(s) = tex_scene_of(ctx, d);    // (slices its texture part off: bind_tex below)
+        s.vertices = reinterpret_cast<const float*>(static_cast<const unsigned char*>(d.refit) + rl.off_vertices);
+        s.face_vertex = nullptr;                                    // (not read: no mesh is ON)
+        s.light_desc = nullptr;
+        s.light_cdf = nullptr;
+        s.tri_light = reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(d.cut) + cl.off_none);
+        s.n_faces = 0u;
+        s.n_pick = s.n_lights;
+        bind_tex(ctx, d, s);
+    }
+    bind_cut(ctx, d, s);
+    return s;
+}
+
+// ... and while an environment is set as well: env_scene_of's argument plus the cutout tables.
+static SceneMeshCutEnv cut_env_scene_of(const rpt_ctx* ctx, const DevState& d)
+{
+    SceneMeshCutEnv s{};
+    static_cast<SceneMeshEnv&>(s) = env_scene_of(ctx, d);
+    bind_cut(ctx, d, s);
+    return s;
+}
+
 // One render launch sequence on one device.
 static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t width, uint32_t height, uint64_t frames_done, uint32_t spp,
                          uint64_t seed, uint32_t flags, uint32_t tile_rows, uint32_t rank, uint32_t world, hipStream_t stream)
@@ -625,6 +675,7 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     const bool lights = kind == SceneKind::mesh && d.light && d.refit && ctx->light.any();        // some mesh is ON: k_light.hip's form, for flat and smooth meshes alike
     const bool textured = kind == SceneKind::mesh && d.tex && d.refit && ctx->tex.any();          // some mesh is textured: k_tex.hip's forms, over either of the two above
     const bool environment = kind == SceneKind::mesh && d.env && d.refit && ctx->env.any();       // an environment is set: k_env.hip's one form, over all of the above
+    const bool cutouts = kind == SceneKind::mesh && d.cut && d.tex && d.refit && ctx->cut.any();  // some mesh's cutout is ON: k_cut.hip's forms, over the textured mesh-light form or the environment's
     scs.cam = scl.cam = scm.cam = make_camera(ctx->scene.camera, (float)width, (float)height);
     const bool in_hbm = kind == SceneKind::large || kind == SceneKind::mesh;     // the scene's tables are in device memory
     const bool has_sdf = !in_hbm && scs.sdf.n_prims > 0;
@@ -687,9 +738,21 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
                         (rp.compact && !nested && nblocks <= kCompactDenseMaxBlocks ? 1u << 22 : 0u) | (nested ? 1u << 23 : 0u) |
                         (media ? 1u << 24 : 0u) | (kind == SceneKind::mesh ? 1u << 25 : 0u) |
                         (smooth ? 1u << 26 : 0u) | (lights ? 1u << 27 : 0u) | (textured ? 1u << 28 : 0u) |
-                        (environment ? 1u << 29 : 0u);
+                        (environment ? 1u << 29 : 0u) | (cutouts ? 1u << 30 : 0u);
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
+        if (cutouts && environment) {
+            SceneMeshCutEnv sce = cut_env_scene_of(ctx, d);
+            sce.cam = scm.cam;
+            sce.flags = scm.flags;
+            return rptlaunch::render_mesh_cut_env(sce, rp, grid, stream);
+        }
+        if (cutouts) {
+            SceneMeshCut smc = cut_scene_of(ctx, d);
+            smc.cam = scm.cam;
+            smc.flags = scm.flags;
+            return rptlaunch::render_mesh_cut(smc, rp, grid, stream);
+        }
         if (environment) {
             SceneMeshEnv sme = env_scene_of(ctx, d);
             sme.cam = scm.cam;
@@ -1099,6 +1162,7 @@ static void commit_scene(rpt_ctx* ctx, SceneImage& img, const std::vector<void*>
     ctx->light = rpthost::LightPlan();                              // every mesh OFF
     ctx->tex = rpthost::TexPlan();                                  // every mesh untextured
     ctx->env = rpthost::EnvPlan();                                  // no environment
+    ctx->cut = rpthost::CutPlan();                                  // every cutout OFF
 }
 
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
@@ -1131,6 +1195,7 @@ static void drop_scene(rpt_ctx* ctx)
     ctx->light = rpthost::LightPlan();
     ctx->tex = rpthost::TexPlan();
     ctx->env = rpthost::EnvPlan();
+    ctx->cut = rpthost::CutPlan();
 }
 
 // Where the named meshes' new positions come from: host arrays (rpt_update_meshes, rpt_rebuild_meshes) or device arrays through a
@@ -1732,6 +1797,11 @@ int rpt_set_mesh_lights(rpt_ctx* ctx, const rpt_mesh_light* items, uint32_t n_it
     const SceneMesh& sc0 = ctx->devs[0].scene;
     const int rc = check_mesh_lights(ctx->refit, mesh_scene, mesh_scene ? sc0.flags : 0u, (mesh_scene ? sc0.n_lights : 0u) + (ctx->env.sampled() ? 1u : 0u), items, n_items, ctx->light.mode, mode, why);
     if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    for (uint32_t m = 0; m < mode.size(); ++m)                      // include/rpt.h, "mesh cutouts": a cutout mesh cannot be a mesh light
+        if (mode[m] == RPT_MESH_LIGHT_ON && ctx->cut.on(m)) {
+            set_err(ctx, "rpt_set_mesh_lights: mesh %u has a cutout: next-event estimation would sample points inside holes (rpt_set_mesh_cutouts)", m);
+            return RPT_ERR_UNSUPPORTED;
+        }
     if (n_items == 0) return RPT_OK;
     LightPlan fresh;
     fresh.mode = mode;
@@ -1797,6 +1867,17 @@ int rpt_download_mesh_light_table(rpt_ctx* ctx, uint32_t mesh, uint64_t* cdf, ui
     if (count) RPT_HIP_CHECK(ctx, hipMemcpy(cdf, base + ll.off_cdf + 8 * (size_t)lp.on_first[ord], 8 * (size_t)count, hipMemcpyDeviceToHost));
     *exponent = desc.exponent;
     *area = desc.area;
+    return RPT_OK;
+}
+
+// The cutout descriptors of device d again, by the texture ordinals and wraps of ctx->tex (host_cut.h, cut_desc_table): after a texture
+// call, and inside rpt_set_mesh_cutouts.  The device is idle (the caller waited) and the masks stay where they are.
+static int cut_desc_device(rpt_ctx* ctx, DevState& d)
+{
+    const rpthost::CutPlan& cp = ctx->cut;
+    const rpthost::CutLayout cl(cp.n_meshes, cp.n_tris, cp.n_words);
+    const std::vector<uint32_t> desc = rpthost::cut_desc_table(cp, ctx->tex);
+    if (!desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(static_cast<unsigned char*>(d.cut) + cl.off_desc, desc.data(), 4 * desc.size(), hipMemcpyHostToDevice));
     return RPT_OK;
 }
 
@@ -1870,6 +1951,11 @@ int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t 
     std::string why;
     const int rc = check_mesh_textures(ctx->refit, ctx->scene.kind == SceneKind::mesh, items, n_items, ctx->tex.image, image, why);
     if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    for (uint32_t m = 0; m < image.size(); ++m)                     // include/rpt.h, "mesh cutouts": the cutout reads the texture's UVs and wrap
+        if (image[m].width == 0u && ctx->cut.on(m)) {
+            set_err(ctx, "rpt_set_mesh_textures: mesh %u has a cutout, which reads its texture's UVs and wrap: remove the cutout first (rpt_set_mesh_cutouts)", m);
+            return RPT_ERR_INVALID_ARG;
+        }
     if (n_items == 0) return RPT_OK;
     bool any = false;
     for (const TexImage& im : image) any = any || im.width != 0u;
@@ -1900,6 +1986,7 @@ int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t 
         DevState& d = ctx->devs[i];
         if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_textures: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
         else rc_dev = tex_device(ctx, d, old, items, n_items);
+        if (rc_dev == RPT_OK && d.cut && ctx->cut.any()) rc_dev = cut_desc_device(ctx, d);      // the ordinals or a wrap may have changed
     }
     if (rc_dev != RPT_OK) {
         const std::string first = ctx->err;
@@ -2053,6 +2140,129 @@ int rpt_download_environment_table(rpt_ctx* ctx, uint64_t* cdf, uint32_t n_texel
     const rpthost::EnvLayout el(ep.size, true, ep.n_tris);
     RPT_HIP_CHECK(ctx, hipMemcpy(cdf, static_cast<const unsigned char*>(d.env) + el.off_cdf, 8 * (size_t)n_texels, hipMemcpyDeviceToHost));
     *exponent = ep.exponent;
+    return RPT_OK;
+}
+
+// ---- rpt_set_mesh_cutouts / rpt_download_mesh_cutout (include/rpt.h, "mesh cutouts") -----------------------------------------------
+// One device's part: wait for its earlier work (a launch may still read the old tables), make the new tables, copy the kept meshes'
+// masks over from the old ones on the device, pack the named meshes' masks, write the descriptors, drop the old tables, and wait.
+// ctx->cut is already the new plan; `old` is the plan the old tables were made by.  (The refit's tables are there: the meshes are
+// textured.)
+static int cut_device(rpt_ctx* ctx, DevState& d, const rpthost::CutPlan& old, const rpt_mesh_cutout* items, uint32_t n_items)
+{
+    const rpthost::CutPlan& cp = ctx->cut;
+    const rpthost::CutLayout cl(cp.n_meshes, cp.n_tris, cp.n_words);
+    const rpthost::CutLayout ol(old.n_meshes, old.n_tris, old.n_words);
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    RPT_CHECK_RC(ensure_refit(ctx, d));
+    void* fresh = nullptr;
+    void* stage = nullptr;
+    RPT_HIP_CHECK(ctx, hipMalloc(&fresh, cl.total));
+    size_t stage_bytes = 0;                                         // the named masks' bytes, in one allocation that lives until the kernels have run
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (items[i].mode == RPT_MESH_CUTOUT_ON) stage_bytes += ((size_t)items[i].width * items[i].height + 15) & ~(size_t)15;
+    const auto fail = [&](int rc) { (void)hipFree(fresh); if (stage) (void)hipFree(stage); return rc; };
+    const auto work = [&]() -> int {
+        if (stage_bytes) RPT_HIP_CHECK(ctx, hipMalloc(&stage, stage_bytes));
+        unsigned char* base = static_cast<unsigned char*>(fresh);
+        uint32_t* words = reinterpret_cast<uint32_t*>(base + cl.off_bits);
+        RPT_HIP_CHECK(ctx, hipMemsetAsync(base, 0, cl.off_none, d.stream));
+        if (cl.off_bits > cl.off_none) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + cl.off_none, 0xFF, cl.off_bits - cl.off_none, d.stream));
+        if (cl.total > cl.off_bits) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + cl.off_bits, 0, cl.total - cl.off_bits, d.stream));
+        std::vector<uint8_t> named(cp.mask.size(), 0);
+        size_t at = 0;
+        for (uint32_t i = 0; i < n_items; ++i) {
+            const rpt_mesh_cutout& it = items[i];
+            named[it.mesh] = 1;
+            if (it.mode != RPT_MESH_CUTOUT_ON) continue;
+            const rpthost::CutMask& c = cp.mask[it.mesh];
+            const size_t n = (size_t)c.width * c.height;
+            uint8_t* at_dev = static_cast<uint8_t*>(stage) + at;
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(at_dev, it.alpha, n, hipMemcpyHostToDevice, d.stream));
+            RPT_HIP_CHECK(ctx, rptlaunch::cut_mask(at_dev, words + c.first, (uint32_t)n, c.threshold, d.stream));
+            at += (n + 15) & ~(size_t)15;
+        }
+        for (uint32_t m = 0; m < cp.mask.size(); ++m) {
+            if (named[m] || !cp.mask[m].width) continue;            // a mesh not named keeps its cutout: the bits move on the device
+            if (!d.cut || !old.on(m)) { set_err(ctx, "rpt_set_mesh_cutouts: device %d holds no mask for mesh %u", d.device, m); return RPT_ERR_HIP; }
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(words + cp.mask[m].first,
+                                              reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(d.cut) + ol.off_bits) + old.mask[m].first,
+                                              4 * (size_t)rpthost::cut_mask_words(cp.mask[m].width, cp.mask[m].height), hipMemcpyDeviceToDevice, d.stream));
+        }
+        RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+        return RPT_OK;
+    };
+    const int rc = work();
+    if (rc != RPT_OK) return fail(rc);
+    if (stage) (void)hipFree(stage);
+    if (d.cut) (void)hipFree(d.cut);
+    d.cut = fresh;
+    return cut_desc_device(ctx, d);
+}
+
+int rpt_set_mesh_cutouts(rpt_ctx* ctx, const rpt_mesh_cutout* items, uint32_t n_items)
+{
+    using namespace rpthost;
+    if (!ctx) { set_err(nullptr, "rpt_set_mesh_cutouts: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    std::vector<CutMask> mask;
+    std::string why;
+    const int rc = check_mesh_cutouts(ctx->refit, ctx->scene.kind == SceneKind::mesh, ctx->tex, ctx->light, items, n_items, ctx->cut.mask, mask, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    if (n_items == 0) return RPT_OK;
+    bool any = false;
+    for (const CutMask& c : mask) any = any || c.width != 0u;
+    if (!any && !ctx->cut.any()) return RPT_OK;                     // every cutout OFF, as before
+    DeviceGuard guard(ctx->devs[0].device);
+    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
+    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_cutouts: cannot select device %d", ctx->devs[0].device);
+    if (rc_dev == RPT_OK && !any) {                                 // every cutout OFF (again): the context is what it was before the first call
+        for (DevState& d : ctx->devs) {
+            if (!d.cut) continue;
+            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
+                set_err(ctx, "rpt_set_mesh_cutouts: cannot wait for device %d", d.device);
+                rc_dev = RPT_ERR_HIP;
+                break;
+            }
+            (void)hipFree(d.cut);
+            d.cut = nullptr;
+        }
+        if (rc_dev == RPT_OK) { ctx->cut = CutPlan(); return RPT_OK; }
+    }
+    CutPlan old;
+    if (rc_dev == RPT_OK) {
+        old = std::move(ctx->cut);
+        build_cut_plan(ctx->refit, std::move(mask), ctx->cut);
+    }
+    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
+        DevState& d = ctx->devs[i];
+        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_cutouts: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
+        else rc_dev = cut_device(ctx, d, old, items, n_items);
+    }
+    if (rc_dev != RPT_OK) {
+        const std::string first = ctx->err;
+        drop_scene(ctx);
+        set_err(ctx, "%s; the context now holds no scene", first.c_str());
+        return rc_dev;
+    }
+    return RPT_OK;
+}
+
+int rpt_download_mesh_cutout(rpt_ctx* ctx, uint32_t mesh, uint32_t* bits, uint32_t n_words)
+{
+    if (!ctx) { set_err(nullptr, "rpt_download_mesh_cutout: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_mesh_cutout: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    const rpthost::RefitPlan& plan = ctx->refit;
+    if (mesh >= plan.n_meshes()) { set_err(ctx, "rpt_download_mesh_cutout: mesh %u out of range (the scene has %u)", mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
+    const DevState& d = ctx->devs[0];
+    const rpthost::CutPlan& cp = ctx->cut;
+    if (!cp.on(mesh) || !d.cut) { set_err(ctx, "rpt_download_mesh_cutout: mesh %u has no cutout: the context holds no mask for it (rpt_set_mesh_cutouts)", mesh); return RPT_ERR_INVALID_ARG; }
+    const rpthost::CutMask& c = cp.mask[mesh];
+    const uint64_t want = ((uint64_t)c.width * c.height + 31u) / 32u;
+    if (n_words != want) { set_err(ctx, "rpt_download_mesh_cutout: mesh %u: n_words %u != %llu, the words of its %u x %u mask", mesh, n_words, (unsigned long long)want, c.width, c.height); return RPT_ERR_INVALID_ARG; }
+    if (!bits) { set_err(ctx, "rpt_download_mesh_cutout: bits is NULL"); return RPT_ERR_INVALID_ARG; }
+    RPT_ON_DEVICE(ctx);
+    const rpthost::CutLayout cl(cp.n_meshes, cp.n_tris, cp.n_words);
+    RPT_HIP_CHECK(ctx, hipMemcpy(bits, static_cast<const unsigned char*>(d.cut) + cl.off_bits + 4 * (size_t)c.first, 4 * (size_t)n_words, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
@@ -2657,6 +2867,18 @@ int rpt_debug_mesh_texture_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_texture_query(tex_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_debug_mesh_cutout_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_cutout_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_cutout_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    if (!rays_dev || !out_dev || (flags & ~(uint32_t)(RPT_MESH_QUERY_USE_MAX | RPT_MESH_QUERY_BRUTE))) { set_err(ctx, "rpt_debug_mesh_cutout_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->cut.any() || !ctx->devs[0].cut || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_cutout_query: no mesh has a cutout"); return RPT_ERR_INVALID_ARG; }
+    if (n == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_cutout_query(cut_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
 }
 

@@ -294,6 +294,29 @@ def mesh_texture_scene():
     return s, [spherical_uvs(v, (0.0, 0.0, 0.0)), quad_uv]
 
 
+def checker_mask(w, h, cells=8, opaque=255, hole=0):
+    """-> [h, w] uint8, an A8 mask for Tracer.set_mesh_cutouts in checker_texture()'s pattern: `cells` x `cells` fields over the whole
+    image, alternately `opaque` and `hole`; texel (0, 0) is opaque."""
+    import numpy as np
+    j, i = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    odd = ((i * cells // max(w, 1)) + (j * cells // max(h, 1))) % 2 == 1
+    return np.where(odd, np.uint8(hole), np.uint8(opaque)).astype(np.uint8)
+
+
+def mesh_cutout_scene(cells=6, size=48):
+    """-> (scene, uvs, mask): a small scene for mesh cutouts (include/rpt.h, "mesh cutouts"): mesh_texture_scene()'s content and, in
+    front of it, a two-triangle screen (mesh 2, 2.4 x 1.5, tilted a little, UVs over [0, 1]) for which `mask`, a size x size
+    checker_mask of `cells` fields, is meant: through its holes the camera sees the icosphere and the quad behind, and the light
+    reaches them.  `uvs`: one [n_vertices, 2] f32 array per mesh; give the screen any texture (1 x 1 white is enough) first."""
+    import numpy as np
+    s, uvs = mesh_texture_scene()
+    s.materials.append(full_material(rgb=(0.25, 0.55, 0.3), roughness=0.8))                        # the screen
+    screen = np.array([[-1.2, -0.55, 1.0], [1.2, -0.55, 1.1], [1.2, 0.95, 1.15], [-1.2, 0.95, 1.05]], dtype=np.float32)
+    s.meshes.append((screen, np.array([[0, 1, 2], [0, 2, 3]], dtype=np.uint32), len(s.materials) - 1))
+    screen_uv = np.array([[0.0, 0.0], [1.0, 0.0], [1.0, 1.0], [0.0, 1.0]], dtype=np.float32)
+    return s, uvs + [screen_uv], checker_mask(size, size, cells)
+
+
 def octahedral_directions(size):
     """-> [size, size, 3] f64: the unit direction of every texel centre of a size x size octahedral image (include/rpt.h,
     "environment lighting"): texel (i, j) is row j, column i; +y is the centre, -y the four corners, +x the middle of the right
