@@ -1031,6 +1031,103 @@ typedef struct rpt_mesh_cutout {
 int rpt_set_mesh_cutouts(rpt_ctx* ctx, const rpt_mesh_cutout* items, uint32_t n_items);
 int rpt_download_mesh_cutout(rpt_ctx* ctx, uint32_t mesh, uint32_t* bits /* host */, uint32_t n_words);
 
+/* ---- mesh normal maps — PROJECT-DEFINED ------------------------------------------------------------------------------------------
+ * Per mesh, surface detail without triangles: one RGBA8 tangent-space normal map, looked up through the mesh's texture UVs at the
+ * winning triangle, bends the SHADING normal — the flat one, or "smooth mesh shading"'s.  Every operation is stated, so that texels,
+ * hit normals and frames stay checkable bit for bit (tests/test_gpu_mesh_normal_map.py holds them to a numpy restatement).  The
+ * statement is written once, in csrc/host_nrm.h, which the kernels and the host harness both compile; it reuses tex_interp,
+ * tex_wrap and tex_lookup of "mesh textures" (csrc/host_tex.h) and does not restate them.  All arithmetic is f32, one rounding per
+ * operation, nothing contracted, with the library's correctly rounded divide and root; dot, cross and F::MAX are those of
+ * "triangle meshes".
+ *
+ * Decode.  Once per call, on the device, one lane per texel.  For a byte k
+ *     c(k) = max(((float)k - 128) / 127, -1)                         c(128) = 0, c(255) = 1, c(0) = c(1) = -1, all exactly
+ * and a decoded texel is four f32, 16 B:
+ *     {sx * c(R), sy * c(G), c(B), 0}                                sx = strength; sy = strength, or -strength with FLIP_GREEN
+ * z is neither scaled nor clamped; alpha is ignored.
+ *
+ * Lookup at the hit.  The triangle test's own u and v are recomputed as "mesh textures" does it — the same operations on the same
+ * words.  (s, t) = tex_interp over the UVs of the mesh's TEXTURE; that texture's wrap applies, the MAP's own filter, and W and H
+ * are the map's, which need not be the texture's.  tex_lookup over the decoded texels gives (x, y, z).
+ *
+ * Bend.  N is the normal the hit would have had without the map; e1, e2 are the triangle row's; (sa, ta), (sb, tb), (sc, tc) the
+ * corners' UVs.
+ *     x == 0 && y == 0                                      -> N     a flat map is the identity, bit for bit
+ *     du1 = sb - sa;  dv1 = tb - ta;  du2 = sc - sa;  dv2 = tc - ta
+ *     D = du1*dv2 - du2*dv1                                          two products, one subtraction
+ *     !(D < 0 || D > 0)                                     -> N     degenerate UVs, NaN
+ *     g = D > 0 ? 1 : -1
+ *     T0.i = g * (e1.i*dv2 - e2.i*dv1);  B0.i = g * (e2.i*du1 - e1.i*du2)                    i = x, y, z
+ *     k = dot(N, T0);  T1.i = T0.i - N.i*k;  l2 = dot(T1, T1)
+ *     !(l2 > 0 && l2 <= F::MAX)                             -> N
+ *     T = T1 / sqrt(l2)                                              one root, three divides
+ *     B = cross(N, T);  dot(B, B0) < 0 -> B = -B                     mirrored UVs; B is not normalised again
+ *     m.i = (x*T.i + y*B.i) + z*N.i;  l2 = dot(m, m)
+ *     !(l2 > 0 && l2 <= F::MAX)                             -> N
+ *     result m / sqrt(l2)                                            one root, three divides
+ * The tangent is per TRIANGLE, from positions and UVs at the hit: there is no per-vertex tangent table, so no move adds a launch
+ * and a rebuild changes nothing.  Stated cost: across a coarse SMOOTH mesh the tangent turns facet by facet.  Stated cost of the
+ * result: like the smooth normal it is not turned toward the ray and not bent back; near grazing view it can face away from the
+ * ray, and the hit is then shaded from the other side.  Unchanged: the triangle test, acceptance, any_hit, materials, emission, the
+ * mesh-light sampler and hit weight (which use the flat normal), cutouts and the environment.
+ *
+ * Composition.  Normal maps compose with FLAT / SMOOTH, OFF / ON lights, textures of any wrap and filter, cutouts, and an
+ * environment in either mode.  A normal map needs the mesh's UVs: an untextured mesh is RPT_ERR_INVALID_ARG (a 1 x 1 white texture
+ * is enough).  rpt_set_mesh_textures that would remove the texture of a mesh whose map is ON is RPT_ERR_INVALID_ARG ("remove the
+ * normal map first"); replacing the texture keeps the map, which then reads the new UVs and wrap.  rpt_upload_scene drops all maps.
+ *
+ * rpt_set_mesh_normal_maps sets (ON) or removes (OFF) the map of the named meshes of the uploaded scene; meshes not named keep
+ * theirs.  `texels` is copied inside the call; on return every map is current on every device of the context.  The checks, in this
+ * order, all on the host before any device is touched — a rejected call changes nothing, and rpt_last_error starts with
+ * "rpt_set_mesh_normal_maps: " and names the item:
+ *   RPT_ERR_INVALID_ARG  ctx is NULL;
+ *   RPT_ERR_NO_SCENE     no scene with meshes is uploaded;
+ *   RPT_ERR_INVALID_ARG  items NULL with a non-zero count; then per item, in order: mesh >= n_meshes, or a mesh named twice; mode
+ *                        neither constant; ON with width or height 0 or above 16384; ON with texels NULL; filter not a constant; an
+ *                        unknown flag bit; strength not finite, negative or above 16; OFF with a non-zero size or a non-NULL
+ *                        texels; ON on an untextured mesh;
+ *   RPT_ERR_UNSUPPORTED  all maps together would hold more than 2^26 texels;
+ *   RPT_OK               n_items == 0: nothing is done;
+ *   RPT_ERR_HIP          a runtime call failed part-way: the context is left with NO scene, as for the other mesh calls.
+ * While some map is ON the scene renders through a kernel of its own — the mesh kernel's body with the hit normal above, one form
+ * each over the textured mesh-light tables (absent lights through empty tables), the environment form and the two cutout forms,
+ * picked by (cutouts, environment).  Turning every map OFF leaves the context rendering through exactly the kernels and tables it
+ * had before the first call.
+ *
+ * Moves.  rpt_update_meshes, rpt_rebuild_meshes and both _device forms leave maps alone and add no launch: the bend reads the
+ * triangle row the walk tested, the refit's slot -> vertex table and the flattened triangle index, never slot order.
+ *
+ * rpt_download_mesh_normal_map copies one mesh's DECODED texels from the context's first device: width * height * 4 f32.  A mesh
+ * out of range, a mesh without a map (it says so), another size or a NULL destination answer RPT_ERR_INVALID_ARG.
+ *
+ * Memory.  While a map is ON every device holds 16 B per map texel, 16 B per mesh of the scene (the descriptors are indexed by
+ * texture ordinal; the table is sized for every mesh being textured), and 4 B per triangle of the SCENE (the empty light table);
+ * during the call, per device, the new tables beside the old ones and 4 B per texel of the maps being set.  Per hit on a mapped mesh
+ * the kernel gathers 4 B (which texture), the 16 B descriptor, three slot -> vertex words, three UVs and one (NEAREST) or four
+ * (BILINEAR) 16 B texels; a hit on another mesh the first 4 B, or with it the descriptor.
+ *
+ * Timings (MI355X, 1080p x 16 spp, medians of 5): 0.794 Gsamples/s with no map, 0.784 under a flat map (0.989) and 0.416 under a
+ * bump map (0.524); rpt_set_mesh_normal_maps for both 1024 x 1024 maps 0.7 ms the first time and 0.7 ms again; the four move calls
+ * without / with maps: update_meshes 0.45 / 0.44 ms; rebuild_meshes 1.19 / 1.18 ms; update_meshes_device 0.16 / 0.16 ms;
+ * rebuild_meshes_device 0.75 / 0.75 ms.  tools/mesh_bench.py --normal-maps alternates, in one process, frames of scenes.mesh_scene textured as
+ * --textures does with no map, under a flat 1024 x 1024 map on both meshes (the pure cost of the lookup: the bend returns at its
+ * first line) and under a 1024 x 1024 BILINEAR bump map, and times the set call and the four move calls with and without maps. */
+enum { RPT_MESH_NORMAL_MAP_OFF = 0, RPT_MESH_NORMAL_MAP_ON = 1 };
+enum { RPT_NORMAL_MAP_FLIP_GREEN = 1u << 0 };      /* a map authored with +y down (the "DirectX" convention) */
+
+typedef struct rpt_mesh_normal_map {
+    uint32_t mesh;                    /* index into the uploaded scene's rpt_scene_desc.meshes */
+    uint32_t mode;                    /* RPT_MESH_NORMAL_MAP_* ; OFF: width == height == 0, texels == NULL */
+    uint32_t width, height;           /* of the map: its own size, need not be the texture's */
+    const uint8_t* texels;            /* HOST, RGBA8 like rpt_mesh_texture (alpha ignored), row 0 first; copied inside the call */
+    uint32_t filter;                  /* RPT_TEX_FILTER_NEAREST / RPT_TEX_FILTER_BILINEAR */
+    uint32_t flags;                   /* RPT_NORMAL_MAP_FLIP_GREEN or 0 */
+    float strength;                   /* finite, 0 .. 16: scales x and y */
+} rpt_mesh_normal_map;
+
+int rpt_set_mesh_normal_maps(rpt_ctx* ctx, const rpt_mesh_normal_map* items, uint32_t n_items);
+int rpt_download_mesh_normal_map(rpt_ctx* ctx, uint32_t mesh, float* texels /* host, width*height*4 f32, decoded */, uint32_t width, uint32_t height);
+
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)
  *   frames_done ColorBuffer.frames before the call; the caller adds `spp` afterwards

@@ -86,6 +86,13 @@ int rpt_debug_mesh_texture_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n
  * cutout is ON (those kernels do not run then). */
 int rpt_debug_mesh_cutout_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
 
+/* The normal a winning triangle is shaded with in a scene some mesh of which has a normal map ON (include/rpt.h, "mesh normal
+ * maps"), through the hit_normal the normal-mapped scenes' render kernels call (the form over the textured mesh-light tables):
+ * rays_dev, out_dev and `flags` exactly as for rpt_debug_mesh_normal_query — per ray {the winning triangle's flattened index or
+ * 0xFFFFFFFF, the normal's three words (zeros when nothing is hit)}, RPT_MESH_QUERY_BRUTE or 0.  RPT_ERR_NO_SCENE unless the uploaded
+ * scene has meshes; RPT_ERR_INVALID_ARG while no map is ON (those kernels do not run then). */
+int rpt_debug_mesh_normal_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
+
 /* The lookup of the environment (include/rpt.h, "environment lighting"), through the device function the miss exit of the environment
  * scenes' render kernel calls: dirs_dev = n x 3 floats, one direction each (taken as given: not normalised); out_dev = n x 5 dwords
  * {the texel k or 0xFFFFFFFF, the radiance's three words, lp as bits: the pdf the sampler has for that direction, 0 where the miss
@@ -137,7 +144,8 @@ int rpt_debug_sched_read(rpt_ctx* ctx, uint32_t* out, uint32_t capacity_tiles, u
  * lights' tables while bit 27 is set as well, else the one over the smooth scenes' tables; bit 29 an environment is set
  * (include/rpt.h, "environment lighting"): the kernel that ran is k_env.hip's one form, whatever bits 26-28 say.; bit 30 some mesh's
  * cutout is ON (include/rpt.h, "mesh cutouts"): the kernel that ran is one of k_cut.hip's two, the one over the environment form while
- * bit 29 is set as well, else the one over the textured mesh-light form.  For tests that must know that the kernel they aim at is the one
+ * bit 29 is set as well, else the one over the textured mesh-light form; bit 31 some mesh's normal map is ON (include/rpt.h, "mesh
+ * normal maps"): the kernel that ran is one of k_nrm.hip's four, picked by bits 30 and 29.  For tests that must know that the kernel they aim at is the one
  * that ran. */
 int rpt_debug_kernel_choice(rpt_ctx* ctx, uint32_t* out);
 

@@ -606,6 +606,48 @@ class Tracer:
         bits = (words[:, None] >> np.arange(32, dtype=np.uint32)[None, :]) & 1
         return bits.reshape(-1)[:n].astype(bool).reshape(int(height), int(width))
 
+    def set_mesh_normal_maps(self, items):
+        """Mesh normal maps (include/rpt.h, "mesh normal maps"): `items` maps a mesh's index in scene().meshes to None — the mesh loses
+        its map — or to a (height, width, 4) uint8 RGBA tangent-space map with row 0 at t = 0 (scenes.height_to_normal_map makes one),
+        or to a dict with "texels" (that array) and optionally "filter" ("bilinear" / "nearest"), "flip_green" (a map authored with
+        +y down) and "strength" (0 .. 16, default 1: scales x and y).  The map is looked up through the mesh's texture UVs and wrap at
+        every hit and bends the shading normal, so the mesh must be textured.  Meshes not named keep their map; upload_scene()
+        drops every map, as in C."""
+        filters = {"nearest": _abi.RPT_TEX_FILTER_NEAREST, "bilinear": _abi.RPT_TEX_FILTER_BILINEAR}
+        items = sorted(items.items())
+        its = (_abi.rpt_mesh_normal_map * max(1, len(items)))()
+        keep = []
+        for it, (m, nm) in zip(its, items):
+            it.mesh, it.mode = int(m), _abi.RPT_MESH_NORMAL_MAP_OFF
+            if nm is None:
+                continue
+            if not isinstance(nm, dict):
+                nm = {"texels": nm}
+            filt = nm.get("filter", "bilinear")
+            if filt not in filters:
+                raise ValueError("mesh %d: filter must be \"nearest\" or \"bilinear\", not %r" % (m, filt))
+            texels = np.ascontiguousarray(nm["texels"], dtype=np.uint8)
+            if texels.ndim != 3 or texels.shape[2] != 4:
+                raise ValueError("mesh %d: texels must have the shape (height, width, 4)" % m)
+            keep.append(texels)
+            it.mode, it.filter = _abi.RPT_MESH_NORMAL_MAP_ON, filters[filt]
+            it.flags = _abi.RPT_NORMAL_MAP_FLIP_GREEN if nm.get("flip_green", False) else 0
+            it.strength = float(nm.get("strength", 1.0))
+            it.height, it.width, it.texels = texels.shape[0], texels.shape[1], texels.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._checked_move(lib().rpt_set_mesh_normal_maps(self._h, its, len(items)))
+        sizes = self.__dict__.setdefault("_normal_map_sizes", {})
+        for it, (m, nm) in zip(its, items):
+            sizes[int(m)] = (it.width, it.height)
+
+    def mesh_normal_map(self, m, width=None, height=None):
+        """The decoded texels the context holds for the normal-mapped mesh `m` (rpt_download_mesh_normal_map): a new float32 array of
+        shape (height, width, 4), {x, y, z, 0}.  Without a size: the one set_mesh_normal_maps last gave the mesh."""
+        if width is None or height is None:
+            width, height = self.__dict__.get("_normal_map_sizes", {}).get(int(m), (0, 0))
+        out = np.empty((int(height), int(width), 4), np.float32)
+        check(lib().rpt_download_mesh_normal_map(self._h, int(m), out.ctypes.data, int(width), int(height)), self._h)
+        return out
+
     def _refresh_stale_meshes(self):
         """scene().meshes' vertex arrays that a device-source call left stale, read back once (only before an upload)."""
         for m in sorted(self._stale_meshes):

@@ -24,6 +24,7 @@
 #include "host_env.h"
 #include "host_light.h"
 #include "host_move.h"
+#include "host_nrm.h"
 #include "host_refit.h"
 #include "host_smooth.h"
 #include "host_tex.h"
@@ -35,6 +36,7 @@
 #include "launch_env.h"
 #include "launch_light.h"
 #include "launch_move.h"
+#include "launch_nrm.h"
 #include "launch_smooth.h"
 #include "launch_tex.h"
 #ifdef RPT_TEST_HOOKS
@@ -68,6 +70,7 @@ struct DevState {
     void* tex = nullptr;              // mesh textures' tables (host_tex.h, TexLayout): while some mesh is textured (rpt_set_mesh_textures)
     void* env = nullptr;              // the environment's tables (host_env.h, EnvLayout): while one is set (rpt_set_environment)
     void* cut = nullptr;              // mesh cutouts' tables (host_cut.h, CutLayout): while some mesh's cutout is ON (rpt_set_mesh_cutouts)
+    void* nrm = nullptr;              // mesh normal maps' tables (host_nrm.h, NrmLayout): while some mesh's map is ON (rpt_set_mesh_normal_maps)
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -117,6 +120,7 @@ struct rpt_ctx {
     rpthost::TexPlan tex;             // which of its meshes are textured, their UVs and the sizes of every device's texture tables (host_tex.h)
     rpthost::EnvPlan env;             // its environment's size, mode and scale, and Q as the devices computed it (host_env.h)
     rpthost::CutPlan cut;             // which of its meshes have a cutout and where each one's mask lies on every device (host_cut.h)
+    rpthost::NrmPlan nrm;             // which of its meshes have a normal map and where each one's texels lie on every device (host_nrm.h)
     // resident ColorBuffer (buffer.rs:6-14): pixels as per-rank tiles + frames
     uint32_t res_w = 0, res_h = 0, res_tile_rows = 0, res_rows_padded = 0;
     uint64_t res_frames = 0;
@@ -303,6 +307,7 @@ static void free_mesh_work(DevState& d)
     if (d.tex) { (void)hipFree(d.tex); d.tex = nullptr; }
     if (d.env) { (void)hipFree(d.env); d.env = nullptr; }
     if (d.cut) { (void)hipFree(d.cut); d.cut = nullptr; }
+    if (d.nrm) { (void)hipFree(d.nrm); d.nrm = nullptr; }
     d.refit_full = false;
     d.build_temp_bytes = 0;
 }
@@ -657,6 +662,67 @@ static SceneMeshCutEnv cut_env_scene_of(const rpt_ctx* ctx, const DevState& d)
     return s;
 }
 
+// What the normal-mapped forms add to their base: pointers into device d's map tables (ctx->nrm says their sizes).
+template <class Base> static void bind_nrm(const rpt_ctx* ctx, const DevState& d, SceneMeshNrmT<Base>& s)
+{
+    const rpthost::NrmPlan& np = ctx->nrm;
+    const rpthost::NrmLayout nl(np.n_meshes, np.n_tris, np.n_texels);
+    const unsigned char* base = static_cast<const unsigned char*>(d.nrm);
+    s.nrm_desc = reinterpret_cast<const rpthost::NrmDesc*>(base + nl.off_desc);
+    s.nrm_texels = reinterpret_cast<const float4*>(base + nl.off_texels);
+}
+
+// A mesh scene's kernel argument while some mesh's normal map is ON, no cutout is and no environment is set: the textured mesh-light
+// form's argument — no mesh ON: the smooth or flat tables as tex_scene_of binds them, tri_light all 0xFFFFFFFF from the map
+// allocation — plus the map tables.  (A normal-mapped mesh is textured: device d holds texture tables.)
+static SceneMeshNrm nrm_scene_of(const rpt_ctx* ctx, const DevState& d)
+{
+    SceneMeshNrm s{};
+    if (d.light && ctx->light.any()) {
+        static_cast<SceneMeshLightTex&>(s) = light_tex_scene_of(ctx, d);
+    } else {
+        const rpthost::NrmPlan& np = ctx->nrm;
+        const rpthost::RefitLayout rl(ctx->refit.n_vertices(), 0, 0);
+        const rpthost::NrmLayout nl(np.n_meshes, np.n_tris, np.n_texels);
+        static_cast<SceneMeshSmooth&>(s) = tex_scene_of(ctx, d);    // (slices its texture part off: bind_tex below)
+        s.vertices = reinterpret_cast<const float*>(static_cast<const unsigned char*>(d.refit) + rl.off_vertices);
+        s.face_vertex = nullptr;                                    // (not read: no mesh is ON)
+        s.light_desc = nullptr;
+        s.light_cdf = nullptr;
+        s.tri_light = reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(d.nrm) + nl.off_none);
+        s.n_faces = 0u;
+        s.n_pick = s.n_lights;
+        bind_tex(ctx, d, s);
+    }
+    bind_nrm(ctx, d, s);
+    return s;
+}
+
+// ... and over the environment form, the cutout form and the cutout form under an environment: their arguments plus the map tables.
+static SceneMeshNrmEnv nrm_env_scene_of(const rpt_ctx* ctx, const DevState& d)
+{
+    SceneMeshNrmEnv s{};
+    static_cast<SceneMeshEnv&>(s) = env_scene_of(ctx, d);
+    bind_nrm(ctx, d, s);
+    return s;
+}
+
+static SceneMeshNrmCut nrm_cut_scene_of(const rpt_ctx* ctx, const DevState& d)
+{
+    SceneMeshNrmCut s{};
+    static_cast<SceneMeshCut&>(s) = cut_scene_of(ctx, d);
+    bind_nrm(ctx, d, s);
+    return s;
+}
+
+static SceneMeshNrmCutEnv nrm_cut_env_scene_of(const rpt_ctx* ctx, const DevState& d)
+{
+    SceneMeshNrmCutEnv s{};
+    static_cast<SceneMeshCutEnv&>(s) = cut_env_scene_of(ctx, d);
+    bind_nrm(ctx, d, s);
+    return s;
+}
+
 // One render launch sequence on one device.
 static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t width, uint32_t height, uint64_t frames_done, uint32_t spp,
                          uint64_t seed, uint32_t flags, uint32_t tile_rows, uint32_t rank, uint32_t world, hipStream_t stream)
@@ -676,6 +742,7 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     const bool textured = kind == SceneKind::mesh && d.tex && d.refit && ctx->tex.any();          // some mesh is textured: k_tex.hip's forms, over either of the two above
     const bool environment = kind == SceneKind::mesh && d.env && d.refit && ctx->env.any();       // an environment is set: k_env.hip's one form, over all of the above
     const bool cutouts = kind == SceneKind::mesh && d.cut && d.tex && d.refit && ctx->cut.any();  // some mesh's cutout is ON: k_cut.hip's forms, over the textured mesh-light form or the environment's
+    const bool normal_maps = kind == SceneKind::mesh && d.nrm && d.tex && d.refit && ctx->nrm.any();   // some mesh's normal map is ON: k_nrm.hip's forms, over the four above that hold every table
     scs.cam = scl.cam = scm.cam = make_camera(ctx->scene.camera, (float)width, (float)height);
     const bool in_hbm = kind == SceneKind::large || kind == SceneKind::mesh;     // the scene's tables are in device memory
     const bool has_sdf = !in_hbm && scs.sdf.n_prims > 0;
@@ -738,9 +805,33 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
                         (rp.compact && !nested && nblocks <= kCompactDenseMaxBlocks ? 1u << 22 : 0u) | (nested ? 1u << 23 : 0u) |
                         (media ? 1u << 24 : 0u) | (kind == SceneKind::mesh ? 1u << 25 : 0u) |
                         (smooth ? 1u << 26 : 0u) | (lights ? 1u << 27 : 0u) | (textured ? 1u << 28 : 0u) |
-                        (environment ? 1u << 29 : 0u) | (cutouts ? 1u << 30 : 0u);
+                        (environment ? 1u << 29 : 0u) | (cutouts ? 1u << 30 : 0u) | (normal_maps ? 1u << 31 : 0u);
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
+        if (normal_maps && cutouts && environment) {
+            SceneMeshNrmCutEnv sn = nrm_cut_env_scene_of(ctx, d);
+            sn.cam = scm.cam;
+            sn.flags = scm.flags;
+            return rptlaunch::render_mesh_nrm_cut_env(sn, rp, grid, stream);
+        }
+        if (normal_maps && cutouts) {
+            SceneMeshNrmCut sn = nrm_cut_scene_of(ctx, d);
+            sn.cam = scm.cam;
+            sn.flags = scm.flags;
+            return rptlaunch::render_mesh_nrm_cut(sn, rp, grid, stream);
+        }
+        if (normal_maps && environment) {
+            SceneMeshNrmEnv sn = nrm_env_scene_of(ctx, d);
+            sn.cam = scm.cam;
+            sn.flags = scm.flags;
+            return rptlaunch::render_mesh_nrm_env(sn, rp, grid, stream);
+        }
+        if (normal_maps) {
+            SceneMeshNrm sn = nrm_scene_of(ctx, d);
+            sn.cam = scm.cam;
+            sn.flags = scm.flags;
+            return rptlaunch::render_mesh_nrm(sn, rp, grid, stream);
+        }
         if (cutouts && environment) {
             SceneMeshCutEnv sce = cut_env_scene_of(ctx, d);
             sce.cam = scm.cam;
@@ -1163,6 +1254,7 @@ static void commit_scene(rpt_ctx* ctx, SceneImage& img, const std::vector<void*>
     ctx->tex = rpthost::TexPlan();                                  // every mesh untextured
     ctx->env = rpthost::EnvPlan();                                  // no environment
     ctx->cut = rpthost::CutPlan();                                  // every cutout OFF
+    ctx->nrm = rpthost::NrmPlan();                                  // every normal map OFF
 }
 
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
@@ -1196,6 +1288,7 @@ static void drop_scene(rpt_ctx* ctx)
     ctx->tex = rpthost::TexPlan();
     ctx->env = rpthost::EnvPlan();
     ctx->cut = rpthost::CutPlan();
+    ctx->nrm = rpthost::NrmPlan();
 }
 
 // Where the named meshes' new positions come from: host arrays (rpt_update_meshes, rpt_rebuild_meshes) or device arrays through a
@@ -1881,6 +1974,17 @@ static int cut_desc_device(rpt_ctx* ctx, DevState& d)
     return RPT_OK;
 }
 
+// The normal maps' descriptors of device d again, by the texture ordinals and wraps of ctx->tex (host_nrm.h, nrm_desc_table): after a
+// texture call, and inside rpt_set_mesh_normal_maps.  The device is idle (the caller waited) and the texels stay where they are.
+static int nrm_desc_device(rpt_ctx* ctx, DevState& d)
+{
+    const rpthost::NrmPlan& np = ctx->nrm;
+    const rpthost::NrmLayout nl(np.n_meshes, np.n_tris, np.n_texels);
+    const std::vector<uint32_t> desc = rpthost::nrm_desc_table(np, ctx->tex);
+    if (!desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(static_cast<unsigned char*>(d.nrm) + nl.off_desc, desc.data(), 4 * desc.size(), hipMemcpyHostToDevice));
+    return RPT_OK;
+}
+
 // ---- rpt_set_mesh_textures / rpt_download_mesh_texture (include/rpt.h, "mesh textures") -------------------------------------------
 // One device's part: wait for its earlier work (a launch may still read the old tables), make its refit tables if it has none, make
 // the new tables, copy the kept meshes' texels over from the old ones on the device, decode the named meshes' images, drop the old
@@ -1956,6 +2060,11 @@ int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t 
             set_err(ctx, "rpt_set_mesh_textures: mesh %u has a cutout, which reads its texture's UVs and wrap: remove the cutout first (rpt_set_mesh_cutouts)", m);
             return RPT_ERR_INVALID_ARG;
         }
+    for (uint32_t m = 0; m < image.size(); ++m)                     // include/rpt.h, "mesh normal maps": the map reads the texture's UVs and wrap
+        if (image[m].width == 0u && ctx->nrm.on(m)) {
+            set_err(ctx, "rpt_set_mesh_textures: mesh %u has a normal map, which reads its texture's UVs and wrap: remove the normal map first (rpt_set_mesh_normal_maps)", m);
+            return RPT_ERR_INVALID_ARG;
+        }
     if (n_items == 0) return RPT_OK;
     bool any = false;
     for (const TexImage& im : image) any = any || im.width != 0u;
@@ -1987,6 +2096,7 @@ int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t 
         if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_textures: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
         else rc_dev = tex_device(ctx, d, old, items, n_items);
         if (rc_dev == RPT_OK && d.cut && ctx->cut.any()) rc_dev = cut_desc_device(ctx, d);      // the ordinals or a wrap may have changed
+        if (rc_dev == RPT_OK && d.nrm && ctx->nrm.any()) rc_dev = nrm_desc_device(ctx, d);
     }
     if (rc_dev != RPT_OK) {
         const std::string first = ctx->err;
@@ -2263,6 +2373,128 @@ int rpt_download_mesh_cutout(rpt_ctx* ctx, uint32_t mesh, uint32_t* bits, uint32
     RPT_ON_DEVICE(ctx);
     const rpthost::CutLayout cl(cp.n_meshes, cp.n_tris, cp.n_words);
     RPT_HIP_CHECK(ctx, hipMemcpy(bits, static_cast<const unsigned char*>(d.cut) + cl.off_bits + 4 * (size_t)c.first, 4 * (size_t)n_words, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
+// ---- rpt_set_mesh_normal_maps / rpt_download_mesh_normal_map (include/rpt.h, "mesh normal maps") -----------------------------------
+// One device's part: wait for its earlier work (a launch may still read the old tables), make the new tables, copy the kept meshes'
+// texels over from the old ones on the device, decode the named meshes' maps, write the descriptors, drop the old tables, and wait.
+// ctx->nrm is already the new plan; `old` is the plan the old tables were made by.  (The refit's tables are there: the meshes are
+// textured.)
+static int nrm_device(rpt_ctx* ctx, DevState& d, const rpthost::NrmPlan& old, const rpt_mesh_normal_map* items, uint32_t n_items)
+{
+    const rpthost::NrmPlan& np = ctx->nrm;
+    const rpthost::NrmLayout nl(np.n_meshes, np.n_tris, np.n_texels);
+    const rpthost::NrmLayout ol(old.n_meshes, old.n_tris, old.n_texels);
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    RPT_CHECK_RC(ensure_refit(ctx, d));
+    void* fresh = nullptr;
+    void* stage = nullptr;
+    RPT_HIP_CHECK(ctx, hipMalloc(&fresh, nl.total));
+    size_t stage_bytes = 0;                                         // the named maps' bytes, in one allocation that lives until the decodes have run
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (items[i].mode == RPT_MESH_NORMAL_MAP_ON) stage_bytes += ((size_t)items[i].width * items[i].height * 4 + 15) & ~(size_t)15;
+    const auto fail = [&](int rc) { (void)hipFree(fresh); if (stage) (void)hipFree(stage); return rc; };
+    const auto work = [&]() -> int {
+        if (stage_bytes) RPT_HIP_CHECK(ctx, hipMalloc(&stage, stage_bytes));
+        unsigned char* base = static_cast<unsigned char*>(fresh);
+        rpthost::TexTexel* texels = reinterpret_cast<rpthost::TexTexel*>(base + nl.off_texels);
+        RPT_HIP_CHECK(ctx, hipMemsetAsync(base, 0, nl.off_none, d.stream));
+        if (nl.off_texels > nl.off_none) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + nl.off_none, 0xFF, nl.off_texels - nl.off_none, d.stream));
+        std::vector<uint8_t> named(np.map.size(), 0);
+        size_t at = 0;
+        for (uint32_t i = 0; i < n_items; ++i) {
+            const rpt_mesh_normal_map& it = items[i];
+            named[it.mesh] = 1;
+            if (it.mode != RPT_MESH_NORMAL_MAP_ON) continue;
+            const rpthost::NrmMap& c = np.map[it.mesh];
+            const size_t n = (size_t)c.width * c.height;
+            uint8_t* at_dev = static_cast<uint8_t*>(stage) + at;
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(at_dev, it.texels, 4 * n, hipMemcpyHostToDevice, d.stream));
+            RPT_HIP_CHECK(ctx, rptlaunch::nrm_decode(at_dev, texels + c.first, (uint32_t)n, c.strength, rpthost::nrm_scale_y(c.strength, c.flags), d.stream));
+            at += (4 * n + 15) & ~(size_t)15;
+        }
+        for (uint32_t m = 0; m < np.map.size(); ++m) {
+            if (named[m] || !np.map[m].width) continue;             // a mesh not named keeps its map: the decoded texels move on the device
+            if (!d.nrm || !old.on(m)) { set_err(ctx, "rpt_set_mesh_normal_maps: device %d holds no texels for mesh %u", d.device, m); return RPT_ERR_HIP; }
+            const size_t n = (size_t)np.map[m].width * np.map[m].height;
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(texels + np.map[m].first,
+                                              reinterpret_cast<const rpthost::TexTexel*>(static_cast<const unsigned char*>(d.nrm) + ol.off_texels) + old.map[m].first,
+                                              16 * n, hipMemcpyDeviceToDevice, d.stream));
+        }
+        RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+        return RPT_OK;
+    };
+    const int rc = work();
+    if (rc != RPT_OK) return fail(rc);
+    if (stage) (void)hipFree(stage);
+    if (d.nrm) (void)hipFree(d.nrm);
+    d.nrm = fresh;
+    return nrm_desc_device(ctx, d);
+}
+
+int rpt_set_mesh_normal_maps(rpt_ctx* ctx, const rpt_mesh_normal_map* items, uint32_t n_items)
+{
+    using namespace rpthost;
+    if (!ctx) { set_err(nullptr, "rpt_set_mesh_normal_maps: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    std::vector<NrmMap> map;
+    std::string why;
+    const int rc = check_mesh_normal_maps(ctx->refit, ctx->scene.kind == SceneKind::mesh, ctx->tex, items, n_items, ctx->nrm.map, map, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    if (n_items == 0) return RPT_OK;
+    bool any = false;
+    for (const NrmMap& c : map) any = any || c.width != 0u;
+    if (!any && !ctx->nrm.any()) return RPT_OK;                     // every map OFF, as before
+    DeviceGuard guard(ctx->devs[0].device);
+    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
+    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_normal_maps: cannot select device %d", ctx->devs[0].device);
+    if (rc_dev == RPT_OK && !any) {                                 // every map OFF (again): the context is what it was before the first call
+        for (DevState& d : ctx->devs) {
+            if (!d.nrm) continue;
+            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
+                set_err(ctx, "rpt_set_mesh_normal_maps: cannot wait for device %d", d.device);
+                rc_dev = RPT_ERR_HIP;
+                break;
+            }
+            (void)hipFree(d.nrm);
+            d.nrm = nullptr;
+        }
+        if (rc_dev == RPT_OK) { ctx->nrm = NrmPlan(); return RPT_OK; }
+    }
+    NrmPlan old;
+    if (rc_dev == RPT_OK) {
+        old = std::move(ctx->nrm);
+        build_nrm_plan(ctx->refit, std::move(map), ctx->nrm);
+    }
+    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
+        DevState& d = ctx->devs[i];
+        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_normal_maps: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
+        else rc_dev = nrm_device(ctx, d, old, items, n_items);
+    }
+    if (rc_dev != RPT_OK) {
+        const std::string first = ctx->err;
+        drop_scene(ctx);
+        set_err(ctx, "%s; the context now holds no scene", first.c_str());
+        return rc_dev;
+    }
+    return RPT_OK;
+}
+
+int rpt_download_mesh_normal_map(rpt_ctx* ctx, uint32_t mesh, float* texels, uint32_t width, uint32_t height)
+{
+    if (!ctx) { set_err(nullptr, "rpt_download_mesh_normal_map: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_mesh_normal_map: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    const rpthost::RefitPlan& plan = ctx->refit;
+    if (mesh >= plan.n_meshes()) { set_err(ctx, "rpt_download_mesh_normal_map: mesh %u out of range (the scene has %u)", mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
+    const DevState& d = ctx->devs[0];
+    const rpthost::NrmPlan& np = ctx->nrm;
+    if (!np.on(mesh) || !d.nrm) { set_err(ctx, "rpt_download_mesh_normal_map: mesh %u has no normal map: the context holds no texels for it (rpt_set_mesh_normal_maps)", mesh); return RPT_ERR_INVALID_ARG; }
+    const rpthost::NrmMap& c = np.map[mesh];
+    if (width != c.width || height != c.height) { set_err(ctx, "rpt_download_mesh_normal_map: mesh %u: %u x %u is not its map's %u x %u", mesh, width, height, c.width, c.height); return RPT_ERR_INVALID_ARG; }
+    if (!texels) { set_err(ctx, "rpt_download_mesh_normal_map: texels is NULL"); return RPT_ERR_INVALID_ARG; }
+    RPT_ON_DEVICE(ctx);
+    const rpthost::NrmLayout nl(np.n_meshes, np.n_tris, np.n_texels);
+    RPT_HIP_CHECK(ctx, hipMemcpy(texels, static_cast<const unsigned char*>(d.nrm) + nl.off_texels + 16 * (size_t)c.first, 16 * (size_t)c.width * c.height, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
 
@@ -2879,6 +3111,18 @@ int rpt_debug_mesh_cutout_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n,
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_cutout_query(cut_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_debug_mesh_normal_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_normal_map_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_normal_map_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    if (!rays_dev || !out_dev || (flags & ~(uint32_t)RPT_MESH_QUERY_BRUTE)) { set_err(ctx, "rpt_debug_mesh_normal_map_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->nrm.any() || !ctx->devs[0].nrm || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_normal_map_query: no mesh has a normal map"); return RPT_ERR_INVALID_ARG; }
+    if (n == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_normal_map_query(nrm_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
 }
 

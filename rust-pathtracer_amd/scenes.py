@@ -317,6 +317,42 @@ def mesh_cutout_scene(cells=6, size=48):
     return s, uvs + [screen_uv], checker_mask(size, size, cells)
 
 
+def height_to_normal_map(height, scale):
+    """-> [h, w, 4] uint8, an RGBA8 tangent-space normal map for Tracer.set_mesh_normal_maps from a [h, w] height field that tiles:
+    the normal of texel (i, j) is normalize(-scale * dh/di, -scale * dh/dj, 1) with central differences over the wrapped
+    neighbours (per texel, so `scale` is the height range in texels), stored as round(128 + 127 c) per component — the inverse of
+    the library's decode — with alpha 255.  A constant field gives (128, 128, 255, 255) everywhere; +y is up (no FLIP_GREEN)."""
+    import numpy as np
+    h = np.asarray(height, np.float64)
+    if h.ndim != 2:
+        raise ValueError("height must be a 2-D array (height, width)")
+    di = 0.5 * (np.roll(h, -1, 1) - np.roll(h, 1, 1))
+    dj = 0.5 * (np.roll(h, -1, 0) - np.roll(h, 1, 0))
+    n = np.stack([-float(scale) * di, -float(scale) * dj, np.ones_like(h)], -1)
+    n /= np.sqrt((n * n).sum(-1, keepdims=True))
+    out = np.full(h.shape + (4,), 255, np.uint8)
+    out[..., :3] = np.clip(np.rint(128.0 + 127.0 * n), 0, 255).astype(np.uint8)
+    return out
+
+
+def bump_height(w, h, waves=3):
+    """-> [h, w] f64 in [0, 1]: `waves` x `waves` smooth bumps that tile, the height field behind mesh_normal_map_scene()'s map."""
+    import numpy as np
+    j, i = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    return 0.5 + 0.5 * np.sin(2.0 * np.pi * waves * (i + 0.5) / w) * np.sin(2.0 * np.pi * waves * (j + 0.5) / h)
+
+
+def mesh_normal_map_scene(size=32, tilt_degrees=15.0):
+    """-> (scene, uvs, normal_map): a small scene for mesh normal maps (include/rpt.h, "mesh normal maps"): mesh_texture_scene()
+    as it is, and a size x size bump map (height_to_normal_map of bump_height, three waves each way) whose steepest tilt is about
+    `tilt_degrees`, meant for either mesh.  `uvs`: one [n_vertices, 2] f32 array per mesh; texture a mesh (1 x 1 white is enough)
+    before giving it the map."""
+    import numpy as np
+    s, uvs = mesh_texture_scene()
+    steepest = 0.5 * np.sin(2.0 * np.pi * 3 / size)                  # of bump_height's central differences
+    return s, uvs, height_to_normal_map(bump_height(size, size, 3), np.tan(np.radians(tilt_degrees)) / steepest)
+
+
 def octahedral_directions(size):
     """-> [size, size, 3] f64: the unit direction of every texel centre of a size x size octahedral image (include/rpt.h,
     "environment lighting"): texel (i, j) is row j, column i; +y is the centre, -y the four corners, +x the middle of the right
