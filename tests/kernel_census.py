@@ -1,6 +1,7 @@
 """Which render kernels there are, and which one ran: the kernels of a library's gfx950 code object, and the kernel a launch took
 according to rpt_debug_kernel_choice (include/rpt_test.h).  Shared by the strict and the relaxed kernel matrices
-(tests/test_gpu_strict_kernels.py, tests/test_gpu_relaxed.py).  Reading the code object needs no GPU."""
+(tests/test_gpu_strict_kernels.py, tests/test_gpu_relaxed.py) and, for mesh scenes, by the float64 comparisons
+(tests/test_gpu_mesh_*_f64.py).  Reading the code object needs no GPU."""
 import os
 import re
 import struct
@@ -44,6 +45,46 @@ def kernel_of(choice, klass):
     if mapped:
         return "render_small_regen_maptable_kernel" + fast
     return "render_small_regen_kernel" + fast
+
+
+MESH_BIT, SMOOTH_BIT, LIGHT_BIT, TEX_BIT, ENV_BIT, CUT_BIT, NRM_BIT = (1 << b for b in range(25, 32))
+MESH_FORM_BITS = 0x7F << 25
+# every name mesh_kernel_of can return, in launch_render's order
+MESH_RENDER_KERNELS = ["meshnrm_cut_env_regen_kernel", "meshnrm_cut_regen_kernel", "meshnrm_env_regen_kernel", "meshnrm_regen_kernel",
+                       "meshcut_env_regen_kernel", "meshcut_regen_kernel", "meshenv_regen_kernel", "meshtex_light_regen_kernel",
+                       "meshtex_regen_kernel", "meshlight_regen_kernel", "meshsmooth_regen_kernel", "mesh_regen_kernel"]
+
+
+def mesh_kernel_of(choice):
+    """The kernel launch_render (csrc/capi.hip) takes for a mesh scene with rpt_debug_kernel_choice's bits 25-31 (MESH, SMOOTH, LIGHT,
+    TEX, ENV, CUT, NRM), its `if`s in its order: normal maps first, picked by (cutouts, environment), then cutouts, picked by the
+    environment, then the environment's one form, then textures over the lights' tables or the smooth ones', lights, smooth, flat."""
+    assert choice & MESH_BIT, "not a mesh scene's launch: 0x%x" % choice
+    smooth, lights, textured = choice & SMOOTH_BIT, choice & LIGHT_BIT, choice & TEX_BIT
+    environment, cutouts, normal_maps = choice & ENV_BIT, choice & CUT_BIT, choice & NRM_BIT
+    if normal_maps and cutouts and environment:
+        return "meshnrm_cut_env_regen_kernel"
+    if normal_maps and cutouts:
+        return "meshnrm_cut_regen_kernel"
+    if normal_maps and environment:
+        return "meshnrm_env_regen_kernel"
+    if normal_maps:
+        return "meshnrm_regen_kernel"
+    if cutouts and environment:
+        return "meshcut_env_regen_kernel"
+    if cutouts:
+        return "meshcut_regen_kernel"
+    if environment:
+        return "meshenv_regen_kernel"
+    if textured and lights:
+        return "meshtex_light_regen_kernel"
+    if textured:
+        return "meshtex_regen_kernel"
+    if lights:
+        return "meshlight_regen_kernel"
+    if smooth:
+        return "meshsmooth_regen_kernel"
+    return "mesh_regen_kernel"
 
 
 # ---- which kernels there are ------------------------------------------------------------------------------------------------------

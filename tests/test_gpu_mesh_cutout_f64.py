@@ -4,7 +4,8 @@ last line of its triangle test: u and v of that test, the UV interpolation, the 
 sample renders are compared sample by sample with test_path_f64's TAU / REL_CLEAN / NEAR_TIE_MAX over test_gpu_mesh_f64's own
 draws, 200 pixels x 3 seeds x 2 scenes (needs an MI355X).  Every mesh carries test_gpu_mesh_texture_f64's texture (the first scene
 BILINEAR / REPEAT, the second NEAREST / CLAMP) and a 4 x 2 checker mask of single texels over the same UVs (not square: swapping
-s and t must not map the mask onto itself).
+s and t must not map the mask onto itself).  The statements themselves are
+functions of tests/mesh_compose_f64.py, which the composed restatement (tests/test_gpu_mesh_compose_f64.py) calls as well.
 
 Margins.  The mask is a step function: for every triangle that passes the rest of the test, the distance of x*W and of y*H to the
 next integer is recorded through M.of(., 1.0), where the coordinate is not clamped — as NEAREST does in the textured restatement.
@@ -18,9 +19,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import mesh_compose_f64 as MC
 import pt_f64 as P
+from kernel_census import mesh_kernel_of
 from test_gpu_mesh_smooth_f64 import _draws
-from test_gpu_mesh_texture_f64 import CLAMP, GAMMA, MODES, REPEAT, TexMeshDescScene, scene_textures
+from test_gpu_mesh_texture_f64 import GAMMA, MODES, TexMeshDescScene, scene_textures
 from test_gpu_path_f64 import Tally
 from test_path_f64 import NEAR_TIE_MAX, REL_CLEAN, TAU, rel_distance
 
@@ -52,36 +55,11 @@ class CutMeshDescScene(TexMeshDescScene):
         self.cut_fault = cut_fault
         self.opaque = [mask >= 128 for _, mask in sorted(scene_masks(scene).items())]
 
-    def _cut_axis(self, s, n, M):
-        x = min(max(s, 0.0), 1.0) if self.wrap == CLAMP else s - np.floor(s)
-        p = x * n
-        if self.wrap == REPEAT or 0.0 < s < 1.0:
-            M.of(p - np.round(p), 1.0)
-        i = int(np.floor(p))
-        return min(i, n - 1) if self.wrap == CLAMP else i % n
-
     def _triangles(self, o, d, M):
         """The triangle test with its last line: a triangle that passes everything else misses where its mesh's mask has a hole."""
         hit, t = super()._triangles(o, d, M)
-        if self.cut_fault == "ignore":
-            return hit, t
-        o, d = np.array(o), np.array(d)
-        for k in np.nonzero(hit)[0]:
-            p = np.cross(d, self.e2[k])
-            inv = 1.0 / float((self.e1[k] * p).sum())
-            sv = o - self.ta[k]
-            u = float((sv * p).sum()) * inv
-            v = float((d * np.cross(sv, self.e1[k])).sum()) * inv
-            ua, ub, uc = (self.uv[j] for j in self.corner[k])
-            s, tt = ((1.0 - u) - v) * ua + u * ub + v * uc
-            if self.cut_fault == "swap":
-                s, tt = tt, s
-            bits = self.opaque[int(self.tri_mesh[k])]
-            h, w = bits.shape
-            i = self._cut_axis(float(s), w, M)
-            j = self._cut_axis(float(tt), h, M)
-            if not bits[j, i]:
-                hit[k] = False
+        if self.cut_fault != "ignore":
+            MC.cut_test(self, hit, o, d, M, lambda k: (self.opaque[int(self.tri_mesh[k])], self.wrap), swap=self.cut_fault == "swap")
         return hit, t
 
 
@@ -112,7 +90,8 @@ def test_cutout_mesh_renders_against_the_restatement(rpt, oracle, torch_cuda):
             refs[k] = CutMeshDescScene(s.describe(), s, wrap, filt)
         frame, choice = _one_cut_sample(rpt, torch_cuda, s, wrap, filt, w, h, seed)
         assert choice & (1 << 25) and choice & CUT_BIT, "the cutout mesh kernel ran"
-        t.ran.add("meshcut_regen_kernel")
+        assert mesh_kernel_of(choice) == "meshcut_regen_kernel"
+        t.ran.add(mesh_kernel_of(choice))
         restated, margins, _ = P.sample_many(refs[k], oracle, seed, [(c, r, 0) for c, r in pixels], w, h)
         print("%s (seed %d): %d of %d samples below TAU" % (what, seed, int((margins <= TAU).sum()), len(margins)))
         t.add("%s, cut out (seed %d)" % (what, seed), frame, restated, margins, pixels)

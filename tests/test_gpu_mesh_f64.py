@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import pt_f64 as P
+from kernel_census import mesh_kernel_of
 from test_gpu_path_f64 import Tally, _one_sample
 from test_path_f64 import NEAR_TIE_MAX, TAU
 
@@ -155,7 +156,8 @@ def test_mesh_renders_against_the_restatement(rpt, oracle, torch_cuda, monkeypat
             pixels = list(zip(rng.integers(0, w, 200).tolist(), rng.integers(0, h, 200).tolist()))
             frame, choice = _one_sample(rpt, torch_cuda, s, w, h, 50 + 10 * k + seed, False, monkeypatch)
             assert choice & (1 << 25), "the mesh kernel ran"
-            t.ran.add("mesh_regen_kernel")
+            assert mesh_kernel_of(choice) == "mesh_regen_kernel"
+            t.ran.add(mesh_kernel_of(choice))
             restated, margins, _ = P.sample_many(ref, oracle, 50 + 10 * k + seed, [(c, r, 0) for c, r in pixels], w, h)
             t.add("%s (seed %d)" % (what, 50 + 10 * k + seed), frame, restated, margins, pixels)
     t.check("mesh scenes")

@@ -5,7 +5,8 @@ and the f32 positions as float64.  LightPath is pt_f64.Path with direct_light ov
 the mesh sampler in float64: the pick in integers, the point, direction, turned normal and pdf — and sample with the hit-side weight.
 It records the margins of the `c > 0` turn, of the facing test, of the hit side's `c > 0`, and of the CDF pick (the distance of T to
 the next step below and above, relative to q_k).  One-sample renders are compared sample by sample with test_path_f64's TAU /
-REL_CLEAN / NEAR_TIE_MAX through test_gpu_path_f64.Tally (needs an MI355X); the two other tests need no GPU.
+REL_CLEAN / NEAR_TIE_MAX through test_gpu_path_f64.Tally (needs an MI355X); the two other tests need no GPU.  The statements themselves are
+functions of tests/mesh_compose_f64.py, which the composed restatement (tests/test_gpu_mesh_compose_f64.py) calls as well.
 
 Draws: 64 x 48, 200 pixels x 3 seeds x 2 scenes — scenes.mesh_light_scene() at the reference's four bounces, with the spherical
 light (N = 2) and every mesh FLAT, and without it (N = 1) and every mesh SMOOTH.  The restatement alone, on the CPU, for exactly
@@ -13,20 +14,19 @@ these draws: 108 of 1 200 samples lie below TAU (9.0 %, under the 12 % cap; BELO
 test_the_draws_leave_enough_clean_samples counts again on every run), 775 samples carry radiance; a restatement without the hit-side
 weight moves 40 clean samples beyond REL_CLEAN and one with n_lights where N belongs 264 (test_the_restatement_sees_the_weight_and_
 the_count, on a scene whose lamp is eight times as wide so that paths find it by themselves)."""
-import bisect
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import mesh_compose_f64 as MC
 import pt_f64 as P
+from kernel_census import mesh_kernel_of
 from test_gpu_mesh_smooth_f64 import SmoothMeshDescScene
 from test_gpu_path_f64 import Tally
-from test_mesh_light_host import restate_table
 from test_path_f64 import NEAR_TIE_MAX, REL_CLEAN, TAU, rel_distance
 
 LIGHT_BIT, SMOOTH_BIT, MESH_BIT = 1 << 27, 1 << 26, 1 << 25
-N_DRAWS = 128
 # Counted on the CPU (test_the_draws_leave_enough_clean_samples prints the figures): samples of the 1 200 below TAU.
 BELOW_TAU = 108
 
@@ -44,176 +44,55 @@ class LightMeshDescScene(SmoothMeshDescScene):
     def __init__(self, desc, scene, smooth=(), on=()):
         super().__init__(desc, scene)
         self.smooth_tri = np.concatenate([np.full(len(t), m in smooth) for m, (_, t, _) in enumerate(scene.meshes)])
-        self.tri_ord = np.concatenate([np.full(len(t), sorted(on).index(m) if m in on else -1) for m, (_, t, _) in enumerate(scene.meshes)])
-        self.mesh_lights = []                                          # ordinal -> (cdf list, Q, A_tot, corners f64 [n, 3, 3], emission)
-        for m in sorted(on):
-            v, t, mat = scene.meshes[m]
-            cdf, _, a_tot = restate_table(v, t)
-            tri = np.asarray(v, np.float32)[np.asarray(t, np.int64)].astype(np.float64)
-            em = tuple(float(x) for x in desc.materials[mat].emission)
-            self.mesh_lights.append(([int(c) for c in cdf], int(cdf[-1]) if len(cdf) else 0, float(a_tot), tri, em))
-        self.won = None
+        MC.bind_mesh_lights(self, desc, scene, on)                    # tri_ord, mesh_lights, won
 
     def triangle_normal(self, k, o, d, M):
         self.won = k
         if self.smooth_tri[k]:
             return super().triangle_normal(k, o, d, M)
-        return P.normalize(tuple(float(x) for x in np.cross(self.e1[k], self.e2[k])))
+        return MC.flat_normal(self, k)
 
     def closest_hit(self, o, d, st, ls, mut, M):
         self.won = None
         return super().closest_hit(o, d, st, ls, mut, M)
 
     def flat_normal(self, k):
-        return P.normalize(tuple(float(x) for x in np.cross(self.e1[k], self.e2[k])))
+        return MC.flat_normal(self, k)
 
 
 class LightPath(P.Path):
-    """pt_f64.Path for a LightMeshDescScene.  `no_hit_weight` and `n_lights_for_n` are the two faults the mutation check plants."""
+    """pt_f64.Path for a LightMeshDescScene: mesh_compose_f64's statements over N = n_lights + ON meshes pickable lights.
+    `no_hit_weight` and `n_lights_for_n` are the two faults the mutation check plants."""
 
     def __init__(self, scene, no_hit_weight=False, n_lights_for_n=False):
         super().__init__(scene)
         self.no_hit_weight, self.n_lights_for_n = no_hit_weight, n_lights_for_n
 
-    def n_pick(self):
+    def picks(self):
         sc = self.scene
-        return len(sc.lights) if self.n_lights_for_n else len(sc.lights) + len(sc.mesh_lights)
+        return [("light", light) for light in sc.lights] + ([] if self.n_lights_for_n else [("mesh", j) for j in range(len(sc.mesh_lights))])
+
+    def n_pick(self):
+        return len(self.picks())
 
     def sample_mesh_light(self, ordinal, scatter_pos, draw, M):
-        """include/rpt.h, "sampling an ON mesh" -> (LightSampleRec, light.area)."""
-        cdf, q_all, a_tot, tri, em = self.scene.mesh_lights[ordinal]
-        r0a, r0b, r1, r2 = draw(), draw(), draw(), draw()
-        ls = P.LightSampleRec()
-        if not a_tot > 0.0:
-            return ls, 0.0
-        j = (int(r0a * 16777216.0) << 24) | int(r0b * 16777216.0)
-        t = (j * q_all) >> 48
-        k = bisect.bisect_right(cdf, t)                               # the first index with C_k > T
-        below = cdf[k - 1] if k else 0
-        M.of(min(t - below + 1, cdf[k] - t) / float(cdf[k] - below), 1.0)     # the pick: integer steps to the neighbours, over q_k
-        a, b, c = (tuple(float(x) for x in p) for p in tri[k])
-        e1, e2 = P.sub(b, a), P.sub(c, a)
-        su = P.sqrt(r1)
-        bu = 1.0 - su
-        bv = r2 * su
-        p = P.add(P.add(a, P.scale(bu, e1)), P.scale(bv, e2))
-        direction = P.sub(p, scatter_pos)
-        ls.dist = P.length(direction)
-        dist_sq = ls.dist * ls.dist
-        ls.direction = P.div3(direction, (ls.dist, ls.dist, ls.dist))
-        n = P.normalize(P.cross(e1, e2))
-        cs = P.dot(n, ls.direction)
-        M.of(cs, 1.0)                                                 # the `c > 0` turn
-        ls.normal = P.neg(n) if cs > 0.0 else n
-        ls.emission = P.scale(float(self.n_pick()), em)
-        ls.pdf = P.dv(dist_sq, a_tot * abs(cs))
-        return ls, a_tot
+        return MC.sample_mesh_light(self.scene, ordinal, float(self.n_pick()), scatter_pos, draw, M)
 
     def direct_light(self, d, st, draw, M, rays):                    # tracer.rs:126-170 over N pickable lights
-        sc, mut = self.scene, self.mut
-        ld = P.ZERO3
-        scatter_pos = P.add(st.fhp, P.scale(self.eps, st.ffnormal))
-        n = self.n_pick()
-        if n > 0:
-            random = draw() * float(n)
-            k = round(random)
-            if 1 <= k <= n - 1:
-                M.rel(random, float(k))
-            index = min(int(random), n - 1)
-            if index < len(sc.lights):
-                light = sc.lights[index]
-                ls = P.sample_light(sc, light, scatter_pos, draw, M)
-                if light[0] == P.LIGHT_SPHERICAL or sc.flags & P.SCENE_SAMPLE_ALL_LIGHT_TYPES:
-                    ls.emission = P.scale(float(n), light[2])         # N_f takes the place of n_lights as F
-                area = light[6]
-            else:
-                ls, area = self.sample_mesh_light(index - len(sc.lights), scatter_pos, draw, M)
-            li = ls.emission
-            fac = P.dot(ls.direction, ls.normal)
-            M.of(fac, 1.0)                                            # the facing test
-            if fac < 0.0:
-                max_dist = ls.dist - self.eps
-                rays.append(scatter_pos + ls.direction + (max_dist,))
-                if not sc.any_hit(scatter_pos, ls.direction, max_dist, mut, M):
-                    f, pdf = P.disney_eval(st.material, st.eta, P.neg(d), st.ffnormal, ls.direction, mut, M)
-                    mis = 1.0
-                    if area > 0.0:
-                        mis = P.power_heuristic(ls.pdf, pdf, mut)
-                    if pdf > 0.0:
-                        ld = P.add(ld, P.scale(mis, P.mul(li, P.div3(f, (ls.pdf, ls.pdf, ls.pdf)))))
-        return ld
+        return MC.direct_light(self, d, st, draw, M, rays)
 
     def hit_weight(self, bounce, d, st, ss_pdf, M):
-        """include/rpt.h, "hit side": the weight of the hit's emission term."""
-        sc = self.scene
-        if self.no_hit_weight or bounce == 0 or sc.won is None or sc.tri_ord[sc.won] < 0:
-            return 1.0
-        a_tot = sc.mesh_lights[int(sc.tri_ord[sc.won])][2]
-        if not a_tot > 0.0:
-            return 1.0
-        cs = abs(P.dot(d, sc.flat_normal(sc.won)))
-        M.of(cs, 1.0)
-        if not cs > 0.0:
-            return 1.0
-        lp = P.dv(st.hit_dist * st.hit_dist, a_tot * cs)
-        return P.power_heuristic(ss_pdf, lp, self.mut)
+        return 1.0 if self.no_hit_weight else MC.hit_weight(self.scene, bounce, d, st, ss_pdf, self.mut, M)
+
+    def miss(self, bounce, d, ss_pdf, M):
+        return self.scene.background(d)
 
     def sample(self, col, row, width, height, draws):
-        """pt_f64.Path.sample (its mutants left out) with the hit-side weight on the emission term."""
-        assert not self.mut and not self.roulette
-        sc, mut = self.scene, self.mut
-        M = P.Margin()
-        rays = []
-        it = iter(draws)
-        draw = lambda: float(next(it))                                # noqa: E731
-        j = height - 1 - row
-        x = float(col)
-        y = float(height) - float(j)
-        a = draw()
-        b = draw()
-        o, d = P.gen_ray(sc.cam, (x / width, 1.0 - y / height), (a, b), float(width), float(height))
-        radiance = P.ZERO3
-        throughput = P.ONE3
-        st = P.State()
-        ls = P.LightSampleRec()
-        ss_l, ss_pdf = P.ZERO3, 0.0
-        depth = sc.depth
-        for bounce in range(depth):
-            st.material = P.Material(1.5)
-            rays.append(o + d + (-1.0,))
-            if not sc.closest_hit(o, d, st, ls, mut, M):
-                radiance = P.add(radiance, P.mul(sc.background(d), throughput))
-                break
-            st.fhp = P.add(o, P.scale(st.hit_dist, d))
-            nd = P.dot(st.normal, d)
-            M.of(nd, 1.0)
-            st.ffnormal = st.normal if nd <= 0.0 else P.neg(st.normal)
-            st.material.finalize()
-            st.eta = P.dv(1.0, st.material.ior) if nd < 0.0 else st.material.ior
-            w = self.hit_weight(bounce, d, st, ss_pdf, M)
-            radiance = P.add(radiance, P.mul(P.scale(w, st.material.emission), throughput))
-            if st.is_emitter:
-                mis = P.power_heuristic(ss_pdf, ls.pdf, mut) if depth > 0 else 1.0
-                radiance = P.add(radiance, P.mul(P.scale(mis, ls.emission), throughput))
-                break
-            radiance = P.add(radiance, P.mul(self.direct_light(d, st, draw, M, rays), throughput))
-            f, ss_l, ss_pdf = P.disney_sample(st.material, st.eta, P.neg(d), st.ffnormal, ss_l, draw, mut, M)
-            if ss_pdf > 0.0:
-                throughput = P.mul(throughput, P.div3(f, (ss_pdf, ss_pdf, ss_pdf)))
-            else:
-                break
-            d = ss_l
-            o = P.add(st.fhp, P.scale(self.eps, d))
-        return radiance, rays, M.m
+        return MC.trace(self, col, row, width, height, draws)
 
 
 def sample_many(ref, oracle, seed, pixels, w, h, **faults):
-    path = LightPath(ref, **faults)
-    out, marg = np.zeros((len(pixels), 3)), np.zeros(len(pixels))
-    for k, (c, r) in enumerate(pixels):
-        dr = oracle.rng_f32(seed, 0, int(r) * w + int(c), N_DRAWS)
-        out[k], _, marg[k] = path.sample(int(c), int(r), w, h, dr)
-    return out, marg
+    return MC.sample_pixels(LightPath(ref, **faults), oracle, seed, pixels, w, h)
 
 
 def _scenes():
@@ -261,7 +140,8 @@ def test_mesh_light_renders_against_the_restatement(rpt, oracle, torch_cuda):
             refs[k] = LightMeshDescScene(s.describe(), s, smooth, on)
         frame, choice = _one_light_sample(rpt, torch_cuda, s, smooth, on, w, h, seed)
         assert choice & MESH_BIT and choice & LIGHT_BIT and bool(choice & SMOOTH_BIT) == bool(smooth), "the mesh light kernel ran"
-        t.ran.add("meshlight_regen_kernel")
+        assert mesh_kernel_of(choice) == "meshlight_regen_kernel"
+        t.ran.add(mesh_kernel_of(choice))
         restated, margins = sample_many(refs[k], oracle, seed, pixels, w, h)
         print("%s (seed %d): %d of %d samples below TAU" % (what, seed, int((margins <= TAU).sum()), len(margins)))
         t.add("%s (seed %d)" % (what, seed), frame, restated, margins, pixels)

@@ -4,7 +4,8 @@ triangle's normal bent in float64: the decode c(k) = max((k - 128) / 127, -1), t
 v, the texture's wrap, a BILINEAR lookup and the bend.  One-sample renders are compared sample by sample with test_path_f64's TAU /
 REL_CLEAN / NEAR_TIE_MAX over test_gpu_mesh_f64's own draws, 200 pixels x 3 seeds x 2 scenes (needs an MI355X).  Every mesh carries
 scenes.mesh_normal_map_scene()'s 32 x 32 bump map (tilts of at most about 15 degrees), BILINEAR, strength 1, over the textures of
-test_gpu_mesh_texture_f64: the first scene REPEAT, the second CLAMP.
+test_gpu_mesh_texture_f64: the first scene REPEAT, the second CLAMP.  The statements themselves are
+functions of tests/mesh_compose_f64.py, which the composed restatement (tests/test_gpu_mesh_compose_f64.py) calls as well.
 
 Margins.  The BILINEAR lookup adds none: it is continuous across texels and across the wrap.  The bend records the sign of D
 through M.of(D, |du1 dv2| + |du2 dv1|), the sign of dot(B, B0) through M.of(., |B0|) (B is a unit vector), and the two `l2 > 0`
@@ -20,9 +21,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import mesh_compose_f64 as MC
 import pt_f64 as P
+from kernel_census import mesh_kernel_of
 from test_gpu_mesh_smooth_f64 import _draws
-from test_gpu_mesh_texture_f64 import BILINEAR, CLAMP, GAMMA, MODES, REPEAT, TexMeshDescScene, scene_textures
+from test_gpu_mesh_texture_f64 import BILINEAR, GAMMA, MODES, TexMeshDescScene, scene_textures
 from test_gpu_path_f64 import Tally
 from test_path_f64 import NEAR_TIE_MAX, REL_CLEAN, TAU, rel_distance
 
@@ -45,7 +48,7 @@ def bump_map():
 
 def decode_f64(rgba):
     """include/rpt.h's decode in float64 at strength 1, no flip: [h, w, 3]."""
-    return np.maximum((np.asarray(rgba, np.uint8)[..., :3].astype(np.float64) - 128.0) / 127.0, -1.0)
+    return MC.decode_normal_map_f64(rgba)
 
 
 class NrmMeshDescScene(TexMeshDescScene):
@@ -58,65 +61,16 @@ class NrmMeshDescScene(TexMeshDescScene):
         self.nrm = decode_f64(bump_map())
 
     def triangle_normal(self, k, o, d, M):
-        N = np.array(super().triangle_normal(k, o, d, M))             # (flat; remembers the winner for the texture)
+        N = super().triangle_normal(k, o, d, M)                       # (flat; remembers the winner for the texture)
         if self.nrm_fault == "ignore":
-            return tuple(float(c) for c in N)
-        o, d = np.array(o), np.array(d)
-        e1, e2 = self.e1[k], self.e2[k]
-        p = np.cross(d, e2)
-        inv = 1.0 / float((e1 * p).sum())
-        sv = o - self.ta[k]
-        u = float((sv * p).sum()) * inv
-        v = float((d * np.cross(sv, e1)).sum()) * inv
+            return N
+        s, t = MC.interp_uv(self, k, *self.barycentrics(k, o, d))
         ua, ub, uc = (self.uv[j] for j in self.corner[k])
-        s, t = ((1.0 - u) - v) * ua + u * ub + v * uc
-        x, y, z = self.bilinear(float(s), float(t))
-        if x == 0.0 and y == 0.0:
-            return tuple(float(c) for c in N)
-        (du1, dv1), (du2, dv2) = ub - ua, uc - ua
-        D = du1 * dv2 - du2 * dv1
-        M.of(D, abs(du1 * dv2) + abs(du2 * dv1))
-        if not (D < 0.0 or D > 0.0):
-            return tuple(float(c) for c in N)
-        g = 1.0 if D > 0.0 else -1.0
-        T0, B0 = g * (e1 * dv2 - e2 * dv1), g * (e2 * du1 - e1 * du2)
-        T1 = T0 - N * float((N * T0).sum())
-        l2 = float((T1 * T1).sum())
-        M.of(l2, float((T0 * T0).sum()))
-        if not l2 > 0.0:
-            return tuple(float(c) for c in N)
-        T = T1 / np.sqrt(l2)
-        B = np.cross(N, T)
-        side = float((B * B0).sum())
-        M.of(side, float(np.sqrt((B0 * B0).sum())))
-        if side < 0.0:
-            B = -B
-        if self.nrm_fault == "swap":
-            T, B = B, T
-        m = x * T + y * B + z * N
-        l2 = float((m * m).sum())
-        M.of(l2, x * x + y * y + z * z)
-        if not l2 > 0.0:
-            return tuple(float(c) for c in N)
-        return tuple(float(c) for c in m / np.sqrt(l2))
+        return MC.bend(np.array(N), self.e1[k], self.e2[k], ua, ub, uc, self.bilinear(s, t), M, swap=self.nrm_fault == "swap")
 
     def bilinear(self, s, t):
         """tex_lookup, BILINEAR, over the decoded map with the TEXTURE's wrap."""
-        h, w = self.nrm.shape[:2]
-
-        def axis(c, n):
-            q = (min(max(c, 0.0), 1.0) if self.wrap == CLAMP else c - np.floor(c)) * n - 0.5
-            f0 = np.floor(q)
-            i0, i1 = int(f0), int(f0) + 1
-            if self.wrap == CLAMP:
-                return min(max(i0, 0), n - 1), min(max(i1, 0), n - 1), q - f0
-            return i0 % n, i1 % n, q - f0
-
-        i0, i1, fx = axis(s, w)
-        j0, j1, fy = axis(t, h)
-        top = (1.0 - fx) * self.nrm[j0, i0] + fx * self.nrm[j0, i1]
-        bot = (1.0 - fx) * self.nrm[j1, i0] + fx * self.nrm[j1, i1]
-        return (1.0 - fy) * top + fy * bot
+        return MC.tex_lookup(self.nrm, s, t, self.wrap, BILINEAR, None)
 
 
 def _one_mapped_sample(rpt, torch, scene, wrap, filt, w, h, seed):
@@ -146,7 +100,8 @@ def test_normal_mapped_mesh_renders_against_the_restatement(rpt, oracle, torch_c
             refs[k] = NrmMeshDescScene(s.describe(), s, wrap, filt)
         frame, choice = _one_mapped_sample(rpt, torch_cuda, s, wrap, filt, w, h, seed)
         assert choice & (1 << 25) and choice & TEX_BIT and choice & NRM_BIT, "the normal-mapped mesh kernel ran"
-        t.ran.add("meshnrm_regen_kernel")
+        assert mesh_kernel_of(choice) == "meshnrm_regen_kernel"
+        t.ran.add(mesh_kernel_of(choice))
         restated, margins, _ = P.sample_many(refs[k], oracle, seed, [(c, r, 0) for c, r in pixels], w, h)
         print("%s (seed %d): %d of %d samples below TAU" % (what, seed, int((margins <= TAU).sum()), len(margins)))
         t.add("%s, normal-mapped (seed %d)" % (what, seed), frame, restated, margins, pixels)

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import pt_f64 as P
+from kernel_census import mesh_kernel_of
 from test_gpu_mesh_f64 import MeshDescScene, _scenes
 from test_gpu_path_f64 import Tally
 from test_path_f64 import NEAR_TIE_MAX, REL_CLEAN, TAU, rel_distance
@@ -58,13 +59,21 @@ class SmoothMeshDescScene(MeshDescScene):
         self.corner = np.concatenate(corners)
         self.l2_min = np.inf
 
-    def triangle_normal(self, k, o, d, M):
+    def barycentrics(self, k, o, d):
+        """The triangle test's own u and v for this ray and triangle k, recomputed."""
         o, d = np.array(o), np.array(d)
         p = np.cross(d, self.e2[k])
         inv = 1.0 / float((self.e1[k] * p).sum())
         s = o - self.ta[k]
         u = float((s * p).sum()) * inv
         v = float((d * np.cross(s, self.e1[k])).sum()) * inv
+        return u, v
+
+    def triangle_normal(self, k, o, d, M):
+        return self.interpolated_normal(k, *self.barycentrics(k, o, d), M)
+
+    def interpolated_normal(self, k, u, v, M):
+        """include/rpt.h, "normal of a winning triangle of a SMOOTH mesh", at the barycentrics u, v of triangle k."""
         na, nb, nc = (self.vn[j] for j in self.corner[k])
         m = ((1.0 - u) - v) * na + u * nb + v * nc
         l2 = float((m * m).sum())
@@ -156,7 +165,8 @@ def test_smooth_mesh_renders_against_the_restatement(rpt, oracle, torch_cuda):
         ref, flat = refs[k]
         frame, choice = _one_smooth_sample(rpt, torch_cuda, s, w, h, seed)
         assert choice & (1 << 25) and choice & SMOOTH_BIT, "the smooth mesh kernel ran"
-        t.ran.add("meshsmooth_regen_kernel")
+        assert mesh_kernel_of(choice) == "meshsmooth_regen_kernel"
+        t.ran.add(mesh_kernel_of(choice))
         items = [(c, r, 0) for c, r in pixels]
         restated, margins, _ = P.sample_many(ref, oracle, seed, items, w, h)
         print("%s (seed %d): %d of %d samples below TAU" % (what, seed, int((margins <= TAU).sum()), len(margins)))

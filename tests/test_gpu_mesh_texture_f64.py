@@ -3,7 +3,8 @@ TexMeshDescScene is test_gpu_mesh_smooth_f64.SmoothMeshDescScene — shading fla
 triangle's rgb restated in float64: the decode by P.powf with the end-point rule, the UV interpolation with the triangle test's u
 and v, the wrap and the filter.  One-sample renders are compared sample by sample with test_path_f64's TAU / REL_CLEAN /
 NEAR_TIE_MAX over test_gpu_mesh_f64's own draws, 200 pixels x 3 seeds x 2 scenes (needs an MI355X).  Every mesh carries a 5 x 3
-two-colour texture over spherical UVs; the first scene is BILINEAR / REPEAT, the second NEAREST / CLAMP.
+two-colour texture over spherical UVs; the first scene is BILINEAR / REPEAT, the second NEAREST / CLAMP.  The statements themselves are
+functions of tests/mesh_compose_f64.py, which the composed restatement (tests/test_gpu_mesh_compose_f64.py) calls as well.
 
 Margins.  BILINEAR adds none: the filter is continuous across texels and across the wrap, so floorf's choice moves no value.
 NEAREST records the distance of x*W (and y*H) to the next integer through M.of(., 1.0), where the coordinate is not clamped.
@@ -17,12 +18,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import mesh_compose_f64 as MC
 import pt_f64 as P
+from kernel_census import mesh_kernel_of
+from mesh_compose_f64 import BILINEAR, CLAMP, NEAREST, REPEAT
 from test_gpu_mesh_smooth_f64 import SmoothMeshDescScene, _draws
 from test_gpu_path_f64 import Tally
 from test_path_f64 import NEAR_TIE_MAX, REL_CLEAN, TAU, rel_distance
 
-REPEAT, CLAMP, NEAREST, BILINEAR = 0, 1, 0, 1
 TEX_BIT = 1 << 28
 GAMMA = 2.2
 MODES = ((REPEAT, BILINEAR), (CLAMP, NEAREST))                      # per scene of test_gpu_mesh_f64._scenes()
@@ -52,12 +55,7 @@ def scene_textures(scene):
     return out
 
 
-def decode_f64(rgba, gamma):
-    """include/rpt.h's decode in float64: [h, w, 3]."""
-    table = np.array([0.0 if k == 0 else 1.0 if k == 255 else P.powf(k / 255.0, gamma) for k in range(256)])
-    if gamma == 1.0:
-        table = np.arange(256) / 255.0
-    return table[np.asarray(rgba, np.uint8)[..., :3]]
+decode_f64 = MC.decode_texture_f64                                   # include/rpt.h's decode in float64: [h, w, 3]
 
 
 class TexMeshDescScene(SmoothMeshDescScene):
@@ -74,7 +72,7 @@ class TexMeshDescScene(SmoothMeshDescScene):
 
     def triangle_normal(self, k, o, d, M):
         self._won = (k, np.array(o), np.array(d))
-        return P.normalize(tuple(float(x) for x in np.cross(self.e1[k], self.e2[k])))
+        return MC.flat_normal(self, k)
 
     def patch(self, m, d, hp, mat, mut, M):
         super().patch(m, d, hp, mat, mut, M)
@@ -83,40 +81,11 @@ class TexMeshDescScene(SmoothMeshDescScene):
             tex = self.lookup(*won, M)
             mat.rgb = tuple(float(c) * float(x) for c, x in zip(mat.rgb, tex))
 
-    def _axis(self, s, n, M):
-        x = min(max(s, 0.0), 1.0) if self.wrap == CLAMP else s - np.floor(s)
-        p = x * n
-        if self.filt == NEAREST:
-            if self.wrap == REPEAT or 0.0 < s < 1.0:
-                M.of(p - np.round(p), 1.0)
-            i = int(np.floor(p))
-            return (min(i, n - 1) if self.wrap == CLAMP else i % n), None, None
-        p -= 0.5
-        f0 = np.floor(p)
-        i0, i1 = int(f0), int(f0) + 1
-        if self.wrap == CLAMP:
-            return min(max(i0, 0), n - 1), min(max(i1, 0), n - 1), p - f0
-        return i0 % n, i1 % n, p - f0
-
     def lookup(self, k, o, d, M):
-        p = np.cross(d, self.e2[k])
-        inv = 1.0 / float((self.e1[k] * p).sum())
-        sv = o - self.ta[k]
-        u = float((sv * p).sum()) * inv
-        v = float((d * np.cross(sv, self.e1[k])).sum()) * inv
-        ua, ub, uc = (self.uv[j] for j in self.corner[k])
-        s, t = ((1.0 - u) - v) * ua + u * ub + v * uc
+        s, t = MC.interp_uv(self, k, *self.barycentrics(k, o, d))
         if self.fault == "swap":
             s, t = t, s
-        texels = self.texels[int(self.tri_mesh[k])]
-        h, w = texels.shape[:2]
-        i0, i1, fx = self._axis(float(s), w, M)
-        j0, j1, fy = self._axis(float(t), h, M)
-        if self.filt == NEAREST:
-            return texels[j0, i0]
-        top = (1.0 - fx) * texels[j0, i0] + fx * texels[j0, i1]
-        bot = (1.0 - fx) * texels[j1, i0] + fx * texels[j1, i1]
-        return (1.0 - fy) * top + fy * bot
+        return MC.tex_lookup(self.texels[int(self.tri_mesh[k])], s, t, self.wrap, self.filt, M)
 
 
 def _one_textured_sample(rpt, torch, scene, wrap, filt, w, h, seed):
@@ -145,7 +114,8 @@ def test_textured_mesh_renders_against_the_restatement(rpt, oracle, torch_cuda):
             refs[k] = TexMeshDescScene(s.describe(), s, wrap, filt)
         frame, choice = _one_textured_sample(rpt, torch_cuda, s, wrap, filt, w, h, seed)
         assert choice & (1 << 25) and choice & TEX_BIT, "the textured mesh kernel ran"
-        t.ran.add("meshtex_regen_kernel")
+        assert mesh_kernel_of(choice) == "meshtex_regen_kernel"
+        t.ran.add(mesh_kernel_of(choice))
         restated, margins, _ = P.sample_many(refs[k], oracle, seed, [(c, r, 0) for c, r in pixels], w, h)
         print("%s (seed %d): %d of %d samples below TAU" % (what, seed, int((margins <= TAU).sum()), len(margins)))
         t.add("%s, textured (seed %d)" % (what, seed), frame, restated, margins, pixels)

@@ -78,11 +78,14 @@ def test_bvh_invariants_under_sanitizers(tmp_path):
     assert len(lines) == len(args) // 2 and all(line.endswith("OK") for line in lines), r.stdout
 
 
+MESH_KERNELS = ["mesh_query_kernel", "mesh_regen_kernel"]
+
+
 def test_the_code_object_holds_the_mesh_kernels():
     """The mesh class's kernels are named mesh_* and live in librpt_hip_mesh.so (build.py, MESH_LIB): the megakernel and the test hook's
     query kernel, nothing else; both libraries load it through their run path."""
     pkg = os.path.join(ROOT, "rust-pathtracer_amd")
-    assert sorted(code_object_kernels(os.path.join(pkg, "librpt_hip_mesh.so"))) == ["mesh_query_kernel", "mesh_regen_kernel"]
+    assert sorted(code_object_kernels(os.path.join(pkg, "librpt_hip_mesh.so"))) == MESH_KERNELS
     for lib in ("librpt_hip.so", "librpt_hip_test.so"):
         assert not [n for n in code_object_kernels(os.path.join(pkg, lib)) if n.startswith("mesh_")], lib
         dyn = subprocess.run(["readelf", "-d", os.path.join(pkg, lib)], check=True, capture_output=True, text=True).stdout
