@@ -39,6 +39,7 @@
 #include "launch_nrm.h"
 #include "launch_smooth.h"
 #include "launch_tex.h"
+#include "mesh_args.h"
 #ifdef RPT_TEST_HOOKS
 #include "../../include/rpt_test.h"
 #endif
@@ -457,270 +458,21 @@ static int sched_for(rpt_ctx* ctx, DevState& d, uint32_t nblocks, uint32_t width
     return RPT_OK;
 }
 
-// A mesh scene's kernel argument while some mesh is SMOOTH: device d's scene plus pointers into its refit and smooth tables.
-static SceneMeshSmooth smooth_scene_of(const rpt_ctx* ctx, const DevState& d)
+// Device d's mesh scene as mesh_args.h binds kernel arguments from it: mesh_scene_of<S>(mesh_view_of(ctx, d)), light_tables_of.
+static rptargs::MeshView mesh_view_of(const rpt_ctx* ctx, const DevState& d)
 {
-    const rpthost::SmoothPlan& sp = ctx->smooth;
-    const rpthost::RefitLayout rl(ctx->refit.n_vertices(), 0, 0);   // (the vertices and slot_vertex come first whatever follows them)
-    const rpthost::SmoothLayout sl(sp.n_vertices, sp.n_tris, sp.n_faces, sp.n_adj);
-    const unsigned char* refit = static_cast<const unsigned char*>(d.refit);
-    const unsigned char* base = static_cast<const unsigned char*>(d.smooth);
-    SceneMeshSmooth s{};
-    static_cast<SceneMesh&>(s) = d.scene;
-    s.slot_vertex = reinterpret_cast<const uint32_t*>(refit + rl.off_slot_vertex);
-    s.vnormals = reinterpret_cast<const float4*>(base + sl.off_normals);
-    s.smooth_bits = reinterpret_cast<const uint32_t*>(base + sl.off_bits);
-    return s;
+    return rptargs::MeshView{d.scene, d.refit, d.smooth, d.light, d.tex, d.env, d.cut, d.nrm,
+                             ctx->refit, ctx->smooth, ctx->light, ctx->tex, ctx->env, ctx->cut, ctx->nrm};
 }
 
-// The table kernels' argument: pointers into device d's light tables (ctx->light says their sizes).
-static LightTables light_tables_of(const rpt_ctx* ctx, const DevState& d)
+// One mesh render form: its argument (mesh_args.h) with the launch's camera and flags, through its launcher.
+template <class S, class Launcher>
+static hipError_t launch_mesh_form(const rptargs::MeshView& view, const SceneMesh& scm, Launcher launcher, const RenderParams& rp, uint32_t grid, hipStream_t stream)
 {
-    const rpthost::LightPlan& lp = ctx->light;
-    const rpthost::LightLayout ll(lp.n_on(), lp.n_faces, lp.n_tris);
-    unsigned char* base = static_cast<unsigned char*>(d.light);
-    LightTables t{};
-    t.desc = reinterpret_cast<LightMeshDesc*>(base + ll.off_desc);
-    t.cdf = reinterpret_cast<uint64_t*>(base + ll.off_cdf);
-    t.part = reinterpret_cast<uint64_t*>(base + ll.off_part);
-    t.block = reinterpret_cast<uint64_t*>(base + ll.off_block);
-    t.area = reinterpret_cast<float*>(base + ll.off_area);
-    t.face_vertex = reinterpret_cast<const uint32_t*>(base + ll.off_face_vertex);
-    t.face_mesh = reinterpret_cast<const uint32_t*>(base + ll.off_face_mesh);
-    t.n_on = lp.n_on();
-    t.n_faces = lp.n_faces;
-    return t;
-}
-
-// A mesh scene's kernel argument while some mesh is ON: device d's scene, its smooth tables if some mesh is SMOOTH (else the
-// refit's slot_vertex and all-zero smooth bits: every hit takes the flat normal), and pointers into its refit and light tables.
-static SceneMeshLight light_scene_of(const rpt_ctx* ctx, const DevState& d)
-{
-    const rpthost::LightPlan& lp = ctx->light;
-    const rpthost::RefitLayout rl(ctx->refit.n_vertices(), 0, 0);
-    const rpthost::LightLayout ll(lp.n_on(), lp.n_faces, lp.n_tris);
-    const unsigned char* refit = static_cast<const unsigned char*>(d.refit);
-    const unsigned char* base = static_cast<const unsigned char*>(d.light);
-    SceneMeshLight s{};
-    if (d.smooth && ctx->smooth.any()) {
-        static_cast<SceneMeshSmooth&>(s) = smooth_scene_of(ctx, d);
-    } else {
-        static_cast<SceneMesh&>(s) = d.scene;
-        s.slot_vertex = reinterpret_cast<const uint32_t*>(refit + rl.off_slot_vertex);
-        s.vnormals = nullptr;                                       // (not read: no smooth bit is set)
-        s.smooth_bits = reinterpret_cast<const uint32_t*>(base + ll.off_flat_bits);
-    }
-    const LightTables t = light_tables_of(ctx, d);
-    s.vertices = reinterpret_cast<const float*>(refit + rl.off_vertices);
-    s.face_vertex = t.face_vertex;
-    s.light_desc = t.desc;
-    s.light_cdf = t.cdf;
-    s.tri_light = reinterpret_cast<const uint32_t*>(base + ll.off_tri_light);
-    s.n_faces = lp.n_faces;
-    s.n_pick = s.n_lights + lp.n_on();
-    s.n_lights_f = (float)s.n_pick;                                 // include/rpt.h, "pickable lights": N_f
-    return s;
-}
-
-// What the textured forms add to their base: pointers into device d's texture tables (ctx->tex says their sizes).
-template <class Base> static void bind_tex(const rpt_ctx* ctx, const DevState& d, SceneMeshTexT<Base>& s)
-{
-    const rpthost::TexPlan& tp = ctx->tex;
-    const rpthost::TexLayout tl(tp.n_tex(), tp.n_tris, tp.n_vertices, tp.n_texels);
-    const unsigned char* base = static_cast<const unsigned char*>(d.tex);
-    s.tex_desc = reinterpret_cast<const rpthost::TexDesc*>(base + tl.off_desc);
-    s.tri_tex = reinterpret_cast<const uint32_t*>(base + tl.off_tri_tex);
-    s.uvs = reinterpret_cast<const float*>(base + tl.off_uvs);
-    s.texels = reinterpret_cast<const rpthost::TexTexel*>(base + tl.off_texels);
-}
-
-// A mesh scene's kernel argument while some mesh is textured and none is ON: device d's scene, its smooth tables if some mesh is
-// SMOOTH (else the refit's slot_vertex and all-zero smooth bits: every hit takes the flat normal), and its texture tables.
-static SceneMeshTex tex_scene_of(const rpt_ctx* ctx, const DevState& d)
-{
-    const rpthost::TexPlan& tp = ctx->tex;
-    const rpthost::RefitLayout rl(ctx->refit.n_vertices(), 0, 0);
-    const rpthost::TexLayout tl(tp.n_tex(), tp.n_tris, tp.n_vertices, tp.n_texels);
-    SceneMeshTex s{};
-    if (d.smooth && ctx->smooth.any()) {
-        static_cast<SceneMeshSmooth&>(s) = smooth_scene_of(ctx, d);
-    } else {
-        static_cast<SceneMesh&>(s) = d.scene;
-        s.slot_vertex = reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(d.refit) + rl.off_slot_vertex);
-        s.vnormals = nullptr;                                       // (not read: no smooth bit is set)
-        s.smooth_bits = reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(d.tex) + tl.off_flat_bits);
-    }
-    bind_tex(ctx, d, s);
-    return s;
-}
-
-// ... and while some mesh is ON as well: light_scene_of's argument plus the texture tables.
-static SceneMeshLightTex light_tex_scene_of(const rpt_ctx* ctx, const DevState& d)
-{
-    SceneMeshLightTex s{};
-    static_cast<SceneMeshLight&>(s) = light_scene_of(ctx, d);
-    bind_tex(ctx, d, s);
-    return s;
-}
-
-// A mesh scene's kernel argument while an environment is set: whatever of the smooth, light and texture tables device d holds, a
-// feature the scene does not use through the empty tables of its environment allocation (all-zero smooth bits; tri_light and tri_tex
-// all 0xFFFFFFFF, no ON mesh), and pointers into its environment tables.
-static SceneMeshEnv env_scene_of(const rpt_ctx* ctx, const DevState& d)
-{
-    const rpthost::EnvPlan& ep = ctx->env;
-    const rpthost::RefitLayout rl(ctx->refit.n_vertices(), 0, 0);
-    const rpthost::EnvLayout el(ep.size, ep.sampled(), ep.n_tris);
-    const unsigned char* refit = static_cast<const unsigned char*>(d.refit);
-    const unsigned char* base = static_cast<const unsigned char*>(d.env);
-    const uint32_t* none = reinterpret_cast<const uint32_t*>(base + el.off_none);
-    SceneMeshEnv s{};
-    if (d.light && ctx->light.any()) {
-        static_cast<SceneMeshLight&>(s) = light_scene_of(ctx, d);
-    } else {
-        if (d.smooth && ctx->smooth.any()) {
-            static_cast<SceneMeshSmooth&>(s) = smooth_scene_of(ctx, d);
-        } else {
-            static_cast<SceneMesh&>(s) = d.scene;
-            s.slot_vertex = reinterpret_cast<const uint32_t*>(refit + rl.off_slot_vertex);
-            s.vnormals = nullptr;                                   // (not read: no smooth bit is set)
-            s.smooth_bits = reinterpret_cast<const uint32_t*>(base + el.off_flat_bits);
-        }
-        s.vertices = reinterpret_cast<const float*>(refit + rl.off_vertices);
-        s.face_vertex = nullptr;                                    // (not read: no mesh is ON)
-        s.light_desc = nullptr;
-        s.light_cdf = nullptr;
-        s.tri_light = none;
-        s.n_faces = 0u;
-        s.n_pick = s.n_lights;
-    }
-    if (d.tex && ctx->tex.any()) {
-        bind_tex(ctx, d, s);
-    } else {
-        s.tex_desc = nullptr;                                       // (not read: no triangle names a texture)
-        s.tri_tex = none;
-        s.uvs = nullptr;
-        s.texels = nullptr;
-    }
-    s.env_texels = reinterpret_cast<const rpthost::EnvTexel*>(base + el.off_texels);
-    s.env_cdf = ep.sampled() ? reinterpret_cast<const uint64_t*>(base + el.off_cdf) : nullptr;
-    s.env_q = ep.q_total;
-    s.env_q_f = (float)ep.q_total;
-    s.env_scale = ep.scale;
-    s.env_size = ep.size;
-    s.env_pick = rpthost::kEnvNone;
-    if (ep.sampled()) {
-        s.env_pick = s.n_pick;                                      // include/rpt.h, "pickable lights": the environment is the last one
-        s.n_pick += 1u;
-        s.n_lights_f = (float)s.n_pick;
-    }
-    return s;
-}
-
-// What the cutout forms add to their base: pointers into device d's cutout tables (ctx->cut says their sizes).
-template <class Base> static void bind_cut(const rpt_ctx* ctx, const DevState& d, SceneMeshCutT<Base>& s)
-{
-    const rpthost::CutPlan& cp = ctx->cut;
-    const rpthost::CutLayout cl(cp.n_meshes, cp.n_tris, cp.n_words);
-    const unsigned char* base = static_cast<const unsigned char*>(d.cut);
-    s.cut_desc = reinterpret_cast<const rpthost::CutDesc*>(base + cl.off_desc);
-    s.cut_bits = reinterpret_cast<const uint32_t*>(base + cl.off_bits);
-}
-
-// A mesh scene's kernel argument while some mesh's cutout is ON and no environment is set: the textured mesh-light form's argument —
-// no mesh ON: the smooth or flat tables as tex_scene_of binds them, tri_light all 0xFFFFFFFF from the cutout allocation — plus the
-// cutout tables.  (A cutout mesh is textured: device d holds texture tables.)
-static SceneMeshCut cut_scene_of(const rpt_ctx* ctx, const DevState& d)
-{
-    SceneMeshCut s{};
-    if (d.light && ctx->light.any()) {
-        static_cast<SceneMeshLightTex&>(s) = light_tex_scene_of(ctx, d);
-    } else {
-        const rpthost::CutPlan& cp = ctx->cut;
-        const rpthost::RefitLayout rl(ctx->refit.n_vertices(), 0, 0);
-        const rpthost::CutLayout cl(cp.n_meshes, cp.n_tris, cp.n_words);
-        static_cast<SceneMeshSmooth&>(s) = tex_scene_of(ctx, d);    // (slices its texture part off: bind_tex below)
-        s.vertices = reinterpret_cast<const float*>(static_cast<const unsigned char*>(d.refit) + rl.off_vertices);
-        s.face_vertex = nullptr;                                    // (not read: no mesh is ON)
-        s.light_desc = nullptr;
-        s.light_cdf = nullptr;
-        s.tri_light = reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(d.cut) + cl.off_none);
-        s.n_faces = 0u;
-        s.n_pick = s.n_lights;
-        bind_tex(ctx, d, s);
-    }
-    bind_cut(ctx, d, s);
-    return s;
-}
-
-// ... and while an environment is set as well: env_scene_of's argument plus the cutout tables.
-static SceneMeshCutEnv cut_env_scene_of(const rpt_ctx* ctx, const DevState& d)
-{
-    SceneMeshCutEnv s{};
-    static_cast<SceneMeshEnv&>(s) = env_scene_of(ctx, d);
-    bind_cut(ctx, d, s);
-    return s;
-}
-
-// What the normal-mapped forms add to their base: pointers into device d's map tables (ctx->nrm says their sizes).
-template <class Base> static void bind_nrm(const rpt_ctx* ctx, const DevState& d, SceneMeshNrmT<Base>& s)
-{
-    const rpthost::NrmPlan& np = ctx->nrm;
-    const rpthost::NrmLayout nl(np.n_meshes, np.n_tris, np.n_texels);
-    const unsigned char* base = static_cast<const unsigned char*>(d.nrm);
-    s.nrm_desc = reinterpret_cast<const rpthost::NrmDesc*>(base + nl.off_desc);
-    s.nrm_texels = reinterpret_cast<const float4*>(base + nl.off_texels);
-}
-
-// A mesh scene's kernel argument while some mesh's normal map is ON, no cutout is and no environment is set: the textured mesh-light
-// form's argument — no mesh ON: the smooth or flat tables as tex_scene_of binds them, tri_light all 0xFFFFFFFF from the map
-// allocation — plus the map tables.  (A normal-mapped mesh is textured: device d holds texture tables.)
-static SceneMeshNrm nrm_scene_of(const rpt_ctx* ctx, const DevState& d)
-{
-    SceneMeshNrm s{};
-    if (d.light && ctx->light.any()) {
-        static_cast<SceneMeshLightTex&>(s) = light_tex_scene_of(ctx, d);
-    } else {
-        const rpthost::NrmPlan& np = ctx->nrm;
-        const rpthost::RefitLayout rl(ctx->refit.n_vertices(), 0, 0);
-        const rpthost::NrmLayout nl(np.n_meshes, np.n_tris, np.n_texels);
-        static_cast<SceneMeshSmooth&>(s) = tex_scene_of(ctx, d);    // (slices its texture part off: bind_tex below)
-        s.vertices = reinterpret_cast<const float*>(static_cast<const unsigned char*>(d.refit) + rl.off_vertices);
-        s.face_vertex = nullptr;                                    // (not read: no mesh is ON)
-        s.light_desc = nullptr;
-        s.light_cdf = nullptr;
-        s.tri_light = reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(d.nrm) + nl.off_none);
-        s.n_faces = 0u;
-        s.n_pick = s.n_lights;
-        bind_tex(ctx, d, s);
-    }
-    bind_nrm(ctx, d, s);
-    return s;
-}
-
-// ... and over the environment form, the cutout form and the cutout form under an environment: their arguments plus the map tables.
-static SceneMeshNrmEnv nrm_env_scene_of(const rpt_ctx* ctx, const DevState& d)
-{
-    SceneMeshNrmEnv s{};
-    static_cast<SceneMeshEnv&>(s) = env_scene_of(ctx, d);
-    bind_nrm(ctx, d, s);
-    return s;
-}
-
-static SceneMeshNrmCut nrm_cut_scene_of(const rpt_ctx* ctx, const DevState& d)
-{
-    SceneMeshNrmCut s{};
-    static_cast<SceneMeshCut&>(s) = cut_scene_of(ctx, d);
-    bind_nrm(ctx, d, s);
-    return s;
-}
-
-static SceneMeshNrmCutEnv nrm_cut_env_scene_of(const rpt_ctx* ctx, const DevState& d)
-{
-    SceneMeshNrmCutEnv s{};
-    static_cast<SceneMeshCutEnv&>(s) = cut_env_scene_of(ctx, d);
-    bind_nrm(ctx, d, s);
-    return s;
+    S s = rptargs::mesh_scene_of<S>(view);
+    s.cam = scm.cam;
+    s.flags = scm.flags;
+    return launcher(s, rp, grid, stream);
 }
 
 // One render launch sequence on one device.
@@ -808,72 +560,24 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
                         (environment ? 1u << 29 : 0u) | (cutouts ? 1u << 30 : 0u) | (normal_maps ? 1u << 31 : 0u);
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
-        if (normal_maps && cutouts && environment) {
-            SceneMeshNrmCutEnv sn = nrm_cut_env_scene_of(ctx, d);
-            sn.cam = scm.cam;
-            sn.flags = scm.flags;
-            return rptlaunch::render_mesh_nrm_cut_env(sn, rp, grid, stream);
+        if (kind == SceneKind::mesh) {
+            using rptargs::MeshForm;
+            const rptargs::MeshView view = mesh_view_of(ctx, d);
+            switch (rptargs::mesh_form_of(smooth, lights, textured, environment, cutouts, normal_maps)) {
+            case MeshForm::nrm_cut_env: return launch_mesh_form<SceneMeshNrmCutEnv>(view, scm, rptlaunch::render_mesh_nrm_cut_env, rp, grid, stream);
+            case MeshForm::nrm_cut: return launch_mesh_form<SceneMeshNrmCut>(view, scm, rptlaunch::render_mesh_nrm_cut, rp, grid, stream);
+            case MeshForm::nrm_env: return launch_mesh_form<SceneMeshNrmEnv>(view, scm, rptlaunch::render_mesh_nrm_env, rp, grid, stream);
+            case MeshForm::nrm: return launch_mesh_form<SceneMeshNrm>(view, scm, rptlaunch::render_mesh_nrm, rp, grid, stream);
+            case MeshForm::cut_env: return launch_mesh_form<SceneMeshCutEnv>(view, scm, rptlaunch::render_mesh_cut_env, rp, grid, stream);
+            case MeshForm::cut: return launch_mesh_form<SceneMeshCut>(view, scm, rptlaunch::render_mesh_cut, rp, grid, stream);
+            case MeshForm::env: return launch_mesh_form<SceneMeshEnv>(view, scm, rptlaunch::render_mesh_env, rp, grid, stream);
+            case MeshForm::light_tex: return launch_mesh_form<SceneMeshLightTex>(view, scm, rptlaunch::render_mesh_light_tex, rp, grid, stream);
+            case MeshForm::tex: return launch_mesh_form<SceneMeshTex>(view, scm, rptlaunch::render_mesh_tex, rp, grid, stream);
+            case MeshForm::light: return launch_mesh_form<SceneMeshLight>(view, scm, rptlaunch::render_mesh_light, rp, grid, stream);
+            case MeshForm::smooth: return launch_mesh_form<SceneMeshSmooth>(view, scm, rptlaunch::render_mesh_smooth, rp, grid, stream);
+            case MeshForm::flat: return launch_mesh_form<SceneMesh>(view, scm, rptlaunch::render_mesh, rp, grid, stream);
+            }
         }
-        if (normal_maps && cutouts) {
-            SceneMeshNrmCut sn = nrm_cut_scene_of(ctx, d);
-            sn.cam = scm.cam;
-            sn.flags = scm.flags;
-            return rptlaunch::render_mesh_nrm_cut(sn, rp, grid, stream);
-        }
-        if (normal_maps && environment) {
-            SceneMeshNrmEnv sn = nrm_env_scene_of(ctx, d);
-            sn.cam = scm.cam;
-            sn.flags = scm.flags;
-            return rptlaunch::render_mesh_nrm_env(sn, rp, grid, stream);
-        }
-        if (normal_maps) {
-            SceneMeshNrm sn = nrm_scene_of(ctx, d);
-            sn.cam = scm.cam;
-            sn.flags = scm.flags;
-            return rptlaunch::render_mesh_nrm(sn, rp, grid, stream);
-        }
-        if (cutouts && environment) {
-            SceneMeshCutEnv sce = cut_env_scene_of(ctx, d);
-            sce.cam = scm.cam;
-            sce.flags = scm.flags;
-            return rptlaunch::render_mesh_cut_env(sce, rp, grid, stream);
-        }
-        if (cutouts) {
-            SceneMeshCut smc = cut_scene_of(ctx, d);
-            smc.cam = scm.cam;
-            smc.flags = scm.flags;
-            return rptlaunch::render_mesh_cut(smc, rp, grid, stream);
-        }
-        if (environment) {
-            SceneMeshEnv sme = env_scene_of(ctx, d);
-            sme.cam = scm.cam;
-            sme.flags = scm.flags;
-            return rptlaunch::render_mesh_env(sme, rp, grid, stream);
-        }
-        if (textured && lights) {
-            SceneMeshLightTex smt = light_tex_scene_of(ctx, d);
-            smt.cam = scm.cam;
-            smt.flags = scm.flags;
-            return rptlaunch::render_mesh_light_tex(smt, rp, grid, stream);
-        }
-        if (textured) {
-            SceneMeshTex smt = tex_scene_of(ctx, d);
-            smt.cam = scm.cam;
-            smt.flags = scm.flags;
-            return rptlaunch::render_mesh_tex(smt, rp, grid, stream);
-        }
-        if (lights) {
-            SceneMeshLight sml = light_scene_of(ctx, d);
-            sml.cam = scm.cam;
-            sml.flags = scm.flags;
-            return rptlaunch::render_mesh_light(sml, rp, grid, stream);
-        }
-        if (smooth) {
-            SceneMeshSmooth sms = smooth_scene_of(ctx, d);
-            static_cast<SceneMesh&>(sms) = scm;
-            return rptlaunch::render_mesh_smooth(sms, rp, grid, stream);
-        }
-        if (kind == SceneKind::mesh) return rptlaunch::render_mesh(scm, rp, grid, stream);
         if (kind == SceneKind::large) return fast ? rptlaunch_fast::render_large(scl, false, rp, grid, stream) : rptlaunch::render_large(scl, media, rp, grid, stream);
         if (has_sdf) return fast ? rptlaunch_fast::render_sdf(scs, false, rp, grid, stream, kc) : rptlaunch::render_sdf(scs, media, rp, grid, stream, kc);
         if (rp.compact && !nested) return fast ? rptlaunch_fast::render_compact(scs, false, rp, grid, stream, kc) : rptlaunch::render_compact(scs, media, rp, grid, stream, kc);
@@ -1358,7 +1062,7 @@ static int smooth_normals_device(rpt_ctx* ctx, DevState& d)
 {
     if (!d.smooth) return RPT_OK;
     const rpthost::SmoothPlan& sp = ctx->smooth;
-    const rpthost::SmoothLayout sl(sp.n_vertices, sp.n_tris, sp.n_faces, sp.n_adj);
+    const rpthost::SmoothLayout sl = sp.layout();
     unsigned char* base = static_cast<unsigned char*>(d.smooth);
     RPT_HIP_CHECK(ctx, rptlaunch::smooth_normals(static_cast<const float*>(d.refit), reinterpret_cast<const uint32_t*>(base + sl.off_face_vertex),
                                                  reinterpret_cast<float4*>(base + sl.off_face), sp.n_faces, reinterpret_cast<const uint32_t*>(base + sl.off_adj_first),
@@ -1372,7 +1076,7 @@ static int smooth_normals_device(rpt_ctx* ctx, DevState& d)
 static int light_tables_device(rpt_ctx* ctx, DevState& d)
 {
     if (!d.light) return RPT_OK;
-    RPT_HIP_CHECK(ctx, rptlaunch::light_tables(static_cast<const float*>(d.refit), light_tables_of(ctx, d), d.stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::light_tables(static_cast<const float*>(d.refit), rptargs::light_tables_of(mesh_view_of(ctx, d)), d.stream));
     return RPT_OK;
 }
 
@@ -1740,7 +1444,7 @@ int rpt_download_mesh_vertices(rpt_ctx* ctx, uint32_t mesh, float* vertices, uin
 static int shade_device(rpt_ctx* ctx, DevState& d)
 {
     const rpthost::SmoothPlan& sp = ctx->smooth;
-    const rpthost::SmoothLayout sl(sp.n_vertices, sp.n_tris, sp.n_faces, sp.n_adj);
+    const rpthost::SmoothLayout sl = sp.layout();
     RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
     RPT_CHECK_RC(ensure_refit(ctx, d));
     if (d.smooth) { (void)hipFree(d.smooth); d.smooth = nullptr; }
@@ -1848,7 +1552,7 @@ int rpt_download_mesh_normals(rpt_ctx* ctx, uint32_t mesh, float* normals, uint3
     if (!normals) { set_err(ctx, "rpt_download_mesh_normals: normals is NULL"); return RPT_ERR_INVALID_ARG; }
     RPT_ON_DEVICE(ctx);
     const rpthost::SmoothPlan& sp = ctx->smooth;
-    const rpthost::SmoothLayout sl(sp.n_vertices, sp.n_tris, sp.n_faces, sp.n_adj);
+    const rpthost::SmoothLayout sl = sp.layout();
     std::vector<float> rows(4 * (size_t)count);
     RPT_HIP_CHECK(ctx, hipMemcpy(rows.data(), static_cast<const unsigned char*>(d.smooth) + sl.off_normals + 16 * (size_t)first, 16 * (size_t)count, hipMemcpyDeviceToHost));
     for (size_t v = 0; v < count; ++v) memcpy(normals + 3 * v, &rows[4 * v], 12);
@@ -1861,7 +1565,7 @@ int rpt_download_mesh_normals(rpt_ctx* ctx, uint32_t mesh, float* normals, uint3
 static int light_device(rpt_ctx* ctx, DevState& d)
 {
     const rpthost::LightPlan& lp = ctx->light;
-    const rpthost::LightLayout ll(lp.n_on(), lp.n_faces, lp.n_tris);
+    const rpthost::LightLayout ll = lp.layout();
     RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
     RPT_CHECK_RC(ensure_refit(ctx, d));
     if (d.light) { (void)hipFree(d.light); d.light = nullptr; }
@@ -1953,7 +1657,7 @@ int rpt_download_mesh_light_table(rpt_ctx* ctx, uint32_t mesh, uint64_t* cdf, ui
     if (ord == rpthost::kLightNone || !d.light) { set_err(ctx, "rpt_download_mesh_light_table: mesh %u is OFF: the context holds no table for it (rpt_set_mesh_lights)", mesh); return RPT_ERR_INVALID_ARG; }
     if (!exponent || !area || (count && !cdf)) { set_err(ctx, "rpt_download_mesh_light_table: cdf, exponent or area is NULL"); return RPT_ERR_INVALID_ARG; }
     RPT_ON_DEVICE(ctx);
-    const rpthost::LightLayout ll(lp.n_on(), lp.n_faces, lp.n_tris);
+    const rpthost::LightLayout ll = lp.layout();
     const unsigned char* base = static_cast<const unsigned char*>(d.light);
     LightMeshDesc desc;
     RPT_HIP_CHECK(ctx, hipMemcpy(&desc, base + ll.off_desc + sizeof(LightMeshDesc) * (size_t)ord, sizeof(desc), hipMemcpyDeviceToHost));
@@ -1968,7 +1672,7 @@ int rpt_download_mesh_light_table(rpt_ctx* ctx, uint32_t mesh, uint64_t* cdf, ui
 static int cut_desc_device(rpt_ctx* ctx, DevState& d)
 {
     const rpthost::CutPlan& cp = ctx->cut;
-    const rpthost::CutLayout cl(cp.n_meshes, cp.n_tris, cp.n_words);
+    const rpthost::CutLayout cl = cp.layout();
     const std::vector<uint32_t> desc = rpthost::cut_desc_table(cp, ctx->tex);
     if (!desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(static_cast<unsigned char*>(d.cut) + cl.off_desc, desc.data(), 4 * desc.size(), hipMemcpyHostToDevice));
     return RPT_OK;
@@ -1979,7 +1683,7 @@ static int cut_desc_device(rpt_ctx* ctx, DevState& d)
 static int nrm_desc_device(rpt_ctx* ctx, DevState& d)
 {
     const rpthost::NrmPlan& np = ctx->nrm;
-    const rpthost::NrmLayout nl(np.n_meshes, np.n_tris, np.n_texels);
+    const rpthost::NrmLayout nl = np.layout();
     const std::vector<uint32_t> desc = rpthost::nrm_desc_table(np, ctx->tex);
     if (!desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(static_cast<unsigned char*>(d.nrm) + nl.off_desc, desc.data(), 4 * desc.size(), hipMemcpyHostToDevice));
     return RPT_OK;
@@ -1992,8 +1696,8 @@ static int nrm_desc_device(rpt_ctx* ctx, DevState& d)
 static int tex_device(rpt_ctx* ctx, DevState& d, const rpthost::TexPlan& old, const rpt_mesh_texture* items, uint32_t n_items)
 {
     const rpthost::TexPlan& tp = ctx->tex;
-    const rpthost::TexLayout tl(tp.n_tex(), tp.n_tris, tp.n_vertices, tp.n_texels);
-    const rpthost::TexLayout ol(old.n_tex(), old.n_tris, old.n_vertices, old.n_texels);
+    const rpthost::TexLayout tl = tp.layout();
+    const rpthost::TexLayout ol = old.layout();
     RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
     RPT_CHECK_RC(ensure_refit(ctx, d));
     void* fresh = nullptr;
@@ -2123,7 +1827,7 @@ int rpt_download_mesh_texture(rpt_ctx* ctx, uint32_t mesh, float* texels, uint32
     if (width != im.width || height != im.height) { set_err(ctx, "rpt_download_mesh_texture: mesh %u: %u x %u is not its texture's %u x %u", mesh, width, height, im.width, im.height); return RPT_ERR_INVALID_ARG; }
     if (!texels) { set_err(ctx, "rpt_download_mesh_texture: texels is NULL"); return RPT_ERR_INVALID_ARG; }
     RPT_ON_DEVICE(ctx);
-    const rpthost::TexLayout tl(tp.n_tex(), tp.n_tris, tp.n_vertices, tp.n_texels);
+    const rpthost::TexLayout tl = tp.layout();
     RPT_HIP_CHECK(ctx, hipMemcpy(texels, static_cast<const unsigned char*>(d.tex) + tl.off_texels + 16 * (size_t)im.first, 16 * (size_t)im.width * im.height, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
@@ -2134,7 +1838,7 @@ int rpt_download_mesh_texture(rpt_ctx* ctx, uint32_t mesh, float* texels, uint32
 // the new plan (ctx->env still the old one); *q and *w_max: what this device computed.
 static int env_device(rpt_ctx* ctx, DevState& d, const rpthost::EnvPlan& ep, const float* texels, uint64_t* q, uint32_t* w_max)
 {
-    const rpthost::EnvLayout el(ep.size, ep.sampled(), ep.n_tris);
+    const rpthost::EnvLayout el = ep.layout();
     const size_t n = ep.n_texels();
     RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
     RPT_CHECK_RC(ensure_refit(ctx, d));
@@ -2247,7 +1951,7 @@ int rpt_download_environment_table(rpt_ctx* ctx, uint64_t* cdf, uint32_t n_texel
     if (n_texels != ep.n_texels()) { set_err(ctx, "rpt_download_environment_table: n_texels %u != the environment's %u x %u", n_texels, ep.size, ep.size); return RPT_ERR_INVALID_ARG; }
     if (!cdf || !exponent) { set_err(ctx, "rpt_download_environment_table: cdf or exponent is NULL"); return RPT_ERR_INVALID_ARG; }
     RPT_ON_DEVICE(ctx);
-    const rpthost::EnvLayout el(ep.size, true, ep.n_tris);
+    const rpthost::EnvLayout el = ep.layout();                      // (SAMPLED: checked above)
     RPT_HIP_CHECK(ctx, hipMemcpy(cdf, static_cast<const unsigned char*>(d.env) + el.off_cdf, 8 * (size_t)n_texels, hipMemcpyDeviceToHost));
     *exponent = ep.exponent;
     return RPT_OK;
@@ -2261,8 +1965,8 @@ int rpt_download_environment_table(rpt_ctx* ctx, uint64_t* cdf, uint32_t n_texel
 static int cut_device(rpt_ctx* ctx, DevState& d, const rpthost::CutPlan& old, const rpt_mesh_cutout* items, uint32_t n_items)
 {
     const rpthost::CutPlan& cp = ctx->cut;
-    const rpthost::CutLayout cl(cp.n_meshes, cp.n_tris, cp.n_words);
-    const rpthost::CutLayout ol(old.n_meshes, old.n_tris, old.n_words);
+    const rpthost::CutLayout cl = cp.layout();
+    const rpthost::CutLayout ol = old.layout();
     RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
     RPT_CHECK_RC(ensure_refit(ctx, d));
     void* fresh = nullptr;
@@ -2371,7 +2075,7 @@ int rpt_download_mesh_cutout(rpt_ctx* ctx, uint32_t mesh, uint32_t* bits, uint32
     if (n_words != want) { set_err(ctx, "rpt_download_mesh_cutout: mesh %u: n_words %u != %llu, the words of its %u x %u mask", mesh, n_words, (unsigned long long)want, c.width, c.height); return RPT_ERR_INVALID_ARG; }
     if (!bits) { set_err(ctx, "rpt_download_mesh_cutout: bits is NULL"); return RPT_ERR_INVALID_ARG; }
     RPT_ON_DEVICE(ctx);
-    const rpthost::CutLayout cl(cp.n_meshes, cp.n_tris, cp.n_words);
+    const rpthost::CutLayout cl = cp.layout();
     RPT_HIP_CHECK(ctx, hipMemcpy(bits, static_cast<const unsigned char*>(d.cut) + cl.off_bits + 4 * (size_t)c.first, 4 * (size_t)n_words, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
@@ -2384,8 +2088,8 @@ int rpt_download_mesh_cutout(rpt_ctx* ctx, uint32_t mesh, uint32_t* bits, uint32
 static int nrm_device(rpt_ctx* ctx, DevState& d, const rpthost::NrmPlan& old, const rpt_mesh_normal_map* items, uint32_t n_items)
 {
     const rpthost::NrmPlan& np = ctx->nrm;
-    const rpthost::NrmLayout nl(np.n_meshes, np.n_tris, np.n_texels);
-    const rpthost::NrmLayout ol(old.n_meshes, old.n_tris, old.n_texels);
+    const rpthost::NrmLayout nl = np.layout();
+    const rpthost::NrmLayout ol = old.layout();
     RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
     RPT_CHECK_RC(ensure_refit(ctx, d));
     void* fresh = nullptr;
@@ -2493,7 +2197,7 @@ int rpt_download_mesh_normal_map(rpt_ctx* ctx, uint32_t mesh, float* texels, uin
     if (width != c.width || height != c.height) { set_err(ctx, "rpt_download_mesh_normal_map: mesh %u: %u x %u is not its map's %u x %u", mesh, width, height, c.width, c.height); return RPT_ERR_INVALID_ARG; }
     if (!texels) { set_err(ctx, "rpt_download_mesh_normal_map: texels is NULL"); return RPT_ERR_INVALID_ARG; }
     RPT_ON_DEVICE(ctx);
-    const rpthost::NrmLayout nl(np.n_meshes, np.n_tris, np.n_texels);
+    const rpthost::NrmLayout nl = np.layout();
     RPT_HIP_CHECK(ctx, hipMemcpy(texels, static_cast<const unsigned char*>(d.nrm) + nl.off_texels + 16 * (size_t)c.first, 16 * (size_t)c.width * c.height, hipMemcpyDeviceToHost));
     return RPT_OK;
 }
@@ -3074,7 +2778,7 @@ int rpt_debug_mesh_normal_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n,
     if (!ctx->smooth.any() || !ctx->devs[0].smooth) { set_err(ctx, "rpt_debug_mesh_normal_query: no mesh is SMOOTH"); return RPT_ERR_INVALID_ARG; }
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
-    RPT_HIP_CHECK(ctx, rptlaunch::mesh_normal_query(smooth_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_normal_query(rptargs::mesh_scene_of<SceneMeshSmooth>(mesh_view_of(ctx, ctx->devs[0])), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
 }
 
@@ -3086,7 +2790,7 @@ int rpt_debug_mesh_light_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, u
     if (!ctx->light.any() || !ctx->devs[0].light) { set_err(ctx, "rpt_debug_mesh_light_sample: no mesh is ON"); return RPT_ERR_INVALID_ARG; }
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
-    RPT_HIP_CHECK(ctx, rptlaunch::mesh_light_sample(light_scene_of(ctx, ctx->devs[0]), in_dev, out_dev, n, (hipStream_t)stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_light_sample(rptargs::mesh_scene_of<SceneMeshLight>(mesh_view_of(ctx, ctx->devs[0])), in_dev, out_dev, n, (hipStream_t)stream));
     return RPT_OK;
 }
 
@@ -3098,7 +2802,7 @@ int rpt_debug_mesh_texture_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n
     if (!ctx->tex.any() || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_texture_query: no mesh is textured"); return RPT_ERR_INVALID_ARG; }
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
-    RPT_HIP_CHECK(ctx, rptlaunch::mesh_texture_query(tex_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_texture_query(rptargs::mesh_scene_of<SceneMeshTex>(mesh_view_of(ctx, ctx->devs[0])), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
 }
 
@@ -3110,7 +2814,7 @@ int rpt_debug_mesh_cutout_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n,
     if (!ctx->cut.any() || !ctx->devs[0].cut || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_cutout_query: no mesh has a cutout"); return RPT_ERR_INVALID_ARG; }
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
-    RPT_HIP_CHECK(ctx, rptlaunch::mesh_cutout_query(cut_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_cutout_query(rptargs::mesh_scene_of<SceneMeshCut>(mesh_view_of(ctx, ctx->devs[0])), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
 }
 
@@ -3122,7 +2826,7 @@ int rpt_debug_mesh_normal_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_
     if (!ctx->nrm.any() || !ctx->devs[0].nrm || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_normal_map_query: no mesh has a normal map"); return RPT_ERR_INVALID_ARG; }
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
-    RPT_HIP_CHECK(ctx, rptlaunch::mesh_normal_map_query(nrm_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_normal_map_query(rptargs::mesh_scene_of<SceneMeshNrm>(mesh_view_of(ctx, ctx->devs[0])), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
 }
 
@@ -3134,7 +2838,7 @@ int rpt_debug_env_query(rpt_ctx* ctx, const float* dirs_dev, uint64_t n, uint32_
     if (!ctx->env.any() || !ctx->devs[0].env) { set_err(ctx, "rpt_debug_env_query: no environment is set"); return RPT_ERR_INVALID_ARG; }
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
-    RPT_HIP_CHECK(ctx, rptlaunch::env_query(env_scene_of(ctx, ctx->devs[0]), dirs_dev, out_dev, n, (hipStream_t)stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::env_query(rptargs::mesh_scene_of<SceneMeshEnv>(mesh_view_of(ctx, ctx->devs[0])), dirs_dev, out_dev, n, (hipStream_t)stream));
     return RPT_OK;
 }
 
@@ -3146,7 +2850,7 @@ int rpt_debug_env_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, uint32_t
     if (!ctx->env.any() || !ctx->devs[0].env) { set_err(ctx, "rpt_debug_env_sample: no environment is set"); return RPT_ERR_INVALID_ARG; }
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
-    RPT_HIP_CHECK(ctx, rptlaunch::env_sample(env_scene_of(ctx, ctx->devs[0]), in_dev, out_dev, n, (hipStream_t)stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::env_sample(rptargs::mesh_scene_of<SceneMeshEnv>(mesh_view_of(ctx, ctx->devs[0])), in_dev, out_dev, n, (hipStream_t)stream));
     return RPT_OK;
 }
 

@@ -84,6 +84,19 @@ struct CutMask {
     uint64_t first = 0;               // its first word in the devices' mask table
 };
 
+// The device's cutout tables (DevState::cut), one allocation: per mesh of the SCENE 16 B (the descriptors, by texture ordinal); per
+// triangle of the scene 4 B (the all-0xFFFFFFFF tri_light the render kernel reads while no mesh is ON); one bit per mask texel.
+struct CutLayout {
+    size_t off_desc = 0, off_none = 0, off_bits = 0, total = 0;
+    CutLayout(uint32_t n_meshes, uint32_t n_tris, uint64_t n_words)
+    {
+        const auto round16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        off_none = round16(4 * (size_t)kCutDescWords * n_meshes);
+        off_bits = off_none + round16(4 * (size_t)n_tris);
+        total = off_bits + 4 * (size_t)n_words;
+    }
+};
+
 // What rpt_set_mesh_cutouts leaves on the host for the life of the cutouts.
 struct CutPlan {
     std::vector<CutMask> mask;        // mesh -> its cutout; empty: every mesh OFF
@@ -96,19 +109,7 @@ struct CutPlan {
         for (const CutMask& m : mask) if (m.width != 0u) return true;
         return false;
     }
-};
-
-// The device's cutout tables (DevState::cut), one allocation: per mesh of the SCENE 16 B (the descriptors, by texture ordinal); per
-// triangle of the scene 4 B (the all-0xFFFFFFFF tri_light the render kernel reads while no mesh is ON); one bit per mask texel.
-struct CutLayout {
-    size_t off_desc = 0, off_none = 0, off_bits = 0, total = 0;
-    CutLayout(uint32_t n_meshes, uint32_t n_tris, uint64_t n_words)
-    {
-        const auto round16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        off_none = round16(4 * (size_t)kCutDescWords * n_meshes);
-        off_bits = off_none + round16(4 * (size_t)n_tris);
-        total = off_bits + 4 * (size_t)n_words;
-    }
+    CutLayout layout() const { return CutLayout(n_meshes, n_tris, n_words); }     // of every device's tables
 };
 
 // The plan of `mask` (one entry per mesh, `first` not yet set) over a scene.

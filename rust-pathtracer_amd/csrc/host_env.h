@@ -173,20 +173,6 @@ RPT_ENV_FN uint32_t env_sample(const EnvTexel* texels, const uint64_t* cdf, uint
     return k;
 }
 
-// What the context remembers of its environment (size == 0: none is set).
-struct EnvPlan {
-    uint32_t size = 0;
-    uint32_t mode = RPT_ENV_BACKGROUND_ONLY;
-    float scale = 0.0f;
-    uint32_t n_tris = 0;                       // of the scene: the sizes of the empty tables of the absent features
-    uint64_t q_total = 0;                      // Q as the devices computed it (0: BACKGROUND_ONLY, or the table is dark)
-    int32_t exponent = 0;                      // E (0 then as well)
-
-    bool any() const { return size != 0u; }
-    bool sampled() const { return size != 0u && mode == RPT_ENV_SAMPLED; }
-    uint32_t n_texels() const { return size * size; }
-};
-
 // The device's environment tables (DevState::env), one allocation.  Per texel 16 B and, SAMPLED, 8 B (its CDF entry, the scan's
 // partial sum before the last pass) plus 8 B per 256 texels (the scan's block sums); 16 B of scratch (the bits of W_max); per triangle
 // of the SCENE 4 B (0xFFFFFFFF: the tri_light and tri_tex the render kernel reads while no mesh is ON or textured) and one bit (the
@@ -206,6 +192,21 @@ struct EnvLayout {
         off_flat_bits = off_none + round16(4 * (size_t)n_tris);
         total = off_flat_bits + round16(4 * (((size_t)n_tris + 31) / 32));
     }
+};
+
+// What the context remembers of its environment (size == 0: none is set).
+struct EnvPlan {
+    uint32_t size = 0;
+    uint32_t mode = RPT_ENV_BACKGROUND_ONLY;
+    float scale = 0.0f;
+    uint32_t n_tris = 0;                       // of the scene: the sizes of the empty tables of the absent features
+    uint64_t q_total = 0;                      // Q as the devices computed it (0: BACKGROUND_ONLY, or the table is dark)
+    int32_t exponent = 0;                      // E (0 then as well)
+
+    bool any() const { return size != 0u; }
+    bool sampled() const { return size != 0u && mode == RPT_ENV_SAMPLED; }
+    uint32_t n_texels() const { return size * size; }
+    EnvLayout layout() const { return EnvLayout(size, sampled(), n_tris); }     // of every device's tables
 };
 
 // `err` = "rpt_set_environment: " + the message; returns `code`.

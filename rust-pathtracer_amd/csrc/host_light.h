@@ -70,6 +70,30 @@ RPT_LIGHT_FN float light_total_area(uint64_t q, int32_t e)
     return (float)q * scale;
 }
 
+// The device's mesh light tables (DevState::light), one allocation.  Per ON mesh 32 B; per face 36 B (its CDF entry and the scan's
+// partial sum, 8 B each, its area, 4 B, its corners, 12 B, its ordinal, 4 B) and 8 B per 256 faces (the scan's block sums); per
+// triangle of the SCENE 4 B (the hit side's lookup) and one bit (the all-FLAT smooth bits the render kernel reads while no mesh is
+// SMOOTH).
+struct LightLayout {
+    size_t off_desc = 0, off_cdf = 0, off_part = 0, off_block = 0, off_area = 0, off_face_vertex = 0, off_face_mesh = 0, off_tri_light = 0,
+           off_flat_bits = 0, total = 0;
+    uint32_t n_blocks = 0;
+    LightLayout(uint32_t n_on, uint32_t n_faces, uint32_t n_tris)
+    {
+        const auto round16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        n_blocks = (uint32_t)(((size_t)n_faces + kLightScanBlock - 1) / kLightScanBlock);
+        off_cdf = round16(4 * (size_t)kLightDescWords * n_on);
+        off_part = off_cdf + round16(8 * (size_t)n_faces);
+        off_block = off_part + round16(8 * (size_t)n_faces);
+        off_area = off_block + round16(8 * (size_t)n_blocks);
+        off_face_vertex = off_area + round16(4 * (size_t)n_faces);
+        off_face_mesh = off_face_vertex + round16(12 * (size_t)n_faces);
+        off_tri_light = off_face_mesh + round16(4 * (size_t)n_faces);
+        off_flat_bits = off_tri_light + round16(4 * (size_t)n_tris);
+        total = off_flat_bits + round16(4 * (((size_t)n_tris + 31) / 32));
+    }
+};
+
 // What rpt_set_mesh_lights leaves on the host for the life of the modes, and (the staging vectors) what every device gets.
 struct LightPlan {
     std::vector<uint8_t> mode;                 // mesh -> RPT_MESH_LIGHT_*; empty: every mesh OFF
@@ -103,30 +127,7 @@ struct LightPlan {
         std::vector<uint32_t>().swap(face_mesh);
         std::vector<uint32_t>().swap(tri_light);
     }
-};
-
-// The device's mesh light tables (DevState::light), one allocation.  Per ON mesh 32 B; per face 36 B (its CDF entry and the scan's
-// partial sum, 8 B each, its area, 4 B, its corners, 12 B, its ordinal, 4 B) and 8 B per 256 faces (the scan's block sums); per
-// triangle of the SCENE 4 B (the hit side's lookup) and one bit (the all-FLAT smooth bits the render kernel reads while no mesh is
-// SMOOTH).
-struct LightLayout {
-    size_t off_desc = 0, off_cdf = 0, off_part = 0, off_block = 0, off_area = 0, off_face_vertex = 0, off_face_mesh = 0, off_tri_light = 0,
-           off_flat_bits = 0, total = 0;
-    uint32_t n_blocks = 0;
-    LightLayout(uint32_t n_on, uint32_t n_faces, uint32_t n_tris)
-    {
-        const auto round16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        n_blocks = (uint32_t)(((size_t)n_faces + kLightScanBlock - 1) / kLightScanBlock);
-        off_cdf = round16(4 * (size_t)kLightDescWords * n_on);
-        off_part = off_cdf + round16(8 * (size_t)n_faces);
-        off_block = off_part + round16(8 * (size_t)n_faces);
-        off_area = off_block + round16(8 * (size_t)n_blocks);
-        off_face_vertex = off_area + round16(4 * (size_t)n_faces);
-        off_face_mesh = off_face_vertex + round16(12 * (size_t)n_faces);
-        off_tri_light = off_face_mesh + round16(4 * (size_t)n_faces);
-        off_flat_bits = off_tri_light + round16(4 * (size_t)n_tris);
-        total = off_flat_bits + round16(4 * (((size_t)n_tris + 31) / 32));
-    }
+    LightLayout layout() const { return LightLayout(n_on(), n_faces, n_tris); }     // of every device's tables
 };
 
 // The plan of `mode` over a scene's flattened triangles (`flat`: 3 corners each, concatenated vertex indices).

@@ -119,20 +119,6 @@ struct NrmMap {
     uint64_t first = 0;               // its first texel in the devices' map table
 };
 
-// What rpt_set_mesh_normal_maps leaves on the host for the life of the maps.
-struct NrmPlan {
-    std::vector<NrmMap> map;          // mesh -> its map; empty: every mesh OFF
-    uint32_t n_meshes = 0, n_tris = 0;
-    uint64_t n_texels = 0;            // of all maps
-
-    bool on(uint32_t mesh) const { return mesh < map.size() && map[mesh].width != 0u; }
-    bool any() const
-    {
-        for (const NrmMap& m : map) if (m.width != 0u) return true;
-        return false;
-    }
-};
-
 // The device's map tables (DevState::nrm), one allocation: per mesh of the SCENE 16 B (the descriptors, by texture ordinal); per
 // triangle of the scene 4 B (the all-0xFFFFFFFF tri_light the render kernel reads while no mesh is ON and no cutout or environment
 // supplies one); per map texel 16 B.
@@ -145,6 +131,21 @@ struct NrmLayout {
         off_texels = off_none + round16(4 * (size_t)n_tris);
         total = off_texels + 16 * (size_t)n_texels;
     }
+};
+
+// What rpt_set_mesh_normal_maps leaves on the host for the life of the maps.
+struct NrmPlan {
+    std::vector<NrmMap> map;          // mesh -> its map; empty: every mesh OFF
+    uint32_t n_meshes = 0, n_tris = 0;
+    uint64_t n_texels = 0;            // of all maps
+
+    bool on(uint32_t mesh) const { return mesh < map.size() && map[mesh].width != 0u; }
+    bool any() const
+    {
+        for (const NrmMap& m : map) if (m.width != 0u) return true;
+        return false;
+    }
+    NrmLayout layout() const { return NrmLayout(n_meshes, n_tris, n_texels); }     // of every device's tables
 };
 
 // The plan of `map` (one entry per mesh, `first` not yet set) over a scene.

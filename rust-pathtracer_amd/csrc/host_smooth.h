@@ -69,6 +69,21 @@ RPT_SMOOTH_FN void smooth_vertex_normal(const float* face, const uint32_t* faces
     smooth_normalize(s, n);
 }
 
+// The device's smooth tables (DevState::smooth), one allocation.
+struct SmoothLayout {
+    size_t off_normals = 0, off_face = 0, off_face_vertex = 0, off_adj_first = 0, off_adj = 0, off_bits = 0, total = 0;
+    SmoothLayout(uint32_t n_vertices, uint32_t n_tris, uint32_t n_faces, uint32_t n_adj)
+    {
+        const auto round16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        off_face = round16(16 * (size_t)n_vertices);                // the normals: 16 B per vertex of the scene
+        off_face_vertex = off_face + round16(16 * (size_t)n_faces);
+        off_adj_first = off_face_vertex + round16(12 * (size_t)n_faces);
+        off_adj = off_adj_first + round16(4 * ((size_t)n_vertices + 1));
+        off_bits = off_adj + round16(4 * (size_t)n_adj);
+        total = off_bits + round16(4 * (((size_t)n_tris + 31) / 32));
+    }
+};
+
 // What rpt_set_mesh_shading leaves on the host for the life of the modes, and (the vectors) what every device gets.
 struct SmoothPlan {
     std::vector<uint8_t> mode;                 // mesh -> RPT_MESH_SHADING_*; empty: every mesh FLAT
@@ -93,21 +108,7 @@ struct SmoothPlan {
         std::vector<uint32_t>().swap(adj);
         std::vector<uint32_t>().swap(bits);
     }
-};
-
-// The device's smooth tables (DevState::smooth), one allocation.
-struct SmoothLayout {
-    size_t off_normals = 0, off_face = 0, off_face_vertex = 0, off_adj_first = 0, off_adj = 0, off_bits = 0, total = 0;
-    SmoothLayout(uint32_t n_vertices, uint32_t n_tris, uint32_t n_faces, uint32_t n_adj)
-    {
-        const auto round16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        off_face = round16(16 * (size_t)n_vertices);                // the normals: 16 B per vertex of the scene
-        off_face_vertex = off_face + round16(16 * (size_t)n_faces);
-        off_adj_first = off_face_vertex + round16(12 * (size_t)n_faces);
-        off_adj = off_adj_first + round16(4 * ((size_t)n_vertices + 1));
-        off_bits = off_adj + round16(4 * (size_t)n_adj);
-        total = off_bits + round16(4 * (((size_t)n_tris + 31) / 32));
-    }
+    SmoothLayout layout() const { return SmoothLayout(n_vertices, n_tris, n_faces, n_adj); }     // of every device's tables
 };
 
 // The flattened triangles' corners, 3 per triangle, from tables in slot order: `rows` (48 B per slot, word 3 = the flattened index)

@@ -137,6 +137,22 @@ struct TexImage {
     uint64_t first = 0;               // its first texel in the devices' texel table
 };
 
+// The device's texture tables (DevState::tex), one allocation.  Per textured mesh 32 B; per triangle of the SCENE 4 B (which
+// texture) and one bit (the all-FLAT smooth bits the render kernel reads while no mesh is SMOOTH or ON); per vertex of the scene 8 B
+// (its UV); per texel 16 B.
+struct TexLayout {
+    size_t off_desc = 0, off_tri_tex = 0, off_uvs = 0, off_flat_bits = 0, off_texels = 0, total = 0;
+    TexLayout(uint32_t n_tex, uint32_t n_tris, uint32_t n_vertices, uint64_t n_texels)
+    {
+        const auto round16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        off_tri_tex = round16(4 * (size_t)kTexDescWords * n_tex);
+        off_uvs = off_tri_tex + round16(4 * (size_t)n_tris);
+        off_flat_bits = off_uvs + round16(8 * (size_t)n_vertices);
+        off_texels = off_flat_bits + round16(4 * (((size_t)n_tris + 31) / 32));
+        total = off_texels + 16 * (size_t)n_texels;
+    }
+};
+
 // What rpt_set_mesh_textures leaves on the host for the life of the textures, and (the staging vectors) what every device gets.
 struct TexPlan {
     std::vector<TexImage> image;               // mesh -> its texture; empty: no mesh is textured
@@ -166,22 +182,7 @@ struct TexPlan {
         std::vector<uint32_t>().swap(desc);
         std::vector<uint32_t>().swap(tri_tex);
     }
-};
-
-// The device's texture tables (DevState::tex), one allocation.  Per textured mesh 32 B; per triangle of the SCENE 4 B (which
-// texture) and one bit (the all-FLAT smooth bits the render kernel reads while no mesh is SMOOTH or ON); per vertex of the scene 8 B
-// (its UV); per texel 16 B.
-struct TexLayout {
-    size_t off_desc = 0, off_tri_tex = 0, off_uvs = 0, off_flat_bits = 0, off_texels = 0, total = 0;
-    TexLayout(uint32_t n_tex, uint32_t n_tris, uint32_t n_vertices, uint64_t n_texels)
-    {
-        const auto round16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        off_tri_tex = round16(4 * (size_t)kTexDescWords * n_tex);
-        off_uvs = off_tri_tex + round16(4 * (size_t)n_tris);
-        off_flat_bits = off_uvs + round16(8 * (size_t)n_vertices);
-        off_texels = off_flat_bits + round16(4 * (((size_t)n_tris + 31) / 32));
-        total = off_texels + 16 * (size_t)n_texels;
-    }
+    TexLayout layout() const { return TexLayout(n_tex(), n_tris, n_vertices, n_texels); }     // of every device's tables
 };
 
 // The plan of `image` (one entry per mesh, `first` not yet set) and `uvs` over a scene: ordinals, texel offsets, descriptors and the

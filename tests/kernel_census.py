@@ -49,7 +49,7 @@ def kernel_of(choice, klass):
 
 MESH_BIT, SMOOTH_BIT, LIGHT_BIT, TEX_BIT, ENV_BIT, CUT_BIT, NRM_BIT = (1 << b for b in range(25, 32))
 MESH_FORM_BITS = 0x7F << 25
-# every name mesh_kernel_of can return, in launch_render's order
+# every name mesh_kernel_of can return, in the order of csrc/mesh_args.h's MeshForm (tests/test_mesh_args_host.py)
 MESH_RENDER_KERNELS = ["meshnrm_cut_env_regen_kernel", "meshnrm_cut_regen_kernel", "meshnrm_env_regen_kernel", "meshnrm_regen_kernel",
                        "meshcut_env_regen_kernel", "meshcut_regen_kernel", "meshenv_regen_kernel", "meshtex_light_regen_kernel",
                        "meshtex_regen_kernel", "meshlight_regen_kernel", "meshsmooth_regen_kernel", "mesh_regen_kernel"]
@@ -57,8 +57,9 @@ MESH_RENDER_KERNELS = ["meshnrm_cut_env_regen_kernel", "meshnrm_cut_regen_kernel
 
 def mesh_kernel_of(choice):
     """The kernel launch_render (csrc/capi.hip) takes for a mesh scene with rpt_debug_kernel_choice's bits 25-31 (MESH, SMOOTH, LIGHT,
-    TEX, ENV, CUT, NRM), its `if`s in its order: normal maps first, picked by (cutouts, environment), then cutouts, picked by the
-    environment, then the environment's one form, then textures over the lights' tables or the smooth ones', lights, smooth, flat."""
+    TEX, ENV, CUT, NRM), restating mesh_form_of (csrc/mesh_args.h): normal maps first, picked by (cutouts, environment), then cutouts,
+    picked by the environment, then the environment's one form, then textures over the lights' tables or the smooth ones', lights,
+    smooth, flat."""
     assert choice & MESH_BIT, "not a mesh scene's launch: 0x%x" % choice
     smooth, lights, textured = choice & SMOOTH_BIT, choice & LIGHT_BIT, choice & TEX_BIT
     environment, cutouts, normal_maps = choice & ENV_BIT, choice & CUT_BIT, choice & NRM_BIT

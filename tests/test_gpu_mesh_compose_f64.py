@@ -14,7 +14,7 @@ scenes.mesh_normal_map_scene()'s 32 x 32 bump map at strength 1, BILINEAR on mes
   case  on top of A                 bits 25-31 (rpt_debug_kernel_choice)      kernel (kernel_census.mesh_kernel_of)
   A     —                           MESH SMOOTH LIGHT TEX                     meshtex_light_regen_kernel
   B     environment                 ... ENV                                   meshenv_regen_kernel, textures bound
-  C     cutout on 0                 ... CUT                                   meshcut_regen_kernel, light branch of cut_scene_of
+  C     cutout on 0                 ... CUT                                   meshcut_regen_kernel, the light tables bound (mesh_args.h)
   D     cutout on 0, environment    ... ENV CUT                               meshcut_env_regen_kernel
   E     maps                        ... NRM                                   meshnrm_regen_kernel, light branch, smooth N
   F     maps, environment           ... ENV NRM                               meshnrm_env_regen_kernel
@@ -249,7 +249,7 @@ def test_the_composed_restatement_reduces_to_the_single_feature_ones(rpt, oracle
 
 def test_every_mesh_kernel_name_is_in_a_code_object():
     """kernel_census.mesh_kernel_of names only kernels that the test_mesh_*_host.py files read from the libraries' code objects, over
-    every combination of bits 26-31, and reaches each of launch_render's twelve mesh forms."""
+    every combination of bits 26-31, and reaches each of the twelve mesh forms (csrc/mesh_args.h, MeshForm)."""
     from test_mesh_cutout_host import CUT_KERNELS
     from test_mesh_env_host import ENV_KERNELS
     from test_mesh_host import MESH_KERNELS
