@@ -1128,6 +1128,100 @@ typedef struct rpt_mesh_normal_map {
 int rpt_set_mesh_normal_maps(rpt_ctx* ctx, const rpt_mesh_normal_map* items, uint32_t n_items);
 int rpt_download_mesh_normal_map(rpt_ctx* ctx, uint32_t mesh, float* texels /* host, width*height*4 f32, decoded */, uint32_t width, uint32_t height);
 
+/* ---- mesh material maps — PROJECT-DEFINED ----------------------------------------------------------------------------------------
+ * Per mesh, a material that varies across the surface: one RGBA8 map, looked up through the mesh's texture UVs at the winning
+ * triangle, scales the mesh material's ROUGHNESS and METALLIC.  Every operation is stated, so that texels, hit materials and frames
+ * stay checkable bit for bit (tests/test_gpu_mesh_material_map.py holds them to a numpy restatement).  The statement is written
+ * once, in csrc/host_mmap.h, which the kernels and the host harness both compile; it reuses tex_interp, tex_wrap and tex_lookup of
+ * "mesh textures" (csrc/host_tex.h) and does not restate them.  All arithmetic is f32, one rounding per operation, nothing
+ * contracted, with the library's correctly rounded divide.
+ *
+ * Decode.  Once per call, on the device, one lane per texel.  For a byte k
+ *     c(k) = (float)k / 255                                          c(0) = 0, c(255) = 1, both exactly
+ * and a decoded texel is four f32, 16 B, so that tex_lookup serves it unchanged:
+ *     {fr, fm, 0, 0}          fr = c(byte of roughness_channel), or exactly 1 for RPT_MATERIAL_MAP_CHANNEL_NONE; fm likewise for
+ *                             metallic_channel
+ * The channel choice is resolved here: the render kernels never see it.
+ *
+ * Lookup at the hit.  The triangle test's own u and v are recomputed as "mesh textures" does it — the same operations on the same
+ * words.  (s, t) = tex_interp over the UVs of the mesh's TEXTURE; that texture's wrap applies, the MAP's own filter, and W and H
+ * are the map's, which need not be the texture's.  tex_lookup over the decoded texels gives (fr, fm, .).
+ * There is no clamp: BILINEAR cannot leave [0, 1].  A weight f below 1/2 comes from p = x*n - 1/2 with x*n >= 1/2, so it is a
+ * multiple of 2^-24 and g = 1 - f is exact (as it is for f >= 1/2); with a, b in [0, 1], rn(g*a) + rn(f*b) <= g + f = 1 and rounding
+ * is monotone; the second blend repeats the argument.  For the same reason an all-255 map looks up exactly 1 (and an all-0 map
+ * exactly 0) under either filter; any other constant image is returned exactly by NEAREST only — BILINEAR rounds g*c and f*c
+ * separately (tests/test_mesh_material_map_host.py counts both over all byte pairs and 65 weights).
+ *
+ * Apply.  After the base's hit_material — after "mesh textures" has written rgb:
+ *     mat.roughness = mat.roughness * fr;  mat.metallic = mat.metallic * fm                   one multiplication each
+ * Everything derived from them follows as for any material: the max(roughness, 0.01), ax, ay, the lobe weights.  Unchanged:
+ * emission, rgb, the triangle test, acceptance, any_hit, normals, the mesh-light sampler and hit weight, cutouts, the environment.
+ *
+ * Composition.  Material maps compose with FLAT / SMOOTH, OFF / ON lights (which emit as before), textures of any wrap and filter,
+ * cutouts, normal maps, and an environment in either mode.  A material map needs the mesh's UVs: an untextured mesh is
+ * RPT_ERR_INVALID_ARG (a 1 x 1 white texture is enough).  rpt_set_mesh_textures that would remove the texture of a mesh whose map is
+ * ON is RPT_ERR_INVALID_ARG ("remove the material map first"); replacing the texture keeps the map, which then reads the new UVs and
+ * wrap.  rpt_upload_scene drops all maps.
+ *
+ * rpt_set_mesh_material_maps sets (ON) or removes (OFF) the map of the named meshes of the uploaded scene; meshes not named keep
+ * theirs.  `texels` is copied inside the call; on return every map is current on every device of the context (one process per GPU:
+ * every rank makes the call).  The checks, in this order, all on the host before any device is touched — a rejected call changes
+ * nothing, and rpt_last_error starts with "rpt_set_mesh_material_maps: " and names the item:
+ *   RPT_ERR_INVALID_ARG  ctx is NULL;
+ *   RPT_ERR_NO_SCENE     no scene with meshes is uploaded;
+ *   RPT_ERR_INVALID_ARG  items NULL with a non-zero count; then per item, in order: mesh >= n_meshes, or a mesh named twice; mode
+ *                        neither constant; ON with width or height 0 or above 16384; ON with texels NULL; filter not a constant; a
+ *                        channel neither 0 .. 3 nor NONE; ON with both channels NONE; OFF with a non-zero size or a non-NULL
+ *                        texels; ON on an untextured mesh;
+ *   RPT_ERR_UNSUPPORTED  all maps together would hold more than 2^26 texels;
+ *   RPT_OK               n_items == 0: nothing is done;
+ *   RPT_ERR_HIP          a runtime call failed part-way: the context is left with NO scene, as for the other mesh calls.
+ * While some map is ON the scene renders through a kernel of its own — the mesh kernel's body with the hit material above, one
+ * form over each of the eight textured forms that hold every table: the textured mesh-light one (absent lights through empty
+ * tables; a scene that would take the plain textured form takes this one), the environment form, the two cutout forms and the four
+ * normal-mapped forms, picked by (normal maps, cutouts, environment).  Turning every map OFF leaves the context rendering through
+ * exactly the kernels and tables it had before the first call.
+ *
+ * Moves.  rpt_update_meshes, rpt_rebuild_meshes and both _device forms leave maps alone and add no launch: the lookup reads the
+ * triangle row the walk tested, the refit's slot -> vertex table and the flattened triangle index, never slot order.
+ *
+ * rpt_download_mesh_material_map copies one mesh's DECODED texels from the context's first device: width * height * 4 f32.  A mesh
+ * out of range, a mesh without a map (it says so), another size or a NULL destination answer RPT_ERR_INVALID_ARG.
+ *
+ * Memory.  While a map is ON every device holds 16 B per map texel, 16 B per mesh of the scene (the descriptors are indexed by
+ * texture ordinal; the table is sized for every mesh being textured), and 4 B per triangle of the SCENE (the empty light table);
+ * during the call, per device, the new tables beside the old ones and 4 B per texel of the maps being set.  Per hit on a mapped mesh
+ * the kernel gathers 4 B (which texture), the 16 B descriptor, three slot -> vertex words, three UVs and one (NEAREST) or four
+ * (BILINEAR) 16 B texels; a hit on another mesh the first 4 B, or with it the descriptor.
+ *
+ * Registers (gfx950, VGPRs / spilled SGPRs, base form in brackets, no scratch in any form; tools/kernel_meta.py): meshmap 111 / 156
+ * (111 / 152), meshmap_env 113 / 154 (113 / 148), meshmap_cut 110 / 188 (110 / 179), meshmap_cut_env 112 / 191 (112 / 187),
+ * meshmap_nrm 111 / 150 (111 / 156), meshmap_nrm_env 113 / 150 (113 / 146), meshmap_nrm_cut 111 / 193 (110 / 189),
+ * meshmap_nrm_cut_env 112 / 185 (112 / 191): the lookup recomputes u, v and the UV interpolation and still fits its base's budget.
+ *
+ * Timings (MI355X, 1080p x 16 spp, medians of 5): 0.794 Gsamples/s with no map, 0.786 under an all-255 map (0.991) and 0.764
+ * under a noise map (0.963); rpt_set_mesh_material_maps for both 1024 x 1024 maps 1.9 ms the first time in a process and 0.6 ms again;
+ * the four move calls without / with maps: update_meshes 0.42 / 0.44 ms; rebuild_meshes 1.02 / 1.02 ms; update_meshes_device 0.16 /
+ * 0.16 ms; rebuild_meshes_device 0.75 / 0.74 ms.  The no-map rate is that of the textured kernel, unchanged (mesh normal maps: 0.794).
+ * tools/mesh_bench.py --material-maps alternates, in one process, frames of scenes.mesh_scene textured as --textures does with no
+ * map, under an all-255 1024 x 1024 map on both meshes (the pure cost of the lookup: both factors are exactly 1) and under a
+ * 1024 x 1024 BILINEAR noise map, and times the set call and the four move calls with and without maps. */
+enum { RPT_MESH_MATERIAL_MAP_OFF = 0, RPT_MESH_MATERIAL_MAP_ON = 1 };
+#define RPT_MATERIAL_MAP_CHANNEL_NONE 0xFFFFFFFFu
+
+typedef struct rpt_mesh_material_map {
+    uint32_t mesh;                    /* index into the uploaded scene's rpt_scene_desc.meshes */
+    uint32_t mode;                    /* RPT_MESH_MATERIAL_MAP_* ; OFF: width == height == 0, texels == NULL */
+    uint32_t width, height;           /* of the map: its own size, need not be the texture's */
+    const uint8_t* texels;            /* HOST, RGBA8, row 0 first; copied inside the call */
+    uint32_t filter;                  /* RPT_TEX_FILTER_NEAREST / RPT_TEX_FILTER_BILINEAR */
+    uint32_t roughness_channel;       /* 0 .. 3 (R, G, B, A) or RPT_MATERIAL_MAP_CHANNEL_NONE; glTF's metallicRoughness: 1 */
+    uint32_t metallic_channel;        /* 0 .. 3 or RPT_MATERIAL_MAP_CHANNEL_NONE; glTF's metallicRoughness: 2 */
+} rpt_mesh_material_map;
+
+int rpt_set_mesh_material_maps(rpt_ctx* ctx, const rpt_mesh_material_map* items, uint32_t n_items);
+int rpt_download_mesh_material_map(rpt_ctx* ctx, uint32_t mesh, float* texels /* host, width*height*4 f32, decoded */, uint32_t width, uint32_t height);
+
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)
  *   frames_done ColorBuffer.frames before the call; the caller adds `spp` afterwards

@@ -287,6 +287,15 @@ public:
         check(rpt_download_mesh_normal_map(ctx_, mesh, out.data(), width, height), ctx_);
         return out;
     }
+    /// Mesh material maps (rpt.h, "mesh material maps"): an RGBA8 map per named mesh, looked up through the mesh's texture UVs at the
+    /// hit, scales the material's roughness and metallic; an item with RPT_MESH_MATERIAL_MAP_OFF removes its mesh's.  sync_scene() drops them all.
+    void set_mesh_material_maps(const std::vector<rpt_mesh_material_map>& items) { check(rpt_set_mesh_material_maps(ctx_, items.data(), (uint32_t)items.size()), ctx_); }
+    /// The decoded texels the context holds for one material-mapped mesh: width * height * 4 floats {fr, fm, 0, 0}.
+    std::vector<float> mesh_material_map(uint32_t mesh, uint32_t width, uint32_t height) {
+        std::vector<float> out((size_t)width * height * 4);
+        check(rpt_download_mesh_material_map(ctx_, mesh, out.data(), width, height), ctx_);
+        return out;
+    }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

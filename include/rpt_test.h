@@ -93,6 +93,21 @@ int rpt_debug_mesh_cutout_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n,
  * scene has meshes; RPT_ERR_INVALID_ARG while no map is ON (those kernels do not run then). */
 int rpt_debug_mesh_normal_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
 
+/* The roughness and metallic a winning triangle is shaded with in a scene some mesh of which has a material map ON (include/rpt.h,
+ * "mesh material maps"), through the hit_material the material-mapped scenes' render kernels call (the form over the textured
+ * mesh-light tables), before the max(roughness, 0.01) every material gets: rays_dev, out_dev and `flags` exactly as for
+ * rpt_debug_mesh_normal_map_query — per ray {the winning triangle's flattened index or 0xFFFFFFFF, mat.roughness' bits,
+ * mat.metallic's bits, 0} (zeros when nothing is hit), RPT_MESH_QUERY_BRUTE or 0.  RPT_ERR_NO_SCENE unless the uploaded scene has
+ * meshes; RPT_ERR_INVALID_ARG while no map is ON (those kernels do not run then). */
+int rpt_debug_mesh_material_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
+
+/* Which mesh render form the context's first device's last launch took: 0 .. 11 the twelve forms of csrc/mesh_args.h in MeshForm's
+ * order (nrm_cut_env, nrm_cut, nrm_env, nrm, cut_env, cut, env, light_tex, tex, light, smooth, flat), 12 .. 19 a material map over
+ * the eight textured forms that hold every table (csrc/mesh_args_mmap.h: light_tex, env, cut, cut_env, nrm, nrm_env, nrm_cut,
+ * nrm_cut_env); 0xFFFFFFFF when that launch was no mesh scene's or there was none.  rpt_debug_kernel_choice has no bit left for
+ * material maps and keeps its meaning: bits 26-31 say which of the other features are present. */
+int rpt_debug_mesh_form(rpt_ctx* ctx, uint32_t* form);
+
 /* The lookup of the environment (include/rpt.h, "environment lighting"), through the device function the miss exit of the environment
  * scenes' render kernel calls: dirs_dev = n x 3 floats, one direction each (taken as given: not normalised); out_dev = n x 5 dwords
  * {the texel k or 0xFFFFFFFF, the radiance's three words, lp as bits: the pdf the sampler has for that direction, 0 where the miss

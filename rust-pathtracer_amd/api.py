@@ -648,6 +648,50 @@ class Tracer:
         check(lib().rpt_download_mesh_normal_map(self._h, int(m), out.ctypes.data, int(width), int(height)), self._h)
         return out
 
+    def set_mesh_material_maps(self, items):
+        """Mesh material maps (include/rpt.h, "mesh material maps"): `items` maps a mesh's index in scene().meshes to None — the mesh
+        loses its map — or to a (height, width, 4) uint8 RGBA map with row 0 at t = 0, or to a dict with "texels" (that array) and
+        optionally "filter" ("bilinear" / "nearest"), "roughness_channel" (0 .. 3 or None, default 1) and "metallic_channel" (default
+        2: glTF's metallicRoughness texture).  The map is looked up through the mesh's texture UVs and wrap at every hit and scales
+        the material's roughness and metallic, so the mesh must be textured.  Meshes not named keep their map; upload_scene() drops
+        every map, as in C."""
+        filters = {"nearest": _abi.RPT_TEX_FILTER_NEAREST, "bilinear": _abi.RPT_TEX_FILTER_BILINEAR}
+        items = sorted(items.items())
+        its = (_abi.rpt_mesh_material_map * max(1, len(items)))()
+        keep = []
+        for it, (m, mm) in zip(its, items):
+            it.mesh, it.mode = int(m), _abi.RPT_MESH_MATERIAL_MAP_OFF
+            it.roughness_channel = it.metallic_channel = _abi.RPT_MATERIAL_MAP_CHANNEL_NONE
+            if mm is None:
+                continue
+            if not isinstance(mm, dict):
+                mm = {"texels": mm}
+            filt = mm.get("filter", "bilinear")
+            if filt not in filters:
+                raise ValueError("mesh %d: filter must be \"nearest\" or \"bilinear\", not %r" % (m, filt))
+            texels = np.ascontiguousarray(mm["texels"], dtype=np.uint8)
+            if texels.ndim != 3 or texels.shape[2] != 4:
+                raise ValueError("mesh %d: texels must have the shape (height, width, 4)" % m)
+            keep.append(texels)
+            it.mode, it.filter = _abi.RPT_MESH_MATERIAL_MAP_ON, filters[filt]
+            for name, default in (("roughness_channel", 1), ("metallic_channel", 2)):
+                c = mm.get(name, default)
+                setattr(it, name, _abi.RPT_MATERIAL_MAP_CHANNEL_NONE if c is None else int(c) & 0xFFFFFFFF)
+            it.height, it.width, it.texels = texels.shape[0], texels.shape[1], texels.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._checked_move(lib().rpt_set_mesh_material_maps(self._h, its, len(items)))
+        sizes = self.__dict__.setdefault("_material_map_sizes", {})
+        for it, (m, mm) in zip(its, items):
+            sizes[int(m)] = (it.width, it.height)
+
+    def mesh_material_map(self, m, width=None, height=None):
+        """The decoded texels the context holds for the material-mapped mesh `m` (rpt_download_mesh_material_map): a new float32 array
+        of shape (height, width, 4), {fr, fm, 0, 0}.  Without a size: the one set_mesh_material_maps last gave the mesh."""
+        if width is None or height is None:
+            width, height = self.__dict__.get("_material_map_sizes", {}).get(int(m), (0, 0))
+        out = np.empty((int(height), int(width), 4), np.float32)
+        check(lib().rpt_download_mesh_material_map(self._h, int(m), out.ctypes.data, int(width), int(height)), self._h)
+        return out
+
     def _refresh_stale_meshes(self):
         """scene().meshes' vertex arrays that a device-source call left stale, read back once (only before an upload)."""
         for m in sorted(self._stale_meshes):

@@ -23,6 +23,7 @@
 #include "host_cut.h"
 #include "host_env.h"
 #include "host_light.h"
+#include "host_mmap.h"
 #include "host_move.h"
 #include "host_nrm.h"
 #include "host_refit.h"
@@ -35,11 +36,13 @@
 #include "launch_cut.h"
 #include "launch_env.h"
 #include "launch_light.h"
+#include "launch_mmap.h"
 #include "launch_move.h"
 #include "launch_nrm.h"
 #include "launch_smooth.h"
 #include "launch_tex.h"
 #include "mesh_args.h"
+#include "mesh_args_mmap.h"
 #ifdef RPT_TEST_HOOKS
 #include "../../include/rpt_test.h"
 #endif
@@ -72,6 +75,7 @@ struct DevState {
     void* env = nullptr;              // the environment's tables (host_env.h, EnvLayout): while one is set (rpt_set_environment)
     void* cut = nullptr;              // mesh cutouts' tables (host_cut.h, CutLayout): while some mesh's cutout is ON (rpt_set_mesh_cutouts)
     void* nrm = nullptr;              // mesh normal maps' tables (host_nrm.h, NrmLayout): while some mesh's map is ON (rpt_set_mesh_normal_maps)
+    void* mmap = nullptr;             // mesh material maps' tables (host_mmap.h, MmapLayout): while some mesh's map is ON (rpt_set_mesh_material_maps)
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -92,6 +96,7 @@ struct DevState {
     // cost, 1 of order, 1 of sorting scratch, 4 of start stamps (development), then the hand-off words (SchedLayout)
     uint32_t* sched = nullptr;        // the tables of the CURRENT launch shape (an entry of sched_cache)
     uint32_t last_choice = 0;         // the last launch's KernelChoice as bits (include/rpt_test.h, rpt_debug_kernel_choice)
+    uint32_t last_form = 0xFFFFFFFFu; // the last launch's mesh form (mesh_args_mmap.h, mesh_form_ext_of; include/rpt_test.h, rpt_debug_mesh_form), 0xFFFFFFFF: none
     uint32_t sched_tiles = 0;
     uint64_t sched_launches = 0;      // launches since the order was last started from scratch (the costs are re-sorted after the 1st, 2nd, 4th, ...)
     // A context that alternates between launch shapes (a viewer's preview and full frames, bench.py's legs, one rank's tile and the
@@ -122,6 +127,7 @@ struct rpt_ctx {
     rpthost::EnvPlan env;             // its environment's size, mode and scale, and Q as the devices computed it (host_env.h)
     rpthost::CutPlan cut;             // which of its meshes have a cutout and where each one's mask lies on every device (host_cut.h)
     rpthost::NrmPlan nrm;             // which of its meshes have a normal map and where each one's texels lie on every device (host_nrm.h)
+    rpthost::MmapPlan mmap;           // which of its meshes have a material map and where each one's texels lie on every device (host_mmap.h)
     // resident ColorBuffer (buffer.rs:6-14): pixels as per-rank tiles + frames
     uint32_t res_w = 0, res_h = 0, res_tile_rows = 0, res_rows_padded = 0;
     uint64_t res_frames = 0;
@@ -309,6 +315,7 @@ static void free_mesh_work(DevState& d)
     if (d.env) { (void)hipFree(d.env); d.env = nullptr; }
     if (d.cut) { (void)hipFree(d.cut); d.cut = nullptr; }
     if (d.nrm) { (void)hipFree(d.nrm); d.nrm = nullptr; }
+    if (d.mmap) { (void)hipFree(d.mmap); d.mmap = nullptr; }
     d.refit_full = false;
     d.build_temp_bytes = 0;
 }
@@ -475,6 +482,17 @@ static hipError_t launch_mesh_form(const rptargs::MeshView& view, const SceneMes
     return launcher(s, rp, grid, stream);
 }
 
+// One material-mapped render form (mesh_args_mmap.h), likewise.
+template <class S, class Launcher>
+static hipError_t launch_mesh_map_form(const rptargs::MeshView& view, const rptargs::MmapView& maps, const SceneMesh& scm, Launcher launcher, const RenderParams& rp,
+                                       uint32_t grid, hipStream_t stream)
+{
+    S s = rptargs::mesh_map_scene_of<S>(view, maps);
+    s.cam = scm.cam;
+    s.flags = scm.flags;
+    return launcher(s, rp, grid, stream);
+}
+
 // One render launch sequence on one device.
 static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t width, uint32_t height, uint64_t frames_done, uint32_t spp,
                          uint64_t seed, uint32_t flags, uint32_t tile_rows, uint32_t rank, uint32_t world, hipStream_t stream)
@@ -495,6 +513,7 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     const bool environment = kind == SceneKind::mesh && d.env && d.refit && ctx->env.any();       // an environment is set: k_env.hip's one form, over all of the above
     const bool cutouts = kind == SceneKind::mesh && d.cut && d.tex && d.refit && ctx->cut.any();  // some mesh's cutout is ON: k_cut.hip's forms, over the textured mesh-light form or the environment's
     const bool normal_maps = kind == SceneKind::mesh && d.nrm && d.tex && d.refit && ctx->nrm.any();   // some mesh's normal map is ON: k_nrm.hip's forms, over the four above that hold every table
+    const bool material_maps = kind == SceneKind::mesh && d.mmap && d.tex && d.refit && ctx->mmap.any();   // some mesh's material map is ON: k_mmap.hip's forms, over the eight textured forms that hold every table
     scs.cam = scl.cam = scm.cam = make_camera(ctx->scene.camera, (float)width, (float)height);
     const bool in_hbm = kind == SceneKind::large || kind == SceneKind::mesh;     // the scene's tables are in device memory
     const bool has_sdf = !in_hbm && scs.sdf.n_prims > 0;
@@ -558,11 +577,27 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
                         (media ? 1u << 24 : 0u) | (kind == SceneKind::mesh ? 1u << 25 : 0u) |
                         (smooth ? 1u << 26 : 0u) | (lights ? 1u << 27 : 0u) | (textured ? 1u << 28 : 0u) |
                         (environment ? 1u << 29 : 0u) | (cutouts ? 1u << 30 : 0u) | (normal_maps ? 1u << 31 : 0u);
+        // (material maps have no bit: the mesh form says it — 12 .. 19, include/rpt_test.h, rpt_debug_mesh_form)
+        d.last_form = kind == SceneKind::mesh ? rptargs::mesh_form_ext_of(smooth, lights, textured, environment, cutouts, normal_maps, material_maps) : 0xFFFFFFFFu;
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
         if (kind == SceneKind::mesh) {
             using rptargs::MeshForm;
             const rptargs::MeshView view = mesh_view_of(ctx, d);
+            if (d.last_form >= rptargs::kMeshFormMapFirst) {
+                using rptargs::MeshMapForm;
+                const rptargs::MmapView maps{d.mmap, ctx->mmap};
+                switch ((MeshMapForm)d.last_form) {
+                case MeshMapForm::light_tex: return launch_mesh_map_form<SceneMeshMap>(view, maps, scm, rptlaunch::render_mesh_map, rp, grid, stream);
+                case MeshMapForm::env: return launch_mesh_map_form<SceneMeshMapEnv>(view, maps, scm, rptlaunch::render_mesh_map_env, rp, grid, stream);
+                case MeshMapForm::cut: return launch_mesh_map_form<SceneMeshMapCut>(view, maps, scm, rptlaunch::render_mesh_map_cut, rp, grid, stream);
+                case MeshMapForm::cut_env: return launch_mesh_map_form<SceneMeshMapCutEnv>(view, maps, scm, rptlaunch::render_mesh_map_cut_env, rp, grid, stream);
+                case MeshMapForm::nrm: return launch_mesh_map_form<SceneMeshMapNrm>(view, maps, scm, rptlaunch::render_mesh_map_nrm, rp, grid, stream);
+                case MeshMapForm::nrm_env: return launch_mesh_map_form<SceneMeshMapNrmEnv>(view, maps, scm, rptlaunch::render_mesh_map_nrm_env, rp, grid, stream);
+                case MeshMapForm::nrm_cut: return launch_mesh_map_form<SceneMeshMapNrmCut>(view, maps, scm, rptlaunch::render_mesh_map_nrm_cut, rp, grid, stream);
+                case MeshMapForm::nrm_cut_env: return launch_mesh_map_form<SceneMeshMapNrmCutEnv>(view, maps, scm, rptlaunch::render_mesh_map_nrm_cut_env, rp, grid, stream);
+                }
+            }
             switch (rptargs::mesh_form_of(smooth, lights, textured, environment, cutouts, normal_maps)) {
             case MeshForm::nrm_cut_env: return launch_mesh_form<SceneMeshNrmCutEnv>(view, scm, rptlaunch::render_mesh_nrm_cut_env, rp, grid, stream);
             case MeshForm::nrm_cut: return launch_mesh_form<SceneMeshNrmCut>(view, scm, rptlaunch::render_mesh_nrm_cut, rp, grid, stream);
@@ -959,6 +994,7 @@ static void commit_scene(rpt_ctx* ctx, SceneImage& img, const std::vector<void*>
     ctx->env = rpthost::EnvPlan();                                  // no environment
     ctx->cut = rpthost::CutPlan();                                  // every cutout OFF
     ctx->nrm = rpthost::NrmPlan();                                  // every normal map OFF
+    ctx->mmap = rpthost::MmapPlan();                                // every material map OFF
 }
 
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
@@ -993,6 +1029,7 @@ static void drop_scene(rpt_ctx* ctx)
     ctx->env = rpthost::EnvPlan();
     ctx->cut = rpthost::CutPlan();
     ctx->nrm = rpthost::NrmPlan();
+    ctx->mmap = rpthost::MmapPlan();
 }
 
 // Where the named meshes' new positions come from: host arrays (rpt_update_meshes, rpt_rebuild_meshes) or device arrays through a
@@ -1689,6 +1726,17 @@ static int nrm_desc_device(rpt_ctx* ctx, DevState& d)
     return RPT_OK;
 }
 
+// The material maps' descriptors of device d again, likewise (host_mmap.h, mmap_desc_table): after a texture call, and inside
+// rpt_set_mesh_material_maps.
+static int mmap_desc_device(rpt_ctx* ctx, DevState& d)
+{
+    const rpthost::MmapPlan& mp = ctx->mmap;
+    const rpthost::MmapLayout ml = mp.layout();
+    const std::vector<uint32_t> desc = rpthost::mmap_desc_table(mp, ctx->tex);
+    if (!desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(static_cast<unsigned char*>(d.mmap) + ml.off_desc, desc.data(), 4 * desc.size(), hipMemcpyHostToDevice));
+    return RPT_OK;
+}
+
 // ---- rpt_set_mesh_textures / rpt_download_mesh_texture (include/rpt.h, "mesh textures") -------------------------------------------
 // One device's part: wait for its earlier work (a launch may still read the old tables), make its refit tables if it has none, make
 // the new tables, copy the kept meshes' texels over from the old ones on the device, decode the named meshes' images, drop the old
@@ -1769,6 +1817,11 @@ int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t 
             set_err(ctx, "rpt_set_mesh_textures: mesh %u has a normal map, which reads its texture's UVs and wrap: remove the normal map first (rpt_set_mesh_normal_maps)", m);
             return RPT_ERR_INVALID_ARG;
         }
+    for (uint32_t m = 0; m < image.size(); ++m)                     // include/rpt.h, "mesh material maps": the map reads the texture's UVs and wrap
+        if (image[m].width == 0u && ctx->mmap.on(m)) {
+            set_err(ctx, "rpt_set_mesh_textures: mesh %u has a material map, which reads its texture's UVs and wrap: remove the material map first (rpt_set_mesh_material_maps)", m);
+            return RPT_ERR_INVALID_ARG;
+        }
     if (n_items == 0) return RPT_OK;
     bool any = false;
     for (const TexImage& im : image) any = any || im.width != 0u;
@@ -1801,6 +1854,7 @@ int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t 
         else rc_dev = tex_device(ctx, d, old, items, n_items);
         if (rc_dev == RPT_OK && d.cut && ctx->cut.any()) rc_dev = cut_desc_device(ctx, d);      // the ordinals or a wrap may have changed
         if (rc_dev == RPT_OK && d.nrm && ctx->nrm.any()) rc_dev = nrm_desc_device(ctx, d);
+        if (rc_dev == RPT_OK && d.mmap && ctx->mmap.any()) rc_dev = mmap_desc_device(ctx, d);
     }
     if (rc_dev != RPT_OK) {
         const std::string first = ctx->err;
@@ -2202,6 +2256,127 @@ int rpt_download_mesh_normal_map(rpt_ctx* ctx, uint32_t mesh, float* texels, uin
     return RPT_OK;
 }
 
+// ---- rpt_set_mesh_material_maps / rpt_download_mesh_material_map (include/rpt.h, "mesh material maps") -----------------------------
+// One device's part, as nrm_device: wait for its earlier work (a launch may still read the old tables), make the new tables, copy the
+// kept meshes' texels over from the old ones on the device, decode the named meshes' maps, write the descriptors, drop the old
+// tables, and wait.  ctx->mmap is already the new plan; `old` is the plan the old tables were made by.
+static int mmap_device(rpt_ctx* ctx, DevState& d, const rpthost::MmapPlan& old, const rpt_mesh_material_map* items, uint32_t n_items)
+{
+    const rpthost::MmapPlan& mp = ctx->mmap;
+    const rpthost::MmapLayout ml = mp.layout();
+    const rpthost::MmapLayout ol = old.layout();
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    RPT_CHECK_RC(ensure_refit(ctx, d));
+    void* fresh = nullptr;
+    void* stage = nullptr;
+    RPT_HIP_CHECK(ctx, hipMalloc(&fresh, ml.total));
+    size_t stage_bytes = 0;                                         // the named maps' bytes, in one allocation that lives until the decodes have run
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (items[i].mode == RPT_MESH_MATERIAL_MAP_ON) stage_bytes += ((size_t)items[i].width * items[i].height * 4 + 15) & ~(size_t)15;
+    const auto fail = [&](int rc) { (void)hipFree(fresh); if (stage) (void)hipFree(stage); return rc; };
+    const auto work = [&]() -> int {
+        if (stage_bytes) RPT_HIP_CHECK(ctx, hipMalloc(&stage, stage_bytes));
+        unsigned char* base = static_cast<unsigned char*>(fresh);
+        rpthost::TexTexel* texels = reinterpret_cast<rpthost::TexTexel*>(base + ml.off_texels);
+        RPT_HIP_CHECK(ctx, hipMemsetAsync(base, 0, ml.off_none, d.stream));
+        if (ml.off_texels > ml.off_none) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + ml.off_none, 0xFF, ml.off_texels - ml.off_none, d.stream));
+        std::vector<uint8_t> named(mp.map.size(), 0);
+        size_t at = 0;
+        for (uint32_t i = 0; i < n_items; ++i) {
+            const rpt_mesh_material_map& it = items[i];
+            named[it.mesh] = 1;
+            if (it.mode != RPT_MESH_MATERIAL_MAP_ON) continue;
+            const rpthost::MmapMap& c = mp.map[it.mesh];
+            const size_t n = (size_t)c.width * c.height;
+            uint8_t* at_dev = static_cast<uint8_t*>(stage) + at;
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(at_dev, it.texels, 4 * n, hipMemcpyHostToDevice, d.stream));
+            RPT_HIP_CHECK(ctx, rptlaunch::mmap_decode(at_dev, texels + c.first, (uint32_t)n, c.roughness_channel, c.metallic_channel, d.stream));
+            at += (4 * n + 15) & ~(size_t)15;
+        }
+        for (uint32_t m = 0; m < mp.map.size(); ++m) {
+            if (named[m] || !mp.map[m].width) continue;             // a mesh not named keeps its map: the decoded texels move on the device
+            if (!d.mmap || !old.on(m)) { set_err(ctx, "rpt_set_mesh_material_maps: device %d holds no texels for mesh %u", d.device, m); return RPT_ERR_HIP; }
+            const size_t n = (size_t)mp.map[m].width * mp.map[m].height;
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(texels + mp.map[m].first,
+                                              reinterpret_cast<const rpthost::TexTexel*>(static_cast<const unsigned char*>(d.mmap) + ol.off_texels) + old.map[m].first,
+                                              16 * n, hipMemcpyDeviceToDevice, d.stream));
+        }
+        RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+        return RPT_OK;
+    };
+    const int rc = work();
+    if (rc != RPT_OK) return fail(rc);
+    if (stage) (void)hipFree(stage);
+    if (d.mmap) (void)hipFree(d.mmap);
+    d.mmap = fresh;
+    return mmap_desc_device(ctx, d);
+}
+
+int rpt_set_mesh_material_maps(rpt_ctx* ctx, const rpt_mesh_material_map* items, uint32_t n_items)
+{
+    using namespace rpthost;
+    if (!ctx) { set_err(nullptr, "rpt_set_mesh_material_maps: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    std::vector<MmapMap> map;
+    std::string why;
+    const int rc = check_mesh_material_maps(ctx->refit, ctx->scene.kind == SceneKind::mesh, ctx->tex, items, n_items, ctx->mmap.map, map, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    if (n_items == 0) return RPT_OK;
+    bool any = false;
+    for (const MmapMap& c : map) any = any || c.width != 0u;
+    if (!any && !ctx->mmap.any()) return RPT_OK;                    // every map OFF, as before
+    DeviceGuard guard(ctx->devs[0].device);
+    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
+    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_material_maps: cannot select device %d", ctx->devs[0].device);
+    if (rc_dev == RPT_OK && !any) {                                 // every map OFF (again): the context is what it was before the first call
+        for (DevState& d : ctx->devs) {
+            if (!d.mmap) continue;
+            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
+                set_err(ctx, "rpt_set_mesh_material_maps: cannot wait for device %d", d.device);
+                rc_dev = RPT_ERR_HIP;
+                break;
+            }
+            (void)hipFree(d.mmap);
+            d.mmap = nullptr;
+        }
+        if (rc_dev == RPT_OK) { ctx->mmap = MmapPlan(); return RPT_OK; }
+    }
+    MmapPlan old;
+    if (rc_dev == RPT_OK) {
+        old = std::move(ctx->mmap);
+        build_mmap_plan(ctx->refit, std::move(map), ctx->mmap);
+    }
+    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
+        DevState& d = ctx->devs[i];
+        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_material_maps: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
+        else rc_dev = mmap_device(ctx, d, old, items, n_items);
+    }
+    if (rc_dev != RPT_OK) {
+        const std::string first = ctx->err;
+        drop_scene(ctx);
+        set_err(ctx, "%s; the context now holds no scene", first.c_str());
+        return rc_dev;
+    }
+    return RPT_OK;
+}
+
+int rpt_download_mesh_material_map(rpt_ctx* ctx, uint32_t mesh, float* texels, uint32_t width, uint32_t height)
+{
+    if (!ctx) { set_err(nullptr, "rpt_download_mesh_material_map: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_mesh_material_map: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    const rpthost::RefitPlan& plan = ctx->refit;
+    if (mesh >= plan.n_meshes()) { set_err(ctx, "rpt_download_mesh_material_map: mesh %u out of range (the scene has %u)", mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
+    const DevState& d = ctx->devs[0];
+    const rpthost::MmapPlan& mp = ctx->mmap;
+    if (!mp.on(mesh) || !d.mmap) { set_err(ctx, "rpt_download_mesh_material_map: mesh %u has no material map: the context holds no texels for it (rpt_set_mesh_material_maps)", mesh); return RPT_ERR_INVALID_ARG; }
+    const rpthost::MmapMap& c = mp.map[mesh];
+    if (width != c.width || height != c.height) { set_err(ctx, "rpt_download_mesh_material_map: mesh %u: %u x %u is not its map's %u x %u", mesh, width, height, c.width, c.height); return RPT_ERR_INVALID_ARG; }
+    if (!texels) { set_err(ctx, "rpt_download_mesh_material_map: texels is NULL"); return RPT_ERR_INVALID_ARG; }
+    RPT_ON_DEVICE(ctx);
+    const rpthost::MmapLayout ml = mp.layout();
+    RPT_HIP_CHECK(ctx, hipMemcpy(texels, static_cast<const unsigned char*>(d.mmap) + ml.off_texels + 16 * (size_t)c.first, 16 * (size_t)c.width * c.height, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
 uint32_t rpt_tile_row_count(uint32_t height, uint32_t tile_rows, uint32_t rank, uint32_t world)
 {
     return tile_row_count(height, tile_rows, rank, world);
@@ -2321,6 +2496,14 @@ int rpt_debug_kernel_choice(rpt_ctx* ctx, uint32_t* out)
 {
     if (!ctx || !out) return RPT_ERR_INVALID_ARG;
     *out = ctx->devs[0].last_choice;
+    return RPT_OK;
+}
+
+// (include/rpt_test.h) the last launch's mesh form: 0 .. 11 a MeshForm of mesh_args.h, 12 .. 19 a material-mapped one (mesh_args_mmap.h)
+int rpt_debug_mesh_form(rpt_ctx* ctx, uint32_t* form)
+{
+    if (!ctx || !form) return RPT_ERR_INVALID_ARG;
+    *form = ctx->devs[0].last_form;
     return RPT_OK;
 }
 
@@ -2827,6 +3010,20 @@ int rpt_debug_mesh_normal_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_
     if (n == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_normal_map_query(rptargs::mesh_scene_of<SceneMeshNrm>(mesh_view_of(ctx, ctx->devs[0])), rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_debug_mesh_material_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_material_map_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_material_map_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    if (!rays_dev || !out_dev || (flags & ~(uint32_t)RPT_MESH_QUERY_BRUTE)) { set_err(ctx, "rpt_debug_mesh_material_map_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->mmap.any() || !ctx->devs[0].mmap || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_material_map_query: no mesh has a material map"); return RPT_ERR_INVALID_ARG; }
+    if (n == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    const DevState& d = ctx->devs[0];
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_material_map_query(rptargs::mesh_map_scene_of<SceneMeshMap>(mesh_view_of(ctx, d), rptargs::MmapView{d.mmap, ctx->mmap}), rays_dev, out_dev, n,
+                                                          flags, (hipStream_t)stream));
     return RPT_OK;
 }
 

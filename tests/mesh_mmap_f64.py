@@ -1,0 +1,76 @@
+"""Mesh material maps (include/rpt.h, "mesh material maps") in float64, over the composed restatement of tests/mesh_compose_f64.py:
+MmapMeshDescScene is ComposedMeshDescScene with one more step at a winning triangle — after the base's patch (which has written the
+textured rgb), roughness *= fr and metallic *= fm, the factors looked up through the TEXTURE's UVs and wrap with the MAP's own filter
+and size by the same tex_lookup, NEAREST margins included.  The decode is k / 255, or exactly 1 for a channel that is None.
+
+`material_maps` is the very dict Tracer.set_mesh_material_maps takes.  One planted fault, factor_on_wrong_field: roughness takes the
+metallic factor and metallic the roughness one.  The scene and the maps the float64 tests use are here as well, so the GPU file and
+the CPU file hand both sides one value."""
+import numpy as np
+
+from mesh_compose_f64 import FILTERS, ComposedMeshDescScene, interp_uv, tex_lookup
+
+OBJECT_METALLIC = 0.7
+
+
+def decode_material_map_f64(rgba, roughness_channel=1, metallic_channel=2):
+    """include/rpt.h's decode in float64: [h, w, 2] = {fr, fm}."""
+    rgba = np.asarray(rgba, np.uint8)
+    out = np.ones(rgba.shape[:2] + (2,))
+    for i, ch in enumerate((roughness_channel, metallic_channel)):
+        if ch is not None:
+            out[..., i] = rgba[..., ch] / 255.0
+    return out
+
+
+class MmapMeshDescScene(ComposedMeshDescScene):
+    def __init__(self, desc, scene, material_maps=None, factor_on_wrong_field=False, **composed):
+        super().__init__(desc, scene, **composed)
+        self.factor_on_wrong_field = factor_on_wrong_field
+        self.mmaps = {}
+        for m, mm in (material_maps or {}).items():
+            assert m in self.tex, "a material map needs the mesh's UVs (include/rpt.h, \"mesh material maps\": Composition)"
+            mm = mm if isinstance(mm, dict) else {"texels": mm}
+            self.mmaps[m] = (decode_material_map_f64(mm["texels"], mm.get("roughness_channel", 1), mm.get("metallic_channel", 2)),
+                             FILTERS[mm.get("filter", "bilinear")])
+
+    def patch(self, m, d, hp, mat, mut, M):
+        won = self._won                                               # (the base's patch consumes it)
+        super().patch(m, d, hp, mat, mut, M)
+        if won is None:
+            return
+        k, u, v = won
+        mesh = int(self.tri_mesh[k])
+        if mesh not in self.mmaps:
+            return
+        texels, filt = self.mmaps[mesh]
+        fr, fm = (float(x) for x in tex_lookup(texels, *interp_uv(self, k, u, v), self.tex[mesh][1], filt, M))
+        if self.factor_on_wrong_field:
+            fr, fm = fm, fr
+        mat.roughness = mat.roughness * fr
+        mat.metallic = mat.metallic * fm
+
+
+def scene():
+    """test_gpu_mesh_compose_f64's scene with a metallic object: both factors change what a path sees."""
+    from rust_pathtracer_amd import scenes
+    from test_gpu_mesh_compose_f64 import _scene
+    s = _scene()
+    s.materials[0] = scenes.full_material(rgb=(0.8, 0.3, 0.25), roughness=0.9, metallic=OBJECT_METALLIC)
+    return s
+
+
+def noise_map(w=16, h=16, seed=77):
+    """A strongly varying map whose two channels disagree: G is noise, B = 255 - G."""
+    m = np.random.default_rng(seed).integers(0, 256, (h, w, 4), dtype=np.uint8)
+    m[..., 2] = 255 - m[..., 1]
+    return m
+
+
+def material_maps(identity=False):
+    """The maps of the float64 cases: mesh 0 (the object) BILINEAR over the noise map, mesh 1 (the lamp) NEAREST over another, its
+    roughness channel R and no metallic channel.  identity: all-255 maps of the same sizes and filters."""
+    a, b = noise_map(16, 16, 77), noise_map(5, 3, 78)
+    if identity:
+        a, b = np.full_like(a, 255), np.full_like(b, 255)
+    return {0: dict(texels=a, filter="bilinear"), 1: dict(texels=b, filter="nearest", roughness_channel=0, metallic_channel=None)}
