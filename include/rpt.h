@@ -164,7 +164,25 @@ typedef struct rpt_background {
  * found by sphere marching from t = 0:  p = o + t*d;  hit when sdf(p) < hit_eps * t;  t += sdf(p);
  * miss after max_steps steps or when t > max_t.  Normal = normalised tetrahedral gradient with step
  * normal_eps.  The object is tested AFTER the spheres and planes (accepted when nearer) and counts as
- * an occluder in any_hit.  All arithmetic is f32 in the order written in oracle/rpt_oracle.hpp. */
+ * an occluder in any_hit.  All arithmetic is f32, in exactly this order (tests/media_sdf_f64.py restates it from this text):
+ *   Primitives, with q = p - center:
+ *     sphere        length(q) - r                                  (length = sqrt(q.x*q.x + q.y*q.y + q.z*q.z), fx.rs)
+ *     torus about y sqrt(qx*qx + q.y*q.y) - r_minor,   qx = sqrt(q.x*q.x + q.z*q.z) - R
+ *   Fold, left to right from primitive 0 (a = the running value, b = the next primitive's; one primitive: no fold):
+ *     h = max(k - |a - b|, 0) * (1/k);   m = a < b ? a : b;   a = m - h*h*k*0.25       (products left to right)
+ *   March:  t = 0;  at most max_steps times:
+ *     1. dist = sdf(o + t*d)                                       (o + t*d = origin + direction * t, ray.rs)
+ *     2. if dist < hit_eps * t: a hit at t        (at t = 0 that is dist < 0: an origin inside the object hits at t = 0)
+ *     3. t = t + dist
+ *     4. if t > max_t: a miss
+ *     and a miss when the steps run out.
+ *   Normal at p:  n = sdf(p + e*k0)*k0 + sdf(p + e*k1)*k1 + sdf(p + e*k2)*k2 + sdf(p + e*k3)*k3, summed in that order, with
+ *     e = normal_eps and k0..k3 = (1,-1,-1), (-1,-1,1), (-1,1,-1), (1,1,1);  then n / length(n).
+ *   closest_hit:  after the last plane, with `first` and `dist` as the spheres and planes left them (first: no primitive was tested yet,
+ *     whether or not one was hit): a hit of the march at t is accepted when first || t < dist; then state.hit_dist = t, state.normal =
+ *     the normal at o + t*d, the material patch `material` is applied, dist = t.  After it come Scene::sample_lights.
+ *   any_hit:  the object goes last; a hit of the march at t occludes under the scene's rule (RPT_SCENE_ANYHIT_USES_MAX_DIST: only when
+ *     t < max_dist). */
 enum { RPT_SDF_SPHERE = 0, RPT_SDF_TORUS_Y = 1 };
 
 typedef struct rpt_sdf_prim {
@@ -218,7 +236,9 @@ enum {                                /* rpt_scene_desc.flags */
  *                    throughput *= color;
  *                    next-event estimation from p exactly as direct_light (tracer.rs:126-170) with scatter_pos = p (no
  *                    offset) and the phase function in place of the BSDF: f = pdf = phase_hg(dot(-ray.direction,
- *                    light.direction), g), same MIS weight, same `pdf > 0` guard;
+ *                    light.direction), g), same MIS weight, same `pdf > 0` guard;  * the unoccluded light's `li` is
+ *                    attenuated over light_sample.dist exactly as in step 3 (the scatter point lies inside the medium: the medium is
+ *                    both the phase function and what the light crosses), the max_dist of the shadow ray is dist - eps as always;
  *                    two draws r1, r2;  dir = sample_hg(-ray.direction, g, r1, r2);  scatter_sample.pdf =
  *                    phase_hg(dot(-ray.direction, dir), g);  scatter_sample.l = dir;  ray = Ray(p, dir)  (no eps offset);
  *                    then Russian roulette as after a surface bounce, and the next iteration.  The iteration counts

@@ -470,6 +470,38 @@ void oracle_sample_hg(const float* v, float g, float r1, float r2, float* out)
     F3 d = Tracer::sample_hg(F3(v[0], v[1], v[2]), g, r1, r2);
     out[0] = rawf(d.x); out[1] = rawf(d.y); out[2] = rawf(d.z);
 }
+// ... and a medium's transmittance over `dist` (color: three floats).
+void oracle_medium_transmittance(uint32_t medium_type, float density, const float* color, float dist, float* out)
+{
+    Medium md;
+    md.medium_type = medium_type;
+    md.density = density;
+    md.color = F3(color[0], color[1], color[2]);
+    F3 t = Tracer::medium_transmittance(md, dist);
+    out[0] = rawf(t.x); out[1] = rawf(t.y); out[2] = rawf(t.z);
+}
+
+// SDF object leaves (PROJECT-DEFINED, include/rpt.h, rpt_sdf): the distance, the march and the normal of an object on its own.
+static Scene sdf_alone(const rpt_sdf* sdf)
+{
+    rpt_scene_desc d;
+    std::memset(&d, 0, sizeof(d));
+    d.sdf = *sdf;
+    return Scene(d);
+}
+float oracle_sdf_eval(const rpt_sdf* sdf, const float* p) { return rawf(sdf_alone(sdf).sdf_eval(F3(p[0], p[1], p[2]))); }
+int oracle_sdf_march(const rpt_sdf* sdf, const float* o, const float* d, float* t)
+{
+    F tt(0.0f);
+    bool hit = sdf_alone(sdf).sdf_march(Ray(F3(o[0], o[1], o[2]), F3(d[0], d[1], d[2])), tt);
+    *t = rawf(tt);
+    return hit ? 1 : 0;
+}
+void oracle_sdf_normal(const rpt_sdf* sdf, const float* p, float* out)
+{
+    F3 n = sdf_alone(sdf).sdf_normal(F3(p[0], p[1], p[2]));
+    out[0] = rawf(n.x); out[1] = rawf(n.y); out[2] = rawf(n.z);
+}
 
 // ColorBuffer::convert_to_u8, buffer.rs:55-64: (p.powf(0.4545) * 255.0) as u8 for
 // r,g,b and (a * 255.0) as u8; Rust's `as u8` saturates and maps NaN to 0.

@@ -181,6 +181,46 @@ class Oracle:
                                       counter, out.ctypes.data)
         return out
 
+    def phase_hg(self, cos_theta, g):
+        self.lib.oracle_phase_hg.restype = C.c_float
+        self.lib.oracle_phase_hg.argtypes = [C.c_float, C.c_float]
+        return self.lib.oracle_phase_hg(cos_theta, g)
+
+    def sample_hg(self, v, g, r1, r2):
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        out = np.zeros(3, dtype=np.float32)
+        self.lib.oracle_sample_hg.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]
+        self.lib.oracle_sample_hg(v.ctypes.data, g, r1, r2, out.ctypes.data)
+        return out
+
+    def medium_transmittance(self, medium_type, density, color, dist):
+        color = np.ascontiguousarray(color, dtype=np.float32)
+        out = np.zeros(3, dtype=np.float32)
+        self.lib.oracle_medium_transmittance.argtypes = [C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p]
+        self.lib.oracle_medium_transmittance(medium_type, density, color.ctypes.data, dist, out.ctypes.data)
+        return out
+
+    def sdf_eval(self, sdf, p):
+        """sdf: an rpt_sdf (a scene description's .sdf)."""
+        p = np.ascontiguousarray(p, dtype=np.float32)
+        self.lib.oracle_sdf_eval.restype = C.c_float
+        self.lib.oracle_sdf_eval.argtypes = [C.c_void_p, C.c_void_p]
+        return self.lib.oracle_sdf_eval(C.byref(sdf), p.ctypes.data)
+
+    def sdf_march(self, sdf, o, d):
+        o, d = (np.ascontiguousarray(v, dtype=np.float32) for v in (o, d))
+        t = C.c_float(0)
+        self.lib.oracle_sdf_march.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        hit = self.lib.oracle_sdf_march(C.byref(sdf), o.ctypes.data, d.ctypes.data, C.byref(t))
+        return bool(hit), t.value
+
+    def sdf_normal(self, sdf, p):
+        p = np.ascontiguousarray(p, dtype=np.float32)
+        out = np.zeros(3, dtype=np.float32)
+        self.lib.oracle_sdf_normal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self.lib.oracle_sdf_normal(C.byref(sdf), p.ctypes.data, out.ctypes.data)
+        return out
+
     def rng_u32(self, seed, frame, pixel, n):
         out = np.zeros(n, dtype=np.uint32)
         self.lib.oracle_rng_u32(seed, frame, pixel, n, out.ctypes.data)

@@ -41,7 +41,8 @@ Project-defined semantics (include/rpt.h, not the reference), restated from the 
     normalize(scatter_pos - position) is taken (the one statement not from the header), and the light-types scene keeps the facing
     test of that light far from its edge, so the comparison does not rest on it;
   * a non-finite sample is blended as black (render-level; oracle_sample_pixels reports the raw radiance).
-Media, the SDF object and the denoiser are out of scope here (tests/test_oracle_media.py, tests/dn_f64.py have their own).
+Media and the SDF object are restated on top of this file by tests/media_sdf_f64.py (DescScene refuses a description that has
+either); the denoiser is out of scope here (tests/dn_f64.py).
 
 Outputs of sample(): the radiance (three doubles), the rays it queried in oracle_sample_rays' layout ({o, d, max_dist}, max_dist =
 -1 for closest_hit), and the smallest relative BRANCH MARGIN over every comparison the sample took: how far (relatively) the two
@@ -72,7 +73,7 @@ MAT_RGB, MAT_EMISSION, MAT_ANISOTROPIC, MAT_METALLIC, MAT_ROUGHNESS, MAT_SUBSURF
 PROC_CHECKER_DIR = 1
 LIGHT_RECTANGULAR, LIGHT_SPHERICAL, LIGHT_DISTANT = 0, 1, 2
 BG_CONSTANT, BG_GRADIENT_Y = 0, 1
-SCENE_ANYHIT_USES_MAX_DIST, SCENE_SAMPLE_ALL_LIGHT_TYPES = 1, 2
+SCENE_ANYHIT_USES_MAX_DIST, SCENE_SAMPLE_ALL_LIGHT_TYPES, SCENE_MEDIA = 1, 2, 4
 RENDER_RUSSIAN_ROULETTE = 1 << 5
 
 # Wrong restatements, each a plausible mis-transcription; tests/test_path_f64.py shows that every one is caught.
@@ -685,8 +686,12 @@ class DescScene:
             (MAT_SPECULAR_TINT, "specular_tint"), (MAT_SHEEN, "sheen"), (MAT_SHEEN_TINT, "sheen_tint"), (MAT_CLEARCOAT, "clearcoat"),
             (MAT_CLEARCOAT_GLOSS, "clearcoat_gloss"), (MAT_SPEC_TRANS, "spec_trans"), (MAT_IOR, "ior")]
 
+    MEDIA_AND_SDF = False                           # tests/media_sdf_f64.py's scene class restates them; this one does not
+
     def __init__(self, desc):
         v3 = lambda a: (float(a[0]), float(a[1]), float(a[2]))              # noqa: E731
+        if not self.MEDIA_AND_SDF and (int(desc.flags) & SCENE_MEDIA or int(desc.sdf.n_prims) > 0):
+            raise ValueError("a description with RPT_SCENE_MEDIA or an SDF object: restate it with media_sdf_f64.MediaSdfDescScene")
         self.flags = int(desc.flags)
         self.cam = (v3(desc.camera.origin), v3(desc.camera.center), float(desc.camera.fov_deg))
         bg = desc.background

@@ -789,11 +789,9 @@ def test_random_large_scenes_match_oracle_in_both_forms(rpt, oracle, seed):
     t.close()
 
 
-@pytest.mark.parametrize("seed", range(20))
-def test_random_sdf_scenes_match_oracle(rpt, oracle, seed):
-    """Fuzz the SDF object: 1-8 random spheres/tori, any smoothing radius, short and long step budgets, on top of
-    random analytical scenes (including none at all, where the SDF hit is accepted unconditionally, and no
-    lights, where no shadow ray is marched) — in all three kernel forms."""
+def _random_sdf_scene(rpt, seed):
+    """-> (scene, rng, prims): 1-8 random spheres/tori, any smoothing radius, short and long step budgets, on top of a random analytical
+    scene (none at all when seed % 4 == 1, no lights when seed % 4 == 2).  Also tests/test_media_sdf_f64.py's SDF fuzz."""
     A = rpt._abi
     rng = np.random.default_rng(7000 + seed)
     s = _random_small_scene(rpt, rng)
@@ -811,6 +809,15 @@ def test_random_sdf_scenes_match_oracle(rpt, oracle, seed):
     s.sdf = dict(prims=prims, material=int(rng.integers(0, len(s.materials))), smooth_k=float(rng.choice([0.05, 0.35, 1.0])),
                  max_steps=int(rng.choice([1, 7, 48, 200])), hit_eps=float(rng.choice([1e-3, 1e-2])), max_t=float(rng.choice([8.0, 60.0])),
                  normal_eps=float(rng.choice([1e-3, 1e-2])))
+    return s, rng, prims
+
+
+@pytest.mark.parametrize("seed", range(20))
+def test_random_sdf_scenes_match_oracle(rpt, oracle, seed):
+    """Fuzz the SDF object: 1-8 random spheres/tori, any smoothing radius, short and long step budgets, on top of
+    random analytical scenes (including none at all, where the SDF hit is accepted unconditionally, and no
+    lights, where no shadow ray is marched) — in all three kernel forms."""
+    s, rng, prims = _random_sdf_scene(rpt, seed)
     w, h, spp = int(rng.integers(8, 90)), int(rng.integers(8, 60)), int(rng.integers(1, 4))
     want = oracle.render(s.describe(), w, h, spp, seed=seed)
     t = rpt.Tracer(s, device=0, seed=seed)

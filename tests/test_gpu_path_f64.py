@@ -31,9 +31,9 @@ def torch_cuda():
     return torch
 
 
-def _one_sample(rpt, torch, scene, w, h, seed, megakernel, monkeypatch):
+def _one_sample(rpt, torch, scene, w, h, seed, megakernel, monkeypatch, flags=0):
     """A one-sample render into a fresh buffer -> (frame, kernel choice).  megakernel: RPT_COMPACT_MAX_SPP=0, so that the launch takes
-    the class's megakernel instead of the compacting kernel."""
+    the class's megakernel instead of the compacting kernel.  flags: render flags (RPT_RENDER_RUSSIAN_ROULETTE)."""
     from test_gpu_strict_kernels import _render
     if megakernel:
         monkeypatch.setenv("RPT_COMPACT_MAX_SPP", "0")
@@ -41,7 +41,7 @@ def _one_sample(rpt, torch, scene, w, h, seed, megakernel, monkeypatch):
         monkeypatch.delenv("RPT_COMPACT_MAX_SPP", raising=False)
     rpt.lib().rpt_debug_reload_knobs()
     try:
-        return _render(rpt, torch, scene, w, h, (1,), 0, seed=seed)
+        return _render(rpt, torch, scene, w, h, (1,), flags, seed=seed)
     finally:
         monkeypatch.delenv("RPT_COMPACT_MAX_SPP", raising=False)
         rpt.lib().rpt_debug_reload_knobs()
@@ -74,10 +74,17 @@ class Tally:
         assert self.near <= self.near_max * self.n
 
 
-def _compare(rpt, torch, oracle, tally, what, scene, w, h, seed, megakernel, monkeypatch, pixels, klass="small"):
-    frame, choice = _one_sample(rpt, torch, scene, w, h, seed, megakernel, monkeypatch)
+def _compare(rpt, torch, oracle, tally, what, scene, w, h, seed, megakernel, monkeypatch, pixels, klass="small", flags=0, restate=None):
+    """restate(oracle, seed, items, w, h) -> (radiance, margins, ...): another restatement than pt_f64's of scene.describe()
+    (tests/media_sdf_f64.py's); flags: render flags of the launch, which that restatement has to follow."""
+    frame, choice = _one_sample(rpt, torch, scene, w, h, seed, megakernel, monkeypatch, flags)
     tally.ran.add(kernel_of(choice, klass))
-    restated, margins, _ = P.sample_many(P.DescScene(scene.describe()), oracle, seed, [(c, r, 0) for c, r in pixels], w, h)
+    items = [(c, r, 0) for c, r in pixels]
+    if restate is not None:
+        restated, margins = restate(oracle, seed, items, w, h)[:2]
+    else:
+        assert flags == 0
+        restated, margins, _ = P.sample_many(P.DescScene(scene.describe()), oracle, seed, items, w, h)
     tally.add("%s (seed %d, %s)" % (what, seed, kernel_of(choice, klass)), frame, restated, margins, pixels)
     return choice
 
