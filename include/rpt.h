@@ -782,8 +782,8 @@ int rpt_download_mesh_light_table(rpt_ctx* ctx, uint32_t mesh, uint64_t* cdf /* 
  *
  * Scope.  A textured mesh keeps its full-patch material.  At a winning triangle of that mesh only mat.rgb changes:
  *     rgb.c = m.rgb[c] * tex.c                                       c = r, g, b; one product each
- * Emission is never textured.  hit_emission, the sampler of mesh lights and its hit weight, the triangle test, the acceptance
- * order, any_hit and the normals are unchanged.  One texture per mesh, one UV per vertex: a UV seam needs duplicated vertices, as
+ * A texture never touches emission (an emission map does: "mesh emission maps" below).  hit_emission, the sampler of mesh lights and
+ * its hit weight, the triangle test, the acceptance order, any_hit and the normals are unchanged.  One texture per mesh, one UV per vertex: a UV seam needs duplicated vertices, as
  * any OBJ loader produces them.
  *
  * Decode, once per rpt_set_mesh_textures, on the device.  The input is RGBA8, alpha ignored, width * height * 4 bytes, row 0 first.
@@ -1241,6 +1241,114 @@ typedef struct rpt_mesh_material_map {
 
 int rpt_set_mesh_material_maps(rpt_ctx* ctx, const rpt_mesh_material_map* items, uint32_t n_items);
 int rpt_download_mesh_material_map(rpt_ctx* ctx, uint32_t mesh, float* texels /* host, width*height*4 f32, decoded */, uint32_t width, uint32_t height);
+
+/* ---- mesh emission maps — PROJECT-DEFINED ----------------------------------------------------------------------------------------
+ * Per mesh, an emission that varies across the surface: one RGBA8 map, looked up through the mesh's texture UVs, scales the mesh
+ * material's EMISSION — where a path hits the mesh, where the mesh-light sampler picks a point on it, and at the emitter exit.  The
+ * three act together, so the estimator stays unbiased with next-event estimation; the sampler's pdf does not change, so every
+ * multiple-importance weight of the integrator is what it was.  Every operation is stated, so that texels, probed emissions and
+ * frames stay checkable bit for bit (tests/test_gpu_mesh_emission_map.py holds them to a numpy restatement).  The statement is
+ * written once, in csrc/host_emap.h, which the kernels and the host harness both compile; it reuses tex_decode_value, tex_interp,
+ * tex_wrap and tex_lookup of "mesh textures" (csrc/host_tex.h) and does not restate them.  All arithmetic is f32, one rounding per
+ * operation, nothing contracted, with the library's correctly rounded divide and root.
+ *
+ * Scope.  A map is per mesh.  It needs the mesh's texture UVs, as a material map does: an untextured mesh is RPT_ERR_INVALID_ARG (a
+ * 1 x 1 white texture is enough).  It has its own size, its own filter and its own gamma; the wrap is the texture's.
+ *
+ * Decode.  Exactly the decode of "mesh textures", by that section's own launch (no second decode kernel exists): once per call, on
+ * the device, the table L[0 .. 255] of the map's `gamma` — L[0] = 0 and L[255] = 1 by definition, rpt_powf(k / 255, gamma) in
+ * between, k / 255 when gamma == 1 — then one lane per texel.  A decoded texel is four f32, 16 B: {L[R], L[G], L[B], 0}.
+ *
+ * Lookup.  E(u, v; a, b, c) for barycentrics (u, v) over a triangle with corners a, b, c in its own order:
+ *     w = (1 - u) - v;  s = tex_interp(w, u, v, s_a, s_b, s_c);  t = tex_interp(w, u, v, t_a, t_b, t_c)
+ *     E = tex_lookup(the map's decoded texels, W, H, the TEXTURE's wrap, the MAP's filter, s, t)
+ * (s_x, t_x) are the corners' UVs of the mesh's texture, W and H the map's, which need not be the texture's.  There is no clamp,
+ * for the reason "mesh material maps" gives: BILINEAR over texels in [0, 1] stays in [0, 1].  An all-255 map looks up exactly 1 under
+ * either filter and any gamma; any other constant image is returned exactly by NEAREST only.
+ *
+ * Hit side.  At a winning triangle of a mapped mesh, after the base's hit_material has run (after "mesh textures" has written rgb
+ * and "mesh material maps" roughness and metallic):
+ *     mat.emission.c = mat.emission.c * E.c           c = r, g, b; one product each
+ * with E looked up at the triangle test's own (u, v), recomputed from the ray and the triangle row as "mesh textures" does it — the
+ * same operations on the same words — and the corners' UVs read through the refit's slot -> vertex table.  The hit weight w of "mesh
+ * lights" is unchanged.
+ *
+ * Emitter exit.  Where an rpt_light is found in front of the hit, the term the exit adds for the triangle behind it takes the same
+ * value: hit_emission's material emission, then the same product with the same E.
+ *
+ * Sampler side.  For an ON mesh with a map, "sampling an ON mesh" is unchanged except for its emission line: the draws, the
+ * triangle pick, the point, the normal and pdf = dist_sq / (A_tot * |c|) all stay.  With su = sqrt(r1), bu = 1 - su, bv = r2 * su
+ * (the sampler's own three operations, so the bits are the sampled point's) and a, b, c the picked triangle's corners through the
+ * vertex indices the sampler already reads:
+ *     E = E(bu, bv; a, b, c);   e.c = m.emission[c] * E.c;   emission.c = N_f * e.c             the products in this order
+ * A_tot and the CDF stay area-only: moves add no launch and rpt_download_mesh_light_table is unchanged.  (Weighting the triangle
+ * pick by the map's luminance is not done: a map that is dark over most of a mesh makes most samples of it carry no light.)
+ *
+ * Composition.  Emission maps compose with FLAT / SMOOTH, OFF / ON lights, textures of any wrap and filter, material maps, cutouts,
+ * normal maps, and an environment in either mode.  A cutout mesh cannot be a mesh light, so there the map acts on the hit side and
+ * at the emitter exit only.  A mesh whose material emission is 0 renders as without the map.  rpt_set_mesh_textures that would
+ * remove the texture of a mesh whose map is ON is RPT_ERR_INVALID_ARG ("remove the emission map first"); replacing the texture
+ * keeps the map, which then reads the new UVs and wrap.  rpt_set_mesh_lights keeps the maps.  rpt_upload_scene drops all maps.
+ *
+ * rpt_set_mesh_emission_maps sets (ON) or removes (OFF) the map of the named meshes of the uploaded scene; meshes not named keep
+ * theirs.  `texels` is copied inside the call; on return every map is current on every device of the context (one process per GPU:
+ * every rank makes the call).  The checks, in this order, all on the host before any device is touched — a rejected call changes
+ * nothing, and rpt_last_error starts with "rpt_set_mesh_emission_maps: " and names the item:
+ *   RPT_ERR_INVALID_ARG  ctx is NULL;
+ *   RPT_ERR_NO_SCENE     no scene with meshes is uploaded;
+ *   RPT_ERR_INVALID_ARG  items NULL with a non-zero count; then per item, in order: mesh >= n_meshes, or a mesh named twice; mode
+ *                        neither constant; ON with width or height 0 or above 16384; ON with texels NULL; filter not a constant; ON
+ *                        with a gamma that is not finite, not above 0 or above 16; OFF with a non-zero size or a non-NULL texels;
+ *                        ON on an untextured mesh;
+ *   RPT_ERR_UNSUPPORTED  all maps together would hold more than 2^26 texels;
+ *   RPT_OK               n_items == 0: nothing is done;
+ *   RPT_ERR_HIP          a runtime call failed part-way: the context is left with NO scene, as for the other mesh calls.
+ * While some map is ON the scene renders through a kernel of its own — the mesh kernel's body with the three functions above, one
+ * form over each of the eight material-mapped forms, picked by (normal maps, cutouts, environment) as those are.  A scene with no
+ * material map ON takes them through an all-zero material-map descriptor table carried in the emission maps' own allocation ("no map
+ * on this mesh" for every mesh).  Turning every map OFF leaves the context rendering through exactly the kernels and tables it had
+ * before the first call.
+ *
+ * Moves.  rpt_update_meshes, rpt_rebuild_meshes and both _device forms leave maps alone and add no launch: the hit side reads the
+ * triangle row the walk tested, the refit's slot -> vertex table and the flattened triangle index, the sampler its own face ->
+ * vertex table; neither reads slot order.
+ *
+ * rpt_download_mesh_emission_map copies one mesh's DECODED texels from the context's first device: width * height * 4 f32.  A mesh
+ * out of range, a mesh without a map (it says so), another size or a NULL destination answer RPT_ERR_INVALID_ARG.
+ *
+ * Memory.  While a map is ON every device holds 16 B per map texel, 48 B per mesh of the scene (the hit side's descriptors by texture
+ * ordinal, the sampler's by light ordinal, the all-zero material-map descriptors) and 4 B per triangle of the SCENE (the empty light
+ * table); during the call, per device, the new tables beside the old ones and 4 B per texel plus 1 KiB per map being set.  Per hit on
+ * a mapped mesh the kernel gathers what a material map's lookup gathers; per sample of a mapped ON mesh the 16 B descriptor, three
+ * face -> vertex words, three UVs, the material row and one (NEAREST) or four (BILINEAR) 16 B texels.
+ *
+ * Registers (gfx950, VGPRs / spilled SGPRs, the material-mapped base form in brackets, no scratch in any form;
+ * tools/kernel_meta.py): meshemit 111 / 158 (111 / 156), meshemit_env 113 / 160 (113 / 154), meshemit_cut 111 / 197 (110 / 188),
+ * meshemit_cut_env 112 / 185 (112 / 191), meshemit_nrm 111 / 164 (111 / 150), meshemit_nrm_env 113 / 166 (113 / 150),
+ * meshemit_nrm_cut 111 / 201 (111 / 193), meshemit_nrm_cut_env 113 / 201 (112 / 185): at most 113 of the 128 VGPRs that four
+ * waves per SIMD allow.  The one edit to a header other kernels include (dev_integrator.h: the emitter exit calls a forwarding
+ * function that defaults to hit_emission) left every other object of the build byte for byte what it was.
+ *
+ * Timings (MI355X, 1080p x 16 spp, medians of 5): 0.585 Gsamples/s with the torus ON and no map, 0.572 under an all-255 map (0.977)
+ * and 0.571 under a noise map (0.975); rpt_set_mesh_emission_maps for the 1024 x 1024 map 0.6 ms the first time and 0.5 ms again; the
+ * four move calls without / with the map, the torus ON in both: update_meshes 1.18 / 1.18 ms; rebuild_meshes 1.74 / 1.76 ms;
+ * update_meshes_device 0.92 / 0.91 ms; rebuild_meshes_device 1.49 / 1.50 ms.  tools/mesh_bench.py --emission-maps alternates, in one
+ * process, frames of scenes.mesh_scene textured as --textures does with its torus emissive and ON under no map, under an all-255
+ * 1024 x 1024 map on the torus (the pure cost of the lookups: every factor is exactly 1) and under a 1024 x 1024 BILINEAR noise map,
+ * and times the set call and the four move calls with and without the map. */
+enum { RPT_MESH_EMISSION_MAP_OFF = 0, RPT_MESH_EMISSION_MAP_ON = 1 };
+
+typedef struct rpt_mesh_emission_map {
+    uint32_t mesh;                    /* index into the uploaded scene's rpt_scene_desc.meshes */
+    uint32_t mode;                    /* RPT_MESH_EMISSION_MAP_* ; OFF: width == height == 0, texels == NULL */
+    uint32_t width, height;           /* of the map: its own size, need not be the texture's */
+    const uint8_t* texels;            /* HOST, RGBA8, row 0 first (alpha is ignored); copied inside the call */
+    uint32_t filter;                  /* RPT_TEX_FILTER_NEAREST / RPT_TEX_FILTER_BILINEAR */
+    float gamma;                      /* the decode's exponent, as rpt_mesh_texture's: finite, > 0, <= 16; 1: the bytes are linear */
+} rpt_mesh_emission_map;
+
+int rpt_set_mesh_emission_maps(rpt_ctx* ctx, const rpt_mesh_emission_map* items, uint32_t n_items);
+int rpt_download_mesh_emission_map(rpt_ctx* ctx, uint32_t mesh, float* texels /* host, width*height*4 f32, decoded */, uint32_t width, uint32_t height);
 
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)

@@ -296,6 +296,16 @@ public:
         check(rpt_download_mesh_material_map(ctx_, mesh, out.data(), width, height), ctx_);
         return out;
     }
+    /// Mesh emission maps (rpt.h, "mesh emission maps"): an RGBA8 map per named mesh, looked up through the mesh's texture UVs, scales the
+    /// material's emission at the hit, in the mesh-light sampler and at the emitter exit; an item with RPT_MESH_EMISSION_MAP_OFF removes its
+    /// mesh's.  sync_scene() drops them all.
+    void set_mesh_emission_maps(const std::vector<rpt_mesh_emission_map>& items) { check(rpt_set_mesh_emission_maps(ctx_, items.data(), (uint32_t)items.size()), ctx_); }
+    /// The decoded texels the context holds for one emission-mapped mesh: width * height * 4 floats {r, g, b, 0}.
+    std::vector<float> mesh_emission_map(uint32_t mesh, uint32_t width, uint32_t height) {
+        std::vector<float> out((size_t)width * height * 4);
+        check(rpt_download_mesh_emission_map(ctx_, mesh, out.data(), width, height), ctx_);
+        return out;
+    }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

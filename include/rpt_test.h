@@ -101,11 +101,26 @@ int rpt_debug_mesh_normal_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_
  * meshes; RPT_ERR_INVALID_ARG while no map is ON (those kernels do not run then). */
 int rpt_debug_mesh_material_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
 
+/* The emission a winning triangle is shaded with in a scene some mesh of which has an emission map ON (include/rpt.h, "mesh emission
+ * maps"), through the hit_material and the emitter exit's hit_emission_at the emission-mapped scenes' render kernels call (the form
+ * over the textured mesh-light tables): rays_dev and `flags` exactly as for rpt_debug_mesh_material_map_query; out_dev = n x 7 dwords
+ * — per ray {the winning triangle's flattened index or 0xFFFFFFFF, the three words of mat.emission, the three words of the emitter
+ * exit's emission} (zeros when nothing is hit).  RPT_ERR_NO_SCENE unless the uploaded scene has meshes; RPT_ERR_INVALID_ARG while no
+ * map is ON (those kernels do not run then). */
+int rpt_debug_mesh_emission_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
+
+/* The mesh-light sampler of such a scene, through the function its render kernels' mesh_light_nee calls: in_dev exactly as for
+ * rpt_debug_mesh_light_sample — n x 8 floats {scatter_pos, r0a, r0b, r1, r2, the ON mesh's ordinal as bits}; out_dev = n x 8 dwords
+ * {k (0xFFFFFFFF: a dark mesh or an ordinal out of range), the three words of emission, the three words of direction, pdf's bits}.
+ * RPT_ERR_INVALID_ARG while no map is ON or no mesh is ON. */
+int rpt_debug_mesh_emission_map_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, uint32_t* out_dev, void* stream);
+
 /* Which mesh render form the context's first device's last launch took: 0 .. 11 the twelve forms of csrc/mesh_args.h in MeshForm's
  * order (nrm_cut_env, nrm_cut, nrm_env, nrm, cut_env, cut, env, light_tex, tex, light, smooth, flat), 12 .. 19 a material map over
  * the eight textured forms that hold every table (csrc/mesh_args_mmap.h: light_tex, env, cut, cut_env, nrm, nrm_env, nrm_cut,
- * nrm_cut_env); 0xFFFFFFFF when that launch was no mesh scene's or there was none.  rpt_debug_kernel_choice has no bit left for
- * material maps and keeps its meaning: bits 26-31 say which of the other features are present. */
+ * nrm_cut_env), 20 .. 27 an emission map over those eight in the same order (csrc/mesh_args_emap.h), with or without a material
+ * map; 0xFFFFFFFF when that launch was no mesh scene's or there was none.  rpt_debug_kernel_choice has no bit left for material or
+ * emission maps and keeps its meaning: bits 26-31 say which of the other features are present. */
 int rpt_debug_mesh_form(rpt_ctx* ctx, uint32_t* form);
 
 /* The lookup of the environment (include/rpt.h, "environment lighting"), through the device function the miss exit of the environment

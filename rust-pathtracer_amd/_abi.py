@@ -183,6 +183,14 @@ class rpt_mesh_material_map(C.Structure):
                 ("texels", C.POINTER(C.c_uint8)), ("filter", C.c_uint32), ("roughness_channel", C.c_uint32), ("metallic_channel", C.c_uint32)]
 
 
+RPT_MESH_EMISSION_MAP_OFF, RPT_MESH_EMISSION_MAP_ON = 0, 1
+
+
+class rpt_mesh_emission_map(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("mode", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("texels", C.POINTER(C.c_uint8)), ("filter", C.c_uint32), ("gamma", C.c_float)]
+
+
 class rpt_scene_desc(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("flags", C.c_uint32),
@@ -247,6 +255,8 @@ SYMBOLS = {
     "rpt_download_mesh_normal_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
     "rpt_set_mesh_material_maps": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_material_map), C.c_uint32]),
     "rpt_download_mesh_material_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "rpt_set_mesh_emission_maps": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_emission_map), C.c_uint32]),
+    "rpt_download_mesh_emission_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
     "rpt_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -286,6 +296,8 @@ TEST_SYMBOLS = {
     "rpt_debug_mesh_cutout_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rpt_debug_mesh_normal_map_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rpt_debug_mesh_material_map_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rpt_debug_mesh_emission_map_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rpt_debug_mesh_emission_map_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "rpt_debug_mesh_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rpt_debug_env_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "rpt_debug_env_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

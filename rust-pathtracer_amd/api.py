@@ -692,6 +692,46 @@ class Tracer:
         check(lib().rpt_download_mesh_material_map(self._h, int(m), out.ctypes.data, int(width), int(height)), self._h)
         return out
 
+    def set_mesh_emission_maps(self, items):
+        """Mesh emission maps (include/rpt.h, "mesh emission maps"): `items` maps a mesh's index in scene().meshes to None — the mesh
+        loses its map — or to a (height, width, 4) uint8 RGBA map with row 0 at t = 0, or to a dict with "texels" (that array) and
+        optionally "filter" ("bilinear" / "nearest") and "gamma" (default 1: the bytes are linear).  The map is looked up through
+        the mesh's texture UVs and wrap and scales the material's emission where a path hits the mesh, where the mesh-light sampler
+        picks a point on it and at the emitter exit, so the mesh must be textured.  Meshes not named keep their map; upload_scene()
+        drops every map, as in C."""
+        filters = {"nearest": _abi.RPT_TEX_FILTER_NEAREST, "bilinear": _abi.RPT_TEX_FILTER_BILINEAR}
+        items = sorted(items.items())
+        its = (_abi.rpt_mesh_emission_map * max(1, len(items)))()
+        keep = []
+        for it, (m, em) in zip(its, items):
+            it.mesh, it.mode, it.gamma = int(m), _abi.RPT_MESH_EMISSION_MAP_OFF, 1.0
+            if em is None:
+                continue
+            if not isinstance(em, dict):
+                em = {"texels": em}
+            filt = em.get("filter", "bilinear")
+            if filt not in filters:
+                raise ValueError("mesh %d: filter must be \"nearest\" or \"bilinear\", not %r" % (m, filt))
+            texels = np.ascontiguousarray(em["texels"], dtype=np.uint8)
+            if texels.ndim != 3 or texels.shape[2] != 4:
+                raise ValueError("mesh %d: texels must have the shape (height, width, 4)" % m)
+            keep.append(texels)
+            it.mode, it.filter, it.gamma = _abi.RPT_MESH_EMISSION_MAP_ON, filters[filt], float(em.get("gamma", 1.0))
+            it.height, it.width, it.texels = texels.shape[0], texels.shape[1], texels.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._checked_move(lib().rpt_set_mesh_emission_maps(self._h, its, len(items)))
+        sizes = self.__dict__.setdefault("_emission_map_sizes", {})
+        for it, (m, em) in zip(its, items):
+            sizes[int(m)] = (it.width, it.height)
+
+    def download_mesh_emission_map(self, m, width=None, height=None):
+        """The decoded texels the context holds for the emission-mapped mesh `m` (rpt_download_mesh_emission_map): a new float32 array
+        of shape (height, width, 4), {r, g, b, 0}.  Without a size: the one set_mesh_emission_maps last gave the mesh."""
+        if width is None or height is None:
+            width, height = self.__dict__.get("_emission_map_sizes", {}).get(int(m), (0, 0))
+        out = np.empty((int(height), int(width), 4), np.float32)
+        check(lib().rpt_download_mesh_emission_map(self._h, int(m), out.ctypes.data, int(width), int(height)), self._h)
+        return out
+
     def _refresh_stale_meshes(self):
         """scene().meshes' vertex arrays that a device-source call left stale, read back once (only before an upload)."""
         for m in sorted(self._stale_meshes):

@@ -21,6 +21,7 @@
 #include "../../include/rpt.h"
 #include "host_build.h"
 #include "host_cut.h"
+#include "host_emap.h"
 #include "host_env.h"
 #include "host_light.h"
 #include "host_mmap.h"
@@ -34,6 +35,7 @@
 #include "launch.h"
 #include "launch_build.h"
 #include "launch_cut.h"
+#include "launch_emap.h"
 #include "launch_env.h"
 #include "launch_light.h"
 #include "launch_mmap.h"
@@ -43,6 +45,7 @@
 #include "launch_tex.h"
 #include "mesh_args.h"
 #include "mesh_args_mmap.h"
+#include "mesh_args_emap.h"
 #ifdef RPT_TEST_HOOKS
 #include "../../include/rpt_test.h"
 #endif
@@ -76,6 +79,7 @@ struct DevState {
     void* cut = nullptr;              // mesh cutouts' tables (host_cut.h, CutLayout): while some mesh's cutout is ON (rpt_set_mesh_cutouts)
     void* nrm = nullptr;              // mesh normal maps' tables (host_nrm.h, NrmLayout): while some mesh's map is ON (rpt_set_mesh_normal_maps)
     void* mmap = nullptr;             // mesh material maps' tables (host_mmap.h, MmapLayout): while some mesh's map is ON (rpt_set_mesh_material_maps)
+    void* emap = nullptr;             // mesh emission maps' tables (host_emap.h, EmapLayout): while some mesh's map is ON (rpt_set_mesh_emission_maps)
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -128,6 +132,7 @@ struct rpt_ctx {
     rpthost::CutPlan cut;             // which of its meshes have a cutout and where each one's mask lies on every device (host_cut.h)
     rpthost::NrmPlan nrm;             // which of its meshes have a normal map and where each one's texels lie on every device (host_nrm.h)
     rpthost::MmapPlan mmap;           // which of its meshes have a material map and where each one's texels lie on every device (host_mmap.h)
+    rpthost::EmapPlan emap;           // which of its meshes have an emission map and where each one's texels lie on every device (host_emap.h)
     // resident ColorBuffer (buffer.rs:6-14): pixels as per-rank tiles + frames
     uint32_t res_w = 0, res_h = 0, res_tile_rows = 0, res_rows_padded = 0;
     uint64_t res_frames = 0;
@@ -316,6 +321,7 @@ static void free_mesh_work(DevState& d)
     if (d.cut) { (void)hipFree(d.cut); d.cut = nullptr; }
     if (d.nrm) { (void)hipFree(d.nrm); d.nrm = nullptr; }
     if (d.mmap) { (void)hipFree(d.mmap); d.mmap = nullptr; }
+    if (d.emap) { (void)hipFree(d.emap); d.emap = nullptr; }
     d.refit_full = false;
     d.build_temp_bytes = 0;
 }
@@ -493,6 +499,17 @@ static hipError_t launch_mesh_map_form(const rptargs::MeshView& view, const rpta
     return launcher(s, rp, grid, stream);
 }
 
+// One emission-mapped render form (mesh_args_emap.h), likewise.
+template <class S, class Launcher>
+static hipError_t launch_mesh_emit_form(const rptargs::MeshView& view, const rptargs::MmapView& maps, bool material_maps, const rptargs::EmapView& emits,
+                                        const SceneMesh& scm, Launcher launcher, const RenderParams& rp, uint32_t grid, hipStream_t stream)
+{
+    S s = rptargs::mesh_emit_scene_of<S>(view, maps, material_maps, emits);
+    s.cam = scm.cam;
+    s.flags = scm.flags;
+    return launcher(s, rp, grid, stream);
+}
+
 // One render launch sequence on one device.
 static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t width, uint32_t height, uint64_t frames_done, uint32_t spp,
                          uint64_t seed, uint32_t flags, uint32_t tile_rows, uint32_t rank, uint32_t world, hipStream_t stream)
@@ -514,6 +531,7 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     const bool cutouts = kind == SceneKind::mesh && d.cut && d.tex && d.refit && ctx->cut.any();  // some mesh's cutout is ON: k_cut.hip's forms, over the textured mesh-light form or the environment's
     const bool normal_maps = kind == SceneKind::mesh && d.nrm && d.tex && d.refit && ctx->nrm.any();   // some mesh's normal map is ON: k_nrm.hip's forms, over the four above that hold every table
     const bool material_maps = kind == SceneKind::mesh && d.mmap && d.tex && d.refit && ctx->mmap.any();   // some mesh's material map is ON: k_mmap.hip's forms, over the eight textured forms that hold every table
+    const bool emission_maps = kind == SceneKind::mesh && d.emap && d.tex && d.refit && ctx->emap.any();   // some mesh's emission map is ON: k_emap.hip's forms, over the eight material-mapped forms
     scs.cam = scl.cam = scm.cam = make_camera(ctx->scene.camera, (float)width, (float)height);
     const bool in_hbm = kind == SceneKind::large || kind == SceneKind::mesh;     // the scene's tables are in device memory
     const bool has_sdf = !in_hbm && scs.sdf.n_prims > 0;
@@ -577,13 +595,29 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
                         (media ? 1u << 24 : 0u) | (kind == SceneKind::mesh ? 1u << 25 : 0u) |
                         (smooth ? 1u << 26 : 0u) | (lights ? 1u << 27 : 0u) | (textured ? 1u << 28 : 0u) |
                         (environment ? 1u << 29 : 0u) | (cutouts ? 1u << 30 : 0u) | (normal_maps ? 1u << 31 : 0u);
-        // (material maps have no bit: the mesh form says it — 12 .. 19, include/rpt_test.h, rpt_debug_mesh_form)
-        d.last_form = kind == SceneKind::mesh ? rptargs::mesh_form_ext_of(smooth, lights, textured, environment, cutouts, normal_maps, material_maps) : 0xFFFFFFFFu;
+        // (material and emission maps have no bit: the mesh form says it — 12 .. 19 and 20 .. 27, include/rpt_test.h, rpt_debug_mesh_form)
+        d.last_form = kind == SceneKind::mesh ? rptargs::mesh_form_emit_of(smooth, lights, textured, environment, cutouts, normal_maps, material_maps, emission_maps)
+                                              : 0xFFFFFFFFu;
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
         if (kind == SceneKind::mesh) {
             using rptargs::MeshForm;
             const rptargs::MeshView view = mesh_view_of(ctx, d);
+            if (d.last_form >= rptargs::kMeshFormEmitFirst) {
+                using rptargs::MeshEmitForm;
+                const rptargs::MmapView maps{d.mmap, ctx->mmap};
+                const rptargs::EmapView emits{d.emap, ctx->emap};
+                switch ((MeshEmitForm)d.last_form) {
+                case MeshEmitForm::light_tex: return launch_mesh_emit_form<SceneMeshEmit>(view, maps, material_maps, emits, scm, rptlaunch::render_mesh_emit, rp, grid, stream);
+                case MeshEmitForm::env: return launch_mesh_emit_form<SceneMeshEmitEnv>(view, maps, material_maps, emits, scm, rptlaunch::render_mesh_emit_env, rp, grid, stream);
+                case MeshEmitForm::cut: return launch_mesh_emit_form<SceneMeshEmitCut>(view, maps, material_maps, emits, scm, rptlaunch::render_mesh_emit_cut, rp, grid, stream);
+                case MeshEmitForm::cut_env: return launch_mesh_emit_form<SceneMeshEmitCutEnv>(view, maps, material_maps, emits, scm, rptlaunch::render_mesh_emit_cut_env, rp, grid, stream);
+                case MeshEmitForm::nrm: return launch_mesh_emit_form<SceneMeshEmitNrm>(view, maps, material_maps, emits, scm, rptlaunch::render_mesh_emit_nrm, rp, grid, stream);
+                case MeshEmitForm::nrm_env: return launch_mesh_emit_form<SceneMeshEmitNrmEnv>(view, maps, material_maps, emits, scm, rptlaunch::render_mesh_emit_nrm_env, rp, grid, stream);
+                case MeshEmitForm::nrm_cut: return launch_mesh_emit_form<SceneMeshEmitNrmCut>(view, maps, material_maps, emits, scm, rptlaunch::render_mesh_emit_nrm_cut, rp, grid, stream);
+                case MeshEmitForm::nrm_cut_env: return launch_mesh_emit_form<SceneMeshEmitNrmCutEnv>(view, maps, material_maps, emits, scm, rptlaunch::render_mesh_emit_nrm_cut_env, rp, grid, stream);
+                }
+            }
             if (d.last_form >= rptargs::kMeshFormMapFirst) {
                 using rptargs::MeshMapForm;
                 const rptargs::MmapView maps{d.mmap, ctx->mmap};
@@ -995,6 +1029,7 @@ static void commit_scene(rpt_ctx* ctx, SceneImage& img, const std::vector<void*>
     ctx->cut = rpthost::CutPlan();                                  // every cutout OFF
     ctx->nrm = rpthost::NrmPlan();                                  // every normal map OFF
     ctx->mmap = rpthost::MmapPlan();                                // every material map OFF
+    ctx->emap = rpthost::EmapPlan();                                // every emission map OFF
 }
 
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
@@ -1030,6 +1065,7 @@ static void drop_scene(rpt_ctx* ctx)
     ctx->cut = rpthost::CutPlan();
     ctx->nrm = rpthost::NrmPlan();
     ctx->mmap = rpthost::MmapPlan();
+    ctx->emap = rpthost::EmapPlan();
 }
 
 // Where the named meshes' new positions come from: host arrays (rpt_update_meshes, rpt_rebuild_meshes) or device arrays through a
@@ -1596,6 +1632,21 @@ int rpt_download_mesh_normals(rpt_ctx* ctx, uint32_t mesh, float* normals, uint3
     return RPT_OK;
 }
 
+// The emission maps' two descriptor tables of device d again (host_emap.h, emap_desc_table and emap_light_desc_table): after a
+// texture call (the texture ordinals or a wrap may have changed), after a light call (the light ordinals), and inside
+// rpt_set_mesh_emission_maps.  The device is idle (the caller waited) and the texels stay where they are.
+static int emap_desc_device(rpt_ctx* ctx, DevState& d)
+{
+    const rpthost::EmapPlan& ep = ctx->emap;
+    const rpthost::EmapLayout el = ep.layout();
+    const std::vector<uint32_t> desc = rpthost::emap_desc_table(ep, ctx->tex);
+    const std::vector<uint32_t> light_desc = rpthost::emap_light_desc_table(ep, ctx->tex, ctx->light);
+    unsigned char* base = static_cast<unsigned char*>(d.emap);
+    if (!desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(base + el.off_desc, desc.data(), 4 * desc.size(), hipMemcpyHostToDevice));
+    if (!light_desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(base + el.off_light_desc, light_desc.data(), 4 * light_desc.size(), hipMemcpyHostToDevice));
+    return RPT_OK;
+}
+
 // ---- rpt_set_mesh_lights / rpt_download_mesh_light_table (include/rpt.h, "mesh lights") --------------------------------------------
 // One device's part: wait for its earlier work (a launch may still read the old tables), make its refit tables if it has none, drop
 // the old light tables, copy the new ones in, compute the ON meshes' tables, and wait.  ctx->light is already the new plan.
@@ -1667,6 +1718,7 @@ int rpt_set_mesh_lights(rpt_ctx* ctx, const rpt_mesh_light* items, uint32_t n_it
         DevState& d = ctx->devs[i];
         if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_lights: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
         else rc_dev = light_device(ctx, d);
+        if (rc_dev == RPT_OK && d.emap && ctx->emap.any()) rc_dev = emap_desc_device(ctx, d);    // the sampler's table goes by light ordinal
     }
     if (rc_dev != RPT_OK) {
         const std::string first = ctx->err;
@@ -1822,6 +1874,11 @@ int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t 
             set_err(ctx, "rpt_set_mesh_textures: mesh %u has a material map, which reads its texture's UVs and wrap: remove the material map first (rpt_set_mesh_material_maps)", m);
             return RPT_ERR_INVALID_ARG;
         }
+    for (uint32_t m = 0; m < image.size(); ++m)                     // include/rpt.h, "mesh emission maps": the map reads the texture's UVs and wrap
+        if (image[m].width == 0u && ctx->emap.on(m)) {
+            set_err(ctx, "rpt_set_mesh_textures: mesh %u has an emission map, which reads its texture's UVs and wrap: remove the emission map first (rpt_set_mesh_emission_maps)", m);
+            return RPT_ERR_INVALID_ARG;
+        }
     if (n_items == 0) return RPT_OK;
     bool any = false;
     for (const TexImage& im : image) any = any || im.width != 0u;
@@ -1855,6 +1912,7 @@ int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t 
         if (rc_dev == RPT_OK && d.cut && ctx->cut.any()) rc_dev = cut_desc_device(ctx, d);      // the ordinals or a wrap may have changed
         if (rc_dev == RPT_OK && d.nrm && ctx->nrm.any()) rc_dev = nrm_desc_device(ctx, d);
         if (rc_dev == RPT_OK && d.mmap && ctx->mmap.any()) rc_dev = mmap_desc_device(ctx, d);
+        if (rc_dev == RPT_OK && d.emap && ctx->emap.any()) rc_dev = emap_desc_device(ctx, d);
     }
     if (rc_dev != RPT_OK) {
         const std::string first = ctx->err;
@@ -2377,6 +2435,128 @@ int rpt_download_mesh_material_map(rpt_ctx* ctx, uint32_t mesh, float* texels, u
     return RPT_OK;
 }
 
+// ---- rpt_set_mesh_emission_maps / rpt_download_mesh_emission_map (include/rpt.h, "mesh emission maps") -----------------------------
+// One device's part, as mmap_device: wait for its earlier work (a launch may still read the old tables), make the new tables, copy the
+// kept meshes' texels over from the old ones on the device, decode the named meshes' maps with "mesh textures"' own launch, write the
+// descriptors, drop the old tables, and wait.  ctx->emap is already the new plan; `old` is the plan the old tables were made by.
+static int emap_device(rpt_ctx* ctx, DevState& d, const rpthost::EmapPlan& old, const rpt_mesh_emission_map* items, uint32_t n_items)
+{
+    const rpthost::EmapPlan& ep = ctx->emap;
+    const rpthost::EmapLayout el = ep.layout();
+    const rpthost::EmapLayout ol = old.layout();
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    RPT_CHECK_RC(ensure_refit(ctx, d));
+    void* fresh = nullptr;
+    void* stage = nullptr;
+    RPT_HIP_CHECK(ctx, hipMalloc(&fresh, el.total));
+    size_t stage_bytes = 0;                                         // the named maps' bytes and one L table each, in one allocation that lives until the decodes have run
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (items[i].mode == RPT_MESH_EMISSION_MAP_ON) stage_bytes += 1024 + (((size_t)items[i].width * items[i].height * 4 + 15) & ~(size_t)15);
+    const auto fail = [&](int rc) { (void)hipFree(fresh); if (stage) (void)hipFree(stage); return rc; };
+    const auto work = [&]() -> int {
+        if (stage_bytes) RPT_HIP_CHECK(ctx, hipMalloc(&stage, stage_bytes));
+        unsigned char* base = static_cast<unsigned char*>(fresh);
+        rpthost::TexTexel* texels = reinterpret_cast<rpthost::TexTexel*>(base + el.off_texels);
+        RPT_HIP_CHECK(ctx, hipMemsetAsync(base, 0, el.off_texels, d.stream));      // both descriptor tables and the zero block's descriptors
+        if (el.zero.off_texels > el.zero.off_none)                                  // the zero block's empty light table
+            RPT_HIP_CHECK(ctx, hipMemsetAsync(base + el.off_zero + el.zero.off_none, 0xFF, el.zero.off_texels - el.zero.off_none, d.stream));
+        std::vector<uint8_t> named(ep.map.size(), 0);
+        size_t at = 0;
+        for (uint32_t i = 0; i < n_items; ++i) {
+            const rpt_mesh_emission_map& it = items[i];
+            named[it.mesh] = 1;
+            if (it.mode != RPT_MESH_EMISSION_MAP_ON) continue;
+            const rpthost::EmapMap& c = ep.map[it.mesh];
+            const size_t n = (size_t)c.width * c.height;
+            unsigned char* at_dev = static_cast<unsigned char*>(stage) + at;
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(at_dev + 1024, it.texels, 4 * n, hipMemcpyHostToDevice, d.stream));
+            RPT_HIP_CHECK(ctx, rptlaunch::tex_decode(at_dev + 1024, reinterpret_cast<float*>(at_dev), texels + c.first, (uint32_t)n, c.gamma, d.stream));
+            at += 1024 + ((4 * n + 15) & ~(size_t)15);
+        }
+        for (uint32_t m = 0; m < ep.map.size(); ++m) {
+            if (named[m] || !ep.map[m].width) continue;             // a mesh not named keeps its map: the decoded texels move on the device
+            if (!d.emap || !old.on(m)) { set_err(ctx, "rpt_set_mesh_emission_maps: device %d holds no texels for mesh %u", d.device, m); return RPT_ERR_HIP; }
+            const size_t n = (size_t)ep.map[m].width * ep.map[m].height;
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(texels + ep.map[m].first,
+                                              reinterpret_cast<const rpthost::TexTexel*>(static_cast<const unsigned char*>(d.emap) + ol.off_texels) + old.map[m].first,
+                                              16 * n, hipMemcpyDeviceToDevice, d.stream));
+        }
+        RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+        return RPT_OK;
+    };
+    const int rc = work();
+    if (rc != RPT_OK) return fail(rc);
+    if (stage) (void)hipFree(stage);
+    if (d.emap) (void)hipFree(d.emap);
+    d.emap = fresh;
+    return emap_desc_device(ctx, d);
+}
+
+int rpt_set_mesh_emission_maps(rpt_ctx* ctx, const rpt_mesh_emission_map* items, uint32_t n_items)
+{
+    using namespace rpthost;
+    if (!ctx) { set_err(nullptr, "rpt_set_mesh_emission_maps: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    std::vector<EmapMap> map;
+    std::string why;
+    const int rc = check_mesh_emission_maps(ctx->refit, ctx->scene.kind == SceneKind::mesh, ctx->tex, items, n_items, ctx->emap.map, map, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    if (n_items == 0) return RPT_OK;
+    bool any = false;
+    for (const EmapMap& c : map) any = any || c.width != 0u;
+    if (!any && !ctx->emap.any()) return RPT_OK;                    // every map OFF, as before
+    DeviceGuard guard(ctx->devs[0].device);
+    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
+    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_emission_maps: cannot select device %d", ctx->devs[0].device);
+    if (rc_dev == RPT_OK && !any) {                                 // every map OFF (again): the context is what it was before the first call
+        for (DevState& d : ctx->devs) {
+            if (!d.emap) continue;
+            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
+                set_err(ctx, "rpt_set_mesh_emission_maps: cannot wait for device %d", d.device);
+                rc_dev = RPT_ERR_HIP;
+                break;
+            }
+            (void)hipFree(d.emap);
+            d.emap = nullptr;
+        }
+        if (rc_dev == RPT_OK) { ctx->emap = EmapPlan(); return RPT_OK; }
+    }
+    EmapPlan old;
+    if (rc_dev == RPT_OK) {
+        old = std::move(ctx->emap);
+        build_emap_plan(ctx->refit, std::move(map), ctx->emap);
+    }
+    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
+        DevState& d = ctx->devs[i];
+        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_emission_maps: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
+        else rc_dev = emap_device(ctx, d, old, items, n_items);
+    }
+    if (rc_dev != RPT_OK) {
+        const std::string first = ctx->err;
+        drop_scene(ctx);
+        set_err(ctx, "%s; the context now holds no scene", first.c_str());
+        return rc_dev;
+    }
+    return RPT_OK;
+}
+
+int rpt_download_mesh_emission_map(rpt_ctx* ctx, uint32_t mesh, float* texels, uint32_t width, uint32_t height)
+{
+    if (!ctx) { set_err(nullptr, "rpt_download_mesh_emission_map: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_mesh_emission_map: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    const rpthost::RefitPlan& plan = ctx->refit;
+    if (mesh >= plan.n_meshes()) { set_err(ctx, "rpt_download_mesh_emission_map: mesh %u out of range (the scene has %u)", mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
+    const DevState& d = ctx->devs[0];
+    const rpthost::EmapPlan& ep = ctx->emap;
+    if (!ep.on(mesh) || !d.emap) { set_err(ctx, "rpt_download_mesh_emission_map: mesh %u has no emission map: the context holds no texels for it (rpt_set_mesh_emission_maps)", mesh); return RPT_ERR_INVALID_ARG; }
+    const rpthost::EmapMap& c = ep.map[mesh];
+    if (width != c.width || height != c.height) { set_err(ctx, "rpt_download_mesh_emission_map: mesh %u: %u x %u is not its map's %u x %u", mesh, width, height, c.width, c.height); return RPT_ERR_INVALID_ARG; }
+    if (!texels) { set_err(ctx, "rpt_download_mesh_emission_map: texels is NULL"); return RPT_ERR_INVALID_ARG; }
+    RPT_ON_DEVICE(ctx);
+    const rpthost::EmapLayout el = ep.layout();
+    RPT_HIP_CHECK(ctx, hipMemcpy(texels, static_cast<const unsigned char*>(d.emap) + el.off_texels + 16 * (size_t)c.first, 16 * (size_t)c.width * c.height, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+
 uint32_t rpt_tile_row_count(uint32_t height, uint32_t tile_rows, uint32_t rank, uint32_t world)
 {
     return tile_row_count(height, tile_rows, rank, world);
@@ -2499,7 +2679,7 @@ int rpt_debug_kernel_choice(rpt_ctx* ctx, uint32_t* out)
     return RPT_OK;
 }
 
-// (include/rpt_test.h) the last launch's mesh form: 0 .. 11 a MeshForm of mesh_args.h, 12 .. 19 a material-mapped one (mesh_args_mmap.h)
+// (include/rpt_test.h) the last launch's mesh form: 0 .. 11 a MeshForm of mesh_args.h, 12 .. 19 a material-mapped one (mesh_args_mmap.h), 20 .. 27 an emission-mapped one (mesh_args_emap.h)
 int rpt_debug_mesh_form(rpt_ctx* ctx, uint32_t* form)
 {
     if (!ctx || !form) return RPT_ERR_INVALID_ARG;
@@ -3024,6 +3204,38 @@ int rpt_debug_mesh_material_map_query(rpt_ctx* ctx, const float* rays_dev, uint6
     const DevState& d = ctx->devs[0];
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_material_map_query(rptargs::mesh_map_scene_of<SceneMeshMap>(mesh_view_of(ctx, d), rptargs::MmapView{d.mmap, ctx->mmap}), rays_dev, out_dev, n,
                                                           flags, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+// The argument of the emission-map probes: the form over the textured mesh-light tables, bound as a launch binds it.
+static SceneMeshEmit emit_probe_scene_of(rpt_ctx* ctx, const DevState& d)
+{
+    const bool material_maps = d.mmap && ctx->mmap.any();
+    return rptargs::mesh_emit_scene_of<SceneMeshEmit>(mesh_view_of(ctx, d), rptargs::MmapView{d.mmap, ctx->mmap}, material_maps, rptargs::EmapView{d.emap, ctx->emap});
+}
+
+int rpt_debug_mesh_emission_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_emission_map_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_emission_map_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    if (!rays_dev || !out_dev || (flags & ~(uint32_t)RPT_MESH_QUERY_BRUTE)) { set_err(ctx, "rpt_debug_mesh_emission_map_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->emap.any() || !ctx->devs[0].emap || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_emission_map_query: no mesh has an emission map"); return RPT_ERR_INVALID_ARG; }
+    if (n == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_emission_map_query(emit_probe_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_debug_mesh_emission_map_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, uint32_t* out_dev, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_emission_map_sample: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_emission_map_sample: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    if (!in_dev || !out_dev) { set_err(ctx, "rpt_debug_mesh_emission_map_sample: invalid argument"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->emap.any() || !ctx->devs[0].emap || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_emission_map_sample: no mesh has an emission map"); return RPT_ERR_INVALID_ARG; }
+    if (!ctx->light.any() || !ctx->devs[0].light) { set_err(ctx, "rpt_debug_mesh_emission_map_sample: no mesh is ON"); return RPT_ERR_INVALID_ARG; }
+    if (n == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_emission_map_sample(emit_probe_scene_of(ctx, ctx->devs[0]), in_dev, out_dev, n, (hipStream_t)stream));
     return RPT_OK;
 }
 

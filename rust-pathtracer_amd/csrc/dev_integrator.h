@@ -969,6 +969,14 @@ RPT_DEV void path_begin(const S& sc, PathRegs& p, float px, float py, FrameKey f
 // operations and their order are unchanged, so images stay bit-identical.
 // 0: the ray left the scene (the background is still to be added), 1: it ended on an emitter (radiance updated), 2: the bounce
 // goes on in SHADE — a surface was hit, or (media kernels) the path scatters inside the medium it is in.
+// The emission of the hit `g` of `ray` as the emitter exit below adds it: hit_emission(sc, g).  A scene type whose emission depends
+// on where the ray met the triangle overloads this (dev_mesh_emap.h); for every other scene type it is that call and nothing else.
+template <class S> RPT_DEV v3 hit_emission_at(const S& sc, const RayD& ray, const GeomHit& g)
+{
+    (void)ray;
+    return hit_emission(sc, g);
+}
+
 template <class S, class Q>
 RPT_DEV uint32_t path_trace_geom_split(const S& sc, const Q& q, PathRegs& p, GeomHit& g)
 {
@@ -1002,7 +1010,7 @@ RPT_DEV uint32_t path_trace_geom_split(const S& sc, const Q& q, PathRegs& p, Geo
     }
     if (e.is_emitter) {
         RPT_PROF(PB_FINALIZE);
-        if constexpr (MeshLights<S>::value) p.radiance = p.radiance + (mesh_light_hit_weight(sc, p.ray, p.ps, p.bounce, g) * hit_emission(sc, g)) * p.throughput;
+        if constexpr (MeshLights<S>::value) p.radiance = p.radiance + (mesh_light_hit_weight(sc, p.ray, p.ps, p.bounce, g) * hit_emission_at(sc, p.ray, g)) * p.throughput;
         else p.radiance = p.radiance + hit_emission(sc, g) * p.throughput;                 // tracer.rs:74
         // state.depth > 0 always holds (tracer.rs:57,80): the MIS weight is always applied
         float mis_weight = power_heuristic(p.ps.scatter_pdf, e.light_pdf);

@@ -294,6 +294,21 @@ def mesh_texture_scene():
     return s, [spherical_uvs(v, (0.0, 0.0, 0.0)), quad_uv]
 
 
+def mesh_emission_scene(sphere_light=False, lamp_emission=(40.0, 36.0, 30.0)):
+    """-> (scene, textures, emission_maps): mesh_light_scene() with its lamp (mesh 1) textured — a 1 x 1 white texture over UVs that
+    run from 0 to 1 across the quad — and emission-mapped by a small striped image (include/rpt.h, "mesh emission maps"): 8 x 4
+    texels, NEAREST, four bright stripes (255, 230, 200) and four dim ones (40, 25, 10) along s.  `textures` and `emission_maps` are
+    what Tracer.set_mesh_textures and Tracer.set_mesh_emission_maps take, in this order, after the upload."""
+    import numpy as np
+    s = mesh_light_scene(sphere_light, lamp_emission)
+    uvs = np.array([[0.0, 0.0], [1.0, 0.0], [1.0, 1.0], [0.0, 1.0]], dtype=np.float32)
+    stripes = np.empty((4, 8, 4), np.uint8)
+    stripes[:, 0::2] = (255, 230, 200, 255)
+    stripes[:, 1::2] = (40, 25, 10, 255)
+    textures = {1: dict(uvs=uvs, texels=np.full((1, 1, 4), 255, np.uint8), wrap="clamp", filter="nearest")}
+    return s, textures, {1: dict(texels=stripes, filter="nearest", gamma=1.0)}
+
+
 def checker_mask(w, h, cells=8, opaque=255, hole=0):
     """-> [h, w] uint8, an A8 mask for Tracer.set_mesh_cutouts in checker_texture()'s pattern: `cells` x `cells` fields over the whole
     image, alternately `opaque` and `hole`; texel (0, 0) is opaque."""

@@ -52,8 +52,14 @@ scene textured as --textures does with no map ("textured": the textured kernel, 
 meshes ("ones": the pure cost of the lookup, both factors are exactly 1) and under a 1024 x 1024 BILINEAR noise map ("noise"), on three
 contexts, alternating; the time of rpt_set_mesh_material_maps itself; and the wall time of the four move calls with and without maps.
 
+--emission-maps: one JSON line more, for mesh emission maps (include/rpt.h, "mesh emission maps"): the resident render rate of the
+scene textured as --textures does, its torus emissive and ON, with no map ("lit": the textured mesh-light kernel, unchanged), under an
+all-255 1024 x 1024 map on the torus ("ones": the pure cost of the lookups, every factor is exactly 1) and under a 1024 x 1024 BILINEAR
+noise map ("noise"), on three contexts, alternating; the time of rpt_set_mesh_emission_maps itself; and the wall time of the four move
+calls with and without maps.
+
     python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild] [--device] [--smooth] [--lights] [--textures] [--environment]
-                               [--cutouts] [--normal-maps] [--material-maps]
+                               [--cutouts] [--normal-maps] [--material-maps] [--emission-maps]
 """
 import argparse
 import ctypes as C
@@ -82,6 +88,7 @@ def main():
     ap.add_argument("--cutouts", action="store_true")
     ap.add_argument("--normal-maps", action="store_true")
     ap.add_argument("--material-maps", action="store_true")
+    ap.add_argument("--emission-maps", action="store_true")
     a = ap.parse_args()
     os.environ.setdefault("RPT_LIB", os.path.join(ROOT, "rust-pathtracer_amd", "librpt_hip_test.so"))     # (the product has no hooks)
     import __graft_entry__
@@ -113,6 +120,7 @@ def main():
     cutouts = measure_cutouts(pkg, s, a) if a.cutouts else None
     normal_maps = measure_normal_maps(pkg, s, a) if a.normal_maps else None
     material_maps = measure_material_maps(pkg, s, a) if a.material_maps else None
+    emission_maps = measure_emission_maps(pkg, s, a) if a.emission_maps else None
     t.close()
     print(json.dumps({"workload": "mesh_scene %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "triangles": n_tris,
                       "gsamples_per_s_median": sorted(rates)[len(rates) // 2], "gsamples_per_s": rates,
@@ -137,6 +145,8 @@ def main():
         print(json.dumps(normal_maps))
     if material_maps:
         print(json.dumps(material_maps))
+    if emission_maps:
+        print(json.dumps(emission_maps))
 
 
 def measure_updates(pkg, t, s, a):
@@ -797,6 +807,95 @@ def measure_material_maps(pkg, s, a):
            "first_set_mesh_material_maps_ms": first, "set_mesh_material_maps_again_ms": {k: stats(v) for k, v in again.items()},
            "gsamples_per_s": {k: stats(rates[k]) for k in sides},
            "ones_over_textured_rate": med["ones"] / med["textured"], "noise_over_textured_rate": med["noise"] / med["textured"]}
+    # moves: the medium move and back, so that every call moves every vertex
+    moved = scenes.mesh_scene_moved(s, 0.5)
+    dev = lambda arrays: {m: torch.from_numpy(np.ascontiguousarray(v, np.float32)).to("cuda:0") for m, v in enumerate(arrays)}   # noqa: E731
+    there, back = {"host": dict(enumerate(moved)), "device": dev(moved)}, {"host": dict(enumerate(original)), "device": dev(original)}
+    torch.cuda.synchronize()
+    calls = (("update_meshes", "host"), ("rebuild_meshes", "host"), ("update_meshes_device", "device"), ("rebuild_meshes_device", "device"))
+    for name, where in calls:
+        pair = {"off": context(None), "on": context("noise")}
+        for t in pair.values():
+            getattr(t, name)(back[where])                           # the context's first call of its kind: allocates
+        ms = {"off": [], "on": []}
+        for _ in range(reps):
+            for arg in (there[where], back[where]):
+                for side in ("off", "on"):
+                    ms[side].append(timed(getattr(pair[side], name), arg))
+        for t in pair.values():
+            t.close()
+        fo, fn = stats(ms["off"]), stats(ms["on"])
+        out[name] = {"off_ms": fo, "on_ms": fn, "on_adds_ms": fn["median"] - fo["median"]}
+    return out
+
+
+def measure_emission_maps(pkg, s, a):
+    """-> the --emission-maps line.  scenes.mesh_scene() textured as measure_textures does, with the shadow rays' flag and its torus
+    emissive and ON as measure_lights has it: with no map ("lit"), under an all-255 1024 x 1024 map on the torus ("ones") and under a
+    1024 x 1024 BILINEAR noise map ("noise"): three contexts, alternating within a repetition, medians of `reps`; the set call; and
+    the four move calls on a "lit" and a "noise" context."""
+    import numpy as np
+    import torch
+    from rust_pathtracer_amd import scenes
+
+    def make():
+        sc = scenes.mesh_scene()
+        sc.any_hit_uses_max_dist = True
+        sc.materials[1].fields["emission"] = (4.0, 3.0, 2.0)
+        return sc
+
+    original = [np.array(v, np.float32, copy=True) for v, _, _ in s.meshes]
+    image = scenes.checker_texture(1024, 1024, (255, 255, 255), (60, 60, 60), cells=32)
+    both = {m: dict(uvs=scenes.spherical_uvs(v, 0.5 * (v.min(0).astype(np.float64) + v.max(0))) * np.float32(4.0), texels=image,
+                    wrap="repeat", filter="bilinear", gamma=2.2) for m, v in enumerate(original)}
+    maps = {"ones": np.full((1024, 1024, 4), 255, np.uint8),
+            "noise": np.random.default_rng(0x5EED0008).integers(0, 256, (1024, 1024, 4), dtype=np.uint8)}
+
+    def stats(xs):
+        xs = sorted(xs)
+        return {"median": xs[len(xs) // 2], "min": xs[0], "max": xs[-1]}
+
+    def timed(call, arg):
+        t0 = time.perf_counter()
+        call(arg)
+        return (time.perf_counter() - t0) * 1e3
+
+    def rate(tr):
+        tr.render_resident(a.width, a.height, a.spp)
+        return a.width * a.height * a.spp / (tr.resident_kernel_ms() * 1e-3) / 1e9
+
+    def context(which):
+        tr = pkg.Tracer(make(), device=0, seed=1)
+        tr.set_mesh_textures(both)
+        tr.set_mesh_lights({1: True})
+        if which is not None:
+            tr.set_mesh_emission_maps({1: dict(texels=maps[which], filter="bilinear", gamma=2.2)})
+        return tr
+
+    reps = max(5, a.reps)
+    sides = ("lit", "ones", "noise")
+    tr = {"lit": context(None)}
+    first, again = {}, {}
+    for k in sides[1:]:
+        tr[k] = context(None)
+        items = {1: dict(texels=maps[k], filter="bilinear", gamma=2.2)}
+        first[k] = timed(tr[k].set_mesh_emission_maps, items)       # 2^20 texels: 4 B each up, 16 B each kept
+        again[k] = [timed(tr[k].set_mesh_emission_maps, items) for _ in range(reps)]
+    for t in tr.values():
+        rate(t)                                                     # warm-up (and the dispatch order's first costs)
+        rate(t)
+    rates = {k: [] for k in sides}
+    for _ in range(reps):
+        for k in sides:
+            rates[k].append(rate(tr[k]))
+    for t in tr.values():
+        t.close()
+    med = {k: stats(rates[k])["median"] for k in sides}
+    out = {"workload": "mesh_scene mesh emission maps %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "reps": reps,
+           "map": "1024x1024 RGBA8, bilinear, gamma 2.2, on the ON torus, over 2 x 1024x1024 RGBA8, bilinear, repeat",
+           "first_set_mesh_emission_maps_ms": first, "set_mesh_emission_maps_again_ms": {k: stats(v) for k, v in again.items()},
+           "gsamples_per_s": {k: stats(rates[k]) for k in sides},
+           "ones_over_lit_rate": med["ones"] / med["lit"], "noise_over_lit_rate": med["noise"] / med["lit"]}
     # moves: the medium move and back, so that every call moves every vertex
     moved = scenes.mesh_scene_moved(s, 0.5)
     dev = lambda arrays: {m: torch.from_numpy(np.ascontiguousarray(v, np.float32)).to("cuda:0") for m, v in enumerate(arrays)}   # noqa: E731
