@@ -415,12 +415,12 @@ def trace(path, col, row, width, height, draws):
     return radiance, rays, M.m
 
 
-def sample_pixels(path, oracle, seed, pixels, w, h):
-    """One sample of each of `pixels` [(col, row)] through `path`, frame 0 -> (radiance [n, 3], margins [n]).  The oracle only
-    supplies the random draws (rng_f32)."""
+def sample_pixels(path, oracle, seed, pixels, w, h, frame=0):
+    """One sample of each of `pixels` [(col, row)] through `path`, of frame `frame` -> (radiance [n, 3], margins [n]).  The oracle
+    only supplies the random draws (rng_f32)."""
     out, marg = np.zeros((len(pixels), 3)), np.zeros(len(pixels))
     for k, (c, r) in enumerate(pixels):
-        dr = oracle.rng_f32(seed, 0, int(r) * w + int(c), N_DRAWS)
+        dr = oracle.rng_f32(seed, frame, int(r) * w + int(c), N_DRAWS)
         out[k], _, marg[k] = path.sample(int(c), int(r), w, h, dr)
     return out, marg
 
