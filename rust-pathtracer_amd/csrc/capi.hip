@@ -24,6 +24,7 @@
 #include "host_emap.h"
 #include "host_env.h"
 #include "host_light.h"
+#include "host_map.h"
 #include "host_mmap.h"
 #include "host_move.h"
 #include "host_nrm.h"
@@ -1632,19 +1633,25 @@ int rpt_download_mesh_normals(rpt_ctx* ctx, uint32_t mesh, float* normals, uint3
     return RPT_OK;
 }
 
-// The emission maps' two descriptor tables of device d again (host_emap.h, emap_desc_table and emap_light_desc_table): after a
-// texture call (the texture ordinals or a wrap may have changed), after a light call (the light ordinals), and inside
-// rpt_set_mesh_emission_maps.  The device is idle (the caller waited) and the texels stay where they are.
+// A descriptor table written at `off` of a device's map tables.  The device is idle (the caller waited).
+static int put_desc(rpt_ctx* ctx, void* tables, size_t off, const std::vector<uint32_t>& desc)
+{
+    if (!desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(static_cast<unsigned char*>(tables) + off, desc.data(), 4 * desc.size(), hipMemcpyHostToDevice));
+    return RPT_OK;
+}
+
+// The descriptors of device d's cutouts, normal maps, material maps and emission maps again, by the texture ordinals and wraps of
+// ctx->tex (host_cut.h, cut_desc_table; host_map.h, map_desc_table): after a texture call, and inside the feature's own setter.  The
+// masks and the texels stay where they are.  The emission maps have a second table by light ordinal (host_emap.h,
+// emap_light_desc_table), so theirs are written after a light call too.
+static int cut_desc_device(rpt_ctx* ctx, DevState& d) { return put_desc(ctx, d.cut, ctx->cut.layout().off_desc, rpthost::cut_desc_table(ctx->cut, ctx->tex)); }
+static int nrm_desc_device(rpt_ctx* ctx, DevState& d) { return put_desc(ctx, d.nrm, ctx->nrm.layout().off_desc, rpthost::nrm_desc_table(ctx->nrm, ctx->tex)); }
+static int mmap_desc_device(rpt_ctx* ctx, DevState& d) { return put_desc(ctx, d.mmap, ctx->mmap.layout().off_desc, rpthost::mmap_desc_table(ctx->mmap, ctx->tex)); }
 static int emap_desc_device(rpt_ctx* ctx, DevState& d)
 {
-    const rpthost::EmapPlan& ep = ctx->emap;
-    const rpthost::EmapLayout el = ep.layout();
-    const std::vector<uint32_t> desc = rpthost::emap_desc_table(ep, ctx->tex);
-    const std::vector<uint32_t> light_desc = rpthost::emap_light_desc_table(ep, ctx->tex, ctx->light);
-    unsigned char* base = static_cast<unsigned char*>(d.emap);
-    if (!desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(base + el.off_desc, desc.data(), 4 * desc.size(), hipMemcpyHostToDevice));
-    if (!light_desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(base + el.off_light_desc, light_desc.data(), 4 * light_desc.size(), hipMemcpyHostToDevice));
-    return RPT_OK;
+    const rpthost::EmapLayout el = ctx->emap.layout();
+    RPT_CHECK_RC(put_desc(ctx, d.emap, el.off_desc, rpthost::emap_desc_table(ctx->emap, ctx->tex)));
+    return put_desc(ctx, d.emap, el.off_light_desc, rpthost::emap_light_desc_table(ctx->emap, ctx->tex, ctx->light));
 }
 
 // ---- rpt_set_mesh_lights / rpt_download_mesh_light_table (include/rpt.h, "mesh lights") --------------------------------------------
@@ -1756,38 +1763,49 @@ int rpt_download_mesh_light_table(rpt_ctx* ctx, uint32_t mesh, uint64_t* cdf, ui
     return RPT_OK;
 }
 
-// The cutout descriptors of device d again, by the texture ordinals and wraps of ctx->tex (host_cut.h, cut_desc_table): after a texture
-// call, and inside rpt_set_mesh_cutouts.  The device is idle (the caller waited) and the masks stay where they are.
-static int cut_desc_device(rpt_ctx* ctx, DevState& d)
+// ---- what rpt_set_mesh_textures and the four image-map setters share ----------------------------------------------------------------
+// "Every mesh OFF (again)": wait on every device that holds `slot` tables (a launch may still read them) and free them.
+static int free_tables(rpt_ctx* ctx, DeviceGuard& guard, void* DevState::*slot, const char* call)
 {
-    const rpthost::CutPlan& cp = ctx->cut;
-    const rpthost::CutLayout cl = cp.layout();
-    const std::vector<uint32_t> desc = rpthost::cut_desc_table(cp, ctx->tex);
-    if (!desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(static_cast<unsigned char*>(d.cut) + cl.off_desc, desc.data(), 4 * desc.size(), hipMemcpyHostToDevice));
+    for (DevState& d : ctx->devs) {
+        if (!(d.*slot)) continue;
+        if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+            set_err(ctx, "%s: cannot wait for device %d", call, d.device);
+            return RPT_ERR_HIP;
+        }
+        (void)hipFree(d.*slot);
+        d.*slot = nullptr;
+    }
     return RPT_OK;
 }
 
-// The normal maps' descriptors of device d again, by the texture ordinals and wraps of ctx->tex (host_nrm.h, nrm_desc_table): after a
-// texture call, and inside rpt_set_mesh_normal_maps.  The device is idle (the caller waited) and the texels stay where they are.
-static int nrm_desc_device(rpt_ctx* ctx, DevState& d)
+// A setter failed on some device after it began to change the context: the scene goes, the first message stays.
+static int fail_without_scene(rpt_ctx* ctx, int rc)
 {
-    const rpthost::NrmPlan& np = ctx->nrm;
-    const rpthost::NrmLayout nl = np.layout();
-    const std::vector<uint32_t> desc = rpthost::nrm_desc_table(np, ctx->tex);
-    if (!desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(static_cast<unsigned char*>(d.nrm) + nl.off_desc, desc.data(), 4 * desc.size(), hipMemcpyHostToDevice));
-    return RPT_OK;
+    const std::string first = ctx->err;
+    drop_scene(ctx);
+    set_err(ctx, "%s; the context now holds no scene", first.c_str());
+    return rc;
 }
 
-// The material maps' descriptors of device d again, likewise (host_mmap.h, mmap_desc_table): after a texture call, and inside
-// rpt_set_mesh_material_maps.
-static int mmap_desc_device(rpt_ctx* ctx, DevState& d)
-{
-    const rpthost::MmapPlan& mp = ctx->mmap;
-    const rpthost::MmapLayout ml = mp.layout();
-    const std::vector<uint32_t> desc = rpthost::mmap_desc_table(mp, ctx->tex);
-    if (!desc.empty()) RPT_HIP_CHECK(ctx, hipMemcpy(static_cast<unsigned char*>(d.mmap) + ml.off_desc, desc.data(), 4 * desc.size(), hipMemcpyHostToDevice));
-    return RPT_OK;
-}
+// The four features that read a mesh's texture (its UVs and wrap), in the order rpt_set_mesh_textures visits them.
+struct TexReader {
+    const char *a_thing, *thing, *call;
+    void* DevState::*slot;
+    bool (*on)(const rpt_ctx&, uint32_t mesh);
+    bool (*any)(const rpt_ctx&);
+    int (*desc_device)(rpt_ctx*, DevState&);
+};
+static const TexReader kTexReaders[4] = {
+    {"a cutout", "cutout", "rpt_set_mesh_cutouts", &DevState::cut,
+     [](const rpt_ctx& c, uint32_t m) { return c.cut.on(m); }, [](const rpt_ctx& c) { return c.cut.any(); }, cut_desc_device},
+    {"a normal map", "normal map", "rpt_set_mesh_normal_maps", &DevState::nrm,
+     [](const rpt_ctx& c, uint32_t m) { return c.nrm.on(m); }, [](const rpt_ctx& c) { return c.nrm.any(); }, nrm_desc_device},
+    {"a material map", "material map", "rpt_set_mesh_material_maps", &DevState::mmap,
+     [](const rpt_ctx& c, uint32_t m) { return c.mmap.on(m); }, [](const rpt_ctx& c) { return c.mmap.any(); }, mmap_desc_device},
+    {"an emission map", "emission map", "rpt_set_mesh_emission_maps", &DevState::emap,
+     [](const rpt_ctx& c, uint32_t m) { return c.emap.on(m); }, [](const rpt_ctx& c) { return c.emap.any(); }, emap_desc_device},
+};
 
 // ---- rpt_set_mesh_textures / rpt_download_mesh_texture (include/rpt.h, "mesh textures") -------------------------------------------
 // One device's part: wait for its earlier work (a launch may still read the old tables), make its refit tables if it has none, make
@@ -1859,26 +1877,12 @@ int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t 
     std::string why;
     const int rc = check_mesh_textures(ctx->refit, ctx->scene.kind == SceneKind::mesh, items, n_items, ctx->tex.image, image, why);
     if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
-    for (uint32_t m = 0; m < image.size(); ++m)                     // include/rpt.h, "mesh cutouts": the cutout reads the texture's UVs and wrap
-        if (image[m].width == 0u && ctx->cut.on(m)) {
-            set_err(ctx, "rpt_set_mesh_textures: mesh %u has a cutout, which reads its texture's UVs and wrap: remove the cutout first (rpt_set_mesh_cutouts)", m);
-            return RPT_ERR_INVALID_ARG;
-        }
-    for (uint32_t m = 0; m < image.size(); ++m)                     // include/rpt.h, "mesh normal maps": the map reads the texture's UVs and wrap
-        if (image[m].width == 0u && ctx->nrm.on(m)) {
-            set_err(ctx, "rpt_set_mesh_textures: mesh %u has a normal map, which reads its texture's UVs and wrap: remove the normal map first (rpt_set_mesh_normal_maps)", m);
-            return RPT_ERR_INVALID_ARG;
-        }
-    for (uint32_t m = 0; m < image.size(); ++m)                     // include/rpt.h, "mesh material maps": the map reads the texture's UVs and wrap
-        if (image[m].width == 0u && ctx->mmap.on(m)) {
-            set_err(ctx, "rpt_set_mesh_textures: mesh %u has a material map, which reads its texture's UVs and wrap: remove the material map first (rpt_set_mesh_material_maps)", m);
-            return RPT_ERR_INVALID_ARG;
-        }
-    for (uint32_t m = 0; m < image.size(); ++m)                     // include/rpt.h, "mesh emission maps": the map reads the texture's UVs and wrap
-        if (image[m].width == 0u && ctx->emap.on(m)) {
-            set_err(ctx, "rpt_set_mesh_textures: mesh %u has an emission map, which reads its texture's UVs and wrap: remove the emission map first (rpt_set_mesh_emission_maps)", m);
-            return RPT_ERR_INVALID_ARG;
-        }
+    for (const TexReader& r : kTexReaders)                          // include/rpt.h, "mesh cutouts" and the maps: each reads the texture's UVs and wrap
+        for (uint32_t m = 0; m < image.size(); ++m)
+            if (image[m].width == 0u && r.on(*ctx, m)) {
+                set_err(ctx, "rpt_set_mesh_textures: mesh %u has %s, which reads its texture's UVs and wrap: remove the %s first (%s)", m, r.a_thing, r.thing, r.call);
+                return RPT_ERR_INVALID_ARG;
+            }
     if (n_items == 0) return RPT_OK;
     bool any = false;
     for (const TexImage& im : image) any = any || im.width != 0u;
@@ -1886,16 +1890,7 @@ int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t 
     int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
     if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_textures: cannot select device %d", ctx->devs[0].device);
     if (rc_dev == RPT_OK && !any) {                                 // no mesh textured (again): the context is what it was before the first call
-        for (DevState& d : ctx->devs) {
-            if (!d.tex) continue;
-            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
-                set_err(ctx, "rpt_set_mesh_textures: cannot wait for device %d", d.device);
-                rc_dev = RPT_ERR_HIP;
-                break;
-            }
-            (void)hipFree(d.tex);
-            d.tex = nullptr;
-        }
+        rc_dev = free_tables(ctx, guard, &DevState::tex, "rpt_set_mesh_textures");
         if (rc_dev == RPT_OK) { ctx->tex = TexPlan(); return RPT_OK; }
     }
     TexPlan old;
@@ -1909,17 +1904,10 @@ int rpt_set_mesh_textures(rpt_ctx* ctx, const rpt_mesh_texture* items, uint32_t 
         DevState& d = ctx->devs[i];
         if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_textures: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
         else rc_dev = tex_device(ctx, d, old, items, n_items);
-        if (rc_dev == RPT_OK && d.cut && ctx->cut.any()) rc_dev = cut_desc_device(ctx, d);      // the ordinals or a wrap may have changed
-        if (rc_dev == RPT_OK && d.nrm && ctx->nrm.any()) rc_dev = nrm_desc_device(ctx, d);
-        if (rc_dev == RPT_OK && d.mmap && ctx->mmap.any()) rc_dev = mmap_desc_device(ctx, d);
-        if (rc_dev == RPT_OK && d.emap && ctx->emap.any()) rc_dev = emap_desc_device(ctx, d);
+        for (const TexReader& r : kTexReaders)                      // the ordinals or a wrap may have changed
+            if (rc_dev == RPT_OK && d.*r.slot && r.any(*ctx)) rc_dev = r.desc_device(ctx, d);
     }
-    if (rc_dev != RPT_OK) {
-        const std::string first = ctx->err;
-        drop_scene(ctx);
-        set_err(ctx, "%s; the context now holds no scene", first.c_str());
-        return rc_dev;
-    }
+    if (rc_dev != RPT_OK) return fail_without_scene(ctx, rc_dev);
     ctx->refit.release_staging();                                   // every device holds the refit tables
     ctx->tex.release_staging();
     return RPT_OK;
@@ -2069,62 +2057,113 @@ int rpt_download_environment_table(rpt_ctx* ctx, uint64_t* cdf, uint32_t n_texel
     return RPT_OK;
 }
 
-// ---- rpt_set_mesh_cutouts / rpt_download_mesh_cutout (include/rpt.h, "mesh cutouts") -----------------------------------------------
-// One device's part: wait for its earlier work (a launch may still read the old tables), make the new tables, copy the kept meshes'
-// masks over from the old ones on the device, pack the named meshes' masks, write the descriptors, drop the old tables, and wait.
-// ctx->cut is already the new plan; `old` is the plan the old tables were made by.  (The refit's tables are there: the meshes are
-// textured.)
-static int cut_device(rpt_ctx* ctx, DevState& d, const rpthost::CutPlan& old, const rpt_mesh_cutout* items, uint32_t n_items)
+// ---- the image-map setters: rpt_set_mesh_cutouts, rpt_set_mesh_normal_maps, rpt_set_mesh_material_maps, rpt_set_mesh_emission_maps --
+// (include/rpt.h, "mesh cutouts", "mesh normal maps", "mesh material maps", "mesh emission maps").  One path: what a feature adds is
+// its MapFeature, its plan and its decode launch.
+struct MapFeature {
+    void* DevState::*slot;            // its tables on a device
+    const char* call;                 // "rpt_set_mesh_normal_maps"
+    const char* holds;                // what a table holds per mesh, for a message: "texels", "mask"
+    rpthost::MapConsts k;             // host_map.h
+    int (*desc_device)(rpt_ctx*, DevState&);
+};
+
+extern "C++" {                        // (templates)
+// One device's part: wait for its earlier work (a launch may still read the old tables), make the new tables, stage and decode the
+// named meshes' images, copy the kept meshes' over from the old tables on the device, wait, drop the old tables and write the
+// descriptors: host_map.h's recipe, walked.  `now` is already the context's plan; `old` is the plan the old tables were made by.
+// decode(mesh, staged, dst, n, stream) launches the feature's kernel over the n staged texels of `mesh`.  (The refit's tables are
+// there: the meshes are textured.)
+template <class Plan, class Decode>
+static int map_device(rpt_ctx* ctx, DevState& d, const MapFeature& f, const Plan& now, const Plan& old, const std::vector<rpthost::MapNamed>& named, Decode decode)
 {
-    const rpthost::CutPlan& cp = ctx->cut;
-    const rpthost::CutLayout cl = cp.layout();
-    const rpthost::CutLayout ol = old.layout();
+    const auto nl = now.layout();
+    const auto ol = old.layout();
+    void*& tables = d.*f.slot;
+    const rpthost::MapRecipe r = rpthost::map_recipe(now.slots(), old.slots(), tables != nullptr, named, f.k);
+    if (r.missing != rpthost::kMapNoMesh) { set_err(ctx, "%s: device %d holds no %s for mesh %u", f.call, d.device, f.holds, r.missing); return RPT_ERR_HIP; }
     RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
     RPT_CHECK_RC(ensure_refit(ctx, d));
     void* fresh = nullptr;
-    void* stage = nullptr;
-    RPT_HIP_CHECK(ctx, hipMalloc(&fresh, cl.total));
-    size_t stage_bytes = 0;                                         // the named masks' bytes, in one allocation that lives until the kernels have run
-    for (uint32_t i = 0; i < n_items; ++i)
-        if (items[i].mode == RPT_MESH_CUTOUT_ON) stage_bytes += ((size_t)items[i].width * items[i].height + 15) & ~(size_t)15;
+    void* stage = nullptr;                                          // the named images' bytes, in one allocation that lives until the decodes have run
+    RPT_HIP_CHECK(ctx, hipMalloc(&fresh, nl.total));
     const auto fail = [&](int rc) { (void)hipFree(fresh); if (stage) (void)hipFree(stage); return rc; };
     const auto work = [&]() -> int {
-        if (stage_bytes) RPT_HIP_CHECK(ctx, hipMalloc(&stage, stage_bytes));
+        if (r.stage_bytes) RPT_HIP_CHECK(ctx, hipMalloc(&stage, r.stage_bytes));
         unsigned char* base = static_cast<unsigned char*>(fresh);
-        uint32_t* words = reinterpret_cast<uint32_t*>(base + cl.off_bits);
-        RPT_HIP_CHECK(ctx, hipMemsetAsync(base, 0, cl.off_none, d.stream));
-        if (cl.off_bits > cl.off_none) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + cl.off_none, 0xFF, cl.off_bits - cl.off_none, d.stream));
-        if (cl.total > cl.off_bits) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + cl.off_bits, 0, cl.total - cl.off_bits, d.stream));
-        std::vector<uint8_t> named(cp.mask.size(), 0);
-        size_t at = 0;
-        for (uint32_t i = 0; i < n_items; ++i) {
-            const rpt_mesh_cutout& it = items[i];
-            named[it.mesh] = 1;
-            if (it.mode != RPT_MESH_CUTOUT_ON) continue;
-            const rpthost::CutMask& c = cp.mask[it.mesh];
-            const size_t n = (size_t)c.width * c.height;
-            uint8_t* at_dev = static_cast<uint8_t*>(stage) + at;
-            RPT_HIP_CHECK(ctx, hipMemcpyAsync(at_dev, it.alpha, n, hipMemcpyHostToDevice, d.stream));
-            RPT_HIP_CHECK(ctx, rptlaunch::cut_mask(at_dev, words + c.first, (uint32_t)n, c.threshold, d.stream));
-            at += (n + 15) & ~(size_t)15;
+        unsigned char* elems = base + nl.off_elems();
+        for (const rpthost::MapFill& fl : nl.fills())
+            if (fl.bytes) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + fl.off, fl.value, fl.bytes, d.stream));
+        for (const rpthost::MapRecipe::Item& it : r.items) {
+            unsigned char* staged = static_cast<unsigned char*>(stage) + it.stage;
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(staged + f.k.prefix, named[it.index].src, f.k.src_bytes * (size_t)it.count, hipMemcpyHostToDevice, d.stream));
+            RPT_HIP_CHECK(ctx, decode(named[it.index].mesh, staged, elems + f.k.elem_bytes * (size_t)it.dst, (uint32_t)it.count, d.stream));
         }
-        for (uint32_t m = 0; m < cp.mask.size(); ++m) {
-            if (named[m] || !cp.mask[m].width) continue;            // a mesh not named keeps its cutout: the bits move on the device
-            if (!d.cut || !old.on(m)) { set_err(ctx, "rpt_set_mesh_cutouts: device %d holds no mask for mesh %u", d.device, m); return RPT_ERR_HIP; }
-            RPT_HIP_CHECK(ctx, hipMemcpyAsync(words + cp.mask[m].first,
-                                              reinterpret_cast<const uint32_t*>(static_cast<const unsigned char*>(d.cut) + ol.off_bits) + old.mask[m].first,
-                                              4 * (size_t)rpthost::cut_mask_words(cp.mask[m].width, cp.mask[m].height), hipMemcpyDeviceToDevice, d.stream));
-        }
+        for (const rpthost::MapRecipe::Keep& kp : r.keeps)         // a mesh not named keeps its image: it moves on the device
+            RPT_HIP_CHECK(ctx, hipMemcpyAsync(elems + f.k.elem_bytes * (size_t)kp.dst,
+                                              static_cast<const unsigned char*>(tables) + ol.off_elems() + f.k.elem_bytes * (size_t)kp.src, kp.bytes,
+                                              hipMemcpyDeviceToDevice, d.stream));
         RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
         return RPT_OK;
     };
     const int rc = work();
     if (rc != RPT_OK) return fail(rc);
     if (stage) (void)hipFree(stage);
-    if (d.cut) (void)hipFree(d.cut);
-    d.cut = fresh;
-    return cut_desc_device(ctx, d);
+    if (tables) (void)hipFree(tables);
+    tables = fresh;
+    return f.desc_device(ctx, d);
 }
+
+// A setter after its checks: `entries` is what they made of the items, `plan` the context's, `build` the feature's build_*_plan.
+template <class Plan, class Entry, class Decode>
+static int set_mesh_maps(rpt_ctx* ctx, const MapFeature& f, Plan& plan, std::vector<Entry> entries, void (*build)(const rpthost::RefitPlan&, std::vector<Entry>, Plan&),
+                         const std::vector<rpthost::MapNamed>& named, Decode decode)
+{
+    if (named.empty()) return RPT_OK;
+    bool any = false;
+    for (const Entry& c : entries) any = any || c.width != 0u;
+    if (!any && !plan.any()) return RPT_OK;                         // every map OFF, as before
+    DeviceGuard guard(ctx->devs[0].device);
+    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
+    if (rc_dev != RPT_OK) set_err(ctx, "%s: cannot select device %d", f.call, ctx->devs[0].device);
+    if (rc_dev == RPT_OK && !any) {                                 // every map OFF (again): the context is what it was before the first call
+        rc_dev = free_tables(ctx, guard, f.slot, f.call);
+        if (rc_dev == RPT_OK) { plan = Plan(); return RPT_OK; }
+    }
+    Plan old;
+    if (rc_dev == RPT_OK) {
+        old = std::move(plan);
+        build(ctx->refit, std::move(entries), plan);
+    }
+    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
+        DevState& d = ctx->devs[i];
+        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "%s: cannot select device %d", f.call, d.device); rc_dev = RPT_ERR_HIP; }
+        else rc_dev = map_device(ctx, d, f, plan, old, named, decode);
+    }
+    return rc_dev == RPT_OK ? RPT_OK : fail_without_scene(ctx, rc_dev);
+}
+
+// rpt_download_mesh_normal_map, rpt_download_mesh_material_map and rpt_download_mesh_emission_map: `call` is the entry point's name,
+// `thing` "normal map", `setter` "rpt_set_mesh_normal_maps".
+template <class Plan>
+static int download_map(rpt_ctx* ctx, const char* call, const char* thing, const char* setter, Plan rpt_ctx::*plan_of, void* DevState::*slot, uint32_t mesh,
+                        float* texels, uint32_t width, uint32_t height)
+{
+    if (!ctx) { set_err(nullptr, "%s: ctx is NULL", call); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "%s: needs an uploaded scene with meshes", call); return RPT_ERR_NO_SCENE; }
+    const rpthost::RefitPlan& plan = ctx->refit;
+    if (mesh >= plan.n_meshes()) { set_err(ctx, "%s: mesh %u out of range (the scene has %u)", call, mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
+    const void* tables = ctx->devs[0].*slot;
+    const Plan& p = ctx->*plan_of;
+    if (!p.on(mesh) || !tables) { set_err(ctx, "%s: mesh %u has no %s: the context holds no texels for it (%s)", call, mesh, thing, setter); return RPT_ERR_INVALID_ARG; }
+    const auto& c = p.map[mesh];
+    if (width != c.width || height != c.height) { set_err(ctx, "%s: mesh %u: %u x %u is not its map's %u x %u", call, mesh, width, height, c.width, c.height); return RPT_ERR_INVALID_ARG; }
+    if (!texels) { set_err(ctx, "%s: texels is NULL", call); return RPT_ERR_INVALID_ARG; }
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, hipMemcpy(texels, static_cast<const unsigned char*>(tables) + p.layout().off_texels + 16 * (size_t)c.first, 16 * (size_t)c.width * c.height, hipMemcpyDeviceToHost));
+    return RPT_OK;
+}
+}  // extern "C++"
 
 int rpt_set_mesh_cutouts(rpt_ctx* ctx, const rpt_mesh_cutout* items, uint32_t n_items)
 {
@@ -2134,43 +2173,11 @@ int rpt_set_mesh_cutouts(rpt_ctx* ctx, const rpt_mesh_cutout* items, uint32_t n_
     std::string why;
     const int rc = check_mesh_cutouts(ctx->refit, ctx->scene.kind == SceneKind::mesh, ctx->tex, ctx->light, items, n_items, ctx->cut.mask, mask, why);
     if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
-    if (n_items == 0) return RPT_OK;
-    bool any = false;
-    for (const CutMask& c : mask) any = any || c.width != 0u;
-    if (!any && !ctx->cut.any()) return RPT_OK;                     // every cutout OFF, as before
-    DeviceGuard guard(ctx->devs[0].device);
-    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
-    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_cutouts: cannot select device %d", ctx->devs[0].device);
-    if (rc_dev == RPT_OK && !any) {                                 // every cutout OFF (again): the context is what it was before the first call
-        for (DevState& d : ctx->devs) {
-            if (!d.cut) continue;
-            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
-                set_err(ctx, "rpt_set_mesh_cutouts: cannot wait for device %d", d.device);
-                rc_dev = RPT_ERR_HIP;
-                break;
-            }
-            (void)hipFree(d.cut);
-            d.cut = nullptr;
-        }
-        if (rc_dev == RPT_OK) { ctx->cut = CutPlan(); return RPT_OK; }
-    }
-    CutPlan old;
-    if (rc_dev == RPT_OK) {
-        old = std::move(ctx->cut);
-        build_cut_plan(ctx->refit, std::move(mask), ctx->cut);
-    }
-    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
-        DevState& d = ctx->devs[i];
-        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_cutouts: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
-        else rc_dev = cut_device(ctx, d, old, items, n_items);
-    }
-    if (rc_dev != RPT_OK) {
-        const std::string first = ctx->err;
-        drop_scene(ctx);
-        set_err(ctx, "%s; the context now holds no scene", first.c_str());
-        return rc_dev;
-    }
-    return RPT_OK;
+    static const MapFeature f = {&DevState::cut, "rpt_set_mesh_cutouts", "mask", {4, 1, 0}, cut_desc_device};
+    return set_mesh_maps(ctx, f, ctx->cut, std::move(mask), build_cut_plan, map_named(items, n_items, &rpt_mesh_cutout::alpha),
+                         [ctx](uint32_t mesh, unsigned char* staged, unsigned char* dst, uint32_t n, hipStream_t st) {
+                             return rptlaunch::cut_mask(staged, reinterpret_cast<uint32_t*>(dst), n, ctx->cut.mask[mesh].threshold, st);
+                         });
 }
 
 int rpt_download_mesh_cutout(rpt_ctx* ctx, uint32_t mesh, uint32_t* bits, uint32_t n_words)
@@ -2192,63 +2199,6 @@ int rpt_download_mesh_cutout(rpt_ctx* ctx, uint32_t mesh, uint32_t* bits, uint32
     return RPT_OK;
 }
 
-// ---- rpt_set_mesh_normal_maps / rpt_download_mesh_normal_map (include/rpt.h, "mesh normal maps") -----------------------------------
-// One device's part: wait for its earlier work (a launch may still read the old tables), make the new tables, copy the kept meshes'
-// texels over from the old ones on the device, decode the named meshes' maps, write the descriptors, drop the old tables, and wait.
-// ctx->nrm is already the new plan; `old` is the plan the old tables were made by.  (The refit's tables are there: the meshes are
-// textured.)
-static int nrm_device(rpt_ctx* ctx, DevState& d, const rpthost::NrmPlan& old, const rpt_mesh_normal_map* items, uint32_t n_items)
-{
-    const rpthost::NrmPlan& np = ctx->nrm;
-    const rpthost::NrmLayout nl = np.layout();
-    const rpthost::NrmLayout ol = old.layout();
-    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
-    RPT_CHECK_RC(ensure_refit(ctx, d));
-    void* fresh = nullptr;
-    void* stage = nullptr;
-    RPT_HIP_CHECK(ctx, hipMalloc(&fresh, nl.total));
-    size_t stage_bytes = 0;                                         // the named maps' bytes, in one allocation that lives until the decodes have run
-    for (uint32_t i = 0; i < n_items; ++i)
-        if (items[i].mode == RPT_MESH_NORMAL_MAP_ON) stage_bytes += ((size_t)items[i].width * items[i].height * 4 + 15) & ~(size_t)15;
-    const auto fail = [&](int rc) { (void)hipFree(fresh); if (stage) (void)hipFree(stage); return rc; };
-    const auto work = [&]() -> int {
-        if (stage_bytes) RPT_HIP_CHECK(ctx, hipMalloc(&stage, stage_bytes));
-        unsigned char* base = static_cast<unsigned char*>(fresh);
-        rpthost::TexTexel* texels = reinterpret_cast<rpthost::TexTexel*>(base + nl.off_texels);
-        RPT_HIP_CHECK(ctx, hipMemsetAsync(base, 0, nl.off_none, d.stream));
-        if (nl.off_texels > nl.off_none) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + nl.off_none, 0xFF, nl.off_texels - nl.off_none, d.stream));
-        std::vector<uint8_t> named(np.map.size(), 0);
-        size_t at = 0;
-        for (uint32_t i = 0; i < n_items; ++i) {
-            const rpt_mesh_normal_map& it = items[i];
-            named[it.mesh] = 1;
-            if (it.mode != RPT_MESH_NORMAL_MAP_ON) continue;
-            const rpthost::NrmMap& c = np.map[it.mesh];
-            const size_t n = (size_t)c.width * c.height;
-            uint8_t* at_dev = static_cast<uint8_t*>(stage) + at;
-            RPT_HIP_CHECK(ctx, hipMemcpyAsync(at_dev, it.texels, 4 * n, hipMemcpyHostToDevice, d.stream));
-            RPT_HIP_CHECK(ctx, rptlaunch::nrm_decode(at_dev, texels + c.first, (uint32_t)n, c.strength, rpthost::nrm_scale_y(c.strength, c.flags), d.stream));
-            at += (4 * n + 15) & ~(size_t)15;
-        }
-        for (uint32_t m = 0; m < np.map.size(); ++m) {
-            if (named[m] || !np.map[m].width) continue;             // a mesh not named keeps its map: the decoded texels move on the device
-            if (!d.nrm || !old.on(m)) { set_err(ctx, "rpt_set_mesh_normal_maps: device %d holds no texels for mesh %u", d.device, m); return RPT_ERR_HIP; }
-            const size_t n = (size_t)np.map[m].width * np.map[m].height;
-            RPT_HIP_CHECK(ctx, hipMemcpyAsync(texels + np.map[m].first,
-                                              reinterpret_cast<const rpthost::TexTexel*>(static_cast<const unsigned char*>(d.nrm) + ol.off_texels) + old.map[m].first,
-                                              16 * n, hipMemcpyDeviceToDevice, d.stream));
-        }
-        RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
-        return RPT_OK;
-    };
-    const int rc = work();
-    if (rc != RPT_OK) return fail(rc);
-    if (stage) (void)hipFree(stage);
-    if (d.nrm) (void)hipFree(d.nrm);
-    d.nrm = fresh;
-    return nrm_desc_device(ctx, d);
-}
-
 int rpt_set_mesh_normal_maps(rpt_ctx* ctx, const rpt_mesh_normal_map* items, uint32_t n_items)
 {
     using namespace rpthost;
@@ -2257,117 +2207,17 @@ int rpt_set_mesh_normal_maps(rpt_ctx* ctx, const rpt_mesh_normal_map* items, uin
     std::string why;
     const int rc = check_mesh_normal_maps(ctx->refit, ctx->scene.kind == SceneKind::mesh, ctx->tex, items, n_items, ctx->nrm.map, map, why);
     if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
-    if (n_items == 0) return RPT_OK;
-    bool any = false;
-    for (const NrmMap& c : map) any = any || c.width != 0u;
-    if (!any && !ctx->nrm.any()) return RPT_OK;                     // every map OFF, as before
-    DeviceGuard guard(ctx->devs[0].device);
-    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
-    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_normal_maps: cannot select device %d", ctx->devs[0].device);
-    if (rc_dev == RPT_OK && !any) {                                 // every map OFF (again): the context is what it was before the first call
-        for (DevState& d : ctx->devs) {
-            if (!d.nrm) continue;
-            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
-                set_err(ctx, "rpt_set_mesh_normal_maps: cannot wait for device %d", d.device);
-                rc_dev = RPT_ERR_HIP;
-                break;
-            }
-            (void)hipFree(d.nrm);
-            d.nrm = nullptr;
-        }
-        if (rc_dev == RPT_OK) { ctx->nrm = NrmPlan(); return RPT_OK; }
-    }
-    NrmPlan old;
-    if (rc_dev == RPT_OK) {
-        old = std::move(ctx->nrm);
-        build_nrm_plan(ctx->refit, std::move(map), ctx->nrm);
-    }
-    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
-        DevState& d = ctx->devs[i];
-        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_normal_maps: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
-        else rc_dev = nrm_device(ctx, d, old, items, n_items);
-    }
-    if (rc_dev != RPT_OK) {
-        const std::string first = ctx->err;
-        drop_scene(ctx);
-        set_err(ctx, "%s; the context now holds no scene", first.c_str());
-        return rc_dev;
-    }
-    return RPT_OK;
+    static const MapFeature f = {&DevState::nrm, "rpt_set_mesh_normal_maps", "texels", {16, 4, 0}, nrm_desc_device};
+    return set_mesh_maps(ctx, f, ctx->nrm, std::move(map), build_nrm_plan, map_named(items, n_items, &rpt_mesh_normal_map::texels),
+                         [ctx](uint32_t mesh, unsigned char* staged, unsigned char* dst, uint32_t n, hipStream_t st) {
+                             const NrmMap& c = ctx->nrm.map[mesh];
+                             return rptlaunch::nrm_decode(staged, reinterpret_cast<TexTexel*>(dst), n, c.strength, nrm_scale_y(c.strength, c.flags), st);
+                         });
 }
 
 int rpt_download_mesh_normal_map(rpt_ctx* ctx, uint32_t mesh, float* texels, uint32_t width, uint32_t height)
 {
-    if (!ctx) { set_err(nullptr, "rpt_download_mesh_normal_map: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_mesh_normal_map: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    const rpthost::RefitPlan& plan = ctx->refit;
-    if (mesh >= plan.n_meshes()) { set_err(ctx, "rpt_download_mesh_normal_map: mesh %u out of range (the scene has %u)", mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
-    const DevState& d = ctx->devs[0];
-    const rpthost::NrmPlan& np = ctx->nrm;
-    if (!np.on(mesh) || !d.nrm) { set_err(ctx, "rpt_download_mesh_normal_map: mesh %u has no normal map: the context holds no texels for it (rpt_set_mesh_normal_maps)", mesh); return RPT_ERR_INVALID_ARG; }
-    const rpthost::NrmMap& c = np.map[mesh];
-    if (width != c.width || height != c.height) { set_err(ctx, "rpt_download_mesh_normal_map: mesh %u: %u x %u is not its map's %u x %u", mesh, width, height, c.width, c.height); return RPT_ERR_INVALID_ARG; }
-    if (!texels) { set_err(ctx, "rpt_download_mesh_normal_map: texels is NULL"); return RPT_ERR_INVALID_ARG; }
-    RPT_ON_DEVICE(ctx);
-    const rpthost::NrmLayout nl = np.layout();
-    RPT_HIP_CHECK(ctx, hipMemcpy(texels, static_cast<const unsigned char*>(d.nrm) + nl.off_texels + 16 * (size_t)c.first, 16 * (size_t)c.width * c.height, hipMemcpyDeviceToHost));
-    return RPT_OK;
-}
-
-// ---- rpt_set_mesh_material_maps / rpt_download_mesh_material_map (include/rpt.h, "mesh material maps") -----------------------------
-// One device's part, as nrm_device: wait for its earlier work (a launch may still read the old tables), make the new tables, copy the
-// kept meshes' texels over from the old ones on the device, decode the named meshes' maps, write the descriptors, drop the old
-// tables, and wait.  ctx->mmap is already the new plan; `old` is the plan the old tables were made by.
-static int mmap_device(rpt_ctx* ctx, DevState& d, const rpthost::MmapPlan& old, const rpt_mesh_material_map* items, uint32_t n_items)
-{
-    const rpthost::MmapPlan& mp = ctx->mmap;
-    const rpthost::MmapLayout ml = mp.layout();
-    const rpthost::MmapLayout ol = old.layout();
-    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
-    RPT_CHECK_RC(ensure_refit(ctx, d));
-    void* fresh = nullptr;
-    void* stage = nullptr;
-    RPT_HIP_CHECK(ctx, hipMalloc(&fresh, ml.total));
-    size_t stage_bytes = 0;                                         // the named maps' bytes, in one allocation that lives until the decodes have run
-    for (uint32_t i = 0; i < n_items; ++i)
-        if (items[i].mode == RPT_MESH_MATERIAL_MAP_ON) stage_bytes += ((size_t)items[i].width * items[i].height * 4 + 15) & ~(size_t)15;
-    const auto fail = [&](int rc) { (void)hipFree(fresh); if (stage) (void)hipFree(stage); return rc; };
-    const auto work = [&]() -> int {
-        if (stage_bytes) RPT_HIP_CHECK(ctx, hipMalloc(&stage, stage_bytes));
-        unsigned char* base = static_cast<unsigned char*>(fresh);
-        rpthost::TexTexel* texels = reinterpret_cast<rpthost::TexTexel*>(base + ml.off_texels);
-        RPT_HIP_CHECK(ctx, hipMemsetAsync(base, 0, ml.off_none, d.stream));
-        if (ml.off_texels > ml.off_none) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + ml.off_none, 0xFF, ml.off_texels - ml.off_none, d.stream));
-        std::vector<uint8_t> named(mp.map.size(), 0);
-        size_t at = 0;
-        for (uint32_t i = 0; i < n_items; ++i) {
-            const rpt_mesh_material_map& it = items[i];
-            named[it.mesh] = 1;
-            if (it.mode != RPT_MESH_MATERIAL_MAP_ON) continue;
-            const rpthost::MmapMap& c = mp.map[it.mesh];
-            const size_t n = (size_t)c.width * c.height;
-            uint8_t* at_dev = static_cast<uint8_t*>(stage) + at;
-            RPT_HIP_CHECK(ctx, hipMemcpyAsync(at_dev, it.texels, 4 * n, hipMemcpyHostToDevice, d.stream));
-            RPT_HIP_CHECK(ctx, rptlaunch::mmap_decode(at_dev, texels + c.first, (uint32_t)n, c.roughness_channel, c.metallic_channel, d.stream));
-            at += (4 * n + 15) & ~(size_t)15;
-        }
-        for (uint32_t m = 0; m < mp.map.size(); ++m) {
-            if (named[m] || !mp.map[m].width) continue;             // a mesh not named keeps its map: the decoded texels move on the device
-            if (!d.mmap || !old.on(m)) { set_err(ctx, "rpt_set_mesh_material_maps: device %d holds no texels for mesh %u", d.device, m); return RPT_ERR_HIP; }
-            const size_t n = (size_t)mp.map[m].width * mp.map[m].height;
-            RPT_HIP_CHECK(ctx, hipMemcpyAsync(texels + mp.map[m].first,
-                                              reinterpret_cast<const rpthost::TexTexel*>(static_cast<const unsigned char*>(d.mmap) + ol.off_texels) + old.map[m].first,
-                                              16 * n, hipMemcpyDeviceToDevice, d.stream));
-        }
-        RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
-        return RPT_OK;
-    };
-    const int rc = work();
-    if (rc != RPT_OK) return fail(rc);
-    if (stage) (void)hipFree(stage);
-    if (d.mmap) (void)hipFree(d.mmap);
-    d.mmap = fresh;
-    return mmap_desc_device(ctx, d);
+    return download_map(ctx, "rpt_download_mesh_normal_map", "normal map", "rpt_set_mesh_normal_maps", &rpt_ctx::nrm, &DevState::nrm, mesh, texels, width, height);
 }
 
 int rpt_set_mesh_material_maps(rpt_ctx* ctx, const rpt_mesh_material_map* items, uint32_t n_items)
@@ -2378,120 +2228,20 @@ int rpt_set_mesh_material_maps(rpt_ctx* ctx, const rpt_mesh_material_map* items,
     std::string why;
     const int rc = check_mesh_material_maps(ctx->refit, ctx->scene.kind == SceneKind::mesh, ctx->tex, items, n_items, ctx->mmap.map, map, why);
     if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
-    if (n_items == 0) return RPT_OK;
-    bool any = false;
-    for (const MmapMap& c : map) any = any || c.width != 0u;
-    if (!any && !ctx->mmap.any()) return RPT_OK;                    // every map OFF, as before
-    DeviceGuard guard(ctx->devs[0].device);
-    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
-    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_material_maps: cannot select device %d", ctx->devs[0].device);
-    if (rc_dev == RPT_OK && !any) {                                 // every map OFF (again): the context is what it was before the first call
-        for (DevState& d : ctx->devs) {
-            if (!d.mmap) continue;
-            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
-                set_err(ctx, "rpt_set_mesh_material_maps: cannot wait for device %d", d.device);
-                rc_dev = RPT_ERR_HIP;
-                break;
-            }
-            (void)hipFree(d.mmap);
-            d.mmap = nullptr;
-        }
-        if (rc_dev == RPT_OK) { ctx->mmap = MmapPlan(); return RPT_OK; }
-    }
-    MmapPlan old;
-    if (rc_dev == RPT_OK) {
-        old = std::move(ctx->mmap);
-        build_mmap_plan(ctx->refit, std::move(map), ctx->mmap);
-    }
-    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
-        DevState& d = ctx->devs[i];
-        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_material_maps: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
-        else rc_dev = mmap_device(ctx, d, old, items, n_items);
-    }
-    if (rc_dev != RPT_OK) {
-        const std::string first = ctx->err;
-        drop_scene(ctx);
-        set_err(ctx, "%s; the context now holds no scene", first.c_str());
-        return rc_dev;
-    }
-    return RPT_OK;
+    static const MapFeature f = {&DevState::mmap, "rpt_set_mesh_material_maps", "texels", {16, 4, 0}, mmap_desc_device};
+    return set_mesh_maps(ctx, f, ctx->mmap, std::move(map), build_mmap_plan, map_named(items, n_items, &rpt_mesh_material_map::texels),
+                         [ctx](uint32_t mesh, unsigned char* staged, unsigned char* dst, uint32_t n, hipStream_t st) {
+                             const MmapMap& c = ctx->mmap.map[mesh];
+                             return rptlaunch::mmap_decode(staged, reinterpret_cast<TexTexel*>(dst), n, c.roughness_channel, c.metallic_channel, st);
+                         });
 }
 
 int rpt_download_mesh_material_map(rpt_ctx* ctx, uint32_t mesh, float* texels, uint32_t width, uint32_t height)
 {
-    if (!ctx) { set_err(nullptr, "rpt_download_mesh_material_map: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_mesh_material_map: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    const rpthost::RefitPlan& plan = ctx->refit;
-    if (mesh >= plan.n_meshes()) { set_err(ctx, "rpt_download_mesh_material_map: mesh %u out of range (the scene has %u)", mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
-    const DevState& d = ctx->devs[0];
-    const rpthost::MmapPlan& mp = ctx->mmap;
-    if (!mp.on(mesh) || !d.mmap) { set_err(ctx, "rpt_download_mesh_material_map: mesh %u has no material map: the context holds no texels for it (rpt_set_mesh_material_maps)", mesh); return RPT_ERR_INVALID_ARG; }
-    const rpthost::MmapMap& c = mp.map[mesh];
-    if (width != c.width || height != c.height) { set_err(ctx, "rpt_download_mesh_material_map: mesh %u: %u x %u is not its map's %u x %u", mesh, width, height, c.width, c.height); return RPT_ERR_INVALID_ARG; }
-    if (!texels) { set_err(ctx, "rpt_download_mesh_material_map: texels is NULL"); return RPT_ERR_INVALID_ARG; }
-    RPT_ON_DEVICE(ctx);
-    const rpthost::MmapLayout ml = mp.layout();
-    RPT_HIP_CHECK(ctx, hipMemcpy(texels, static_cast<const unsigned char*>(d.mmap) + ml.off_texels + 16 * (size_t)c.first, 16 * (size_t)c.width * c.height, hipMemcpyDeviceToHost));
-    return RPT_OK;
+    return download_map(ctx, "rpt_download_mesh_material_map", "material map", "rpt_set_mesh_material_maps", &rpt_ctx::mmap, &DevState::mmap, mesh, texels, width, height);
 }
 
-// ---- rpt_set_mesh_emission_maps / rpt_download_mesh_emission_map (include/rpt.h, "mesh emission maps") -----------------------------
-// One device's part, as mmap_device: wait for its earlier work (a launch may still read the old tables), make the new tables, copy the
-// kept meshes' texels over from the old ones on the device, decode the named meshes' maps with "mesh textures"' own launch, write the
-// descriptors, drop the old tables, and wait.  ctx->emap is already the new plan; `old` is the plan the old tables were made by.
-static int emap_device(rpt_ctx* ctx, DevState& d, const rpthost::EmapPlan& old, const rpt_mesh_emission_map* items, uint32_t n_items)
-{
-    const rpthost::EmapPlan& ep = ctx->emap;
-    const rpthost::EmapLayout el = ep.layout();
-    const rpthost::EmapLayout ol = old.layout();
-    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
-    RPT_CHECK_RC(ensure_refit(ctx, d));
-    void* fresh = nullptr;
-    void* stage = nullptr;
-    RPT_HIP_CHECK(ctx, hipMalloc(&fresh, el.total));
-    size_t stage_bytes = 0;                                         // the named maps' bytes and one L table each, in one allocation that lives until the decodes have run
-    for (uint32_t i = 0; i < n_items; ++i)
-        if (items[i].mode == RPT_MESH_EMISSION_MAP_ON) stage_bytes += 1024 + (((size_t)items[i].width * items[i].height * 4 + 15) & ~(size_t)15);
-    const auto fail = [&](int rc) { (void)hipFree(fresh); if (stage) (void)hipFree(stage); return rc; };
-    const auto work = [&]() -> int {
-        if (stage_bytes) RPT_HIP_CHECK(ctx, hipMalloc(&stage, stage_bytes));
-        unsigned char* base = static_cast<unsigned char*>(fresh);
-        rpthost::TexTexel* texels = reinterpret_cast<rpthost::TexTexel*>(base + el.off_texels);
-        RPT_HIP_CHECK(ctx, hipMemsetAsync(base, 0, el.off_texels, d.stream));      // both descriptor tables and the zero block's descriptors
-        if (el.zero.off_texels > el.zero.off_none)                                  // the zero block's empty light table
-            RPT_HIP_CHECK(ctx, hipMemsetAsync(base + el.off_zero + el.zero.off_none, 0xFF, el.zero.off_texels - el.zero.off_none, d.stream));
-        std::vector<uint8_t> named(ep.map.size(), 0);
-        size_t at = 0;
-        for (uint32_t i = 0; i < n_items; ++i) {
-            const rpt_mesh_emission_map& it = items[i];
-            named[it.mesh] = 1;
-            if (it.mode != RPT_MESH_EMISSION_MAP_ON) continue;
-            const rpthost::EmapMap& c = ep.map[it.mesh];
-            const size_t n = (size_t)c.width * c.height;
-            unsigned char* at_dev = static_cast<unsigned char*>(stage) + at;
-            RPT_HIP_CHECK(ctx, hipMemcpyAsync(at_dev + 1024, it.texels, 4 * n, hipMemcpyHostToDevice, d.stream));
-            RPT_HIP_CHECK(ctx, rptlaunch::tex_decode(at_dev + 1024, reinterpret_cast<float*>(at_dev), texels + c.first, (uint32_t)n, c.gamma, d.stream));
-            at += 1024 + ((4 * n + 15) & ~(size_t)15);
-        }
-        for (uint32_t m = 0; m < ep.map.size(); ++m) {
-            if (named[m] || !ep.map[m].width) continue;             // a mesh not named keeps its map: the decoded texels move on the device
-            if (!d.emap || !old.on(m)) { set_err(ctx, "rpt_set_mesh_emission_maps: device %d holds no texels for mesh %u", d.device, m); return RPT_ERR_HIP; }
-            const size_t n = (size_t)ep.map[m].width * ep.map[m].height;
-            RPT_HIP_CHECK(ctx, hipMemcpyAsync(texels + ep.map[m].first,
-                                              reinterpret_cast<const rpthost::TexTexel*>(static_cast<const unsigned char*>(d.emap) + ol.off_texels) + old.map[m].first,
-                                              16 * n, hipMemcpyDeviceToDevice, d.stream));
-        }
-        RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
-        return RPT_OK;
-    };
-    const int rc = work();
-    if (rc != RPT_OK) return fail(rc);
-    if (stage) (void)hipFree(stage);
-    if (d.emap) (void)hipFree(d.emap);
-    d.emap = fresh;
-    return emap_desc_device(ctx, d);
-}
-
+// The emission maps are decoded by "mesh textures"' own launch, which wants its L table (1024 B) in front of the staged bytes.
 int rpt_set_mesh_emission_maps(rpt_ctx* ctx, const rpt_mesh_emission_map* items, uint32_t n_items)
 {
     using namespace rpthost;
@@ -2500,61 +2250,16 @@ int rpt_set_mesh_emission_maps(rpt_ctx* ctx, const rpt_mesh_emission_map* items,
     std::string why;
     const int rc = check_mesh_emission_maps(ctx->refit, ctx->scene.kind == SceneKind::mesh, ctx->tex, items, n_items, ctx->emap.map, map, why);
     if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
-    if (n_items == 0) return RPT_OK;
-    bool any = false;
-    for (const EmapMap& c : map) any = any || c.width != 0u;
-    if (!any && !ctx->emap.any()) return RPT_OK;                    // every map OFF, as before
-    DeviceGuard guard(ctx->devs[0].device);
-    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
-    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_emission_maps: cannot select device %d", ctx->devs[0].device);
-    if (rc_dev == RPT_OK && !any) {                                 // every map OFF (again): the context is what it was before the first call
-        for (DevState& d : ctx->devs) {
-            if (!d.emap) continue;
-            if (guard.to(d.device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {      // a launch may still read the tables
-                set_err(ctx, "rpt_set_mesh_emission_maps: cannot wait for device %d", d.device);
-                rc_dev = RPT_ERR_HIP;
-                break;
-            }
-            (void)hipFree(d.emap);
-            d.emap = nullptr;
-        }
-        if (rc_dev == RPT_OK) { ctx->emap = EmapPlan(); return RPT_OK; }
-    }
-    EmapPlan old;
-    if (rc_dev == RPT_OK) {
-        old = std::move(ctx->emap);
-        build_emap_plan(ctx->refit, std::move(map), ctx->emap);
-    }
-    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
-        DevState& d = ctx->devs[i];
-        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_emission_maps: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
-        else rc_dev = emap_device(ctx, d, old, items, n_items);
-    }
-    if (rc_dev != RPT_OK) {
-        const std::string first = ctx->err;
-        drop_scene(ctx);
-        set_err(ctx, "%s; the context now holds no scene", first.c_str());
-        return rc_dev;
-    }
-    return RPT_OK;
+    static const MapFeature f = {&DevState::emap, "rpt_set_mesh_emission_maps", "texels", {16, 4, 1024}, emap_desc_device};
+    return set_mesh_maps(ctx, f, ctx->emap, std::move(map), build_emap_plan, map_named(items, n_items, &rpt_mesh_emission_map::texels),
+                         [ctx](uint32_t mesh, unsigned char* staged, unsigned char* dst, uint32_t n, hipStream_t st) {
+                             return rptlaunch::tex_decode(staged + 1024, reinterpret_cast<float*>(staged), reinterpret_cast<TexTexel*>(dst), n, ctx->emap.map[mesh].gamma, st);
+                         });
 }
 
 int rpt_download_mesh_emission_map(rpt_ctx* ctx, uint32_t mesh, float* texels, uint32_t width, uint32_t height)
 {
-    if (!ctx) { set_err(nullptr, "rpt_download_mesh_emission_map: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_mesh_emission_map: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    const rpthost::RefitPlan& plan = ctx->refit;
-    if (mesh >= plan.n_meshes()) { set_err(ctx, "rpt_download_mesh_emission_map: mesh %u out of range (the scene has %u)", mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
-    const DevState& d = ctx->devs[0];
-    const rpthost::EmapPlan& ep = ctx->emap;
-    if (!ep.on(mesh) || !d.emap) { set_err(ctx, "rpt_download_mesh_emission_map: mesh %u has no emission map: the context holds no texels for it (rpt_set_mesh_emission_maps)", mesh); return RPT_ERR_INVALID_ARG; }
-    const rpthost::EmapMap& c = ep.map[mesh];
-    if (width != c.width || height != c.height) { set_err(ctx, "rpt_download_mesh_emission_map: mesh %u: %u x %u is not its map's %u x %u", mesh, width, height, c.width, c.height); return RPT_ERR_INVALID_ARG; }
-    if (!texels) { set_err(ctx, "rpt_download_mesh_emission_map: texels is NULL"); return RPT_ERR_INVALID_ARG; }
-    RPT_ON_DEVICE(ctx);
-    const rpthost::EmapLayout el = ep.layout();
-    RPT_HIP_CHECK(ctx, hipMemcpy(texels, static_cast<const unsigned char*>(d.emap) + el.off_texels + 16 * (size_t)c.first, 16 * (size_t)c.width * c.height, hipMemcpyDeviceToHost));
-    return RPT_OK;
+    return download_map(ctx, "rpt_download_mesh_emission_map", "emission map", "rpt_set_mesh_emission_maps", &rpt_ctx::emap, &DevState::emap, mesh, texels, width, height);
 }
 
 uint32_t rpt_tile_row_count(uint32_t height, uint32_t tile_rows, uint32_t rank, uint32_t world)

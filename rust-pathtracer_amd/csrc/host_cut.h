@@ -10,9 +10,11 @@
 // Numbering.  The cutout descriptors are indexed by the TEXTURE ordinal of host_tex.h (a cutout mesh is textured), so the walk finds
 // them through tri_tex and needs no per-triangle table of its own; the table has one entry per mesh of the scene, so a texture call
 // that changes the ordinals rewrites entries and moves no mask.  Nothing here knows a slot: a rebuild leaves every table bit for bit.
+//
+// The error formatter, the 16-byte rounding, the descriptor words and the recipe of a device's part (MapSlot, MapFill) are host_map.h's,
+// shared with the three map features; the layout (bits, not texels), the plan (words) and the checks (their own order) stay here.
 #pragma once
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -21,6 +23,7 @@
 
 #include "../../include/rpt.h"
 #include "host_light.h"
+#include "host_map.h"
 #include "host_refit.h"
 #include "host_tex.h"
 
@@ -30,8 +33,9 @@
 
 namespace rpthost {
 
-constexpr uint32_t kCutDescWords = 4;           // CutDesc below, as words
-constexpr uint64_t kCutMaxTexels = 1ull << 26;  // of all masks of a scene
+constexpr uint32_t kCutDescWords = kMapDescWords;  // CutDesc below, as words
+constexpr uint64_t kCutMaxTexels = kMapMaxTexels;  // of all masks of a scene
+static_assert(RPT_MESH_CUTOUT_OFF == kMapOff && RPT_MESH_CUTOUT_ON == kMapOn, "host_map.h");
 constexpr uint32_t kCutPadTexels = 128;         // a mask starts at a 16 B boundary and holds whole 64-texel waves
 
 // One textured mesh, 16 B: one gather per candidate of a cutout mesh.  flags == 0: the mesh has no cutout (the rest is not read).
@@ -90,11 +94,13 @@ struct CutLayout {
     size_t off_desc = 0, off_none = 0, off_bits = 0, total = 0;
     CutLayout(uint32_t n_meshes, uint32_t n_tris, uint64_t n_words)
     {
-        const auto round16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        off_none = round16(4 * (size_t)kCutDescWords * n_meshes);
-        off_bits = off_none + round16(4 * (size_t)n_tris);
+        off_none = map_round16(4 * (size_t)kCutDescWords * n_meshes);
+        off_bits = off_none + map_round16(4 * (size_t)n_tris);
         total = off_bits + 4 * (size_t)n_words;
     }
+    size_t off_elems() const { return off_bits; }
+    // the descriptors; the empty light table; the masks, whose padding stays zero
+    std::vector<MapFill> fills() const { return {{0, off_none, 0}, {off_none, off_bits - off_none, 0xFF}, {off_bits, total - off_bits, 0}}; }
 };
 
 // What rpt_set_mesh_cutouts leaves on the host for the life of the cutouts.
@@ -110,6 +116,12 @@ struct CutPlan {
         return false;
     }
     CutLayout layout() const { return CutLayout(n_meshes, n_tris, n_words); }     // of every device's tables
+    std::vector<MapSlot> slots() const
+    {
+        std::vector<MapSlot> s(mask.size());
+        for (size_t m = 0; m < mask.size(); ++m) s[m] = MapSlot{mask[m].first, mask[m].width ? cut_mask_words(mask[m].width, mask[m].height) : 0u};
+        return s;
+    }
 };
 
 // The plan of `mask` (one entry per mesh, `first` not yet set) over a scene.
@@ -133,28 +145,14 @@ inline std::vector<uint32_t> cut_desc_table(const CutPlan& cp, const TexPlan& tp
     std::vector<uint32_t> d((size_t)kCutDescWords * cp.n_meshes, 0u);
     for (uint32_t j = 0; j < tp.n_tex() && j < cp.n_meshes; ++j) {
         const uint32_t m = tp.tex_mesh[j];
-        if (!cp.on(m)) continue;
-        const CutMask& c = cp.mask[m];
-        d[4u * j] = (uint32_t)c.first;
-        d[4u * j + 1u] = c.width;
-        d[4u * j + 2u] = c.height;
-        d[4u * j + 3u] = 1u | (tp.image[m].wrap == RPT_TEX_WRAP_CLAMP ? 2u : 0u);
+        if (cp.on(m)) map_desc_put(d, j, cp.mask[m], map_desc_flags(tp.image[m].wrap, RPT_TEX_FILTER_NEAREST));      // (no filter bit: the cut test is NEAREST)
     }
     return d;
 }
 
-// `err` = "rpt_set_mesh_cutouts: " + the message; returns `code`.
-inline int cut_error(std::string& err, int code, const char* fmt, ...)
-{
-    char buf[512];
-    const int head = snprintf(buf, sizeof(buf), "rpt_set_mesh_cutouts: ");
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf + head, sizeof(buf) - (size_t)head, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-}
+// `err` = "rpt_set_mesh_cutouts: " + the message; returns `code` (host_map.h's call_error, under this call's name).
+template <class... A>
+inline int cut_error(std::string& err, int code, const char* fmt, A... a) { return call_error(err, "rpt_set_mesh_cutouts", code, fmt, a...); }
 
 // Every check of rpt_set_mesh_cutouts but the NULL context (include/rpt.h), in one fixed order.  RPT_OK: `mask` is `current` (empty:
 // every mesh OFF) with the named meshes' new cutouts (`first` unset), one entry per mesh.  Never reads the items' alpha.

@@ -17,9 +17,12 @@
 // and no material map takes them through a table of all-zero MmapDesc (flags == 0: "no map on this mesh") and the all-0xFFFFFFFF
 // tri_light of MmapLayout::off_none, both carried here: the block at off_zero is laid out as MmapLayout(n_meshes, n_tris, 0), and
 // EmapPlan::zero is the MmapPlan that describes it, so mesh_args_mmap.h binds it as it binds a real one.
+//
+// The plan's members, the hit table, the descriptor words and the order of the checks are host_map.h's (MapPlan, map_desc_table,
+// map_desc_put, check_mesh_maps), shared with the normal and the material maps; here are the names, the second table, the zero
+// block, the map's own field and its own check.
 #pragma once
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -28,6 +31,7 @@
 
 #include "../../include/rpt.h"
 #include "host_light.h"
+#include "host_map.h"
 #include "host_mmap.h"
 #include "host_refit.h"
 #include "host_tex.h"
@@ -38,8 +42,9 @@
 
 namespace rpthost {
 
-constexpr uint32_t kEmapDescWords = 4;           // EmapDesc below, as words
-constexpr uint64_t kEmapMaxTexels = 1ull << 26;  // of all maps of a scene
+constexpr uint32_t kEmapDescWords = kMapDescWords;  // EmapDesc below, as words
+constexpr uint64_t kEmapMaxTexels = kMapMaxTexels;  // of all maps of a scene
+static_assert(RPT_MESH_EMISSION_MAP_OFF == kMapOff && RPT_MESH_EMISSION_MAP_ON == kMapOn, "host_map.h");
 
 // One mesh, 16 B: one gather per hit on a textured mesh, one per sample of an ON mesh.  flags == 0: the mesh has no map (the rest
 // is not read).
@@ -119,68 +124,35 @@ struct EmapMap {
 // 16 B.
 struct EmapLayout {
     size_t off_desc = 0, off_light_desc = 0, off_zero = 0, off_texels = 0, total = 0;
-    MmapLayout zero;
+    MapLayout zero;
     EmapLayout(uint32_t n_meshes, uint32_t n_tris, uint64_t n_texels) : zero(n_meshes, n_tris, 0)
     {
-        const auto round16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        off_light_desc = round16(4 * (size_t)kEmapDescWords * n_meshes);
+        off_light_desc = map_round16(4 * (size_t)kEmapDescWords * n_meshes);
         off_zero = 2 * off_light_desc;
-        off_texels = off_zero + round16(zero.total);
+        off_texels = off_zero + map_round16(zero.total);
         total = off_texels + 16 * (size_t)n_texels;
     }
+    size_t off_elems() const { return off_texels; }
+    // both descriptor tables and the zero block's descriptors; the zero block's empty light table
+    std::vector<MapFill> fills() const { return {{0, off_texels, 0}, {off_zero + zero.off_none, zero.off_texels - zero.off_none, 0xFF}}; }
 };
 
 // What rpt_set_mesh_emission_maps leaves on the host for the life of the maps.
-struct EmapPlan {
-    std::vector<EmapMap> map;         // mesh -> its map; empty: every mesh OFF
-    uint32_t n_meshes = 0, n_tris = 0;
-    uint64_t n_texels = 0;            // of all maps
+struct EmapPlan : MapPlan<EmapMap> {
     MmapPlan zero;                    // the plan of the zero block: no map ON, the scene's sizes
-
-    bool on(uint32_t mesh) const { return mesh < map.size() && map[mesh].width != 0u; }
-    bool any() const
-    {
-        for (const EmapMap& m : map) if (m.width != 0u) return true;
-        return false;
-    }
     EmapLayout layout() const { return EmapLayout(n_meshes, n_tris, n_texels); }   // of every device's tables
 };
 
 // The plan of `map` (one entry per mesh, `first` not yet set) over a scene.
 inline void build_emap_plan(const RefitPlan& plan, std::vector<EmapMap> map, EmapPlan& ep)
 {
-    ep = EmapPlan();
-    ep.map = std::move(map);
-    ep.n_meshes = plan.n_meshes();
-    ep.n_tris = plan.n_slots;
-    ep.map.resize(ep.n_meshes);
-    for (EmapMap& m : ep.map) {
-        if (m.width == 0u) continue;
-        m.first = ep.n_texels;
-        ep.n_texels += (uint64_t)m.width * m.height;
-    }
+    build_map_plan(plan.n_meshes(), plan.n_slots, std::move(map), ep);
     ep.zero.n_meshes = ep.n_meshes;
     ep.zero.n_tris = ep.n_tris;
 }
 
-inline void emap_desc_put(std::vector<uint32_t>& d, uint32_t j, const EmapMap& c, uint32_t wrap)
-{
-    d[4u * j] = (uint32_t)c.first;
-    d[4u * j + 1u] = c.width;
-    d[4u * j + 2u] = c.height;
-    d[4u * j + 3u] = 1u | (wrap == RPT_TEX_WRAP_CLAMP ? 2u : 0u) | (c.filter == RPT_TEX_FILTER_BILINEAR ? 4u : 0u);
-}
-
 // The hit table of `ep` under the textures of `tp`: kEmapDescWords per mesh of the scene, entry j the map of texture ordinal j.
-inline std::vector<uint32_t> emap_desc_table(const EmapPlan& ep, const TexPlan& tp)
-{
-    std::vector<uint32_t> d((size_t)kEmapDescWords * ep.n_meshes, 0u);
-    for (uint32_t j = 0; j < tp.n_tex() && j < ep.n_meshes; ++j) {
-        const uint32_t m = tp.tex_mesh[j];
-        if (ep.on(m)) emap_desc_put(d, j, ep.map[m], tp.image[m].wrap);
-    }
-    return d;
-}
+inline std::vector<uint32_t> emap_desc_table(const EmapPlan& ep, const TexPlan& tp) { return map_desc_table(ep, tp); }
 
 // The sampler table of `ep` under the textures of `tp` and the lights of `lp`: entry j the map of light ordinal j.
 inline std::vector<uint32_t> emap_light_desc_table(const EmapPlan& ep, const TexPlan& tp, const LightPlan& lp)
@@ -188,69 +160,26 @@ inline std::vector<uint32_t> emap_light_desc_table(const EmapPlan& ep, const Tex
     std::vector<uint32_t> d((size_t)kEmapDescWords * ep.n_meshes, 0u);
     for (uint32_t j = 0; j < lp.n_on() && j < ep.n_meshes; ++j) {
         const uint32_t m = lp.on_mesh[j];
-        if (ep.on(m) && tp.textured(m)) emap_desc_put(d, j, ep.map[m], tp.image[m].wrap);
+        if (ep.on(m) && tp.textured(m)) map_desc_put(d, j, ep.map[m], map_desc_flags(tp.image[m].wrap, ep.map[m].filter));
     }
     return d;
 }
 
-// `err` = "rpt_set_mesh_emission_maps: " + the message; returns `code`.
-inline int emap_error(std::string& err, int code, const char* fmt, ...)
-{
-    char buf[512];
-    const int head = snprintf(buf, sizeof(buf), "rpt_set_mesh_emission_maps: ");
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf + head, sizeof(buf) - (size_t)head, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-}
+constexpr MapNames kEmapNames = {"rpt_set_mesh_emission_maps", "RPT_MESH_EMISSION_MAP", "an emission map", "emission maps"};
 
-// Every check of rpt_set_mesh_emission_maps but the NULL context (include/rpt.h), in one fixed order: rpt_set_mesh_material_maps'
-// list with the gamma rule of rpt_set_mesh_textures in the place of the channels'.  RPT_OK: `map` is `current` (empty: every mesh
-// OFF) with the named meshes' new maps (`first` unset), one entry per mesh.  Never reads the items' texels.
+// Every check of rpt_set_mesh_emission_maps but the NULL context (include/rpt.h), in check_mesh_maps' order with the gamma rule of
+// rpt_set_mesh_textures in the feature's place.  RPT_OK: `map` is `current` (empty: every mesh OFF) with the named meshes' new maps
+// (`first` unset), one entry per mesh.  Never reads the items' texels.
 inline int check_mesh_emission_maps(const RefitPlan& plan, bool mesh_scene, const TexPlan& tex, const rpt_mesh_emission_map* items, uint32_t n_items,
                                     const std::vector<EmapMap>& current, std::vector<EmapMap>& map, std::string& err)
 {
-    const int INVALID = RPT_ERR_INVALID_ARG;
-    if (!mesh_scene) return emap_error(err, RPT_ERR_NO_SCENE, "needs an uploaded scene with meshes");
-    if (!items && n_items) return emap_error(err, INVALID, "items is NULL");
-    std::vector<EmapMap> next(current);
-    next.resize(plan.n_meshes());
-    std::vector<uint8_t> named(plan.n_meshes(), 0);
-    for (uint32_t i = 0; i < n_items; ++i) {
-        const rpt_mesh_emission_map& it = items[i];
-        if (it.mesh >= plan.n_meshes()) return emap_error(err, INVALID, "item %u: mesh %u out of range (the scene has %u)", i, it.mesh, plan.n_meshes());
-        if (named[it.mesh]) return emap_error(err, INVALID, "item %u: mesh %u is named twice", i, it.mesh);
-        named[it.mesh] = 1;
-        const bool on = it.mode == RPT_MESH_EMISSION_MAP_ON;
-        if (!on && it.mode != RPT_MESH_EMISSION_MAP_OFF)
-            return emap_error(err, INVALID, "item %u: mode %u of mesh %u is neither RPT_MESH_EMISSION_MAP_OFF nor RPT_MESH_EMISSION_MAP_ON", i, it.mode, it.mesh);
-        if (on && (it.width == 0u || it.height == 0u || it.width > kTexMaxSide || it.height > kTexMaxSide))
-            return emap_error(err, INVALID, "item %u: mesh %u: a map of %u x %u (each side must lie in 1 .. 16384)", i, it.mesh, it.width, it.height);
-        if (on && !it.texels) return emap_error(err, INVALID, "item %u: mesh %u: texels is NULL", i, it.mesh);
-        if (it.filter != RPT_TEX_FILTER_NEAREST && it.filter != RPT_TEX_FILTER_BILINEAR)
-            return emap_error(err, INVALID, "item %u: filter %u of mesh %u is neither RPT_TEX_FILTER_NEAREST nor RPT_TEX_FILTER_BILINEAR", i, it.filter, it.mesh);
+    const auto own = [](uint32_t i, const rpt_mesh_emission_map& it, bool on, EmapMap& c, std::string& err) {
         if (on && (!tex_finite(it.gamma) || !(it.gamma > 0.0f) || it.gamma > 16.0f))
-            return emap_error(err, INVALID, "item %u: mesh %u: gamma %g (it must be finite, above 0 and at most 16)", i, it.mesh, (double)it.gamma);
-        if (!on) {
-            if (it.width != 0u || it.height != 0u || it.texels)
-                return emap_error(err, INVALID, "item %u: mesh %u: RPT_MESH_EMISSION_MAP_OFF takes width == height == 0 and texels == NULL", i, it.mesh);
-            next[it.mesh] = EmapMap();
-            continue;
-        }
-        if (!tex.textured(it.mesh))
-            return emap_error(err, INVALID, "item %u: mesh %u is untextured: an emission map takes its UVs and wrap from the mesh's texture (a 1 x 1 white texture is enough: rpt_set_mesh_textures)", i, it.mesh);
-        EmapMap c;
-        c.width = it.width; c.height = it.height; c.filter = it.filter; c.gamma = it.gamma;
-        next[it.mesh] = c;
-    }
-    uint64_t total = 0;
-    for (const EmapMap& c : next) total += (uint64_t)c.width * c.height;
-    if (total > kEmapMaxTexels)
-        return emap_error(err, RPT_ERR_UNSUPPORTED, "the scene's emission maps would hold %llu texels: more than 2^26 in all", (unsigned long long)total);
-    map = std::move(next);
-    return RPT_OK;
+            return call_error(err, kEmapNames.call, RPT_ERR_INVALID_ARG, "item %u: mesh %u: gamma %g (it must be finite, above 0 and at most 16)", i, it.mesh, (double)it.gamma);
+        c.gamma = it.gamma;
+        return (int)RPT_OK;
+    };
+    return check_mesh_maps(kEmapNames, plan, mesh_scene, tex, items, n_items, current, map, err, own);
 }
 
 }  // namespace rpthost

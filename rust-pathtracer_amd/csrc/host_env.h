@@ -9,7 +9,6 @@
 // The divide and the square root are the correctly rounded ones.
 #pragma once
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -17,6 +16,7 @@
 #include <vector>
 
 #include "../../include/rpt.h"
+#include "host_map.h"
 
 #ifndef RPT_ENV_FN
 #define RPT_ENV_FN inline
@@ -209,18 +209,9 @@ struct EnvPlan {
     EnvLayout layout() const { return EnvLayout(size, sampled(), n_tris); }     // of every device's tables
 };
 
-// `err` = "rpt_set_environment: " + the message; returns `code`.
-inline int env_error(std::string& err, int code, const char* fmt, ...)
-{
-    char buf[512];
-    const int head = snprintf(buf, sizeof(buf), "rpt_set_environment: ");
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf + head, sizeof(buf) - (size_t)head, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-}
+// `err` = "rpt_set_environment: " + the message; returns `code` (host_map.h's call_error, under this call's name).
+template <class... A>
+inline int env_error(std::string& err, int code, const char* fmt, A... a) { return call_error(err, "rpt_set_environment", code, fmt, a...); }
 
 // Every check of rpt_set_environment but the NULL context (include/rpt.h), in one fixed order.  `n_other`: the pickable lights
 // without the environment (n_lights + ON meshes).  env == NULL (remove) passes once a mesh scene is uploaded.

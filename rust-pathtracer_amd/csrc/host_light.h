@@ -10,7 +10,6 @@
 // FACES 0 .. n_faces - 1; the j-th ON mesh is ORDINAL j.  Nothing here knows a slot: a rebuild leaves every table bit for bit.
 #pragma once
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -18,6 +17,7 @@
 #include <vector>
 
 #include "../../include/rpt.h"
+#include "host_map.h"
 #include "host_refit.h"
 #include "host_smooth.h"
 
@@ -163,18 +163,9 @@ inline void build_light_plan(const RefitPlan& plan, const uint32_t* flat, const 
     }
 }
 
-// `err` = "rpt_set_mesh_lights: " + the message; returns `code`.
-inline int light_error(std::string& err, int code, const char* fmt, ...)
-{
-    char buf[512];
-    const int head = snprintf(buf, sizeof(buf), "rpt_set_mesh_lights: ");
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf + head, sizeof(buf) - (size_t)head, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-}
+// `err` = "rpt_set_mesh_lights: " + the message; returns `code` (host_map.h's call_error, under this call's name).
+template <class... A>
+inline int light_error(std::string& err, int code, const char* fmt, A... a) { return call_error(err, "rpt_set_mesh_lights", code, fmt, a...); }
 
 // Every check of rpt_set_mesh_lights but the NULL context (include/rpt.h), in one fixed order.  RPT_OK: `mode` is `current` (empty:
 // every mesh OFF) with the named meshes' new modes, one entry per mesh.  The 2^24 rule comes before the items' own checks, so it

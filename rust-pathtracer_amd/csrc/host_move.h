@@ -5,16 +5,17 @@
 // under the address and undefined-behaviour sanitizers (tests/test_mesh_move_host.py).
 //
 // Every translation unit that includes this file is built with -ffp-contract=off: the transform is three multiplies and three adds
-// per component, each rounded to f32, in the order written.
+// per component, each rounded to f32, in the order written.  The checks format their messages with host_map.h's call_error
+// under the name of the call they were made for.
 #pragma once
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <string>
 #include <vector>
 
 #include "../../include/rpt.h"
+#include "host_map.h"
 #include "host_refit.h"
 
 #ifndef RPT_MOVE_FN
@@ -88,19 +89,6 @@ struct MoveLayout {
     }
 };
 
-// `err` = `call` + ": " + the message; returns `code`.
-inline int move_error(std::string& err, const char* call, int code, const char* fmt, ...)
-{
-    char buf[512];
-    const int head = snprintf(buf, sizeof(buf), "%s: ", call);
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf + head, sizeof(buf) - (size_t)head, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-}
-
 // Is `p` device memory with `bytes` bytes of its allocation from `p` on, and on which device?  capi.hip answers with
 // hipPointerGetAttributes and hipMemGetAddressRange; the harness with a table.
 constexpr int kMoveSourceOk = 0, kMoveSourceNotDevice = 1, kMoveSourceShort = 2;
@@ -113,27 +101,27 @@ inline int check_mesh_sources(const RefitPlan& plan, bool mesh_scene, const rpt_
                               const char* call, std::vector<int>& devices, std::string& err)
 {
     const int INVALID = RPT_ERR_INVALID_ARG;
-    if (!sources) return move_error(err, call, INVALID, "sources is NULL");
-    if (!mesh_scene) return move_error(err, call, RPT_ERR_NO_SCENE, "needs an uploaded scene with meshes");
-    if (!plan.ok) return move_error(err, call, RPT_ERR_UNSUPPORTED, "the scene's meshes hold 2^32 vertices or more");
+    if (!sources) return call_error(err, call, INVALID, "sources is NULL");
+    if (!mesh_scene) return call_error(err, call, RPT_ERR_NO_SCENE, "needs an uploaded scene with meshes");
+    if (!plan.ok) return call_error(err, call, RPT_ERR_UNSUPPORTED, "the scene's meshes hold 2^32 vertices or more");
     std::vector<uint8_t> named(plan.n_meshes(), 0);
     devices.assign(n_sources, -1);
     for (uint32_t u = 0; u < n_sources; ++u) {
         const rpt_mesh_source& so = sources[u];
-        if (so.mesh >= plan.n_meshes()) return move_error(err, call, INVALID, "source %u: mesh %u out of range (the scene has %u)", u, so.mesh, plan.n_meshes());
-        if (named[so.mesh]) return move_error(err, call, INVALID, "source %u: mesh %u is named twice", u, so.mesh);
+        if (so.mesh >= plan.n_meshes()) return call_error(err, call, INVALID, "source %u: mesh %u out of range (the scene has %u)", u, so.mesh, plan.n_meshes());
+        if (named[so.mesh]) return call_error(err, call, INVALID, "source %u: mesh %u is named twice", u, so.mesh);
         named[so.mesh] = 1;
         const uint32_t count = plan.mesh_first[so.mesh + 1u] - plan.mesh_first[so.mesh];
-        if (so.n_vertices != count) return move_error(err, call, INVALID, "mesh %u: n_vertices %u != the uploaded mesh's %u", so.mesh, so.n_vertices, count);
-        if (count && !so.vertices_dev) return move_error(err, call, INVALID, "mesh %u: vertices_dev is NULL", so.mesh);
+        if (so.n_vertices != count) return call_error(err, call, INVALID, "mesh %u: n_vertices %u != the uploaded mesh's %u", so.mesh, so.n_vertices, count);
+        if (count && !so.vertices_dev) return call_error(err, call, INVALID, "mesh %u: vertices_dev is NULL", so.mesh);
         const int where = count ? query(so.vertices_dev, 12 * (size_t)count, &devices[u]) : kMoveSourceOk;
-        if (where == kMoveSourceNotDevice) return move_error(err, call, INVALID, "mesh %u: vertices_dev is not device memory", so.mesh);
+        if (where == kMoveSourceNotDevice) return call_error(err, call, INVALID, "mesh %u: vertices_dev is not device memory", so.mesh);
         if (where != kMoveSourceOk)
-            return move_error(err, call, INVALID, "mesh %u: vertices_dev's allocation ends before %u vertices (%zu bytes)", so.mesh, count, 12 * (size_t)count);
+            return call_error(err, call, INVALID, "mesh %u: vertices_dev's allocation ends before %u vertices (%zu bytes)", so.mesh, count, 12 * (size_t)count);
         if (so.transform)
             for (int k = 0; k < 12; ++k)
                 if ((move_bits(so.transform[k]) & 0x7FFFFFFFu) >= 0x7F800000u)
-                    return move_error(err, call, INVALID, "mesh %u: transform entry %d is not finite", so.mesh, k);
+                    return call_error(err, call, INVALID, "mesh %u: transform entry %d is not finite", so.mesh, k);
     }
     return RPT_OK;
 }
@@ -148,7 +136,7 @@ inline MoveTransform move_transform_of(const float* transform)
 // What the device check's read-back says about source `so`: RPT_OK and the mesh's largest |coordinate|, or the error.
 inline int move_check_result(const rpt_mesh_source& so, const uint32_t* words, const char* call, float& big, std::string& err)
 {
-    if (words[kMoveWordBad]) return move_error(err, call, RPT_ERR_INVALID_ARG, "mesh %u vertex %u is not finite", so.mesh, 0xFFFFFFFFu - words[kMoveWordBad]);
+    if (words[kMoveWordBad]) return call_error(err, call, RPT_ERR_INVALID_ARG, "mesh %u vertex %u is not finite", so.mesh, 0xFFFFFFFFu - words[kMoveWordBad]);
     big = move_big_of(words[kMoveWordBig]);
     return RPT_OK;
 }

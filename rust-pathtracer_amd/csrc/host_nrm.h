@@ -11,9 +11,11 @@
 // Numbering.  The descriptors are indexed by the TEXTURE ordinal of host_tex.h (a normal-mapped mesh is textured), so the hit finds
 // them through tri_tex; the table has one entry per mesh of the scene, so a texture call that changes the ordinals rewrites entries
 // and moves no texel.  Nothing here knows a slot, and there is no per-vertex tangent: a move or a rebuild leaves every table bit for bit.
+//
+// The layout, the plan, the descriptor table and the order of the checks are host_map.h's (MapLayout, MapPlan, map_desc_table,
+// check_mesh_maps), shared with the material and the emission maps; here are the names, the map's own fields and its own checks.
 #pragma once
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -21,6 +23,7 @@
 #include <vector>
 
 #include "../../include/rpt.h"
+#include "host_map.h"
 #include "host_refit.h"
 #include "host_tex.h"
 
@@ -30,8 +33,9 @@
 
 namespace rpthost {
 
-constexpr uint32_t kNrmDescWords = 4;           // NrmDesc below, as words
-constexpr uint64_t kNrmMaxTexels = 1ull << 26;  // of all maps of a scene
+constexpr uint32_t kNrmDescWords = kMapDescWords;  // NrmDesc below, as words
+constexpr uint64_t kNrmMaxTexels = kMapMaxTexels;  // of all maps of a scene
+static_assert(RPT_MESH_NORMAL_MAP_OFF == kMapOff && RPT_MESH_NORMAL_MAP_ON == kMapOn, "host_map.h");
 constexpr float kNrmMaxStrength = 16.0f;
 
 // One textured mesh, 16 B: one gather per hit on a textured mesh.  flags == 0: the mesh has no map (the rest is not read).
@@ -119,125 +123,38 @@ struct NrmMap {
     uint64_t first = 0;               // its first texel in the devices' map table
 };
 
-// The device's map tables (DevState::nrm), one allocation: per mesh of the SCENE 16 B (the descriptors, by texture ordinal); per
-// triangle of the scene 4 B (the all-0xFFFFFFFF tri_light the render kernel reads while no mesh is ON and no cutout or environment
-// supplies one); per map texel 16 B.
-struct NrmLayout {
-    size_t off_desc = 0, off_none = 0, off_texels = 0, total = 0;
-    NrmLayout(uint32_t n_meshes, uint32_t n_tris, uint64_t n_texels)
-    {
-        const auto round16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        off_none = round16(4 * (size_t)kNrmDescWords * n_meshes);
-        off_texels = off_none + round16(4 * (size_t)n_tris);
-        total = off_texels + 16 * (size_t)n_texels;
-    }
-};
+// The device's map tables (DevState::nrm): host_map.h's, whose all-0xFFFFFFFF tri_light the render kernel reads while no mesh is ON and
+// no cutout or environment supplies one.
+using NrmLayout = MapLayout;
 
 // What rpt_set_mesh_normal_maps leaves on the host for the life of the maps.
-struct NrmPlan {
-    std::vector<NrmMap> map;          // mesh -> its map; empty: every mesh OFF
-    uint32_t n_meshes = 0, n_tris = 0;
-    uint64_t n_texels = 0;            // of all maps
-
-    bool on(uint32_t mesh) const { return mesh < map.size() && map[mesh].width != 0u; }
-    bool any() const
-    {
-        for (const NrmMap& m : map) if (m.width != 0u) return true;
-        return false;
-    }
-    NrmLayout layout() const { return NrmLayout(n_meshes, n_tris, n_texels); }     // of every device's tables
-};
+using NrmPlan = MapPlan<NrmMap>;
 
 // The plan of `map` (one entry per mesh, `first` not yet set) over a scene.
-inline void build_nrm_plan(const RefitPlan& plan, std::vector<NrmMap> map, NrmPlan& np)
-{
-    np = NrmPlan();
-    np.map = std::move(map);
-    np.n_meshes = plan.n_meshes();
-    np.n_tris = plan.n_slots;
-    np.map.resize(np.n_meshes);
-    for (NrmMap& m : np.map) {
-        if (m.width == 0u) continue;
-        m.first = np.n_texels;
-        np.n_texels += (uint64_t)m.width * m.height;
-    }
-}
+inline void build_nrm_plan(const RefitPlan& plan, std::vector<NrmMap> map, NrmPlan& np) { build_map_plan(plan.n_meshes(), plan.n_slots, std::move(map), np); }
 
 // The descriptor table of `np` under the textures of `tp`: kNrmDescWords per mesh of the scene, entry j the map of texture ordinal j.
-inline std::vector<uint32_t> nrm_desc_table(const NrmPlan& np, const TexPlan& tp)
-{
-    std::vector<uint32_t> d((size_t)kNrmDescWords * np.n_meshes, 0u);
-    for (uint32_t j = 0; j < tp.n_tex() && j < np.n_meshes; ++j) {
-        const uint32_t m = tp.tex_mesh[j];
-        if (!np.on(m)) continue;
-        const NrmMap& c = np.map[m];
-        d[4u * j] = (uint32_t)c.first;
-        d[4u * j + 1u] = c.width;
-        d[4u * j + 2u] = c.height;
-        d[4u * j + 3u] = 1u | (tp.image[m].wrap == RPT_TEX_WRAP_CLAMP ? 2u : 0u) | (c.filter == RPT_TEX_FILTER_BILINEAR ? 4u : 0u);
-    }
-    return d;
-}
+inline std::vector<uint32_t> nrm_desc_table(const NrmPlan& np, const TexPlan& tp) { return map_desc_table(np, tp); }
 
-// `err` = "rpt_set_mesh_normal_maps: " + the message; returns `code`.
-inline int nrm_error(std::string& err, int code, const char* fmt, ...)
-{
-    char buf[512];
-    const int head = snprintf(buf, sizeof(buf), "rpt_set_mesh_normal_maps: ");
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf + head, sizeof(buf) - (size_t)head, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-}
+constexpr MapNames kNrmNames = {"rpt_set_mesh_normal_maps", "RPT_MESH_NORMAL_MAP", "a normal map", "normal maps"};
 
-// Every check of rpt_set_mesh_normal_maps but the NULL context (include/rpt.h), in one fixed order.  RPT_OK: `map` is `current`
-// (empty: every mesh OFF) with the named meshes' new maps (`first` unset), one entry per mesh.  Never reads the items' texels.
+// Every check of rpt_set_mesh_normal_maps but the NULL context (include/rpt.h), in check_mesh_maps' order with the flags and the
+// strength in the feature's place.  RPT_OK: `map` is `current` (empty: every mesh OFF) with the named meshes' new maps (`first` unset),
+// one entry per mesh.  Never reads the items' texels.
 inline int check_mesh_normal_maps(const RefitPlan& plan, bool mesh_scene, const TexPlan& tex, const rpt_mesh_normal_map* items, uint32_t n_items,
                                   const std::vector<NrmMap>& current, std::vector<NrmMap>& map, std::string& err)
 {
-    const int INVALID = RPT_ERR_INVALID_ARG;
-    if (!mesh_scene) return nrm_error(err, RPT_ERR_NO_SCENE, "needs an uploaded scene with meshes");
-    if (!items && n_items) return nrm_error(err, INVALID, "items is NULL");
-    std::vector<NrmMap> next(current);
-    next.resize(plan.n_meshes());
-    std::vector<uint8_t> named(plan.n_meshes(), 0);
-    for (uint32_t i = 0; i < n_items; ++i) {
-        const rpt_mesh_normal_map& it = items[i];
-        if (it.mesh >= plan.n_meshes()) return nrm_error(err, INVALID, "item %u: mesh %u out of range (the scene has %u)", i, it.mesh, plan.n_meshes());
-        if (named[it.mesh]) return nrm_error(err, INVALID, "item %u: mesh %u is named twice", i, it.mesh);
-        named[it.mesh] = 1;
-        const bool on = it.mode == RPT_MESH_NORMAL_MAP_ON;
-        if (!on && it.mode != RPT_MESH_NORMAL_MAP_OFF)
-            return nrm_error(err, INVALID, "item %u: mode %u of mesh %u is neither RPT_MESH_NORMAL_MAP_OFF nor RPT_MESH_NORMAL_MAP_ON", i, it.mode, it.mesh);
-        if (on && (it.width == 0u || it.height == 0u || it.width > kTexMaxSide || it.height > kTexMaxSide))
-            return nrm_error(err, INVALID, "item %u: mesh %u: a map of %u x %u (each side must lie in 1 .. 16384)", i, it.mesh, it.width, it.height);
-        if (on && !it.texels) return nrm_error(err, INVALID, "item %u: mesh %u: texels is NULL", i, it.mesh);
-        if (it.filter != RPT_TEX_FILTER_NEAREST && it.filter != RPT_TEX_FILTER_BILINEAR)
-            return nrm_error(err, INVALID, "item %u: filter %u of mesh %u is neither RPT_TEX_FILTER_NEAREST nor RPT_TEX_FILTER_BILINEAR", i, it.filter, it.mesh);
+    const auto own = [](uint32_t i, const rpt_mesh_normal_map& it, bool, NrmMap& c, std::string& err) {
+        const int INVALID = RPT_ERR_INVALID_ARG;
+        const char* call = kNrmNames.call;
         if (it.flags & ~(uint32_t)RPT_NORMAL_MAP_FLIP_GREEN)
-            return nrm_error(err, INVALID, "item %u: mesh %u: unknown flag bits 0x%x", i, it.mesh, it.flags & ~(uint32_t)RPT_NORMAL_MAP_FLIP_GREEN);
+            return call_error(err, call, INVALID, "item %u: mesh %u: unknown flag bits 0x%x", i, it.mesh, it.flags & ~(uint32_t)RPT_NORMAL_MAP_FLIP_GREEN);
         if (!tex_finite(it.strength) || !(it.strength >= 0.0f) || it.strength > kNrmMaxStrength)
-            return nrm_error(err, INVALID, "item %u: mesh %u: strength %g (it must be finite and lie in 0 .. 16)", i, it.mesh, (double)it.strength);
-        if (!on) {
-            if (it.width != 0u || it.height != 0u || it.texels)
-                return nrm_error(err, INVALID, "item %u: mesh %u: RPT_MESH_NORMAL_MAP_OFF takes width == height == 0 and texels == NULL", i, it.mesh);
-            next[it.mesh] = NrmMap();
-            continue;
-        }
-        if (!tex.textured(it.mesh))
-            return nrm_error(err, INVALID, "item %u: mesh %u is untextured: a normal map takes its UVs and wrap from the mesh's texture (a 1 x 1 white texture is enough: rpt_set_mesh_textures)", i, it.mesh);
-        NrmMap c;
-        c.width = it.width; c.height = it.height; c.filter = it.filter; c.flags = it.flags; c.strength = it.strength;
-        next[it.mesh] = c;
-    }
-    uint64_t total = 0;
-    for (const NrmMap& c : next) total += (uint64_t)c.width * c.height;
-    if (total > kNrmMaxTexels)
-        return nrm_error(err, RPT_ERR_UNSUPPORTED, "the scene's normal maps would hold %llu texels: more than 2^26 in all", (unsigned long long)total);
-    map = std::move(next);
-    return RPT_OK;
+            return call_error(err, call, INVALID, "item %u: mesh %u: strength %g (it must be finite and lie in 0 .. 16)", i, it.mesh, (double)it.strength);
+        c.flags = it.flags; c.strength = it.strength;
+        return (int)RPT_OK;
+    };
+    return check_mesh_maps(kNrmNames, plan, mesh_scene, tex, items, n_items, current, map, err, own);
 }
 
 }  // namespace rpthost

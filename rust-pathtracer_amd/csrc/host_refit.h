@@ -17,7 +17,6 @@
 #pragma once
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -25,6 +24,7 @@
 
 #include "../../include/rpt.h"
 #include "host_bvh.h"
+#include "host_map.h"
 
 namespace rpthost {
 
@@ -136,18 +136,9 @@ inline bool refit_use_bvh(const std::vector<float>& mesh_max_abs)
     return true;
 }
 
-// `err` = "rpt_update_meshes: " + the message; returns `code`.
-inline int update_error(std::string& err, int code, const char* fmt, ...)
-{
-    char buf[512];
-    const int head = snprintf(buf, sizeof(buf), "rpt_update_meshes: ");
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf + head, sizeof(buf) - (size_t)head, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-}
+// `err` = "rpt_update_meshes: " + the message; returns `code` (host_map.h's call_error, under this call's name).
+template <class... A>
+inline int update_error(std::string& err, int code, const char* fmt, A... a) { return call_error(err, "rpt_update_meshes", code, fmt, a...); }
 
 // Every check of rpt_update_meshes but the NULL context (include/rpt.h), in one fixed order: an update with several faults always
 // answers the first.  `mesh_scene`: the context holds a scene with triangles, and `plan` is its plan.  RPT_OK: `max_abs` is

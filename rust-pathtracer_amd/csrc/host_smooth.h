@@ -12,7 +12,6 @@
 // reorders slots and leaves faces, adjacency and therefore every normal's bits where they were.
 #pragma once
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -20,6 +19,7 @@
 #include <vector>
 
 #include "../../include/rpt.h"
+#include "host_map.h"
 #include "host_refit.h"
 
 #ifndef RPT_SMOOTH_FN
@@ -162,18 +162,9 @@ inline void build_smooth_plan(const RefitPlan& plan, const uint32_t* flat, const
     }
 }
 
-// `err` = "rpt_set_mesh_shading: " + the message; returns `code`.
-inline int shading_error(std::string& err, int code, const char* fmt, ...)
-{
-    char buf[512];
-    const int head = snprintf(buf, sizeof(buf), "rpt_set_mesh_shading: ");
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf + head, sizeof(buf) - (size_t)head, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-}
+// `err` = "rpt_set_mesh_shading: " + the message; returns `code` (host_map.h's call_error, under this call's name).
+template <class... A>
+inline int shading_error(std::string& err, int code, const char* fmt, A... a) { return call_error(err, "rpt_set_mesh_shading", code, fmt, a...); }
 
 // Every check of rpt_set_mesh_shading but the NULL context (include/rpt.h), in one fixed order.  RPT_OK: `mode` is `current` (empty:
 // every mesh FLAT) with the named meshes' new modes, one entry per mesh.

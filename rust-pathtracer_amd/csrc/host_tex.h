@@ -12,7 +12,6 @@
 // in one texel table.  Nothing here knows a slot: a rebuild leaves every table bit for bit.
 #pragma once
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -21,6 +20,7 @@
 
 #include "../../include/rpt.h"
 #include "../../include/rpt_strict_math.h"
+#include "host_map.h"
 #include "host_refit.h"
 
 #ifndef RPT_TEX_FN
@@ -34,7 +34,7 @@ namespace rpthost {
 
 constexpr uint32_t kTexNone = 0xFFFFFFFFu;
 constexpr uint32_t kTexDescWords = 8;           // TexDesc below, as words
-constexpr uint32_t kTexMaxSide = 16384;
+constexpr uint32_t kTexMaxSide = kMapMaxSide;
 constexpr uint64_t kTexMaxTexels = 1ull << 26;  // of all textures of a scene
 constexpr float kTexMaxUv = 1048576.0f;         // 2^20: floorf and the casts of the lookup stay exact
 
@@ -209,18 +209,9 @@ inline void build_tex_plan(const RefitPlan& plan, std::vector<TexImage> image, s
     }
 }
 
-// `err` = "rpt_set_mesh_textures: " + the message; returns `code`.
-inline int tex_error(std::string& err, int code, const char* fmt, ...)
-{
-    char buf[512];
-    const int head = snprintf(buf, sizeof(buf), "rpt_set_mesh_textures: ");
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf + head, sizeof(buf) - (size_t)head, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-}
+// `err` = "rpt_set_mesh_textures: " + the message; returns `code` (host_map.h's call_error, under this call's name).
+template <class... A>
+inline int tex_error(std::string& err, int code, const char* fmt, A... a) { return call_error(err, "rpt_set_mesh_textures", code, fmt, a...); }
 
 inline bool tex_finite(float x)
 {

@@ -6,7 +6,6 @@
 
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -14,6 +13,7 @@
 
 #include "../../include/rpt.h"
 #include "host_bvh.h"
+#include "host_map.h"
 #include "host_refit.h"
 #include "host_scene.h"
 #include "launch.h"
@@ -124,18 +124,9 @@ inline bool material_class_map(const SceneSmall& sc, MatClassMap& map, std::vect
     return true;
 }
 
-// `err` = "rpt_upload_scene: " + the message (at most 511 characters, as capi.hip's set_err keeps); returns `code`.
-inline int upload_error(std::string& err, int code, const char* fmt, ...)
-{
-    char buf[512];
-    const int head = snprintf(buf, sizeof(buf), "rpt_upload_scene: ");
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf + head, sizeof(buf) - (size_t)head, fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-}
+// `err` = "rpt_upload_scene: " + the message (at most 511 characters, as capi.hip's set_err keeps); returns `code` (host_map.h's call_error, under this call's name).
+template <class... A>
+inline int upload_error(std::string& err, int code, const char* fmt, A... a) { return call_error(err, "rpt_upload_scene", code, fmt, a...); }
 
 // Checks `s` (every RPT_ERR_INVALID_ARG and RPT_ERR_UNSUPPORTED case of include/rpt.h, in one fixed order: a descriptor with several
 // faults always answers the first), classifies it and builds `img`.  RPT_OK, or the code with `err` set.  `s` is not NULL.
