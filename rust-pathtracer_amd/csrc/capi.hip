@@ -2827,12 +2827,35 @@ int rpt_probe_rays(rpt_ctx* ctx, const float* rays_dev, uint32_t* out_dev, uint6
     return RPT_OK;
 }
 
+// The mesh and environment probes' shared prefix, in this order: the NULL context, the scene kind, the pointers and the flag bits
+// outside `allowed`, the feature the probe needs (`missing`: what to say of a scene without it, or NULL when it is there or the probe
+// needs none), n == 0.  False: the hook returns *rc.  True: it sets the device (RPT_ON_DEVICE) and launches.
+typedef const char* (*ProbeNeed)(const rpt_ctx*);
+static bool probe_ready(rpt_ctx* ctx, const char* name, const void* in_dev, const void* out_dev, uint32_t flags, uint32_t allowed, uint64_t n, int* rc,
+                        ProbeNeed missing = nullptr)
+{
+    *rc = RPT_ERR_INVALID_ARG;
+    if (!ctx) { set_err(nullptr, "%s: ctx is NULL", name); return false; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "%s: needs an uploaded scene with meshes", name); *rc = RPT_ERR_NO_SCENE; return false; }
+    if (!in_dev || !out_dev || (flags & ~allowed)) { set_err(ctx, "%s: invalid argument", name); return false; }
+    if (const char* what = missing ? missing(ctx) : nullptr) { set_err(ctx, "%s: %s", name, what); return false; }
+    *rc = RPT_OK;
+    return n != 0;
+}
+static const char* probe_needs_smooth(const rpt_ctx* c) { return !c->smooth.any() || !c->devs[0].smooth ? "no mesh is SMOOTH" : nullptr; }
+static const char* probe_needs_lights(const rpt_ctx* c) { return !c->light.any() || !c->devs[0].light ? "no mesh is ON" : nullptr; }
+static const char* probe_needs_tex(const rpt_ctx* c) { return !c->tex.any() || !c->devs[0].tex ? "no mesh is textured" : nullptr; }
+static const char* probe_needs_cut(const rpt_ctx* c) { return !c->cut.any() || !c->devs[0].cut || !c->devs[0].tex ? "no mesh has a cutout" : nullptr; }
+static const char* probe_needs_nrm(const rpt_ctx* c) { return !c->nrm.any() || !c->devs[0].nrm || !c->devs[0].tex ? "no mesh has a normal map" : nullptr; }
+static const char* probe_needs_mmap(const rpt_ctx* c) { return !c->mmap.any() || !c->devs[0].mmap || !c->devs[0].tex ? "no mesh has a material map" : nullptr; }
+static const char* probe_needs_emap(const rpt_ctx* c) { return !c->emap.any() || !c->devs[0].emap || !c->devs[0].tex ? "no mesh has an emission map" : nullptr; }
+static const char* probe_needs_emap_and_lights(const rpt_ctx* c) { const char* what = probe_needs_emap(c); return what ? what : probe_needs_lights(c); }
+static const char* probe_needs_env(const rpt_ctx* c) { return !c->env.any() || !c->devs[0].env ? "no environment is set" : nullptr; }
+
 int rpt_debug_mesh_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
 {
-    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    if (!rays_dev || !out_dev || (flags & ~(uint32_t)(RPT_MESH_QUERY_USE_MAX | RPT_MESH_QUERY_BRUTE))) { set_err(ctx, "rpt_debug_mesh_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
-    if (n == 0) return RPT_OK;
+    int rc;
+    if (!probe_ready(ctx, "rpt_debug_mesh_query", rays_dev, out_dev, flags, RPT_MESH_QUERY_USE_MAX | RPT_MESH_QUERY_BRUTE, n, &rc)) return rc;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_query(ctx->devs[0].scene, rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
@@ -2840,11 +2863,8 @@ int rpt_debug_mesh_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32
 
 int rpt_debug_mesh_normal_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
 {
-    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_normal_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_normal_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    if (!rays_dev || !out_dev || (flags & ~(uint32_t)RPT_MESH_QUERY_BRUTE)) { set_err(ctx, "rpt_debug_mesh_normal_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->smooth.any() || !ctx->devs[0].smooth) { set_err(ctx, "rpt_debug_mesh_normal_query: no mesh is SMOOTH"); return RPT_ERR_INVALID_ARG; }
-    if (n == 0) return RPT_OK;
+    int rc;
+    if (!probe_ready(ctx, "rpt_debug_mesh_normal_query", rays_dev, out_dev, flags, RPT_MESH_QUERY_BRUTE, n, &rc, probe_needs_smooth)) return rc;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_normal_query(rptargs::mesh_scene_of<SceneMeshSmooth>(mesh_view_of(ctx, ctx->devs[0])), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
@@ -2852,11 +2872,8 @@ int rpt_debug_mesh_normal_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n,
 
 int rpt_debug_mesh_light_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, uint32_t* out_dev, void* stream)
 {
-    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_light_sample: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_light_sample: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    if (!in_dev || !out_dev) { set_err(ctx, "rpt_debug_mesh_light_sample: invalid argument"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->light.any() || !ctx->devs[0].light) { set_err(ctx, "rpt_debug_mesh_light_sample: no mesh is ON"); return RPT_ERR_INVALID_ARG; }
-    if (n == 0) return RPT_OK;
+    int rc;
+    if (!probe_ready(ctx, "rpt_debug_mesh_light_sample", in_dev, out_dev, 0u, 0u, n, &rc, probe_needs_lights)) return rc;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_light_sample(rptargs::mesh_scene_of<SceneMeshLight>(mesh_view_of(ctx, ctx->devs[0])), in_dev, out_dev, n, (hipStream_t)stream));
     return RPT_OK;
@@ -2864,11 +2881,8 @@ int rpt_debug_mesh_light_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, u
 
 int rpt_debug_mesh_texture_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
 {
-    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_texture_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_texture_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    if (!rays_dev || !out_dev || (flags & ~(uint32_t)RPT_MESH_QUERY_BRUTE)) { set_err(ctx, "rpt_debug_mesh_texture_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->tex.any() || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_texture_query: no mesh is textured"); return RPT_ERR_INVALID_ARG; }
-    if (n == 0) return RPT_OK;
+    int rc;
+    if (!probe_ready(ctx, "rpt_debug_mesh_texture_query", rays_dev, out_dev, flags, RPT_MESH_QUERY_BRUTE, n, &rc, probe_needs_tex)) return rc;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_texture_query(rptargs::mesh_scene_of<SceneMeshTex>(mesh_view_of(ctx, ctx->devs[0])), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
@@ -2876,11 +2890,8 @@ int rpt_debug_mesh_texture_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n
 
 int rpt_debug_mesh_cutout_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
 {
-    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_cutout_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_cutout_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    if (!rays_dev || !out_dev || (flags & ~(uint32_t)(RPT_MESH_QUERY_USE_MAX | RPT_MESH_QUERY_BRUTE))) { set_err(ctx, "rpt_debug_mesh_cutout_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->cut.any() || !ctx->devs[0].cut || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_cutout_query: no mesh has a cutout"); return RPT_ERR_INVALID_ARG; }
-    if (n == 0) return RPT_OK;
+    int rc;
+    if (!probe_ready(ctx, "rpt_debug_mesh_cutout_query", rays_dev, out_dev, flags, RPT_MESH_QUERY_USE_MAX | RPT_MESH_QUERY_BRUTE, n, &rc, probe_needs_cut)) return rc;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_cutout_query(rptargs::mesh_scene_of<SceneMeshCut>(mesh_view_of(ctx, ctx->devs[0])), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
@@ -2888,11 +2899,8 @@ int rpt_debug_mesh_cutout_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n,
 
 int rpt_debug_mesh_normal_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
 {
-    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_normal_map_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_normal_map_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    if (!rays_dev || !out_dev || (flags & ~(uint32_t)RPT_MESH_QUERY_BRUTE)) { set_err(ctx, "rpt_debug_mesh_normal_map_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->nrm.any() || !ctx->devs[0].nrm || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_normal_map_query: no mesh has a normal map"); return RPT_ERR_INVALID_ARG; }
-    if (n == 0) return RPT_OK;
+    int rc;
+    if (!probe_ready(ctx, "rpt_debug_mesh_normal_map_query", rays_dev, out_dev, flags, RPT_MESH_QUERY_BRUTE, n, &rc, probe_needs_nrm)) return rc;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_normal_map_query(rptargs::mesh_scene_of<SceneMeshNrm>(mesh_view_of(ctx, ctx->devs[0])), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
@@ -2900,15 +2908,10 @@ int rpt_debug_mesh_normal_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_
 
 int rpt_debug_mesh_material_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
 {
-    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_material_map_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_material_map_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    if (!rays_dev || !out_dev || (flags & ~(uint32_t)RPT_MESH_QUERY_BRUTE)) { set_err(ctx, "rpt_debug_mesh_material_map_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->mmap.any() || !ctx->devs[0].mmap || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_material_map_query: no mesh has a material map"); return RPT_ERR_INVALID_ARG; }
-    if (n == 0) return RPT_OK;
+    int rc;
+    if (!probe_ready(ctx, "rpt_debug_mesh_material_map_query", rays_dev, out_dev, flags, RPT_MESH_QUERY_BRUTE, n, &rc, probe_needs_mmap)) return rc;
     RPT_ON_DEVICE(ctx);
-    const DevState& d = ctx->devs[0];
-    RPT_HIP_CHECK(ctx, rptlaunch::mesh_material_map_query(rptargs::mesh_map_scene_of<SceneMeshMap>(mesh_view_of(ctx, d), rptargs::MmapView{d.mmap, ctx->mmap}), rays_dev, out_dev, n,
-                                                          flags, (hipStream_t)stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_material_map_query(rptargs::mesh_map_scene_of<SceneMeshMap>(mesh_view_of(ctx, ctx->devs[0]), rptargs::MmapView{ctx->devs[0].mmap, ctx->mmap}), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
 }
 
@@ -2921,11 +2924,8 @@ static SceneMeshEmit emit_probe_scene_of(rpt_ctx* ctx, const DevState& d)
 
 int rpt_debug_mesh_emission_map_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
 {
-    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_emission_map_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_emission_map_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    if (!rays_dev || !out_dev || (flags & ~(uint32_t)RPT_MESH_QUERY_BRUTE)) { set_err(ctx, "rpt_debug_mesh_emission_map_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->emap.any() || !ctx->devs[0].emap || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_emission_map_query: no mesh has an emission map"); return RPT_ERR_INVALID_ARG; }
-    if (n == 0) return RPT_OK;
+    int rc;
+    if (!probe_ready(ctx, "rpt_debug_mesh_emission_map_query", rays_dev, out_dev, flags, RPT_MESH_QUERY_BRUTE, n, &rc, probe_needs_emap)) return rc;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_emission_map_query(emit_probe_scene_of(ctx, ctx->devs[0]), rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
@@ -2933,12 +2933,8 @@ int rpt_debug_mesh_emission_map_query(rpt_ctx* ctx, const float* rays_dev, uint6
 
 int rpt_debug_mesh_emission_map_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, uint32_t* out_dev, void* stream)
 {
-    if (!ctx) { set_err(nullptr, "rpt_debug_mesh_emission_map_sample: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_mesh_emission_map_sample: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    if (!in_dev || !out_dev) { set_err(ctx, "rpt_debug_mesh_emission_map_sample: invalid argument"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->emap.any() || !ctx->devs[0].emap || !ctx->devs[0].tex) { set_err(ctx, "rpt_debug_mesh_emission_map_sample: no mesh has an emission map"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->light.any() || !ctx->devs[0].light) { set_err(ctx, "rpt_debug_mesh_emission_map_sample: no mesh is ON"); return RPT_ERR_INVALID_ARG; }
-    if (n == 0) return RPT_OK;
+    int rc;
+    if (!probe_ready(ctx, "rpt_debug_mesh_emission_map_sample", in_dev, out_dev, 0u, 0u, n, &rc, probe_needs_emap_and_lights)) return rc;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_emission_map_sample(emit_probe_scene_of(ctx, ctx->devs[0]), in_dev, out_dev, n, (hipStream_t)stream));
     return RPT_OK;
@@ -2946,11 +2942,8 @@ int rpt_debug_mesh_emission_map_sample(rpt_ctx* ctx, const float* in_dev, uint64
 
 int rpt_debug_env_query(rpt_ctx* ctx, const float* dirs_dev, uint64_t n, uint32_t* out_dev, void* stream)
 {
-    if (!ctx) { set_err(nullptr, "rpt_debug_env_query: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_env_query: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    if (!dirs_dev || !out_dev) { set_err(ctx, "rpt_debug_env_query: invalid argument"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->env.any() || !ctx->devs[0].env) { set_err(ctx, "rpt_debug_env_query: no environment is set"); return RPT_ERR_INVALID_ARG; }
-    if (n == 0) return RPT_OK;
+    int rc;
+    if (!probe_ready(ctx, "rpt_debug_env_query", dirs_dev, out_dev, 0u, 0u, n, &rc, probe_needs_env)) return rc;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::env_query(rptargs::mesh_scene_of<SceneMeshEnv>(mesh_view_of(ctx, ctx->devs[0])), dirs_dev, out_dev, n, (hipStream_t)stream));
     return RPT_OK;
@@ -2958,11 +2951,8 @@ int rpt_debug_env_query(rpt_ctx* ctx, const float* dirs_dev, uint64_t n, uint32_
 
 int rpt_debug_env_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, uint32_t* out_dev, void* stream)
 {
-    if (!ctx) { set_err(nullptr, "rpt_debug_env_sample: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
-    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_debug_env_sample: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
-    if (!in_dev || !out_dev) { set_err(ctx, "rpt_debug_env_sample: invalid argument"); return RPT_ERR_INVALID_ARG; }
-    if (!ctx->env.any() || !ctx->devs[0].env) { set_err(ctx, "rpt_debug_env_sample: no environment is set"); return RPT_ERR_INVALID_ARG; }
-    if (n == 0) return RPT_OK;
+    int rc;
+    if (!probe_ready(ctx, "rpt_debug_env_sample", in_dev, out_dev, 0u, 0u, n, &rc, probe_needs_env)) return rc;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::env_sample(rptargs::mesh_scene_of<SceneMeshEnv>(mesh_view_of(ctx, ctx->devs[0])), in_dev, out_dev, n, (hipStream_t)stream));
     return RPT_OK;
