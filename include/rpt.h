@@ -1350,6 +1350,81 @@ typedef struct rpt_mesh_emission_map {
 int rpt_set_mesh_emission_maps(rpt_ctx* ctx, const rpt_mesh_emission_map* items, uint32_t n_items);
 int rpt_download_mesh_emission_map(rpt_ctx* ctx, uint32_t mesh, float* texels /* host, width*height*4 f32, decoded */, uint32_t width, uint32_t height);
 
+/* ---- mesh media — PROJECT-DEFINED ------------------------------------------------------------------------------------------------
+ * A mesh may bound a homogeneous medium: coloured absorption inside a glass mesh (Beer-Lambert), a glowing volume, fog.  The media
+ * arithmetic is "participating media" above, unchanged: phase_hg, sample_hg, the transmittance, steps 1-4 of the bounce loop, the
+ * draw order inside a SCATTER medium, Russian roulette, the max_depth accounting, "no nesting" and "false at the camera".  Here is
+ * only how a mesh scene reads every word of those steps that says "material".
+ *
+ * Media come in through rpt_set_mesh_media after the upload, like every other per-mesh feature; a mesh scene uploaded with
+ * RPT_SCENE_MEDIA stays RPT_ERR_UNSUPPORTED, and the medium fields of a mesh's rpt_material are not read.
+ *
+ * Which medium a hit carries.  A winning triangle carries its mesh's medium, if that mesh has one that is not NONE.  A hit on a
+ * sphere or a plane carries none: in_medium and state.medium stay as they are (the existing rule for a material without a medium).
+ * In a mesh scene only meshes have media.
+ *
+ * Step 4, the side test.  After the next ray is set, if the winning triangle's mesh carries a medium:
+ *     in_medium = dot(new ray direction, G) < 0,   G = normalize(cross(e1, e2))
+ * G is the FLAT normal of the winning triangle — the very value a FLAT mesh without a normal map has as its hit normal, not turned
+ * toward the ray — and when the test is true state.medium = that mesh's medium.  Smooth shading and normal maps bend what the BSDF
+ * sees; they do not move the boundary.  For a FLAT mesh without a map this is bit for bit step 4 as written above.
+ *
+ * Step 1 at a miss.  The background, or the environment with its miss-side MIS weight (which reads scatter_sample.pdf: after a medium
+ * scatter the phase pdf), is added unattenuated, also inside a medium.
+ *
+ * Steps 2 and 3, light samples.  The pick is the mesh scenes' pick ("pickable lights"): N = n_lights + ON meshes + (1 if the
+ * environment is SAMPLED), the environment last.  At a scatter point scatter_pos is the point itself: no eps offset, no normal.  The
+ * facing test of the sampled light is unchanged.  The phase function stands in place of the BSDF for f, pdf and the MIS weight.  The
+ * unoccluded `li` is multiplied by the medium's transmittance over light_sample.dist only when that distance is finite: an
+ * environment sample (dist = +inf) is never attenuated.  The mesh-light hit weight and the emitter exit read scatter_sample.pdf as
+ * always.
+ *
+ * Shadow rays stay the scene's binary any_hit, cutouts included: a medium's own boundary occludes lights outside it.  A hole in a
+ * cutout boundary lets a path through without changing in_medium, because no triangle was hit there.
+ *
+ * Composes with FLAT / SMOOTH, lights OFF / ON (a mesh may be both ON and carry a medium), textures, material, emission and normal
+ * maps, cutouts and an environment.  rpt_update_meshes, rpt_rebuild_meshes and their _device forms leave the media alone and add no
+ * launch: the tables go by mesh and by flattened triangle index, never by slot.  An upload drops every medium.
+ *
+ * rpt_set_mesh_media follows rpt_set_mesh_lights in every convention: listed meshes change, the others stay; n_items == 0 is RPT_OK
+ * and does nothing; everything is checked before anything is stored, so a rejected call changes nothing; a runtime failure part-way
+ * leaves the context with no scene.  RPT_ERR_NO_SCENE unless the scene has meshes.  RPT_ERR_INVALID_ARG, in this order: items NULL
+ * with a non-zero count; then per item mesh >= n_meshes, a mesh named twice, a type beyond RPT_MEDIUM_EMISSIVE, a negative or
+ * non-finite density, a non-finite colour, a non-finite anisotropy.  RPT_ERR_UNSUPPORTED when more than 32766 meshes would carry a
+ * medium (what a path can remember).  The anisotropy is clamped to [-0.9, 0.9] as Material::finalize does, once, in the call.  An
+ * item of type NONE removes the mesh's medium (its other fields are checked and dropped).  When the last medium goes back to NONE
+ * the context renders exactly as if the call had never been made: same kernel, same tables.  On a rpt_create_multi context the call
+ * writes every device; ranks of rpt_create_rank each call it.
+ *
+ * Kernel forms: eight, one over each emission-mapped form (a scene without emission maps, material maps, textures or mesh lights
+ * reaches them through empty tables the media's own allocation carries), strict arithmetic only: RPT_RENDER_FAST_MATH, NESTED_LOOPS
+ * and SMALL_COMPACT stay unsupported for mesh scenes; RPT_RENDER_RUSSIAN_ROULETTE works, as it does after a medium scatter elsewhere.
+ *
+ * Registers (gfx950, VGPRs / spilled SGPRs, the emission-mapped base form in brackets, no scratch in any form;
+ * tools/kernel_meta.py): meshmed 116 / 162 (111 / 158), meshmed_env 118 / 164 (113 / 160), meshmed_cut 116 / 216 (111 / 197),
+ * meshmed_cut_env 118 / 224 (112 / 185), meshmed_nrm 116 / 164 (111 / 164), meshmed_nrm_env 118 / 162 (113 / 166),
+ * meshmed_nrm_cut 116 / 220 (111 / 201), meshmed_nrm_cut_env 118 / 228 (113 / 201): at most 118 of the 128 VGPRs that four waves per
+ * SIMD allow.  The one edit to a header other kernels include (dev_integrator.h: step 4's side test reads its normal through a
+ * forwarding function that defaults to the caller's) left the code objects of every other library what they were.
+ *
+ * Timings (MI355X, 1080p x 16 spp, medians of 5): 0.565 Gsamples/s with no medium, 0.552 with an ABSORB medium on the glass icosphere
+ * (0.977) and 0.421 with a SCATTER medium on it (0.745: the fog frames do more work per path by construction); rpt_set_mesh_media
+ * 6-7 ms the first time on a context (it makes the refit tables) and 0.36 ms again; the four move calls without / with a medium:
+ * update_meshes 0.44 / 0.44 ms; rebuild_meshes 1.02 / 1.00 ms; update_meshes_device 0.16 / 0.16 ms; rebuild_meshes_device 0.73 /
+ * 0.73 ms.  tools/mesh_bench.py --media alternates, in one process, frames of scenes.mesh_scene with its icosphere made glass under no
+ * medium, an ABSORB medium and a SCATTER medium on it, and times the set call and the four move calls with and without a medium. */
+typedef struct rpt_mesh_medium {
+    uint32_t mesh;                    /* index into the uploaded scene's rpt_scene_desc.meshes */
+    uint32_t medium_type;             /* RPT_MEDIUM_* ; RPT_MEDIUM_NONE removes the mesh's medium */
+    float density;
+    float color[3];
+    float anisotropy;                 /* clamped to [-0.9, 0.9] as Material::finalize does */
+} rpt_mesh_medium;
+
+int rpt_set_mesh_media(rpt_ctx* ctx, const rpt_mesh_medium* items, uint32_t n_items);
+/* What the context holds for `mesh`: the clamped anisotropy; RPT_MEDIUM_NONE and zeros for a mesh without a medium. */
+int rpt_download_mesh_medium(rpt_ctx* ctx, uint32_t mesh, rpt_mesh_medium* out);
+
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)
  *   frames_done ColorBuffer.frames before the call; the caller adds `spp` afterwards

@@ -306,6 +306,9 @@ public:
         check(rpt_download_mesh_emission_map(ctx_, mesh, out.data(), width, height), ctx_);
         return out;
     }
+    /// Mesh media (rpt.h, "mesh media"): a homogeneous medium bounded by each named mesh — coloured absorption, a glow or fog; an item of
+    /// type RPT_MEDIUM_NONE removes its mesh's.  sync_scene() drops them all.
+    void set_mesh_media(const std::vector<rpt_mesh_medium>& items) { check(rpt_set_mesh_media(ctx_, items.data(), (uint32_t)items.size()), ctx_); }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

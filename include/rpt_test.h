@@ -115,11 +115,20 @@ int rpt_debug_mesh_emission_map_query(rpt_ctx* ctx, const float* rays_dev, uint6
  * RPT_ERR_INVALID_ARG while no map is ON or no mesh is ON. */
 int rpt_debug_mesh_emission_map_sample(rpt_ctx* ctx, const float* in_dev, uint64_t n, uint32_t* out_dev, void* stream);
 
+/* The join of meshes and media (include/rpt.h, "mesh media"), through the closest walk and the hit_medium_index, medium_at and
+ * medium_side_normal the media scenes' render kernels call (the form over the textured mesh-light tables), one ray per lane: rays_dev
+ * = n x 9 floats {o, d, l}; out_dev = n x 4 dwords — per ray {the winning triangle's flattened index or 0xFFFFFFFF, its mesh's
+ * medium ordinal or 0xFFFF (none), the bits of dot(l, G) with G the winning triangle's flat normal (0 when nothing is hit),
+ * in_medium after step 4 started from false}; `flags`: RPT_MESH_QUERY_BRUTE or 0.  RPT_ERR_NO_SCENE unless the uploaded scene has
+ * meshes; RPT_ERR_INVALID_ARG while no mesh carries a medium (those kernels do not run then). */
+int rpt_debug_mesh_media_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream);
+
 /* Which mesh render form the context's first device's last launch took: 0 .. 11 the twelve forms of csrc/mesh_args.h in MeshForm's
  * order (nrm_cut_env, nrm_cut, nrm_env, nrm, cut_env, cut, env, light_tex, tex, light, smooth, flat), 12 .. 19 a material map over
  * the eight textured forms that hold every table (csrc/mesh_args_mmap.h: light_tex, env, cut, cut_env, nrm, nrm_env, nrm_cut,
  * nrm_cut_env), 20 .. 27 an emission map over those eight in the same order (csrc/mesh_args_emap.h), with or without a material
- * map; 0xFFFFFFFF when that launch was no mesh scene's or there was none.  rpt_debug_kernel_choice has no bit left for material or
+ * map, 28 .. 35 a medium over those eight in the same order (csrc/mesh_args_med.h: some mesh carries a medium; bit 24 of
+ * rpt_debug_kernel_choice, the media form, is set as well); 0xFFFFFFFF when that launch was no mesh scene's or there was none.  rpt_debug_kernel_choice has no bit left for material or
  * emission maps and keeps its meaning: bits 26-31 say which of the other features are present. */
 int rpt_debug_mesh_form(rpt_ctx* ctx, uint32_t* form);
 

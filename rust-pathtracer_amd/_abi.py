@@ -191,6 +191,10 @@ class rpt_mesh_emission_map(C.Structure):
                 ("texels", C.POINTER(C.c_uint8)), ("filter", C.c_uint32), ("gamma", C.c_float)]
 
 
+class rpt_mesh_medium(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("medium_type", C.c_uint32), ("density", C.c_float), ("color", F3), ("anisotropy", C.c_float)]
+
+
 class rpt_scene_desc(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("flags", C.c_uint32),
@@ -257,6 +261,8 @@ SYMBOLS = {
     "rpt_download_mesh_material_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
     "rpt_set_mesh_emission_maps": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_emission_map), C.c_uint32]),
     "rpt_download_mesh_emission_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
+    "rpt_set_mesh_media": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_medium), C.c_uint32]),
+    "rpt_download_mesh_medium": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(rpt_mesh_medium)]),
     "rpt_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -298,6 +304,7 @@ TEST_SYMBOLS = {
     "rpt_debug_mesh_material_map_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rpt_debug_mesh_emission_map_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rpt_debug_mesh_emission_map_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "rpt_debug_mesh_media_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rpt_debug_mesh_form": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rpt_debug_env_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "rpt_debug_env_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -732,6 +732,38 @@ class Tracer:
         check(lib().rpt_download_mesh_emission_map(self._h, int(m), out.ctypes.data, int(width), int(height)), self._h)
         return out
 
+    def set_mesh_media(self, items):
+        """Mesh media (include/rpt.h, "mesh media"): `items` maps a mesh's index in scene().meshes to None — the mesh loses its
+        medium — or to a dict with "type" ("absorb", "scatter", "emissive" or None), "density", "color" (three floats) and optionally
+        "anisotropy" (default 0; the library clamps it to [-0.9, 0.9]).  The mesh bounds the medium: a path that enters through one
+        of its triangles is absorbed, scattered or lit along its way until it leaves through another.  Meshes not named keep their
+        medium; upload_scene() drops every medium, as in C."""
+        types = {None: _abi.RPT_MEDIUM_NONE, "absorb": _abi.RPT_MEDIUM_ABSORB, "scatter": _abi.RPT_MEDIUM_SCATTER, "emissive": _abi.RPT_MEDIUM_EMISSIVE}
+        items = sorted(items.items())
+        its = (_abi.rpt_mesh_medium * max(1, len(items)))()
+        for it, (m, md) in zip(its, items):
+            it.mesh, it.medium_type = int(m), _abi.RPT_MEDIUM_NONE
+            if md is None:
+                continue
+            kind = md.get("type")
+            if kind not in types:
+                raise ValueError("mesh %d: type must be \"absorb\", \"scatter\", \"emissive\" or None, not %r" % (m, kind))
+            color = [float(c) for c in md.get("color", (1.0, 1.0, 1.0))]
+            if len(color) != 3:
+                raise ValueError("mesh %d: color must have three components" % m)
+            it.medium_type, it.density, it.anisotropy = types[kind], float(md.get("density", 0.0)), float(md.get("anisotropy", 0.0))
+            it.color[0], it.color[1], it.color[2] = color
+        self._checked_move(lib().rpt_set_mesh_media(self._h, its, len(items)))
+
+    def download_mesh_medium(self, m):
+        """What the context holds for mesh `m` (rpt_download_mesh_medium): a dict with "type" ("absorb", "scatter", "emissive" or None),
+        "density", "color" and "anisotropy" — the clamped value; type None and zeros for a mesh without a medium."""
+        names = {_abi.RPT_MEDIUM_NONE: None, _abi.RPT_MEDIUM_ABSORB: "absorb", _abi.RPT_MEDIUM_SCATTER: "scatter", _abi.RPT_MEDIUM_EMISSIVE: "emissive"}
+        out = _abi.rpt_mesh_medium()
+        check(lib().rpt_download_mesh_medium(self._h, int(m), C.byref(out)), self._h)
+        return {"type": names[out.medium_type], "density": np.float32(out.density), "color": tuple(np.float32(c) for c in out.color),
+                "anisotropy": np.float32(out.anisotropy)}
+
     def _refresh_stale_meshes(self):
         """scene().meshes' vertex arrays that a device-source call left stale, read back once (only before an upload)."""
         for m in sorted(self._stale_meshes):

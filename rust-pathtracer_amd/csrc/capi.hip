@@ -25,6 +25,7 @@
 #include "host_env.h"
 #include "host_light.h"
 #include "host_map.h"
+#include "host_med.h"
 #include "host_mmap.h"
 #include "host_move.h"
 #include "host_nrm.h"
@@ -39,6 +40,7 @@
 #include "launch_emap.h"
 #include "launch_env.h"
 #include "launch_light.h"
+#include "launch_med.h"
 #include "launch_mmap.h"
 #include "launch_move.h"
 #include "launch_nrm.h"
@@ -47,6 +49,7 @@
 #include "mesh_args.h"
 #include "mesh_args_mmap.h"
 #include "mesh_args_emap.h"
+#include "mesh_args_med.h"
 #ifdef RPT_TEST_HOOKS
 #include "../../include/rpt_test.h"
 #endif
@@ -81,6 +84,7 @@ struct DevState {
     void* nrm = nullptr;              // mesh normal maps' tables (host_nrm.h, NrmLayout): while some mesh's map is ON (rpt_set_mesh_normal_maps)
     void* mmap = nullptr;             // mesh material maps' tables (host_mmap.h, MmapLayout): while some mesh's map is ON (rpt_set_mesh_material_maps)
     void* emap = nullptr;             // mesh emission maps' tables (host_emap.h, EmapLayout): while some mesh's map is ON (rpt_set_mesh_emission_maps)
+    void* med = nullptr;              // mesh media's tables (host_med.h, MedLayout): while some mesh carries a medium (rpt_set_mesh_media)
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -134,6 +138,7 @@ struct rpt_ctx {
     rpthost::NrmPlan nrm;             // which of its meshes have a normal map and where each one's texels lie on every device (host_nrm.h)
     rpthost::MmapPlan mmap;           // which of its meshes have a material map and where each one's texels lie on every device (host_mmap.h)
     rpthost::EmapPlan emap;           // which of its meshes have an emission map and where each one's texels lie on every device (host_emap.h)
+    rpthost::MedPlan med;             // which of its meshes carry a medium and the sizes of every device's media tables (host_med.h)
     // resident ColorBuffer (buffer.rs:6-14): pixels as per-rank tiles + frames
     uint32_t res_w = 0, res_h = 0, res_tile_rows = 0, res_rows_padded = 0;
     uint64_t res_frames = 0;
@@ -323,6 +328,7 @@ static void free_mesh_work(DevState& d)
     if (d.nrm) { (void)hipFree(d.nrm); d.nrm = nullptr; }
     if (d.mmap) { (void)hipFree(d.mmap); d.mmap = nullptr; }
     if (d.emap) { (void)hipFree(d.emap); d.emap = nullptr; }
+    if (d.med) { (void)hipFree(d.med); d.med = nullptr; }
     d.refit_full = false;
     d.build_temp_bytes = 0;
 }
@@ -511,6 +517,18 @@ static hipError_t launch_mesh_emit_form(const rptargs::MeshView& view, const rpt
     return launcher(s, rp, grid, stream);
 }
 
+// One media render form (mesh_args_med.h), likewise.
+template <class S, class Launcher>
+static hipError_t launch_mesh_med_form(const rptargs::MeshView& view, const rptargs::MmapView& maps, bool material_maps, const rptargs::EmapView& emits,
+                                       bool emission_maps, const rptargs::MedView& meds, const SceneMesh& scm, Launcher launcher, const RenderParams& rp,
+                                       uint32_t grid, hipStream_t stream)
+{
+    S s = rptargs::mesh_med_scene_of<S>(view, maps, material_maps, emits, emission_maps, meds);
+    s.cam = scm.cam;
+    s.flags = scm.flags;
+    return launcher(s, rp, grid, stream);
+}
+
 // One render launch sequence on one device.
 static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t width, uint32_t height, uint64_t frames_done, uint32_t spp,
                          uint64_t seed, uint32_t flags, uint32_t tile_rows, uint32_t rank, uint32_t world, hipStream_t stream)
@@ -533,6 +551,7 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
     const bool normal_maps = kind == SceneKind::mesh && d.nrm && d.tex && d.refit && ctx->nrm.any();   // some mesh's normal map is ON: k_nrm.hip's forms, over the four above that hold every table
     const bool material_maps = kind == SceneKind::mesh && d.mmap && d.tex && d.refit && ctx->mmap.any();   // some mesh's material map is ON: k_mmap.hip's forms, over the eight textured forms that hold every table
     const bool emission_maps = kind == SceneKind::mesh && d.emap && d.tex && d.refit && ctx->emap.any();   // some mesh's emission map is ON: k_emap.hip's forms, over the eight material-mapped forms
+    const bool mesh_media = kind == SceneKind::mesh && d.med && d.refit && ctx->med.any();   // some mesh carries a medium: k_med.hip's forms, over the eight emission-mapped forms
     scs.cam = scl.cam = scm.cam = make_camera(ctx->scene.camera, (float)width, (float)height);
     const bool in_hbm = kind == SceneKind::large || kind == SceneKind::mesh;     // the scene's tables are in device memory
     const bool has_sdf = !in_hbm && scs.sdf.n_prims > 0;
@@ -593,17 +612,33 @@ static int launch_render(rpt_ctx* ctx, DevState& d, float* pixels_dev, uint32_t 
                         ((kc.material_table_mapped ? kc.class_map.n_classes : 0u) << 8) | (kc.sized_sdf << 16) |
                         (fast ? 1u << 20 : 0u) | (rp.compact && !nested ? 1u << 21 : 0u) |
                         (rp.compact && !nested && nblocks <= kCompactDenseMaxBlocks ? 1u << 22 : 0u) | (nested ? 1u << 23 : 0u) |
-                        (media ? 1u << 24 : 0u) | (kind == SceneKind::mesh ? 1u << 25 : 0u) |
+                        (media || mesh_media ? 1u << 24 : 0u) | (kind == SceneKind::mesh ? 1u << 25 : 0u) |
                         (smooth ? 1u << 26 : 0u) | (lights ? 1u << 27 : 0u) | (textured ? 1u << 28 : 0u) |
                         (environment ? 1u << 29 : 0u) | (cutouts ? 1u << 30 : 0u) | (normal_maps ? 1u << 31 : 0u);
         // (material and emission maps have no bit: the mesh form says it — 12 .. 19 and 20 .. 27, include/rpt_test.h, rpt_debug_mesh_form)
-        d.last_form = kind == SceneKind::mesh ? rptargs::mesh_form_emit_of(smooth, lights, textured, environment, cutouts, normal_maps, material_maps, emission_maps)
+        d.last_form = kind == SceneKind::mesh ? rptargs::mesh_form_med_of(smooth, lights, textured, environment, cutouts, normal_maps, material_maps, emission_maps, mesh_media)
                                               : 0xFFFFFFFFu;
     }
     const auto launch = [&](uint32_t grid) -> hipError_t {
         if (kind == SceneKind::mesh) {
             using rptargs::MeshForm;
             const rptargs::MeshView view = mesh_view_of(ctx, d);
+            if (d.last_form >= rptargs::kMeshFormMedFirst) {
+                using rptargs::MeshMedForm;
+                const rptargs::MmapView maps{d.mmap, ctx->mmap};
+                const rptargs::EmapView emits{d.emap, ctx->emap};
+                const rptargs::MedView meds{d.med, ctx->med};
+                switch ((MeshMedForm)d.last_form) {
+                case MeshMedForm::light_tex: return launch_mesh_med_form<SceneMeshMed>(view, maps, material_maps, emits, emission_maps, meds, scm, rptlaunch::render_mesh_med, rp, grid, stream);
+                case MeshMedForm::env: return launch_mesh_med_form<SceneMeshMedEnv>(view, maps, material_maps, emits, emission_maps, meds, scm, rptlaunch::render_mesh_med_env, rp, grid, stream);
+                case MeshMedForm::cut: return launch_mesh_med_form<SceneMeshMedCut>(view, maps, material_maps, emits, emission_maps, meds, scm, rptlaunch::render_mesh_med_cut, rp, grid, stream);
+                case MeshMedForm::cut_env: return launch_mesh_med_form<SceneMeshMedCutEnv>(view, maps, material_maps, emits, emission_maps, meds, scm, rptlaunch::render_mesh_med_cut_env, rp, grid, stream);
+                case MeshMedForm::nrm: return launch_mesh_med_form<SceneMeshMedNrm>(view, maps, material_maps, emits, emission_maps, meds, scm, rptlaunch::render_mesh_med_nrm, rp, grid, stream);
+                case MeshMedForm::nrm_env: return launch_mesh_med_form<SceneMeshMedNrmEnv>(view, maps, material_maps, emits, emission_maps, meds, scm, rptlaunch::render_mesh_med_nrm_env, rp, grid, stream);
+                case MeshMedForm::nrm_cut: return launch_mesh_med_form<SceneMeshMedNrmCut>(view, maps, material_maps, emits, emission_maps, meds, scm, rptlaunch::render_mesh_med_nrm_cut, rp, grid, stream);
+                case MeshMedForm::nrm_cut_env: return launch_mesh_med_form<SceneMeshMedNrmCutEnv>(view, maps, material_maps, emits, emission_maps, meds, scm, rptlaunch::render_mesh_med_nrm_cut_env, rp, grid, stream);
+                }
+            }
             if (d.last_form >= rptargs::kMeshFormEmitFirst) {
                 using rptargs::MeshEmitForm;
                 const rptargs::MmapView maps{d.mmap, ctx->mmap};
@@ -1031,6 +1066,7 @@ static void commit_scene(rpt_ctx* ctx, SceneImage& img, const std::vector<void*>
     ctx->nrm = rpthost::NrmPlan();                                  // every normal map OFF
     ctx->mmap = rpthost::MmapPlan();                                // every material map OFF
     ctx->emap = rpthost::EmapPlan();                                // every emission map OFF
+    ctx->med = rpthost::MedPlan();                                  // no mesh carries a medium
 }
 
 int rpt_upload_scene(rpt_ctx* ctx, const rpt_scene_desc* s)
@@ -1067,6 +1103,7 @@ static void drop_scene(rpt_ctx* ctx)
     ctx->nrm = rpthost::NrmPlan();
     ctx->mmap = rpthost::MmapPlan();
     ctx->emap = rpthost::EmapPlan();
+    ctx->med = rpthost::MedPlan();
 }
 
 // Where the named meshes' new positions come from: host arrays (rpt_update_meshes, rpt_rebuild_meshes) or device arrays through a
@@ -1763,6 +1800,89 @@ int rpt_download_mesh_light_table(rpt_ctx* ctx, uint32_t mesh, uint64_t* cdf, ui
     return RPT_OK;
 }
 
+// ---- rpt_set_mesh_media / rpt_download_mesh_medium (include/rpt.h, "mesh media") ---------------------------------------------------
+static int free_tables(rpt_ctx* ctx, DeviceGuard& guard, void* DevState::*slot, const char* call);      // (below)
+// One device's part: wait for its earlier work (a launch may still read the old tables), make its refit tables if it has none (the
+// media forms read slot_vertex and the vertices), drop the old media tables, fill and copy the new ones in, and wait.  ctx->med is
+// already the new plan.
+static int med_device(rpt_ctx* ctx, DevState& d)
+{
+    const rpthost::MedPlan& mp = ctx->med;
+    const rpthost::MedLayout ml = mp.layout();
+    RPT_HIP_CHECK(ctx, hipDeviceSynchronize());
+    RPT_CHECK_RC(ensure_refit(ctx, d));
+    if (d.med) { (void)hipFree(d.med); d.med = nullptr; }
+    RPT_HIP_CHECK(ctx, hipMalloc(&d.med, ml.total));
+    unsigned char* base = static_cast<unsigned char*>(d.med);
+    RPT_HIP_CHECK(ctx, hipMemsetAsync(base, 0, ml.total, d.stream));
+    for (const rpthost::MapFill& f : ml.emap.fills())
+        if (f.bytes && f.value) RPT_HIP_CHECK(ctx, hipMemsetAsync(base + ml.off_emap + f.off, f.value, f.bytes, d.stream));
+    const auto put = [&](size_t off, const std::vector<uint32_t>& v) {
+        return v.empty() ? hipSuccess : hipMemcpyAsync(base + off, v.data(), sizeof(uint32_t) * v.size(), hipMemcpyHostToDevice, d.stream);
+    };
+    RPT_HIP_CHECK(ctx, put(ml.off_rows, mp.rows));
+    RPT_HIP_CHECK(ctx, put(ml.off_tri_medium, mp.tri_medium));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    return RPT_OK;
+}
+
+int rpt_set_mesh_media(rpt_ctx* ctx, const rpt_mesh_medium* items, uint32_t n_items)
+{
+    using namespace rpthost;
+    if (!ctx) { set_err(nullptr, "rpt_set_mesh_media: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    std::vector<MedEntry> medium;
+    std::string why;
+    const int rc = check_mesh_media(ctx->refit, ctx->scene.kind == SceneKind::mesh, items, n_items, ctx->med.medium, medium, why);
+    if (rc != RPT_OK) { set_err(ctx, "%s", why.c_str()); return rc; }
+    if (n_items == 0) return RPT_OK;
+    MedPlan fresh;
+    build_med_plan(ctx->refit, std::move(medium), fresh);
+    DeviceGuard guard(ctx->devs[0].device);
+    int rc_dev = guard.status == hipSuccess ? RPT_OK : RPT_ERR_HIP;
+    if (rc_dev != RPT_OK) set_err(ctx, "rpt_set_mesh_media: cannot select device %d", ctx->devs[0].device);
+    if (rc_dev == RPT_OK && !fresh.any()) {                         // no mesh carries a medium (again): the context is what it was before the first call
+        rc_dev = free_tables(ctx, guard, &DevState::med, "rpt_set_mesh_media");
+        if (rc_dev == RPT_OK) { ctx->med = MedPlan(); return RPT_OK; }
+    }
+    if (rc_dev == RPT_OK) ctx->med = std::move(fresh);
+    for (size_t i = 0; rc_dev == RPT_OK && i < ctx->devs.size(); ++i) {
+        DevState& d = ctx->devs[i];
+        if (guard.to(d.device) != hipSuccess) { set_err(ctx, "rpt_set_mesh_media: cannot select device %d", d.device); rc_dev = RPT_ERR_HIP; }
+        else rc_dev = med_device(ctx, d);
+    }
+    if (rc_dev != RPT_OK) {
+        const std::string first = ctx->err;
+        drop_scene(ctx);
+        set_err(ctx, "%s; the context now holds no scene", first.c_str());
+        return rc_dev;
+    }
+    ctx->refit.release_staging();                                   // every device holds the refit tables
+    ctx->med.release_staging();
+    return RPT_OK;
+}
+
+int rpt_download_mesh_medium(rpt_ctx* ctx, uint32_t mesh, rpt_mesh_medium* out)
+{
+    if (!ctx) { set_err(nullptr, "rpt_download_mesh_medium: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (ctx->scene.kind != SceneKind::mesh) { set_err(ctx, "rpt_download_mesh_medium: needs an uploaded scene with meshes"); return RPT_ERR_NO_SCENE; }
+    const rpthost::RefitPlan& plan = ctx->refit;
+    if (mesh >= plan.n_meshes()) { set_err(ctx, "rpt_download_mesh_medium: mesh %u out of range (the scene has %u)", mesh, plan.n_meshes()); return RPT_ERR_INVALID_ARG; }
+    if (!out) { set_err(ctx, "rpt_download_mesh_medium: out is NULL"); return RPT_ERR_INVALID_ARG; }
+    rpthost::med_item_of(ctx->med, mesh, *out);
+    if (ctx->med.on(mesh) && ctx->devs[0].med) {                    // the row as the first device holds it
+        uint32_t ord = 0;
+        for (uint32_t j = 0; j < ctx->med.n_media(); ++j) if (ctx->med.on_mesh[j] == mesh) ord = j;
+        rpthost::MedRow row;
+        RPT_ON_DEVICE(ctx);
+        RPT_HIP_CHECK(ctx, hipMemcpy(&row, static_cast<const unsigned char*>(ctx->devs[0].med) + ctx->med.layout().off_rows + sizeof(row) * (size_t)ord, sizeof(row), hipMemcpyDeviceToHost));
+        out->medium_type = row.type;
+        out->density = row.density;
+        out->color[0] = row.color[0]; out->color[1] = row.color[1]; out->color[2] = row.color[2];
+        out->anisotropy = row.anisotropy;
+    }
+    return RPT_OK;
+}
+
 // ---- what rpt_set_mesh_textures and the four image-map setters share ----------------------------------------------------------------
 // "Every mesh OFF (again)": wait on every device that holds `slot` tables (a launch may still read them) and free them.
 static int free_tables(rpt_ctx* ctx, DeviceGuard& guard, void* DevState::*slot, const char* call)
@@ -2384,7 +2504,7 @@ int rpt_debug_kernel_choice(rpt_ctx* ctx, uint32_t* out)
     return RPT_OK;
 }
 
-// (include/rpt_test.h) the last launch's mesh form: 0 .. 11 a MeshForm of mesh_args.h, 12 .. 19 a material-mapped one (mesh_args_mmap.h), 20 .. 27 an emission-mapped one (mesh_args_emap.h)
+// (include/rpt_test.h) the last launch's mesh form: 0 .. 11 a MeshForm of mesh_args.h, 12 .. 19 a material-mapped one (mesh_args_mmap.h), 20 .. 27 an emission-mapped one (mesh_args_emap.h), 28 .. 35 a media one (mesh_args_med.h)
 int rpt_debug_mesh_form(rpt_ctx* ctx, uint32_t* form)
 {
     if (!ctx || !form) return RPT_ERR_INVALID_ARG;
@@ -2937,6 +3057,21 @@ int rpt_debug_mesh_emission_map_sample(rpt_ctx* ctx, const float* in_dev, uint64
     if (!probe_ready(ctx, "rpt_debug_mesh_emission_map_sample", in_dev, out_dev, 0u, 0u, n, &rc, probe_needs_emap_and_lights)) return rc;
     RPT_ON_DEVICE(ctx);
     RPT_HIP_CHECK(ctx, rptlaunch::mesh_emission_map_sample(emit_probe_scene_of(ctx, ctx->devs[0]), in_dev, out_dev, n, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+static const char* probe_needs_med(const rpt_ctx* c) { return !c->med.any() || !c->devs[0].med || !c->devs[0].refit ? "no mesh carries a medium" : nullptr; }
+
+int rpt_debug_mesh_media_query(rpt_ctx* ctx, const float* rays_dev, uint64_t n, uint32_t* out_dev, uint32_t flags, void* stream)
+{
+    int rc;
+    if (!probe_ready(ctx, "rpt_debug_mesh_media_query", rays_dev, out_dev, flags, RPT_MESH_QUERY_BRUTE, n, &rc, probe_needs_med)) return rc;
+    RPT_ON_DEVICE(ctx);
+    const DevState& d = ctx->devs[0];
+    const bool material_maps = d.mmap && d.tex && ctx->mmap.any(), emission_maps = d.emap && d.tex && ctx->emap.any();
+    const SceneMeshMed sc = rptargs::mesh_med_scene_of<SceneMeshMed>(mesh_view_of(ctx, d), rptargs::MmapView{d.mmap, ctx->mmap}, material_maps,
+                                                                    rptargs::EmapView{d.emap, ctx->emap}, emission_maps, rptargs::MedView{d.med, ctx->med});
+    RPT_HIP_CHECK(ctx, rptlaunch::mesh_media_query(sc, rays_dev, out_dev, n, flags, (hipStream_t)stream));
     return RPT_OK;
 }
 

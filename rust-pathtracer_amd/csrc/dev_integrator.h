@@ -1083,6 +1083,14 @@ RPT_DEV bool path_shade_medium(const S& sc, const Q& q, PathRegs& p, const volat
     return path_next_bounce(sc, p);
 }
 
+// The normal step 4's side test below reads at the hit `g`: the `normal` the caller has.  A scene type whose shading normal is not
+// its boundary's overloads this (dev_mesh_med.h); for every other scene type it is that value and nothing else.
+template <class S> RPT_DEV v3 medium_side_normal(const S& sc, const GeomHit& g, v3 normal)
+{
+    (void)sc; (void)g;
+    return normal;
+}
+
 // Returns true when the path is over (pdf <= 0 or depth exhausted).
 // `n_pre`: the normal when the caller already has it (the march kernel needs it before the shadow march); `cold`: the
 // hit point parked in LDS when p.ray.o no longer holds the path's origin (the march kernel lends it to the shadow
@@ -1152,7 +1160,7 @@ RPT_DEV bool path_shade_full(const S& sc, const Q& q, PathRegs& p, const GeomHit
         // crossing, or staying on one side of, the boundary of a medium (include/rpt.h, media, step 4)
         const uint32_t mi = hit_medium_index(sc, g);
         if (mi != kNoMediumIdx) {
-            if (medium_at(sc, mi).type != RPT_MEDIUM_NONE) p.medium = (dot3(scatter_l, normal) < 0.0f) ? (mi + 1u) : 0u;
+            if (medium_at(sc, mi).type != RPT_MEDIUM_NONE) p.medium = (dot3(scatter_l, medium_side_normal(sc, g, normal)) < 0.0f) ? (mi + 1u) : 0u;
         }
     }
     return path_next_bounce(sc, p);

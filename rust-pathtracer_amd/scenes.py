@@ -227,6 +227,26 @@ def mesh_light_scene(sphere_light=False, lamp_emission=(40.0, 36.0, 30.0)):
     return s
 
 
+def mesh_media_scene(kind="scatter"):
+    """-> (scene, media): a small scene for mesh media (include/rpt.h, "mesh media"): mesh_light_scene(sphere_light=True) (82
+    triangles) with the icosphere's material made glass (spec_trans 1, ior 1.45, roughness 0.05) so that paths enter it;
+    any_hit_uses_max_dist is set, as mesh lights already require.  `media` is what Tracer.set_mesh_media takes after the upload:
+    a medium of `kind` ("absorb": a coloured Beer-Lambert glass, "scatter": a forward-scattering fog, "emissive": a dim glow,
+    None: the icosphere loses its medium) on mesh 0."""
+    s = mesh_light_scene(sphere_light=True)
+    s.materials[0] = full_material(rgb=(0.95, 0.95, 0.95), roughness=0.05, spec_trans=1.0, ior=1.45)
+    s.any_hit_uses_max_dist = True
+    media = {
+        None: None,
+        "absorb": dict(type="absorb", density=3.0, color=(0.9, 0.45, 0.3)),
+        "scatter": dict(type="scatter", density=2.5, color=(0.85, 0.9, 0.95), anisotropy=0.6),
+        "emissive": dict(type="emissive", density=0.5, color=(0.2, 0.6, 0.9)),
+    }
+    if kind not in media:
+        raise ValueError("kind must be \"absorb\", \"scatter\", \"emissive\" or None, not %r" % (kind,))
+    return s, {0: media[kind]}
+
+
 def checker_texture(w, h, colour_a=(255, 255, 255), colour_b=(40, 40, 40), cells=8):
     """-> [h, w, 4] uint8 RGBA: a checker of `cells` x `cells` fields over the whole image in two colours, alpha 255; texel (0, 0)
     has colour_a."""

@@ -58,8 +58,13 @@ all-255 1024 x 1024 map on the torus ("ones": the pure cost of the lookups, ever
 noise map ("noise"), on three contexts, alternating; the time of rpt_set_mesh_emission_maps itself; and the wall time of the four move
 calls with and without maps.
 
+--media: one JSON line more, for mesh media (include/rpt.h, "mesh media"): the resident render rate of the scene with its icosphere made
+glass and the shadow rays' flag, with no medium ("none": the mesh kernel the scene always ran, a form below 28), with an ABSORB medium
+on the glass mesh ("absorb") and with a SCATTER medium on it ("scatter"), on three contexts, alternating; the time of rpt_set_mesh_media
+itself; and the wall time of the four move calls with and without a medium.
+
     python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild] [--device] [--smooth] [--lights] [--textures] [--environment]
-                               [--cutouts] [--normal-maps] [--material-maps] [--emission-maps]
+                               [--cutouts] [--normal-maps] [--material-maps] [--emission-maps] [--media]
 """
 import argparse
 import ctypes as C
@@ -89,6 +94,7 @@ def main():
     ap.add_argument("--normal-maps", action="store_true")
     ap.add_argument("--material-maps", action="store_true")
     ap.add_argument("--emission-maps", action="store_true")
+    ap.add_argument("--media", action="store_true")
     a = ap.parse_args()
     os.environ.setdefault("RPT_LIB", os.path.join(ROOT, "rust-pathtracer_amd", "librpt_hip_test.so"))     # (the product has no hooks)
     import __graft_entry__
@@ -121,6 +127,7 @@ def main():
     normal_maps = measure_normal_maps(pkg, s, a) if a.normal_maps else None
     material_maps = measure_material_maps(pkg, s, a) if a.material_maps else None
     emission_maps = measure_emission_maps(pkg, s, a) if a.emission_maps else None
+    media = measure_media(pkg, s, a) if a.media else None
     t.close()
     print(json.dumps({"workload": "mesh_scene %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "triangles": n_tris,
                       "gsamples_per_s_median": sorted(rates)[len(rates) // 2], "gsamples_per_s": rates,
@@ -147,6 +154,8 @@ def main():
         print(json.dumps(material_maps))
     if emission_maps:
         print(json.dumps(emission_maps))
+    if media:
+        print(json.dumps(media))
 
 
 def measure_updates(pkg, t, s, a):
@@ -904,6 +913,97 @@ def measure_emission_maps(pkg, s, a):
     calls = (("update_meshes", "host"), ("rebuild_meshes", "host"), ("update_meshes_device", "device"), ("rebuild_meshes_device", "device"))
     for name, where in calls:
         pair = {"off": context(None), "on": context("noise")}
+        for t in pair.values():
+            getattr(t, name)(back[where])                           # the context's first call of its kind: allocates
+        ms = {"off": [], "on": []}
+        for _ in range(reps):
+            for arg in (there[where], back[where]):
+                for side in ("off", "on"):
+                    ms[side].append(timed(getattr(pair[side], name), arg))
+        for t in pair.values():
+            t.close()
+        fo, fn = stats(ms["off"]), stats(ms["on"])
+        out[name] = {"off_ms": fo, "on_ms": fn, "on_adds_ms": fn["median"] - fo["median"]}
+    return out
+
+
+def measure_media(pkg, s, a):
+    """-> the --media line.  scenes.mesh_scene() with its icosphere (mesh 0) made glass and the shadow rays' flag: with no medium
+    ("none": the form the scene always ran), with an ABSORB medium on the glass mesh ("absorb") and with a SCATTER medium on it
+    ("scatter"): three contexts, alternating within a repetition, medians of `reps`; the set call; and the four move calls on a
+    "none" and a "scatter" context."""
+    import numpy as np
+    import torch
+    from rust_pathtracer_amd import scenes
+
+    def make():
+        sc = scenes.mesh_scene()
+        sc.any_hit_uses_max_dist = True
+        sc.materials[sc.meshes[0][2]] = scenes.full_material(rgb=(0.95, 0.95, 0.95), roughness=0.05, spec_trans=1.0, ior=1.45)
+        return sc
+
+    original = [np.array(v, np.float32, copy=True) for v, _, _ in s.meshes]
+    media = {"absorb": dict(type="absorb", density=3.0, color=(0.9, 0.45, 0.3)),
+             "scatter": dict(type="scatter", density=2.5, color=(0.85, 0.9, 0.95), anisotropy=0.6)}
+
+    def stats(xs):
+        xs = sorted(xs)
+        return {"median": xs[len(xs) // 2], "min": xs[0], "max": xs[-1]}
+
+    def timed(call, arg):
+        t0 = time.perf_counter()
+        call(arg)
+        return (time.perf_counter() - t0) * 1e3
+
+    def rate(tr):
+        tr.render_resident(a.width, a.height, a.spp)
+        return a.width * a.height * a.spp / (tr.resident_kernel_ms() * 1e-3) / 1e9
+
+    def form(tr):
+        f = C.c_uint32(0)
+        pkg._lib.check(pkg.lib().rpt_debug_mesh_form(tr._h, C.byref(f)), tr._h)
+        return f.value
+
+    def context(which):
+        tr = pkg.Tracer(make(), device=0, seed=1)
+        if which is not None:
+            tr.set_mesh_media({0: media[which]})
+        return tr
+
+    reps = max(5, a.reps)
+    sides = ("none", "absorb", "scatter")
+    tr = {"none": context(None)}
+    first, again = {}, {}
+    for k in sides[1:]:
+        tr[k] = context(None)
+        first[k] = timed(tr[k].set_mesh_media, {0: media[k]})       # 32 B per medium, 4 B per triangle of the scene, the empty tables
+        again[k] = [timed(tr[k].set_mesh_media, {0: media[k]}) for _ in range(reps)]
+    for t in tr.values():
+        rate(t)                                                     # warm-up (and the dispatch order's first costs)
+        rate(t)
+    forms = {k: form(tr[k]) for k in sides}
+    assert forms["none"] < 28 <= forms["absorb"] == forms["scatter"], forms
+    rates = {k: [] for k in sides}
+    for _ in range(reps):
+        for k in sides:
+            rates[k].append(rate(tr[k]))
+    for t in tr.values():
+        t.close()
+    med = {k: stats(rates[k])["median"] for k in sides}
+    out = {"workload": "mesh_scene mesh media %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "reps": reps,
+           "media": "on the glass icosphere: ABSORB density 3 colour (0.9, 0.45, 0.3); SCATTER density 2.5 colour (0.85, 0.9, 0.95) g 0.6",
+           "mesh_form": forms,
+           "first_set_mesh_media_ms": first, "set_mesh_media_again_ms": {k: stats(v) for k, v in again.items()},
+           "gsamples_per_s": {k: stats(rates[k]) for k in sides},
+           "absorb_over_none_rate": med["absorb"] / med["none"], "scatter_over_none_rate": med["scatter"] / med["none"]}
+    # moves: the medium move and back, so that every call moves every vertex
+    moved = scenes.mesh_scene_moved(s, 0.5)
+    dev = lambda arrays: {m: torch.from_numpy(np.ascontiguousarray(v, np.float32)).to("cuda:0") for m, v in enumerate(arrays)}   # noqa: E731
+    there, back = {"host": dict(enumerate(moved)), "device": dev(moved)}, {"host": dict(enumerate(original)), "device": dev(original)}
+    torch.cuda.synchronize()
+    calls = (("update_meshes", "host"), ("rebuild_meshes", "host"), ("update_meshes_device", "device"), ("rebuild_meshes_device", "device"))
+    for name, where in calls:
+        pair = {"off": context(None), "on": context("scatter")}
         for t in pair.values():
             getattr(t, name)(back[where])                           # the context's first call of its kind: allocates
         ms = {"off": [], "on": []}
