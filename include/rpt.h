@@ -1425,6 +1425,109 @@ int rpt_set_mesh_media(rpt_ctx* ctx, const rpt_mesh_medium* items, uint32_t n_it
 /* What the context holds for `mesh`: the clamped anisotropy; RPT_MEDIUM_NONE and zeros for a mesh without a medium. */
 int rpt_download_mesh_medium(rpt_ctx* ctx, uint32_t mesh, rpt_mesh_medium* out);
 
+/* ---- ray queries — PROJECT-DEFINED ------------------------------------------------------------------------------------------------
+ * A context that holds a mesh scene answers questions about it for rays the caller brings: what a ray hits first (rpt_trace_rays*),
+ * whether anything lies along it (rpt_occluded*), what the surface there is (rpt_surface), and which rays the camera sends
+ * (rpt_camera_rays_device).  One call serves any mesh scene, whatever features are set; no render form, setter or hook changes.
+ *
+ * Closest hit.  The answer is the integrator's: the geometry pass of closest_hit of "triangle meshes", exactly — spheres, then planes,
+ * then the flattened triangles, from dist = F::MAX, with the acceptance rules stated there.  A scene with cutouts ON uses the cut test
+ * inside the walk ("mesh cutouts"): a ray through a hole goes on.  rpt_lights are not geometry and are never reported.  max_dist is not
+ * read by the closest query.
+ *   the winner   the triangle, if the walk returned one; otherwise the last accepted plane, that is, the highest accepted index;
+ *                otherwise the nearest sphere; otherwise RPT_HIT_NONE
+ *   t            the accepted distance, bit for bit; +inf's bits for NONE.  A primitive accepted by the "first primitive" rule —
+ *                sphere 0, or plane 0 of a scene without spheres — carries whatever t its test returned, as in the integrator: for
+ *                a ray with a NaN or infinite component the sphere test can return a NaN, which is then the answer (kind SPHERE,
+ *                t a NaN whose sign and payload are the hardware's), and no later primitive is nearer than a NaN
+ *   primitive    the index into spheres / planes / the flattened triangle list; 0xFFFFFFFF for NONE
+ *   mesh, triangle   the mesh and the index within the mesh; 0xFFFFFFFF unless a triangle won
+ *   u, v         the triangle test's u and v, in its operation order — the very values textures and smooth normals interpolate with;
+ *                0 for anything but a triangle
+ *   reserved     written 0 in outputs, ignored in rpt_ray
+ * A ray with a NaN component hits no triangle ("triangle meshes"); what the spheres and planes answer is what their tests answer.
+ *
+ * rpt_surface is written only when surfaces_dev / surfaces is not NULL.  It holds what SHADE would build for this hit before
+ * State::finalize:
+ *   ng           the geometric normal: for a triangle normalize(cross(e1, e2)), NOT turned toward the ray; for spheres and planes the
+ *                integrator's normal
+ *   ns           the normal the scene's hit_normal returns: smooth interpolation ("smooth mesh shading") and the normal map ("mesh
+ *                normal maps") where they are ON; ng's bits where they are not
+ *   rgb, roughness, metallic   those fields of the material after the scene's hit_material: texture, material map, and the planes'
+ *                layered patches over the nearest sphere's
+ *   emission     hit_emission_at: an emission map multiplies it ("mesh emission maps")
+ *   material     the winner's index into materials
+ * For RPT_HIT_NONE everything is zero.
+ *
+ * Occlusion.  occluded[i] = 1 when some sphere, plane or triangle (one that passes the cut test) is hit with t < max_dist, otherwise 0.
+ * The ray's max_dist is always honoured, whatever RPT_SCENE_ANYHIT_USES_MAX_DIST says; pass +inf for "anything along the ray".  A NaN
+ * max_dist gives 0.
+ *
+ * Camera rays.  rpt_camera_rays_device writes width * height rays, row 0 on top, pixel (x, y) at y * width + x: each the reference
+ * camera's ray for that pixel with both jitter draws replaced by 0.5f — camera_ray(make_camera(...), px, py, 0.5, 0.5), the very
+ * function and frame-invariant part a render uses, px and py what a render launch computes for the pixel — and max_dist = +inf.
+ * Tracing these rays with surfaces_dev gives first-hit depth (t), normal (ng, ns), albedo (rgb) and id (primitive, mesh, material)
+ * buffers: what a compositor or an external denoiser asks for.
+ *
+ * Ordering.  The _device forms enqueue on `stream` and return without waiting.  They see the effect of every earlier call on the
+ * context — uploads, the four move calls, every setter: those calls wait for their own device work before they return.  Work of the
+ * CALLER's on another stream (the kernel that writes rays_dev, a reader of hits_dev) is the caller's to order, as with
+ * rpt_render_device's buffers.  rays_dev, hits_dev and surfaces_dev must be 16-byte aligned (occluded_dev, a byte array, needs no
+ * alignment) and all of them on the context's device; a misaligned pointer is rejected whatever n is.  The host forms stage through device
+ * memory of the context and block.  The first query after an upload makes a small allocation of the query's own (the meshes'
+ * first-triangle offsets and the empty tables that stand for absent features) and waits for it once.
+ *
+ * Errors.  RPT_ERR_NO_SCENE without a scene; RPT_ERR_UNSUPPORTED for a scene that is not a mesh scene (analytical, large and SDF
+ * scenes: not yet) and for a context with more than one local device (an rpt_create_rank context has one and works);
+ * RPT_ERR_INVALID_ARG for a NULL ctx, a NULL array with n > 0, a misaligned pointer, flags != 0 (reserved), zero width or height, and
+ * more rays than a grid of 0x7FFFFFFF workgroups of 256 holds.  n == 0 is RPT_OK and launches nothing.  A rejected call writes
+ * nothing.
+ *
+ * The kernels (csrc/k_query.hip, a code object library of their own) are nine: closest and occluded, each without and with the cut
+ * test; the closest hit with its surface per normal map x cutout; the camera's rays.  One ray per lane, the ray read as two 16-byte
+ * loads, rpt_hit written as two 16-byte stores and rpt_surface as four.  DESIGN.md ("ray queries") has their registers and rates. */
+typedef struct rpt_ray {
+    float origin[3];
+    float max_dist;                   /* occlusion only: hits at t >= max_dist do not count */
+    float direction[3];               /* as handed to the integrator: not normalised here */
+    uint32_t reserved;
+} rpt_ray;                            /* 32 B */
+
+enum { RPT_HIT_NONE = 0, RPT_HIT_SPHERE = 1, RPT_HIT_PLANE = 2, RPT_HIT_TRIANGLE = 3 };
+
+typedef struct rpt_hit {
+    float t;
+    uint32_t kind;                    /* RPT_HIT_* */
+    uint32_t primitive;
+    uint32_t mesh;
+    uint32_t triangle;
+    float u, v;
+    uint32_t reserved;
+} rpt_hit;                            /* 32 B */
+
+typedef struct rpt_surface {
+    float ng[3];
+    float ns[3];
+    float rgb[3];
+    float emission[3];
+    float roughness, metallic;
+    uint32_t material;
+    uint32_t reserved;
+} rpt_surface;                        /* 64 B */
+
+#if defined(__cplusplus)
+static_assert(sizeof(rpt_ray) == 32 && sizeof(rpt_hit) == 32 && sizeof(rpt_surface) == 64, "ray query records are 32, 32 and 64 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rpt_ray) == 32 && sizeof(rpt_hit) == 32 && sizeof(rpt_surface) == 64, "ray query records are 32, 32 and 64 bytes");
+#endif
+
+int rpt_trace_rays_device(rpt_ctx* ctx, const rpt_ray* rays_dev, uint64_t n, rpt_hit* hits_dev, rpt_surface* surfaces_dev /* or NULL */,
+                          uint32_t flags, void* stream);
+int rpt_occluded_device(rpt_ctx* ctx, const rpt_ray* rays_dev, uint64_t n, uint8_t* occluded_dev, uint32_t flags, void* stream);
+int rpt_camera_rays_device(rpt_ctx* ctx, uint32_t width, uint32_t height, rpt_ray* rays_dev, void* stream);
+int rpt_trace_rays(rpt_ctx* ctx, const rpt_ray* rays, uint64_t n, rpt_hit* hits, rpt_surface* surfaces /* or NULL */, uint32_t flags);   /* host memory, blocks */
+int rpt_occluded(rpt_ctx* ctx, const rpt_ray* rays, uint64_t n, uint8_t* occluded, uint32_t flags);                                     /* host memory, blocks */
+
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)
  *   frames_done ColorBuffer.frames before the call; the caller adds `spp` afterwards

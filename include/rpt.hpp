@@ -309,6 +309,28 @@ public:
     /// Mesh media (rpt.h, "mesh media"): a homogeneous medium bounded by each named mesh — coloured absorption, a glow or fog; an item of
     /// type RPT_MEDIUM_NONE removes its mesh's.  sync_scene() drops them all.
     void set_mesh_media(const std::vector<rpt_mesh_medium>& items) { check(rpt_set_mesh_media(ctx_, items.data(), (uint32_t)items.size()), ctx_); }
+    /// Ray queries (rpt.h, "ray queries") on device arrays, enqueued on `stream`: the closest hit of every ray (and, with `surfaces`,
+    /// the surface there), whether anything lies along it before its max_dist, and the camera's rays through the pixel centres.
+    void trace_rays_device(const rpt_ray* rays, uint64_t n, rpt_hit* hits, rpt_surface* surfaces = nullptr, void* stream = nullptr)
+    {
+        check(rpt_trace_rays_device(ctx_, rays, n, hits, surfaces, 0u, stream), ctx_);
+    }
+    void occluded_device(const rpt_ray* rays, uint64_t n, uint8_t* occluded, void* stream = nullptr) { check(rpt_occluded_device(ctx_, rays, n, occluded, 0u, stream), ctx_); }
+    void camera_rays_device(uint32_t width, uint32_t height, rpt_ray* rays, void* stream = nullptr) { check(rpt_camera_rays_device(ctx_, width, height, rays, stream), ctx_); }
+    /// The same on host arrays; they block.
+    std::vector<rpt_hit> trace_rays(const std::vector<rpt_ray>& rays, std::vector<rpt_surface>* surfaces = nullptr)
+    {
+        std::vector<rpt_hit> hits(rays.size());
+        if (surfaces) surfaces->resize(rays.size());
+        check(rpt_trace_rays(ctx_, rays.data(), rays.size(), hits.data(), surfaces ? surfaces->data() : nullptr, 0u), ctx_);
+        return hits;
+    }
+    std::vector<uint8_t> occluded(const std::vector<rpt_ray>& rays)
+    {
+        std::vector<uint8_t> out(rays.size());
+        check(rpt_occluded(ctx_, rays.data(), rays.size(), out.data(), 0u), ctx_);
+        return out;
+    }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

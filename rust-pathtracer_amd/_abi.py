@@ -195,6 +195,23 @@ class rpt_mesh_medium(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("medium_type", C.c_uint32), ("density", C.c_float), ("color", F3), ("anisotropy", C.c_float)]
 
 
+RPT_HIT_NONE, RPT_HIT_SPHERE, RPT_HIT_PLANE, RPT_HIT_TRIANGLE = range(4)
+
+
+class rpt_ray(C.Structure):
+    _fields_ = [("origin", F3), ("max_dist", C.c_float), ("direction", F3), ("reserved", C.c_uint32)]
+
+
+class rpt_hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("kind", C.c_uint32), ("primitive", C.c_uint32), ("mesh", C.c_uint32), ("triangle", C.c_uint32),
+                ("u", C.c_float), ("v", C.c_float), ("reserved", C.c_uint32)]
+
+
+class rpt_surface(C.Structure):
+    _fields_ = [("ng", F3), ("ns", F3), ("rgb", F3), ("emission", F3), ("roughness", C.c_float), ("metallic", C.c_float),
+                ("material", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class rpt_scene_desc(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("flags", C.c_uint32),
@@ -263,6 +280,11 @@ SYMBOLS = {
     "rpt_download_mesh_emission_map": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32]),
     "rpt_set_mesh_media": (C.c_int, [C.c_void_p, C.POINTER(rpt_mesh_medium), C.c_uint32]),
     "rpt_download_mesh_medium": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(rpt_mesh_medium)]),
+    "rpt_trace_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rpt_occluded_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rpt_camera_rays_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rpt_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rpt_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32]),
     "rpt_render": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_render": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]),
     "rpt_resident_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

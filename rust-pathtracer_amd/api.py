@@ -764,6 +764,75 @@ class Tracer:
         return {"type": names[out.medium_type], "density": np.float32(out.density), "color": tuple(np.float32(c) for c in out.color),
                 "anisotropy": np.float32(out.anisotropy)}
 
+    # --- ray queries (include/rpt.h, "ray queries")
+    @staticmethod
+    def _hit_views(hits, surfaces, as_int):
+        """The records as a dict of named views: `hits` [n, 8] and `surfaces` [n, 16] (or None) hold float32 words."""
+        out = {"t": hits[:, 0], "kind": as_int(hits[:, 1]), "primitive": as_int(hits[:, 2]), "mesh": as_int(hits[:, 3]),
+               "triangle": as_int(hits[:, 4]), "u": hits[:, 5], "v": hits[:, 6]}
+        if surfaces is not None:
+            out.update(ng=surfaces[:, 0:3], ns=surfaces[:, 3:6], rgb=surfaces[:, 6:9], emission=surfaces[:, 9:12],
+                       roughness=surfaces[:, 12], metallic=surfaces[:, 13], material=as_int(surfaces[:, 14]))
+        return out
+
+    def _query_rays(self, rays):
+        """`rays` checked: ([n, 8] float32, on the device?).  A row is an rpt_ray: origin, max_dist, direction, reserved."""
+        if isinstance(rays, np.ndarray):
+            if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+                raise ValueError("rays must be float32 [n, 8]: origin, max_dist, direction, reserved")
+            return np.ascontiguousarray(rays), False
+        import torch
+        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8):
+            raise ValueError("rays must be a float32 [n, 8] numpy array or CUDA tensor: origin, max_dist, direction, reserved")
+        if (rays.device.index or 0) != self.device:
+            raise ValueError("rays lie on device %s, the tracer on %d" % (rays.device, self.device))
+        return rays.contiguous(), True
+
+    def trace(self, rays, surfaces=False):
+        """The closest hit of every ray (rpt_trace_rays*): a dict of named views t, kind, primitive, mesh, triangle, u, v and, with
+        `surfaces`, ng, ns, rgb, emission, roughness, metallic, material.  A CUDA float32 tensor [n, 8] goes through the device form on
+        torch's current stream and returns tensors (the index fields as int32: 0xFFFFFFFF reads -1); a numpy array goes through the host
+        form and returns numpy (the index fields as uint32)."""
+        rays, on_device = self._query_rays(rays)
+        n = int(rays.shape[0])
+        if on_device:
+            import torch
+            hits = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+            surf = torch.empty((n, 16), dtype=torch.float32, device=rays.device) if surfaces else None
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+            check(lib().rpt_trace_rays_device(self._h, rays.data_ptr(), n, hits.data_ptr(), surf.data_ptr() if surfaces else None, 0,
+                                              C.c_void_p(stream)), self._h)
+            return self._hit_views(hits, surf, lambda x: x.view(torch.int32))
+        hits = np.empty((n, 8), dtype=np.float32)
+        surf = np.empty((n, 16), dtype=np.float32) if surfaces else None
+        check(lib().rpt_trace_rays(self._h, rays.ctypes.data, n, hits.ctypes.data, surf.ctypes.data if surfaces else None, 0), self._h)
+        return self._hit_views(hits, surf, lambda x: x.view(np.uint32))
+
+    def occluded(self, rays):
+        """Whether anything lies along each ray before its max_dist (rpt_occluded*): uint8 [n], a tensor for a CUDA tensor of rays, a
+        numpy array for a numpy array."""
+        rays, on_device = self._query_rays(rays)
+        n = int(rays.shape[0])
+        if on_device:
+            import torch
+            out = torch.empty((n,), dtype=torch.uint8, device=rays.device)
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+            check(lib().rpt_occluded_device(self._h, rays.data_ptr(), n, out.data_ptr(), 0, C.c_void_p(stream)), self._h)
+            return out
+        out = np.empty((n,), dtype=np.uint8)
+        check(lib().rpt_occluded(self._h, rays.ctypes.data, n, out.ctypes.data, 0), self._h)
+        return out
+
+    def camera_rays(self, width, height):
+        """The camera's ray through the centre of every pixel, row 0 on top (rpt_camera_rays_device): a CUDA float32 tensor
+        [width * height, 8] on the tracer's device, ready for trace() and occluded()."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        rays = torch.empty((int(width) * int(height), 8), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().rpt_camera_rays_device(self._h, int(width), int(height), rays.data_ptr(), C.c_void_p(stream)), self._h)
+        return rays
+
     def _refresh_stale_meshes(self):
         """scene().meshes' vertex arrays that a device-source call left stale, read back once (only before an upload)."""
         for m in sorted(self._stale_meshes):

@@ -44,12 +44,14 @@
 #include "launch_mmap.h"
 #include "launch_move.h"
 #include "launch_nrm.h"
+#include "launch_query.h"
 #include "launch_smooth.h"
 #include "launch_tex.h"
 #include "mesh_args.h"
 #include "mesh_args_mmap.h"
 #include "mesh_args_emap.h"
 #include "mesh_args_med.h"
+#include "mesh_args_query.h"
 #ifdef RPT_TEST_HOOKS
 #include "../../include/rpt_test.h"
 #endif
@@ -85,6 +87,7 @@ struct DevState {
     void* mmap = nullptr;             // mesh material maps' tables (host_mmap.h, MmapLayout): while some mesh's map is ON (rpt_set_mesh_material_maps)
     void* emap = nullptr;             // mesh emission maps' tables (host_emap.h, EmapLayout): while some mesh's map is ON (rpt_set_mesh_emission_maps)
     void* med = nullptr;              // mesh media's tables (host_med.h, MedLayout): while some mesh carries a medium (rpt_set_mesh_media)
+    void* query = nullptr;            // ray queries' own tables (host_query.h, QueryLayout): from a mesh scene's first query to the next upload
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -329,6 +332,7 @@ static void free_mesh_work(DevState& d)
     if (d.mmap) { (void)hipFree(d.mmap); d.mmap = nullptr; }
     if (d.emap) { (void)hipFree(d.emap); d.emap = nullptr; }
     if (d.med) { (void)hipFree(d.med); d.med = nullptr; }
+    if (d.query) { (void)hipFree(d.query); d.query = nullptr; }
     d.refit_full = false;
     d.build_temp_bytes = 0;
 }
@@ -2923,6 +2927,177 @@ int rpt_convert_to_u8(rpt_ctx* ctx, const float* pixels, uint8_t* frame, uint32_
     RPT_HIP_CHECK(ctx, hipMemcpyAsync(frame, out_dev, n * 4, hipMemcpyDeviceToHost, d.stream));
     RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
     return RPT_OK;
+}
+
+// ---- ray queries (include/rpt.h, "ray queries") ------------------------------------------------------------------------------------
+// What every query checks before anything is enqueued, in this order: the NULL context, the scene (none: RPT_ERR_NO_SCENE; not a mesh
+// scene, or a context with several local devices: RPT_ERR_UNSUPPORTED), the reserved flags, the pointers (`ptrs`: NULL with n > 0,
+// or not 16-byte aligned; `optional`: may be NULL, aligned like the others), the batch size.  False: the call returns *rc.  True:
+// there is something to launch.
+static bool query_ready(rpt_ctx* ctx, const char* name, uint32_t flags, const void* const* ptrs, uint32_t n_ptrs, const void* optional, uint64_t n, bool aligned,
+                        int* rc)
+{
+    *rc = RPT_ERR_INVALID_ARG;
+    if (!ctx) { set_err(nullptr, "%s: ctx is NULL", name); return false; }
+    if (ctx->scene.kind == SceneKind::none) { set_err(ctx, "%s: no scene uploaded", name); *rc = RPT_ERR_NO_SCENE; return false; }
+    if (ctx->scene.kind != SceneKind::mesh) {
+        set_err(ctx, "%s: ray queries exist for scenes with meshes only (analytical, large and SDF scenes: not yet)", name);
+        *rc = RPT_ERR_UNSUPPORTED;
+        return false;
+    }
+    if (ctx->devs.size() != 1) {
+        set_err(ctx, "%s: ray queries run on a context with one local device (rpt_create, rpt_create_rank); this one has %zu", name, ctx->devs.size());
+        *rc = RPT_ERR_UNSUPPORTED;
+        return false;
+    }
+    if (flags != 0u) { set_err(ctx, "%s: flags 0x%x (reserved: must be 0)", name, flags); return false; }
+    for (uint32_t k = 0; k < n_ptrs; ++k) {
+        if (n > 0 && !ptrs[k]) { set_err(ctx, "%s: NULL array with n > 0", name); return false; }
+        if (aligned && ((uintptr_t)ptrs[k] & 15u) != 0) { set_err(ctx, "%s: device arrays must be 16-byte aligned", name); return false; }
+    }
+    if (aligned && ((uintptr_t)optional & 15u) != 0) { set_err(ctx, "%s: device arrays must be 16-byte aligned", name); return false; }
+    if (n / 256u + (n % 256u ? 1u : 0u) > 0x7FFFFFFFull) { set_err(ctx, "%s: %llu rays are more than a grid of 0x7FFFFFFF workgroups holds", name, (unsigned long long)n); return false; }
+    *rc = RPT_OK;
+    return n != 0;
+}
+
+// Device d's query allocation, made at the first query after an upload (host_query.h): filled on d's stream, and waited for — a
+// query may run on any stream.
+static int ensure_query(rpt_ctx* ctx, DevState& d)
+{
+    if (d.query) return RPT_OK;
+    const rpthost::RefitPlan& plan = ctx->refit;
+    const rpthost::QueryLayout ql(plan.n_meshes(), d.scene.n_tris);
+    void* fresh = nullptr;
+    RPT_HIP_CHECK(ctx, hipMalloc(&fresh, ql.total));
+    unsigned char* base = static_cast<unsigned char*>(fresh);
+    hipError_t e = hipMemsetAsync(base, 0, ql.total, d.stream);
+    if (e == hipSuccess && d.scene.n_tris) e = hipMemsetAsync(base + ql.off_none, 0xFF, 4u * (size_t)d.scene.n_tris, d.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + ql.off_tri_first, plan.tri_first.data(), sizeof(uint32_t) * plan.tri_first.size(), hipMemcpyHostToDevice, d.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+    if (e != hipSuccess) {                                          // (a half-filled allocation is never bound: the next query starts over)
+        (void)hipFree(fresh);
+        set_err(ctx, "ray queries: filling the query tables failed: %s", hipGetErrorString(e));
+        return RPT_ERR_HIP;
+    }
+    d.query = fresh;
+    return RPT_OK;
+}
+
+// The batch as the kernels take it.
+static QueryArgs query_args_of(const DevState& d, const rpthost::RefitPlan& plan, const rpt_ray* rays, uint64_t n, rpt_hit* hits, rpt_surface* surfaces, uint8_t* occluded)
+{
+    const rpthost::QueryLayout ql(plan.n_meshes(), d.scene.n_tris);
+    QueryArgs q{};
+    q.rays = rays; q.hits = hits; q.surfaces = surfaces; q.occluded = occluded;
+    q.tri_first = rptargs::table_at<const uint32_t>(d.query, ql.off_tri_first);
+    q.n_meshes = plan.n_meshes();
+    q.n = n;
+    return q;
+}
+
+// The tables are bound as they are NOW: after a rebuild the slot order has changed, after a setter the features have.
+static int launch_query(rpt_ctx* ctx, DevState& d, const rpt_ray* rays, uint64_t n, rpt_hit* hits, rpt_surface* surfaces, uint8_t* occluded, hipStream_t stream)
+{
+    RPT_CHECK_RC(ensure_query(ctx, d));
+    const bool cutouts = d.cut && d.tex && d.refit && ctx->cut.any();
+    const bool normal_maps = d.nrm && d.tex && d.refit && ctx->nrm.any();
+    const bool material_maps = d.mmap && d.tex && d.refit && ctx->mmap.any();
+    const bool emission_maps = d.emap && d.tex && d.refit && ctx->emap.any();
+    const QueryArgs q = query_args_of(d, ctx->refit, rays, n, hits, surfaces, occluded);
+    if (!surfaces) {
+        if (!cutouts) {
+            RPT_HIP_CHECK(ctx, occluded ? rptlaunch::query_occluded(d.scene, q, stream) : rptlaunch::query_closest(d.scene, q, stream));
+        } else {
+            const SceneMeshCut sc = rptargs::mesh_scene_of<SceneMeshCut>(mesh_view_of(ctx, d));
+            RPT_HIP_CHECK(ctx, occluded ? rptlaunch::query_occluded_cut(sc, q, stream) : rptlaunch::query_closest_cut(sc, q, stream));
+        }
+        return RPT_OK;
+    }
+    if (!d.refit) {                                                 // (the surface kernels' arguments name slot_vertex)
+        RPT_CHECK_RC(ensure_refit(ctx, d));
+        RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    }
+    const rptargs::MeshView view = mesh_view_of(ctx, d);
+    const rptargs::MmapView maps{d.mmap, ctx->mmap};
+    const rptargs::EmapView emits{d.emap, ctx->emap};
+    const rptargs::QueryView qv{d.query, rpthost::QueryLayout(ctx->refit.n_meshes(), d.scene.n_tris)};
+    switch (rptargs::query_surface_kind_of(cutouts, normal_maps)) {
+    case 0u: RPT_HIP_CHECK(ctx, rptlaunch::query_surface(rptargs::mesh_query_scene_of<SceneMeshEmit>(view, maps, material_maps, emits, emission_maps, qv), q, stream)); break;
+    case rptargs::kQueryCut: RPT_HIP_CHECK(ctx, rptlaunch::query_surface_cut(rptargs::mesh_query_scene_of<SceneMeshEmitCut>(view, maps, material_maps, emits, emission_maps, qv), q, stream)); break;
+    case rptargs::kQueryNrm: RPT_HIP_CHECK(ctx, rptlaunch::query_surface_nrm(rptargs::mesh_query_scene_of<SceneMeshEmitNrm>(view, maps, material_maps, emits, emission_maps, qv), q, stream)); break;
+    default: RPT_HIP_CHECK(ctx, rptlaunch::query_surface_nrm_cut(rptargs::mesh_query_scene_of<SceneMeshEmitNrmCut>(view, maps, material_maps, emits, emission_maps, qv), q, stream)); break;
+    }
+    return RPT_OK;
+}
+
+int rpt_trace_rays_device(rpt_ctx* ctx, const rpt_ray* rays_dev, uint64_t n, rpt_hit* hits_dev, rpt_surface* surfaces_dev, uint32_t flags, void* stream)
+{
+    int rc;
+    const void* const ptrs[2] = {rays_dev, hits_dev};
+    if (!query_ready(ctx, "rpt_trace_rays_device", flags, ptrs, 2, surfaces_dev, n, true, &rc)) return rc;
+    RPT_ON_DEVICE(ctx);
+    return launch_query(ctx, ctx->devs[0], rays_dev, n, hits_dev, surfaces_dev, nullptr, (hipStream_t)stream);
+}
+
+int rpt_occluded_device(rpt_ctx* ctx, const rpt_ray* rays_dev, uint64_t n, uint8_t* occluded_dev, uint32_t flags, void* stream)
+{
+    int rc;
+    const void* const rays[1] = {rays_dev};
+    if (!query_ready(ctx, "rpt_occluded_device", flags, rays, 1, nullptr, n, true, &rc)) return rc;
+    if (!occluded_dev) { set_err(ctx, "rpt_occluded_device: NULL array with n > 0"); return RPT_ERR_INVALID_ARG; }
+    RPT_ON_DEVICE(ctx);
+    return launch_query(ctx, ctx->devs[0], rays_dev, n, nullptr, nullptr, occluded_dev, (hipStream_t)stream);
+}
+
+int rpt_camera_rays_device(rpt_ctx* ctx, uint32_t width, uint32_t height, rpt_ray* rays_dev, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_camera_rays_device: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (width == 0 || height == 0) { set_err(ctx, "rpt_camera_rays_device: zero width or height"); return RPT_ERR_INVALID_ARG; }
+    int rc;
+    const void* const ptrs[1] = {rays_dev};
+    if (!query_ready(ctx, "rpt_camera_rays_device", 0u, ptrs, 1, nullptr, (uint64_t)width * height, true, &rc)) return rc;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::query_camera_rays(make_camera(ctx->scene.camera, (float)width, (float)height), width, height, rays_dev, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+// The host forms: the rays up, the records down, through the context's staging buffer on its own stream; they block.
+static int query_host(rpt_ctx* ctx, const char* name, const rpt_ray* rays, uint64_t n, rpt_hit* hits, rpt_surface* surfaces, uint8_t* occluded, uint32_t flags)
+{
+    int rc;
+    const void* const ptrs[2] = {rays, occluded ? (const void*)occluded : (const void*)hits};
+    if (!query_ready(ctx, name, flags, ptrs, 2, nullptr, n, false, &rc)) return rc;
+    RPT_ON_DEVICE(ctx);
+    DevState& d = ctx->devs[0];
+    const auto up = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
+    const size_t off_hits = up(sizeof(rpt_ray) * (size_t)n);
+    const size_t off_surfaces = off_hits + up(occluded ? (size_t)n : sizeof(rpt_hit) * (size_t)n);
+    const size_t total = off_surfaces + (surfaces ? up(sizeof(rpt_surface) * (size_t)n) : 0u);
+    RPT_CHECK_RC(ensure_fb(ctx, d, total));
+    unsigned char* base = reinterpret_cast<unsigned char*>(d.fb);
+    rpt_ray* rays_dev = reinterpret_cast<rpt_ray*>(base);
+    rpt_hit* hits_dev = occluded ? nullptr : reinterpret_cast<rpt_hit*>(base + off_hits);
+    uint8_t* occluded_dev = occluded ? base + off_hits : nullptr;
+    rpt_surface* surfaces_dev = surfaces ? reinterpret_cast<rpt_surface*>(base + off_surfaces) : nullptr;
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(rays_dev, rays, sizeof(rpt_ray) * (size_t)n, hipMemcpyHostToDevice, d.stream));
+    RPT_CHECK_RC(launch_query(ctx, d, rays_dev, n, hits_dev, surfaces_dev, occluded_dev, d.stream));
+    if (occluded) RPT_HIP_CHECK(ctx, hipMemcpyAsync(occluded, occluded_dev, (size_t)n, hipMemcpyDeviceToHost, d.stream));
+    else RPT_HIP_CHECK(ctx, hipMemcpyAsync(hits, hits_dev, sizeof(rpt_hit) * (size_t)n, hipMemcpyDeviceToHost, d.stream));
+    if (surfaces) RPT_HIP_CHECK(ctx, hipMemcpyAsync(surfaces, surfaces_dev, sizeof(rpt_surface) * (size_t)n, hipMemcpyDeviceToHost, d.stream));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    return RPT_OK;
+}
+
+int rpt_trace_rays(rpt_ctx* ctx, const rpt_ray* rays, uint64_t n, rpt_hit* hits, rpt_surface* surfaces, uint32_t flags)
+{
+    return query_host(ctx, "rpt_trace_rays", rays, n, hits, surfaces, nullptr, flags);
+}
+
+int rpt_occluded(rpt_ctx* ctx, const rpt_ray* rays, uint64_t n, uint8_t* occluded, uint32_t flags)
+{
+    if (ctx && n > 0 && !occluded) { set_err(ctx, "rpt_occluded: NULL array with n > 0"); return RPT_ERR_INVALID_ARG; }
+    return query_host(ctx, "rpt_occluded", rays, n, nullptr, nullptr, occluded, flags);
 }
 
 int rpt_synchronize(rpt_ctx* ctx, void* stream)

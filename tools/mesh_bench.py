@@ -63,8 +63,15 @@ glass and the shadow rays' flag, with no medium ("none": the mesh kernel the sce
 on the glass mesh ("absorb") and with a SCATTER medium on it ("scatter"), on three contexts, alternating; the time of rpt_set_mesh_media
 itself; and the wall time of the four move calls with and without a medium.
 
+--rays: one JSON line more, for ray queries (include/rpt.h, "ray queries"), on the scene as it is: the camera's 1080p rays
+(rpt_camera_rays_device: coherent) and as many random rays through the scene's box (a uniform origin in the box of the meshes grown
+by a half, a uniform direction: incoherent).  For either set, rays per second of the closest hit, of the closest hit with surfaces
+and of occlusion (max_dist = +inf), each timed with device events around 20 launches in a row, medians of `--reps` (at least 5); the
+1-spp resident render of the same frame next to them, alternating with the closest hit of the camera's rays, and the ratio of that
+rate to the frame's samples per second; the time of rpt_camera_rays_device; and what the camera's rays hit.
+
     python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild] [--device] [--smooth] [--lights] [--textures] [--environment]
-                               [--cutouts] [--normal-maps] [--material-maps] [--emission-maps] [--media]
+                               [--cutouts] [--normal-maps] [--material-maps] [--emission-maps] [--media] [--rays]
 """
 import argparse
 import ctypes as C
@@ -95,6 +102,7 @@ def main():
     ap.add_argument("--material-maps", action="store_true")
     ap.add_argument("--emission-maps", action="store_true")
     ap.add_argument("--media", action="store_true")
+    ap.add_argument("--rays", action="store_true")
     a = ap.parse_args()
     os.environ.setdefault("RPT_LIB", os.path.join(ROOT, "rust-pathtracer_amd", "librpt_hip_test.so"))     # (the product has no hooks)
     import __graft_entry__
@@ -128,6 +136,7 @@ def main():
     material_maps = measure_material_maps(pkg, s, a) if a.material_maps else None
     emission_maps = measure_emission_maps(pkg, s, a) if a.emission_maps else None
     media = measure_media(pkg, s, a) if a.media else None
+    rays = measure_rays(pkg, s, a) if a.rays else None
     t.close()
     print(json.dumps({"workload": "mesh_scene %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "triangles": n_tris,
                       "gsamples_per_s_median": sorted(rates)[len(rates) // 2], "gsamples_per_s": rates,
@@ -156,6 +165,8 @@ def main():
         print(json.dumps(emission_maps))
     if media:
         print(json.dumps(media))
+    if rays:
+        print(json.dumps(rays))
 
 
 def measure_updates(pkg, t, s, a):
@@ -1016,6 +1027,93 @@ def measure_media(pkg, s, a):
         fo, fn = stats(ms["off"]), stats(ms["on"])
         out[name] = {"off_ms": fo, "on_ms": fn, "on_adds_ms": fn["median"] - fo["median"]}
     return out
+
+
+def measure_rays(pkg, s, a):
+    """-> the --rays line.  One context on scenes.mesh_scene() as uploaded (no feature ON: the closest, occluded and surface kernels
+    without the cut test and the normal map).  Two ray sets of width * height rays each: the camera's ("coherent") and random ones
+    through the scene's box ("incoherent").  A sample is `launches` launches in a row between two device events on torch's current
+    stream; medians of `reps`.  The 1-spp resident frame alternates with the closest hit of the camera's rays."""
+    import numpy as np
+    import torch
+
+    def stats(xs):
+        xs = sorted(xs)
+        return {"median": xs[len(xs) // 2], "min": xs[0], "max": xs[-1]}
+
+    reps, launches = max(5, a.reps), 20
+    n = a.width * a.height
+    tr = pkg.Tracer(s, device=0, seed=1)
+    dev = torch.device("cuda", 0)
+    sets = {"coherent": tr.camera_rays(a.width, a.height)}
+    verts = np.concatenate([np.asarray(v, np.float64).reshape(-1, 3) for v, _, _ in s.meshes])
+    lo, hi = verts.min(0), verts.max(0)
+    lo, hi = lo - 0.25 * (hi - lo), hi + 0.25 * (hi - lo)
+    rng = np.random.default_rng(0x5EED0007)
+    d = rng.normal(size=(n, 3))
+    r = np.zeros((n, 8), np.float32)
+    r[:, 0:3] = lo + rng.uniform(size=(n, 3)) * (hi - lo)
+    r[:, 3] = np.inf
+    r[:, 4:7] = d / np.linalg.norm(d, axis=1, keepdims=True)
+    sets["incoherent"] = torch.from_numpy(r).to(dev)
+    hits = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    surf = torch.empty((n, 16), dtype=torch.float32, device=dev)
+    occ = torch.empty((n,), dtype=torch.uint8, device=dev)
+    lib, h = pkg.lib(), tr._h
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    calls = {
+        "closest": lambda rays: lib.rpt_trace_rays_device(h, rays.data_ptr(), n, hits.data_ptr(), None, 0, stream),
+        "closest_with_surfaces": lambda rays: lib.rpt_trace_rays_device(h, rays.data_ptr(), n, hits.data_ptr(), surf.data_ptr(), 0, stream),
+        "occluded": lambda rays: lib.rpt_occluded_device(h, rays.data_ptr(), n, occ.data_ptr(), 0, stream),
+    }
+
+    def rays_per_s(call, rays):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(launches):
+            pkg._lib.check(call(rays), h)
+        e1.record()
+        e1.synchronize()
+        return n * launches / (e0.elapsed_time(e1) * 1e-3)
+
+    def frame_samples_per_s():
+        tr.render_resident(a.width, a.height, 1)
+        return n / (tr.resident_kernel_ms() * 1e-3)
+
+    for call in calls.values():                                     # warm-up: every kernel, both sets (and the query's own allocation)
+        for rays in sets.values():
+            rays_per_s(call, rays)
+    for _ in range(3):
+        frame_samples_per_s()                                       # (and the dispatch order's first costs)
+    rates = {k: {name: [] for name in calls} for k in sets}
+    frame, beside = [], []
+    for _ in range(reps):
+        for k, rays in sets.items():
+            for name, call in calls.items():
+                rates[k][name].append(rays_per_s(call, rays))
+        frame.append(frame_samples_per_s())                         # alternating: the 1-spp frame, then the closest hit of its rays
+        beside.append(rays_per_s(calls["closest"], sets["coherent"]))
+    cam_ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(launches):
+            pkg._lib.check(lib.rpt_camera_rays_device(h, a.width, a.height, sets["coherent"].data_ptr(), stream), h)
+        e1.record()
+        e1.synchronize()
+        cam_ms.append(e0.elapsed_time(e1) / launches)
+    out = tr.trace(sets["coherent"])
+    torch.cuda.synchronize()
+    kinds = torch.bincount(out["kind"].to(torch.int64), minlength=4).cpu().numpy() / float(n)
+    tr.close()
+    f, b = stats(frame), stats(beside)
+    return {"workload": "mesh_scene ray queries, %d rays per launch (%dx%d), %d launches per sample" % (n, a.width, a.height, launches), "reps": reps,
+            "grays_per_s": {k: {name: {kk: vv / 1e9 for kk, vv in stats(v).items()} for name, v in rates[k].items()} for k in sets},
+            "frame_1spp_gsamples_per_s": {kk: vv / 1e9 for kk, vv in f.items()}, "frame_1spp_ms": n / f["median"] * 1e3,
+            "closest_coherent_beside_the_frame_grays_per_s": {kk: vv / 1e9 for kk, vv in b.items()},
+            "closest_rays_over_frame_samples": b["median"] / f["median"],
+            "camera_rays_ms": stats(cam_ms),
+            "camera_rays_hit": {"none": kinds[0], "sphere": kinds[1], "plane": kinds[2], "triangle": kinds[3]}}
 
 
 if __name__ == "__main__":
