@@ -1528,6 +1528,58 @@ int rpt_camera_rays_device(rpt_ctx* ctx, uint32_t width, uint32_t height, rpt_ra
 int rpt_trace_rays(rpt_ctx* ctx, const rpt_ray* rays, uint64_t n, rpt_hit* hits, rpt_surface* surfaces /* or NULL */, uint32_t flags);   /* host memory, blocks */
 int rpt_occluded(rpt_ctx* ctx, const rpt_ray* rays, uint64_t n, uint8_t* occluded, uint32_t flags);                                     /* host memory, blocks */
 
+/* ---- radiance queries — PROJECT-DEFINED ---------------------------------------------------------------------------------------------
+ * How much light arrives along a ray the caller brings: the integrator's own estimate, with every feature the context has set —
+ * smooth shading, mesh lights, textures, the three kinds of maps, cutouts, the environment, media.  Light probes, irradiance volumes,
+ * lightmap baking and a camera model of the caller's own ask this.  Ray queries (above) stop at geometry; these keep path state and
+ * draw random numbers.  One call serves any mesh scene, whatever features are set; no render form, setter or hook changes.
+ *
+ * One sample.  Sample s of ray i is one pass of the integrator's bounce loop (tracer.rs:61-103, as the mesh render forms run it),
+ * started from rays[i].origin and rays[i].direction exactly as given: the direction is not normalised (rpt_ray), and max_dist and
+ * reserved are not read.
+ *   the stream   Rng::init(frame_key(seed, frames_done + s), first_index + i), first_index + i in uint32 arithmetic (it wraps)
+ *   two draws    the stream's first two draws are made and discarded: the draws a camera sample spends on its jitter
+ *   the rest     as a camera path starts: hit_dist = -1, scatter_pdf = 0, bounce 0, throughput 1, radiance 0, not inside any medium.
+ *                A ray whose origin lies inside a mesh that bounds a medium starts OUTSIDE it, as a camera placed there does
+ *                ("mesh media": a path enters a medium by crossing its boundary)
+ * Russian roulette is a render flag and is never applied here.
+ *
+ * Accumulation.  out[i] (4 f32) is a ColorBuffer pixel, read and written.  The spp samples enter it in sample order through the
+ * render's own blend (mix_color, tracer.rs:108-117) with weight 1 / (frames_done + s + 1); alpha is blended toward 1, and a sample
+ * that is not finite is blended as black.  spp = S is bit-identical to S calls with spp = 1 and frames_done counted up; the library
+ * cuts spp above the kernels' samples-per-launch limit (512) into successive launches, which changes no word.  spp == 0 or n == 0 is
+ * RPT_OK and launches nothing.  A scene with max_depth == 0 blends zeros.
+ *
+ * The camera's sample rays.  rpt_camera_sample_rays_device writes width * height rays, row 0 on top, pixel (x, y) at y * width + x:
+ * the ray a render of frame `frame` with `seed` sends for that pixel — camera_ray(make_camera(...), px, py, offx, offy), px and py what
+ * a render launch computes for the pixel, offx and offy the first two draws of the stream (seed, frame, pixel index) — and
+ * max_dist = +inf.  (rpt_camera_rays_device is the same with both draws replaced by 0.5f.)
+ *
+ * Therefore, for every mesh scene and every feature set: rpt_radiance_device over these rays with first_index = 0, frames_done =
+ * frame and spp = 1, into a copy of a ColorBuffer, leaves THE VERY WORDS rpt_render_device (flags 0) leaves there for that frame.
+ * tests/test_gpu_radiance.py holds all 36 render forms to this.
+ *
+ * Ordering.  The _device forms enqueue on `stream` and return without waiting.  They see the effect of every earlier call on the
+ * context — uploads, the four move calls, every setter: those calls wait for their own device work before they return.  Work of the
+ * CALLER's on another stream (the kernel that writes rays_dev, a reader of out_dev) is the caller's to order, as with
+ * rpt_render_device's buffers.  rays_dev and out_dev must be 16-byte aligned and on the context's device; a misaligned pointer is
+ * rejected whatever n is.  rpt_radiance stages through device memory of the context and blocks.  The first radiance query after an
+ * upload makes a small allocation of its own (the empty tables that stand for absent features: host_rad.h) and waits for it once.
+ *
+ * Errors.  RPT_ERR_NO_SCENE without a scene; RPT_ERR_UNSUPPORTED for a scene that is not a mesh scene and for a context with more
+ * than one local device (an rpt_create_rank context has one and works); RPT_ERR_INVALID_ARG for a NULL ctx, a NULL array with n > 0,
+ * a misaligned pointer, flags != 0 (reserved), zero width or height, and more rays than a grid of 0x7FFFFFFF workgroups of 256 holds.
+ * A rejected call writes nothing.  rpt_debug_mesh_form and rpt_debug_kernel_choice (rpt_test.h) keep reporting the last RENDER launch.
+ *
+ * The kernels (csrc/k_rad.hip, a code object library of their own) are nine: the render's path-regenerating state machine over a
+ * 1-D grid of rays, 256 per workgroup, a wave's lanes sharing their rays' samples, per normal map x cutout x environment over the
+ * media forms' scene types; and the camera's sample rays.  DESIGN.md ("radiance queries") has their registers, LDS and rates. */
+int rpt_radiance_device(rpt_ctx* ctx, const rpt_ray* rays_dev, uint64_t n, float* out_dev /* n x 4 f32, in/out */, uint64_t frames_done, uint32_t spp,
+                        uint64_t seed, uint32_t first_index, uint32_t flags /* reserved: 0 */, void* stream);
+int rpt_radiance(rpt_ctx* ctx, const rpt_ray* rays, uint64_t n, float* out, uint64_t frames_done, uint32_t spp, uint64_t seed, uint32_t first_index,
+                 uint32_t flags);                                                                                                       /* host memory, blocks */
+int rpt_camera_sample_rays_device(rpt_ctx* ctx, uint32_t width, uint32_t height, uint64_t frame, uint64_t seed, rpt_ray* rays_dev, void* stream);
+
 /* Tracer::render (tracer.rs:22-123) on a HOST ColorBuffer.
  *   pixels      in/out, width*height*4 f32, RGBA, row 0 = top (buffer.rs:6-26)
  *   frames_done ColorBuffer.frames before the call; the caller adds `spp` afterwards

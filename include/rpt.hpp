@@ -331,6 +331,23 @@ public:
         check(rpt_occluded(ctx_, rays.data(), rays.size(), out.data(), 0u), ctx_);
         return out;
     }
+    /// Radiance queries (rpt.h, "radiance queries"): `spp` samples of the integrator's estimate along every ray, blended into `out`
+    /// (a ColorBuffer pixel per ray, in/out) as frames `frames_done` ..., with the tracer's seed; and the rays a render of `frame` sends.
+    void radiance_device(const rpt_ray* rays, uint64_t n, float* out, uint64_t frames_done = 0, uint32_t spp = 1, uint32_t first_index = 0, void* stream = nullptr)
+    {
+        check(rpt_radiance_device(ctx_, rays, n, out, frames_done, spp, seed_, first_index, 0u, stream), ctx_);
+    }
+    void camera_sample_rays_device(uint32_t width, uint32_t height, uint64_t frame, rpt_ray* rays, void* stream = nullptr)
+    {
+        check(rpt_camera_sample_rays_device(ctx_, width, height, frame, seed_, rays, stream), ctx_);
+    }
+    /// The same on host arrays; it blocks.  Returns n x 4 floats, accumulated from zeros.
+    std::vector<float> radiance(const std::vector<rpt_ray>& rays, uint32_t spp = 1, uint64_t frames_done = 0, uint32_t first_index = 0)
+    {
+        std::vector<float> out(rays.size() * 4, 0.0f);
+        check(rpt_radiance(ctx_, rays.data(), rays.size(), out.data(), frames_done, spp, seed_, first_index, 0u), ctx_);
+        return out;
+    }
 
 private:
     static void check(int rc, const rpt_ctx* ctx) { if (rc != RPT_OK) throw Error(rc, rpt_last_error(ctx)); }

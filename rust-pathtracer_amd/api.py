@@ -833,6 +833,42 @@ class Tracer:
         check(lib().rpt_camera_rays_device(self._h, int(width), int(height), rays.data_ptr(), C.c_void_p(stream)), self._h)
         return rays
 
+    # --- radiance queries (include/rpt.h, "radiance queries")
+    def radiance(self, rays, spp=1, frames_done=0, out=None, first_index=0):
+        """The integrator's estimate along every ray (rpt_radiance*): [n, 4] float32, a ColorBuffer pixel per ray — `spp` samples
+        blended in as frames `frames_done` ... with the tracer's seed, ray i on the stream of index `first_index` + i.  A CUDA float32
+        tensor [n, 8] goes through the device form on torch's current stream and returns a tensor; a numpy array goes through the host
+        form and returns numpy.  `out` (same kind, [n, 4] float32, contiguous) accumulates in place; without it the mean starts from zeros."""
+        rays, on_device = self._query_rays(rays)
+        n = int(rays.shape[0])
+        if on_device:
+            import torch
+            if out is None:
+                out = torch.zeros((n, 4), dtype=torch.float32, device=rays.device)
+            elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == rays.device and out.dtype == torch.float32 and
+                      tuple(out.shape) == (n, 4) and out.is_contiguous()):
+                raise ValueError("out must be a contiguous float32 [n, 4] CUDA tensor on the rays' device")
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+            check(lib().rpt_radiance_device(self._h, rays.data_ptr(), n, out.data_ptr(), int(frames_done), int(spp), self.seed, int(first_index) & 0xFFFFFFFF, 0,
+                                            C.c_void_p(stream)), self._h)
+            return out
+        if out is None:
+            out = np.zeros((n, 4), dtype=np.float32)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float32 and out.shape == (n, 4) and out.flags["C_CONTIGUOUS"]):
+            raise ValueError("out must be a C-contiguous float32 [n, 4] numpy array")
+        check(lib().rpt_radiance(self._h, rays.ctypes.data, n, out.ctypes.data, int(frames_done), int(spp), self.seed, int(first_index) & 0xFFFFFFFF, 0), self._h)
+        return out
+
+    def camera_sample_rays(self, width, height, frame):
+        """The rays a render of frame `frame` sends, one per pixel, row 0 on top (rpt_camera_sample_rays_device, the tracer's seed): a
+        CUDA float32 tensor [width * height, 8].  radiance() over them with frames_done = frame is that frame's render, word for word."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        rays = torch.empty((int(width) * int(height), 8), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib().rpt_camera_sample_rays_device(self._h, int(width), int(height), int(frame), self.seed, rays.data_ptr(), C.c_void_p(stream)), self._h)
+        return rays
+
     def _refresh_stale_meshes(self):
         """scene().meshes' vertex arrays that a device-source call left stale, read back once (only before an upload)."""
         for m in sorted(self._stale_meshes):

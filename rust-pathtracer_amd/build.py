@@ -143,6 +143,15 @@ def query_lib_of(lib):
 
 QUERY_LIB = query_lib_of(LIB)
 
+
+# The kernels of radiance queries (k_rad.hip: radiance_*) are a sixteenth, again named, linked and found the same way:
+# tests/test_radiance_f64.py keeps its census.
+def rad_lib_of(lib):
+    return os.path.splitext(os.path.abspath(lib))[0] + "_rad.so"
+
+
+RAD_LIB = rad_lib_of(LIB)
+
 # One translation unit per kernel class (csrc/kernel_common.h says what each build of them is):
 #   strict    k_small tracks the range tests of the short divide / sqrt; k_compact, k_sdf, k_large, k_mesh test next to every operation
 #   relaxed   the four render TUs once more with hipcc's fast divide / sqrt and FMA contraction: what RPT_RENDER_FAST_MATH selects
@@ -177,6 +186,10 @@ OBJECTS = [
     ("k_med", "k_med.hip", PEROP + ["-DRPT_MED_PART=0"], "med"),
     ("k_med_nrm", "k_med.hip", PEROP + ["-DRPT_MED_PART=1"], "med"),
     ("k_query", "k_query.hip", PEROP, "query"),                    # ray queries: closest, occluded, surfaces and the camera's rays; QUERY_LIB
+    # radiance queries: the integrator over rays the caller brings, eight forms, and the camera's sample rays; RAD_LIB.  One file, two
+    # translation units, as k_med.hip
+    ("k_rad", "k_rad.hip", PEROP + ["-DRPT_RAD_PART=0"], "rad"),
+    ("k_rad_nrm", "k_rad.hip", PEROP + ["-DRPT_RAD_PART=1"], "rad"),
     ("k_small_fast", "k_small.hip", RELAXED, "both"),
     ("k_compact_fast", "k_compact.hip", RELAXED, "both"),
     ("k_sdf_fast", "k_sdf.hip", RELAXED, "both"),
@@ -239,13 +252,14 @@ def _deps():
 
 
 def needs_build(lib=LIB, mesh_lib=None, refit_lib=None, build_lib=None, move_lib=None, smooth_lib=None, light_lib=None, tex_lib=None, env_lib=None,
-                cut_lib=None, nrm_lib=None, mmap_lib=None, emap_lib=None, med_lib=None, query_lib=None):
-    """`mesh_lib`, `refit_lib`, `build_lib`, `move_lib`, `smooth_lib`, `light_lib`, `tex_lib`, `env_lib`, `cut_lib`, `nrm_lib`, `mmap_lib`, `emap_lib`, `med_lib`, `query_lib`: the
+                cut_lib=None, nrm_lib=None, mmap_lib=None, emap_lib=None, med_lib=None, query_lib=None, rad_lib=None):
+    """`mesh_lib`, `refit_lib`, `build_lib`, `move_lib`, `smooth_lib`, `light_lib`, `tex_lib`, `env_lib`, `cut_lib`, `nrm_lib`, `mmap_lib`, `emap_lib`, `med_lib`, `query_lib`, `rad_lib`: the
     code object libraries `lib` loads (default mesh_lib_of(lib), refit_lib_of(lib), build_lib_of(lib), move_lib_of(lib), smooth_lib_of(lib), light_lib_of(lib),
-    tex_lib_of(lib), env_lib_of(lib), cut_lib_of(lib), nrm_lib_of(lib), mmap_lib_of(lib), emap_lib_of(lib), med_lib_of(lib), query_lib_of(lib); the test build loads the product's)."""
+    tex_lib_of(lib), env_lib_of(lib), cut_lib_of(lib), nrm_lib_of(lib), mmap_lib_of(lib), emap_lib_of(lib), med_lib_of(lib), query_lib_of(lib), rad_lib_of(lib); the test build loads the product's)."""
     parts = [lib, mesh_lib or mesh_lib_of(lib), refit_lib or refit_lib_of(lib), build_lib or build_lib_of(lib), move_lib or move_lib_of(lib),
              smooth_lib or smooth_lib_of(lib), light_lib or light_lib_of(lib), tex_lib or tex_lib_of(lib), env_lib or env_lib_of(lib),
-             cut_lib or cut_lib_of(lib), nrm_lib or nrm_lib_of(lib), mmap_lib or mmap_lib_of(lib), emap_lib or emap_lib_of(lib), med_lib or med_lib_of(lib), query_lib or query_lib_of(lib)]
+             cut_lib or cut_lib_of(lib), nrm_lib or nrm_lib_of(lib), mmap_lib or mmap_lib_of(lib), emap_lib or emap_lib_of(lib), med_lib or med_lib_of(lib), query_lib or query_lib_of(lib),
+             rad_lib or rad_lib_of(lib)]
     if not all(os.path.exists(p) for p in parts):
         return True
     t = min(os.path.getmtime(p) for p in parts)
@@ -258,7 +272,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
     objects (the others are taken from `objdir_name`/ as they are — or, if missing there, from the product's build/)."""
     if not force and not needs_build(lib) and (test_lib is None or not needs_build(test_lib, mesh_lib_of(lib), refit_lib_of(lib), build_lib_of(lib), move_lib_of(lib),
                                                                          smooth_lib_of(lib), light_lib_of(lib), tex_lib_of(lib), env_lib_of(lib), cut_lib_of(lib),
-                                                                         nrm_lib_of(lib), mmap_lib_of(lib), emap_lib_of(lib), med_lib_of(lib), query_lib_of(lib))):
+                                                                         nrm_lib_of(lib), mmap_lib_of(lib), emap_lib_of(lib), med_lib_of(lib), query_lib_of(lib), rad_lib_of(lib))):
         return lib
     objdir = os.path.join(HERE, objdir_name)
     os.makedirs(objdir, exist_ok=True)
@@ -290,8 +304,10 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
     mesh_lib, refit_lib, build_lib, move_lib, smooth_lib = mesh_lib_of(lib), refit_lib_of(lib), build_lib_of(lib), move_lib_of(lib), smooth_lib_of(lib)
     light_lib, tex_lib, env_lib, cut_lib, nrm_lib = light_lib_of(lib), tex_lib_of(lib), env_lib_of(lib), cut_lib_of(lib), nrm_lib_of(lib)
     mmap_lib, emap_lib, med_lib, query_lib = mmap_lib_of(lib), emap_lib_of(lib), med_lib_of(lib), query_lib_of(lib)
+    rad_lib = rad_lib_of(lib)
     for part, kind in ((mesh_lib, "mesh"), (refit_lib, "refit"), (build_lib, "bvhbuild"), (move_lib, "move"), (smooth_lib, "smooth"), (light_lib, "light"),
-                       (tex_lib, "tex"), (env_lib, "env"), (cut_lib, "cut"), (nrm_lib, "nrm"), (mmap_lib, "mmap"), (emap_lib, "emap"), (med_lib, "med"), (query_lib, "query")):
+                       (tex_lib, "tex"), (env_lib, "env"), (cut_lib, "cut"), (nrm_lib, "nrm"), (mmap_lib, "mmap"), (emap_lib, "emap"), (med_lib, "med"), (query_lib, "query"),
+                       (rad_lib, "rad")):
         link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w == kind] + [
             "-Wl,-soname," + os.path.basename(part), "-o", part]
         if verbose:
@@ -302,7 +318,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
             continue
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w in kinds] + [
-            mesh_lib, refit_lib, build_lib, move_lib, smooth_lib, light_lib, tex_lib, env_lib, cut_lib, nrm_lib, mmap_lib, emap_lib, med_lib, query_lib, "-Wl,-rpath,$ORIGIN", "-ldl", "-o", out]
+            mesh_lib, refit_lib, build_lib, move_lib, smooth_lib, light_lib, tex_lib, env_lib, cut_lib, nrm_lib, mmap_lib, emap_lib, med_lib, query_lib, rad_lib, "-Wl,-rpath,$ORIGIN", "-ldl", "-o", out]
         if verbose:
             print(" ".join(link))
         subprocess.run(link, check=True, cwd=CSRC)

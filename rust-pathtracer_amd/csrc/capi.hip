@@ -45,6 +45,7 @@
 #include "launch_move.h"
 #include "launch_nrm.h"
 #include "launch_query.h"
+#include "launch_rad.h"
 #include "launch_smooth.h"
 #include "launch_tex.h"
 #include "mesh_args.h"
@@ -52,6 +53,7 @@
 #include "mesh_args_emap.h"
 #include "mesh_args_med.h"
 #include "mesh_args_query.h"
+#include "mesh_args_rad.h"
 #ifdef RPT_TEST_HOOKS
 #include "../../include/rpt_test.h"
 #endif
@@ -88,6 +90,7 @@ struct DevState {
     void* emap = nullptr;             // mesh emission maps' tables (host_emap.h, EmapLayout): while some mesh's map is ON (rpt_set_mesh_emission_maps)
     void* med = nullptr;              // mesh media's tables (host_med.h, MedLayout): while some mesh carries a medium (rpt_set_mesh_media)
     void* query = nullptr;            // ray queries' own tables (host_query.h, QueryLayout): from a mesh scene's first query to the next upload
+    void* rad = nullptr;              // radiance queries' own tables (host_rad.h): from a mesh scene's first radiance query to the next upload
     float* fb = nullptr;              // staging for the host-pointer API (this device's rows, or a whole image)
     size_t fb_bytes = 0;
     float* tile = nullptr;            // resident ColorBuffer rows of this rank: rows_padded x width RGBA f32
@@ -142,6 +145,7 @@ struct rpt_ctx {
     rpthost::MmapPlan mmap;           // which of its meshes have a material map and where each one's texels lie on every device (host_mmap.h)
     rpthost::EmapPlan emap;           // which of its meshes have an emission map and where each one's texels lie on every device (host_emap.h)
     rpthost::MedPlan med;             // which of its meshes carry a medium and the sizes of every device's media tables (host_med.h)
+    rpthost::MedPlan rad;             // the plan of radiance queries' own tables: the scene's sizes, no medium (host_rad.h); made with the tables
     // resident ColorBuffer (buffer.rs:6-14): pixels as per-rank tiles + frames
     uint32_t res_w = 0, res_h = 0, res_tile_rows = 0, res_rows_padded = 0;
     uint64_t res_frames = 0;
@@ -333,6 +337,7 @@ static void free_mesh_work(DevState& d)
     if (d.emap) { (void)hipFree(d.emap); d.emap = nullptr; }
     if (d.med) { (void)hipFree(d.med); d.med = nullptr; }
     if (d.query) { (void)hipFree(d.query); d.query = nullptr; }
+    if (d.rad) { (void)hipFree(d.rad); d.rad = nullptr; }
     d.refit_full = false;
     d.build_temp_bytes = 0;
 }
@@ -3098,6 +3103,129 @@ int rpt_occluded(rpt_ctx* ctx, const rpt_ray* rays, uint64_t n, uint8_t* occlude
 {
     if (ctx && n > 0 && !occluded) { set_err(ctx, "rpt_occluded: NULL array with n > 0"); return RPT_ERR_INVALID_ARG; }
     return query_host(ctx, "rpt_occluded", rays, n, nullptr, nullptr, occluded, flags);
+}
+
+// ---- radiance queries (include/rpt.h, "radiance queries") --------------------------------------------------------------------------
+// Device d's radiance allocation, made at the first radiance query after an upload (host_rad.h): filled on d's stream, and waited for —
+// a query may run on any stream.
+static int ensure_rad(rpt_ctx* ctx, DevState& d)
+{
+    if (d.rad) return RPT_OK;
+    rpthost::build_rad_plan(ctx->refit, ctx->rad);
+    const rpthost::MedLayout ml = ctx->rad.layout();
+    void* fresh = nullptr;
+    RPT_HIP_CHECK(ctx, hipMalloc(&fresh, ml.total ? ml.total : 16u));
+    unsigned char* base = static_cast<unsigned char*>(fresh);
+    hipError_t e = ml.total ? hipMemsetAsync(base, 0, ml.total, d.stream) : hipSuccess;
+    for (const rpthost::RadFill& f : rpthost::rad_fills(ml))
+        if (e == hipSuccess) e = hipMemsetAsync(base + f.off, f.value, f.bytes, d.stream);
+    if (e == hipSuccess && !ctx->rad.tri_medium.empty())
+        e = hipMemcpyAsync(base + ml.off_tri_medium, ctx->rad.tri_medium.data(), sizeof(uint32_t) * ctx->rad.tri_medium.size(), hipMemcpyHostToDevice, d.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
+    if (e != hipSuccess) {                                          // (a half-filled allocation is never bound: the next query starts over)
+        (void)hipFree(fresh);
+        set_err(ctx, "radiance queries: filling the query's tables failed: %s", hipGetErrorString(e));
+        return RPT_ERR_HIP;
+    }
+    ctx->rad.release_staging();
+    d.rad = fresh;
+    return RPT_OK;
+}
+
+// The tables are bound as they are NOW, as launch_query does; the call's samples go out as launches of at most kMaxSppPerLaunch.
+// Nothing of the render's dispatch state is read or written: last_form and last_choice stay the last render's.
+static int launch_radiance(rpt_ctx* ctx, DevState& d, const rpt_ray* rays, uint64_t n, float* out, uint64_t frames_done, uint32_t spp, uint64_t seed,
+                           uint32_t first_index, hipStream_t stream)
+{
+    RPT_CHECK_RC(ensure_rad(ctx, d));
+    if (!d.refit) {                                                 // (the forms' arguments name slot_vertex and the vertices)
+        RPT_CHECK_RC(ensure_refit(ctx, d));
+        RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    }
+    const bool environment = d.env && d.refit && ctx->env.any();
+    const bool cutouts = d.cut && d.tex && d.refit && ctx->cut.any();
+    const bool normal_maps = d.nrm && d.tex && d.refit && ctx->nrm.any();
+    const bool material_maps = d.mmap && d.tex && d.refit && ctx->mmap.any();
+    const bool emission_maps = d.emap && d.tex && d.refit && ctx->emap.any();
+    const bool media = d.med && d.refit && ctx->med.any();
+    const rptargs::MeshView view = mesh_view_of(ctx, d);
+    const rptargs::MmapView maps{d.mmap, ctx->mmap};
+    const rptargs::EmapView emits{d.emap, ctx->emap};
+    const rptargs::MedView meds{d.med, ctx->med};
+    const rptargs::RadView rv{d.rad, ctx->rad};
+    const uint32_t form = rpthost::rad_form_of(normal_maps, cutouts, environment);
+    const uint32_t max_spp = rptlaunch::radiance_max_spp();
+    RadArgs a{};
+    a.rays = rays; a.out = out; a.n = n;
+    a.seed = seed; a.first_index = first_index;
+    a.shade_threshold = knobs().shade_threshold;
+    const auto scene_of = [&](auto tag) {
+        using S = typename decltype(tag)::type;
+        return rptargs::mesh_rad_scene_of<S>(view, maps, material_maps, emits, emission_maps, meds, media, rv);
+    };
+    for (uint32_t k = 0; k < rpthost::rad_launches(spp, max_spp); ++k) {
+        a.frames_done = frames_done + (uint64_t)k * max_spp;
+        a.spp = rpthost::rad_launch_spp(spp, max_spp, k);
+        using rpthost::kRadCut; using rpthost::kRadEnv; using rpthost::kRadNrm;
+        switch (form) {
+        case 0u: RPT_HIP_CHECK(ctx, rptlaunch::radiance(scene_of(std::common_type<SceneMeshMed>{}), a, stream)); break;
+        case kRadEnv: RPT_HIP_CHECK(ctx, rptlaunch::radiance_env(scene_of(std::common_type<SceneMeshMedEnv>{}), a, stream)); break;
+        case kRadCut: RPT_HIP_CHECK(ctx, rptlaunch::radiance_cut(scene_of(std::common_type<SceneMeshMedCut>{}), a, stream)); break;
+        case kRadCut | kRadEnv: RPT_HIP_CHECK(ctx, rptlaunch::radiance_cut_env(scene_of(std::common_type<SceneMeshMedCutEnv>{}), a, stream)); break;
+        case kRadNrm: RPT_HIP_CHECK(ctx, rptlaunch::radiance_nrm(scene_of(std::common_type<SceneMeshMedNrm>{}), a, stream)); break;
+        case kRadNrm | kRadEnv: RPT_HIP_CHECK(ctx, rptlaunch::radiance_nrm_env(scene_of(std::common_type<SceneMeshMedNrmEnv>{}), a, stream)); break;
+        case kRadNrm | kRadCut: RPT_HIP_CHECK(ctx, rptlaunch::radiance_nrm_cut(scene_of(std::common_type<SceneMeshMedNrmCut>{}), a, stream)); break;
+        default: RPT_HIP_CHECK(ctx, rptlaunch::radiance_nrm_cut_env(scene_of(std::common_type<SceneMeshMedNrmCutEnv>{}), a, stream)); break;
+        }
+    }
+    return RPT_OK;
+}
+
+int rpt_radiance_device(rpt_ctx* ctx, const rpt_ray* rays_dev, uint64_t n, float* out_dev, uint64_t frames_done, uint32_t spp, uint64_t seed, uint32_t first_index,
+                        uint32_t flags, void* stream)
+{
+    int rc;
+    const void* const ptrs[2] = {rays_dev, out_dev};
+    if (!query_ready(ctx, "rpt_radiance_device", flags, ptrs, 2, nullptr, n, true, &rc)) return rc;
+    if (spp == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    return launch_radiance(ctx, ctx->devs[0], rays_dev, n, out_dev, frames_done, spp, seed, first_index, (hipStream_t)stream);
+}
+
+// The host form: the rays and the pixels up, the pixels down, through the context's staging buffer on its own stream; it blocks.
+int rpt_radiance(rpt_ctx* ctx, const rpt_ray* rays, uint64_t n, float* out, uint64_t frames_done, uint32_t spp, uint64_t seed, uint32_t first_index, uint32_t flags)
+{
+    int rc;
+    const void* const ptrs[2] = {rays, out};
+    if (!query_ready(ctx, "rpt_radiance", flags, ptrs, 2, nullptr, n, false, &rc)) return rc;
+    if (spp == 0) return RPT_OK;
+    RPT_ON_DEVICE(ctx);
+    DevState& d = ctx->devs[0];
+    const auto up = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
+    const size_t off_out = up(sizeof(rpt_ray) * (size_t)n);
+    RPT_CHECK_RC(ensure_fb(ctx, d, off_out + up(16u * (size_t)n)));
+    unsigned char* base = reinterpret_cast<unsigned char*>(d.fb);
+    rpt_ray* rays_dev = reinterpret_cast<rpt_ray*>(base);
+    float* out_dev = reinterpret_cast<float*>(base + off_out);
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(rays_dev, rays, sizeof(rpt_ray) * (size_t)n, hipMemcpyHostToDevice, d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(out_dev, out, 16u * (size_t)n, hipMemcpyHostToDevice, d.stream));
+    RPT_CHECK_RC(launch_radiance(ctx, d, rays_dev, n, out_dev, frames_done, spp, seed, first_index, d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(out, out_dev, 16u * (size_t)n, hipMemcpyDeviceToHost, d.stream));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    return RPT_OK;
+}
+
+int rpt_camera_sample_rays_device(rpt_ctx* ctx, uint32_t width, uint32_t height, uint64_t frame, uint64_t seed, rpt_ray* rays_dev, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_camera_sample_rays_device: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (width == 0 || height == 0) { set_err(ctx, "rpt_camera_sample_rays_device: zero width or height"); return RPT_ERR_INVALID_ARG; }
+    int rc;
+    const void* const ptrs[1] = {rays_dev};
+    if (!query_ready(ctx, "rpt_camera_sample_rays_device", 0u, ptrs, 1, nullptr, (uint64_t)width * height, true, &rc)) return rc;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::radiance_camera_rays(make_camera(ctx->scene.camera, (float)width, (float)height), width, height, frame_key_hd(seed, frame), rays_dev,
+                                                       (hipStream_t)stream));
+    return RPT_OK;
 }
 
 int rpt_synchronize(rpt_ctx* ctx, void* stream)

@@ -70,8 +70,15 @@ and of occlusion (max_dist = +inf), each timed with device events around 20 laun
 1-spp resident render of the same frame next to them, alternating with the closest hit of the camera's rays, and the ratio of that
 rate to the frame's samples per second; the time of rpt_camera_rays_device; and what the camera's rays hit.
 
+--radiance: one JSON line more, for radiance queries (include/rpt.h, "radiance queries"), on scenes.mesh_scene() as it is ("flat": its
+render takes form 11, the query the all-tables form over empty tables) and on scenes.mesh_media_scene() with its medium set
+("media": render and query run the same arithmetic over the same tables).  Per scene, alternating, medians of `--reps` (at least 5):
+Msamples/s of Tracer.radiance over the camera's sample rays of frame 0 at `--spp` samples — the work of a frame — timed with device
+events around the call, and of the resident render of that frame (resident_kernel_ms); their ratio; and a probe-style batch, 2 000 000
+random rays through the box of the meshes grown by a half at `--spp` samples.
+
     python tools/mesh_bench.py [--spp 16] [--reps 5] [--update] [--rebuild] [--device] [--smooth] [--lights] [--textures] [--environment]
-                               [--cutouts] [--normal-maps] [--material-maps] [--emission-maps] [--media] [--rays]
+                               [--cutouts] [--normal-maps] [--material-maps] [--emission-maps] [--media] [--rays] [--radiance]
 """
 import argparse
 import ctypes as C
@@ -103,6 +110,7 @@ def main():
     ap.add_argument("--emission-maps", action="store_true")
     ap.add_argument("--media", action="store_true")
     ap.add_argument("--rays", action="store_true")
+    ap.add_argument("--radiance", action="store_true")
     a = ap.parse_args()
     os.environ.setdefault("RPT_LIB", os.path.join(ROOT, "rust-pathtracer_amd", "librpt_hip_test.so"))     # (the product has no hooks)
     import __graft_entry__
@@ -137,6 +145,7 @@ def main():
     emission_maps = measure_emission_maps(pkg, s, a) if a.emission_maps else None
     media = measure_media(pkg, s, a) if a.media else None
     rays = measure_rays(pkg, s, a) if a.rays else None
+    radiance = measure_radiance(pkg, a) if a.radiance else None
     t.close()
     print(json.dumps({"workload": "mesh_scene %dx%d x %d spp, resident" % (a.width, a.height, a.spp), "triangles": n_tris,
                       "gsamples_per_s_median": sorted(rates)[len(rates) // 2], "gsamples_per_s": rates,
@@ -167,6 +176,8 @@ def main():
         print(json.dumps(media))
     if rays:
         print(json.dumps(rays))
+    if radiance:
+        print(json.dumps(radiance))
 
 
 def measure_updates(pkg, t, s, a):
@@ -1114,6 +1125,76 @@ def measure_rays(pkg, s, a):
             "closest_rays_over_frame_samples": b["median"] / f["median"],
             "camera_rays_ms": stats(cam_ms),
             "camera_rays_hit": {"none": kinds[0], "sphere": kinds[1], "plane": kinds[2], "triangle": kinds[3]}}
+
+
+def measure_radiance(pkg, a):
+    """-> the --radiance line.  Two contexts, one per scene; on each the radiance query over the camera's sample rays alternates with
+    the resident render of the same frame, then the probe batch runs."""
+    import numpy as np
+    import torch
+    from rust_pathtracer_amd import scenes
+
+    def stats(xs):
+        xs = sorted(xs)
+        return {"median": xs[len(xs) // 2], "min": xs[0], "max": xs[-1]}
+
+    def form(tr):
+        f = C.c_uint32(0)
+        pkg._lib.check(pkg.lib().rpt_debug_mesh_form(tr._h, C.byref(f)), tr._h)
+        return f.value
+
+    reps, probes = max(5, a.reps), 2_000_000
+    n = a.width * a.height
+    dev = torch.device("cuda", 0)
+    media_scene, media = scenes.mesh_media_scene()
+    out = {"workload": "radiance queries, %dx%d x %d spp over the camera's sample rays; %d probe rays x %d spp" % (a.width, a.height, a.spp, probes, a.spp),
+           "reps": reps}
+    for name, scene, setup in (("flat", scenes.mesh_scene(), None), ("media", media_scene, media)):
+        tr = pkg.Tracer(scene, device=0, seed=1)
+        if setup:
+            tr.set_mesh_media(setup)
+        rays = tr.camera_sample_rays(a.width, a.height, 0)
+        acc = torch.zeros((n, 4), dtype=torch.float32, device=dev)
+
+        def query_rate(r, buf):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            buf.zero_()
+            e0.record()
+            tr.radiance(r, spp=a.spp, out=buf)
+            e1.record()
+            e1.synchronize()
+            return r.shape[0] * a.spp / (e0.elapsed_time(e1) * 1e-3) / 1e6
+
+        def render_rate():
+            tr.resident_reset()
+            tr.render_resident(a.width, a.height, a.spp)
+            return n * a.spp / (tr.resident_kernel_ms() * 1e-3) / 1e6
+
+        for _ in range(2):                                          # warm-up (the query's own allocation; the dispatch order's first costs)
+            query_rate(rays, acc)
+            render_rate()
+        q, f = [], []
+        for _ in range(reps):
+            q.append(query_rate(rays, acc))
+            f.append(render_rate())
+        verts = np.concatenate([np.asarray(v, np.float64).reshape(-1, 3) for v, _, _ in scene.meshes])
+        lo, hi = verts.min(0), verts.max(0)
+        lo, hi = lo - 0.25 * (hi - lo), hi + 0.25 * (hi - lo)
+        rng = np.random.default_rng(0x5EED0009)
+        d = rng.normal(size=(probes, 3))
+        r = np.zeros((probes, 8), np.float32)
+        r[:, 0:3] = lo + rng.uniform(size=(probes, 3)) * (hi - lo)
+        r[:, 3] = np.inf
+        r[:, 4:7] = d / np.linalg.norm(d, axis=1, keepdims=True)
+        probe_rays = torch.from_numpy(r).to(dev)
+        probe_acc = torch.zeros((probes, 4), dtype=torch.float32, device=dev)
+        query_rate(probe_rays, probe_acc)
+        p = [query_rate(probe_rays, probe_acc) for _ in range(reps)]
+        qs, fs = stats(q), stats(f)
+        out[name] = {"render_form": form(tr), "radiance_msamples_per_s": qs, "render_msamples_per_s": fs,
+                     "radiance_over_render": qs["median"] / fs["median"], "probe_msamples_per_s": stats(p)}
+        tr.close()
+    return out
 
 
 if __name__ == "__main__":
