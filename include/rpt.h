@@ -1696,6 +1696,83 @@ int rpt_denoise_device(rpt_ctx* ctx, const float* pixels_dev, float* out_dev, ui
 /* The same on HOST buffers (upload, filter, download; blocks). */
 int rpt_denoise(rpt_ctx* ctx, const float* pixels, float* out, uint32_t width, uint32_t height, uint32_t iterations, float edge_k);
 
+/* ---- guided denoiser — PROJECT-DEFINED -------------------------------------------------------------------------------------------------
+ * The filter of "denoiser" with the normal and position buffers of Dammertz et al. restored, a key that no tap crosses, and albedo
+ * demodulation: texture detail is divided out before filtering and multiplied back afterwards.  Its auxiliary buffers are first-hit
+ * GUIDES, one rpt_guide per pixel, packed from the records of "ray queries" (rpt_camera_rays_device, then rpt_trace_rays_device with
+ * surfaces).  Guides are a record of their own so that a static camera packs them once and filters every progressive frame against
+ * them; a caller may also write guides of their own (a key per material, say).  Neither call needs a scene: guides are a function of
+ * the three records alone, the filter of pixels and guides alone.
+ *
+ * Packing (rpt_denoise_guides*), per record i, every operation rounded once, nothing fused:
+ *   kind = hit.kind
+ *   RPT_HIT_NONE     everything 0, except t = +inf and albedo = 1, 1, 1
+ *   otherwise        t = hit.t;  position_c = origin_c + direction_c * t;  ns, ng and albedo = rgb copied from rpt_surface;
+ *                    key = (kind << 28) | (id & 0x0FFFFFFF), id = hit.mesh for a triangle, hit.primitive otherwise
+ *   reserved = 0.
+ *
+ * The filter (rpt_denoise_guided*), f32 in this operation order, H = {0.25, 0.5, 0.25}, FLOOR = 1/64:
+ *   1 compress, per r, g, b of every pixel:  a = albedo < FLOOR ? FLOOR : albedo;  e = c / a (the IEEE quotient);  c' = e / (1 + e)
+ *   2 the pixel's plane scale:  kx_p = plane_k > 0 ? plane_k / (t_p * t_p) : 0
+ *   3 iteration i = 0 .. iterations-1, step s = 2^i, k_i = edge_k * 4^i (f32 products); for every pixel p, over the 3x3 taps
+ *     q = p + s * (dx, dy), dy = -1..1 outer, dx = -1..1 inner:
+ *         d = c'_p - c'_q;  d2 = fma(d.r, d.r, fma(d.g, d.g, d.b*d.b));  dn2 = the same expression on ns_p - ns_q;
+ *         r = position_q - position_p;  dpl = fma(ng_p.x, r.x, fma(ng_p.y, r.y, ng_p.z*r.z));  dp2 = dpl*dpl;
+ *         the tap is skipped when q lies outside the image, when key_q != key_p, or when any of d2, dn2, dp2 is not < inf;
+ *         tc = fma(-d2, k_i, 1);  tn = fma(-dn2, normal_k, 1);  tx = fma(-dp2, kx_p, 1);  each g = t > 0 ? t : 0;
+ *         wt = (((H[dy+1] * H[dx+1]) * (gc*gc)) * (gn*gn)) * (gx*gx);  acc = fma(c'_q, wt, acc);  wsum += wt
+ *     c'_p <- wsum > 0 ? acc / wsum : c'_p               (all pixels at once: out of place; guides are never filtered)
+ *   4 expand:  e = c' / (1 - c');  out = e * a;  alpha = the input's.  A pixel whose e of step 1 has a channel that is NaN, +-inf or
+ *     exactly -1 is copied through unchanged.
+ * Every g lies in [0, 1] and wt in [0, 0.25]; neither can be NaN, because t > 0 is false for a NaN.  Consequences:
+ *   - miss pixels (key 0, t = +inf, normals 0) filter among themselves, and only by colour;
+ *   - a NaN t or position keeps its pixel unchanged: every tap of it, its own included, has a NaN dp2 or a weight of 0;
+ *   - plane_k is dimensionless: the tap's distance from the centre's tangent plane relative to the centre's depth;
+ *   - first-hit guides do not describe what a mirror or a glass shows: there the colour term is the only one that sees the edge;
+ *   - a packed guide is sampled at the pixel's centre, the pixel's colour is the mean over its footprint: a pixel that straddles a
+ *     texture edge is divided by an albedo that is too small or too large by up to the texture's contrast, and the filter spreads
+ *     that.  On frames whose pixels are large against the texture's features and whose contrast is high (60 : 1 at 64 x 48:
+ *     tests/test_gpu_denoise_guided.py) the textured surfaces come out worse than from the colour-only filter; a caller who
+ *     has them can write guides whose albedo is averaged over the footprint;
+ *   - with guides that are all the RPT_HIT_NONE record every extra factor is exactly 1, a and 1/a are 1, and the call returns the
+ *     very words rpt_denoise_device returns.
+ * iterations 1..6, edge_k > 0 and finite, normal_k >= 0 and plane_k >= 0 and both finite (0 switches the term off), flags reserved: 0.
+ * Defaults that serve 1-4 spp: 4 iterations, edge_k 0.25, normal_k 4, plane_k 1000 (the colour term may be much looser than in
+ * "denoiser": the guides hold the geometric edges).  What the guides do not hold — shadows, highlights — only the colour term keeps:
+ * from about 16 spp on, 2-3 iterations and edge_k 2 blur less than the noise costs.
+ *
+ * Arguments and errors.  Every pointer 16-byte aligned and (the _device forms) on the context's device; out must overlap neither
+ * pixels nor guides.  RPT_ERR_INVALID_ARG for a NULL ctx, a NULL array (with n > 0, for the pack), a misaligned pointer whatever n is,
+ * an argument out of the ranges above or a NaN, flags != 0, zero width or height, and more records than a grid of 0x7FFFFFFF workgroups
+ * of 256 holds.  n == 0 is RPT_OK and launches nothing.  A rejected call writes nothing.  The _device forms enqueue on `stream` and
+ * return; the filter shares the context's intermediate buffer with rpt_denoise_device, under the same rule for streams.  The host
+ * forms stage through device memory of the context and block.
+ *
+ * The kernels (csrc/k_gdn.hip, a code object library of their own) are four: the pack; the first two iterations fused through LDS on
+ * 32 x 16 tiles (and its one-iteration form), staging per cell the compressed colour and the 32 bytes of guide a tap reads
+ * (position, key, ns, t), the centre's ng and albedo read once per pixel; a step kernel for the later iterations.  Every record moves
+ * as 16-byte loads and stores.  DESIGN.md ("guided denoiser") has their registers, LDS and rates. */
+typedef struct rpt_guide {
+    float position[3]; uint32_t key;
+    float ns[3];       float t;
+    float ng[3];       uint32_t kind;      /* RPT_HIT_* */
+    float albedo[3];   uint32_t reserved;  /* written 0 */
+} rpt_guide;                               /* 64 B */
+
+#if defined(__cplusplus)
+static_assert(sizeof(rpt_guide) == 64, "a guide is 64 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rpt_guide) == 64, "a guide is 64 bytes");
+#endif
+
+int rpt_denoise_guides_device(rpt_ctx* ctx, const rpt_ray* rays_dev, const rpt_hit* hits_dev, const rpt_surface* surfaces_dev, uint64_t n,
+                              rpt_guide* guides_dev, void* stream);
+int rpt_denoise_guides(rpt_ctx* ctx, const rpt_ray* rays, const rpt_hit* hits, const rpt_surface* surfaces, uint64_t n, rpt_guide* guides);   /* host memory, blocks */
+int rpt_denoise_guided_device(rpt_ctx* ctx, const float* pixels_dev, const rpt_guide* guides_dev, float* out_dev, uint32_t width, uint32_t height,
+                              uint32_t iterations, float edge_k, float normal_k, float plane_k, uint32_t flags /* reserved: 0 */, void* stream);
+int rpt_denoise_guided(rpt_ctx* ctx, const float* pixels, const rpt_guide* guides, float* out, uint32_t width, uint32_t height,
+                       uint32_t iterations, float edge_k, float normal_k, float plane_k, uint32_t flags);                                   /* host memory, blocks */
+
 /* The same on HOST buffers (upload, convert, download; blocks): what ColorBuffer::convert_to_u8
  * does for a caller that owns a host ColorBuffer (buffer.rs:55-64, frame = width*height*4 bytes). */
 int rpt_convert_to_u8(rpt_ctx* ctx, const float* pixels, uint8_t* frame, uint32_t width, uint32_t height);

@@ -212,6 +212,11 @@ class rpt_surface(C.Structure):
                 ("material", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class rpt_guide(C.Structure):
+    _fields_ = [("position", F3), ("key", C.c_uint32), ("ns", F3), ("t", C.c_float), ("ng", F3), ("kind", C.c_uint32),
+                ("albedo", F3), ("reserved", C.c_uint32)]
+
+
 class rpt_scene_desc(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("flags", C.c_uint32),
@@ -309,6 +314,12 @@ SYMBOLS = {
     "rpt_convert_to_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
     "rpt_denoise_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p]),
     "rpt_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float]),
+    "rpt_denoise_guides_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "rpt_denoise_guides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "rpt_denoise_guided_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
+                                            C.c_float, C.c_uint32, C.c_void_p]),
+    "rpt_denoise_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
+                                     C.c_uint32]),
     "rpt_synchronize": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 

@@ -259,6 +259,49 @@ class ColorBuffer:
         out.frames = self.frames
         return out
 
+    def denoise_guided(self, guides, iterations=4, edge_k=0.25, normal_k=4.0, plane_k=1000.0, device=0):
+        """A copy denoised against first-hit guides (include/rpt.h "guided denoiser"): a new ColorBuffer.  `guides`: a float32 numpy
+        array [height * width, 16], one rpt_guide per pixel (pack_guides, or Tracer.denoise_guides(...).cpu().numpy())."""
+        guides = _host_guides(guides, self.width * self.height)
+        out = ColorBuffer(self.width, self.height)
+        ctx = _ctx_for(device)
+        check(lib().rpt_denoise_guided(ctx, self.pixels.ctypes.data, guides.ctypes.data, out.pixels.ctypes.data, self.width, self.height, iterations,
+                                       edge_k, normal_k, plane_k, 0), ctx)
+        out.frames = self.frames
+        return out
+
+
+def _host_guides(guides, n):
+    if not (isinstance(guides, np.ndarray) and guides.dtype == np.float32 and guides.shape == (n, 16)):
+        raise ValueError("guides must be a float32 numpy array [%d, 16]: one rpt_guide per pixel" % n)
+    return np.ascontiguousarray(guides)
+
+
+def pack_guides(rays, hits, surfaces, device=0):
+    """One rpt_guide per (ray, hit, surface) record (rpt_denoise_guides*): float32 [n, 16].  Three float32 arrays [n, 8], [n, 8] and
+    [n, 16] as the ray queries return them: CUDA tensors go through the device form on torch's current stream and return a tensor,
+    numpy arrays go through the host form and return numpy."""
+    n = int(rays.shape[0])
+    if tuple(rays.shape) != (n, 8) or tuple(hits.shape) != (n, 8) or tuple(surfaces.shape) != (n, 16):
+        raise ValueError("rays, hits and surfaces must be [n, 8], [n, 8] and [n, 16]")
+    if all(isinstance(a, np.ndarray) for a in (rays, hits, surfaces)):
+        if any(a.dtype != np.float32 for a in (rays, hits, surfaces)):
+            raise ValueError("rays, hits and surfaces must be float32")
+        rays, hits, surfaces = (np.ascontiguousarray(a) for a in (rays, hits, surfaces))
+        out = np.empty((n, 16), dtype=np.float32)
+        ctx = _ctx_for(device)
+        check(lib().rpt_denoise_guides(ctx, rays.ctypes.data, hits.ctypes.data, surfaces.ctypes.data, n, out.ctypes.data), ctx)
+        return out
+    import torch
+    if not all(isinstance(a, torch.Tensor) and a.is_cuda and a.dtype == torch.float32 and a.device == rays.device for a in (rays, hits, surfaces)):
+        raise ValueError("rays, hits and surfaces must all be float32 numpy arrays, or all float32 CUDA tensors on one device")
+    rays, hits, surfaces = rays.contiguous(), hits.contiguous(), surfaces.contiguous()
+    out = torch.empty((n, 16), dtype=torch.float32, device=rays.device)
+    ctx = _ctx_for(rays.device.index or 0)
+    stream = torch.cuda.current_stream(rays.device).cuda_stream
+    check(lib().rpt_denoise_guides_device(ctx, rays.data_ptr(), hits.data_ptr(), surfaces.data_ptr(), n, out.data_ptr(), C.c_void_p(stream)), ctx)
+    return out
+
 
 class DeviceColorBuffer:
     """ColorBuffer whose pixels live in HBM (a torch CUDA tensor): what the render loop
@@ -290,6 +333,25 @@ class DeviceColorBuffer:
         stream = torch.cuda.current_stream(self.pixels.device).cuda_stream
         check(lib().rpt_denoise_device(ctx, self.pixels.data_ptr(), out.pixels.data_ptr(), self.width, self.height, iterations, edge_k,
                                        C.c_void_p(stream)), ctx)
+        out.frames = self.frames
+        return out
+
+    def denoise_guided(self, guides, iterations=4, edge_k=0.25, normal_k=4.0, plane_k=1000.0, out=None):
+        """A copy denoised against first-hit guides, on the device (include/rpt.h "guided denoiser"): a new DeviceColorBuffer, or
+        `out` (same size).  `guides`: a float32 CUDA tensor [height * width, 16] on the buffer's device, one rpt_guide per pixel
+        (Tracer.denoise_guides, pack_guides, or the caller's own)."""
+        import torch
+        n = self.width * self.height
+        if not (isinstance(guides, torch.Tensor) and guides.is_cuda and guides.device == self.pixels.device and guides.dtype == torch.float32 and
+                tuple(guides.shape) == (n, 16) and guides.is_contiguous()):
+            raise ValueError("guides must be a contiguous float32 CUDA tensor [%d, 16] on the buffer's device" % n)
+        if out is None:
+            out = DeviceColorBuffer(self.width, self.height, device=self.pixels.device)
+        assert out.width == self.width and out.height == self.height
+        ctx = _ctx_for(self.pixels.device.index or 0)
+        stream = torch.cuda.current_stream(self.pixels.device).cuda_stream
+        check(lib().rpt_denoise_guided_device(ctx, self.pixels.data_ptr(), guides.data_ptr(), out.pixels.data_ptr(), self.width, self.height, iterations,
+                                              edge_k, normal_k, plane_k, 0, C.c_void_p(stream)), ctx)
         out.frames = self.frames
         return out
 
@@ -832,6 +894,21 @@ class Tracer:
         stream = torch.cuda.current_stream(dev).cuda_stream
         check(lib().rpt_camera_rays_device(self._h, int(width), int(height), rays.data_ptr(), C.c_void_p(stream)), self._h)
         return rays
+
+    def denoise_guides(self, width, height):
+        """First-hit guides of the scene as the camera sees it now (include/rpt.h "guided denoiser"): the camera's rays, traced with
+        surfaces, packed — a CUDA float32 tensor [height * width, 16], one rpt_guide per pixel, for DeviceColorBuffer.denoise_guided.
+        A static camera packs them once and denoises every progressive frame against them."""
+        import torch
+        rays = self.camera_rays(width, height)
+        n = int(rays.shape[0])
+        hits = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+        surf = torch.empty((n, 16), dtype=torch.float32, device=rays.device)
+        guides = torch.empty((n, 16), dtype=torch.float32, device=rays.device)
+        stream = C.c_void_p(torch.cuda.current_stream(rays.device).cuda_stream)
+        check(lib().rpt_trace_rays_device(self._h, rays.data_ptr(), n, hits.data_ptr(), surf.data_ptr(), 0, stream), self._h)
+        check(lib().rpt_denoise_guides_device(self._h, rays.data_ptr(), hits.data_ptr(), surf.data_ptr(), n, guides.data_ptr(), stream), self._h)
+        return guides
 
     # --- radiance queries (include/rpt.h, "radiance queries")
     def radiance(self, rays, spp=1, frames_done=0, out=None, first_index=0):

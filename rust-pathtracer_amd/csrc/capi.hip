@@ -39,6 +39,7 @@
 #include "launch_cut.h"
 #include "launch_emap.h"
 #include "launch_env.h"
+#include "launch_gdn.h"
 #include "launch_light.h"
 #include "launch_med.h"
 #include "launch_mmap.h"
@@ -2911,6 +2912,121 @@ int rpt_denoise(rpt_ctx* ctx, const float* pixels, float* out, uint32_t width, u
     RPT_HIP_CHECK(ctx, hipMemcpyAsync(d.fb, pixels, bytes, hipMemcpyHostToDevice, d.stream));
     rc = rpt_denoise_device(ctx, d.fb, out_dev, width, height, iterations, edge_k, d.stream);
     if (rc != RPT_OK) return rc;
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(out, out_dev, bytes, hipMemcpyDeviceToHost, d.stream));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    return RPT_OK;
+}
+
+// ---- guided denoiser (include/rpt.h, "guided denoiser") ------------------------------------------------------------------------------
+// What the pack checks before anything is enqueued: the NULL context, the pointers (NULL with n > 0; misaligned whatever n is, the
+// device form only), the batch size.  False: the call returns *rc.  True: there is something to launch.
+static bool guides_ready(rpt_ctx* ctx, const char* name, const void* const* ptrs, uint64_t n, bool aligned, int* rc)
+{
+    *rc = RPT_ERR_INVALID_ARG;
+    if (!ctx) { set_err(nullptr, "%s: ctx is NULL", name); return false; }
+    for (uint32_t k = 0; k < 4u; ++k) {
+        if (n > 0 && !ptrs[k]) { set_err(ctx, "%s: NULL array with n > 0", name); return false; }
+        if (aligned && ((uintptr_t)ptrs[k] & 15u) != 0) { set_err(ctx, "%s: device arrays must be 16-byte aligned", name); return false; }
+    }
+    if (n / 256u + (n % 256u ? 1u : 0u) > 0x7FFFFFFFull) { set_err(ctx, "%s: %llu records are more than a grid of 0x7FFFFFFF workgroups holds", name, (unsigned long long)n); return false; }
+    *rc = RPT_OK;
+    return n != 0;
+}
+
+int rpt_denoise_guides_device(rpt_ctx* ctx, const rpt_ray* rays_dev, const rpt_hit* hits_dev, const rpt_surface* surfaces_dev, uint64_t n,
+                              rpt_guide* guides_dev, void* stream)
+{
+    int rc;
+    const void* const ptrs[4] = {rays_dev, hits_dev, surfaces_dev, guides_dev};
+    if (!guides_ready(ctx, "rpt_denoise_guides_device", ptrs, n, true, &rc)) return rc;
+    RPT_ON_DEVICE(ctx);
+    RPT_HIP_CHECK(ctx, rptlaunch::gdn_pack(rays_dev, hits_dev, surfaces_dev, n, guides_dev, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_denoise_guides(rpt_ctx* ctx, const rpt_ray* rays, const rpt_hit* hits, const rpt_surface* surfaces, uint64_t n, rpt_guide* guides)
+{
+    int rc;
+    const void* const ptrs[4] = {rays, hits, surfaces, guides};
+    if (!guides_ready(ctx, "rpt_denoise_guides", ptrs, n, false, &rc)) return rc;
+    RPT_ON_DEVICE(ctx);
+    DevState& d = ctx->devs[0];
+    const auto up = [](size_t x) { return (x + 255u) & ~(size_t)255u; };
+    const size_t off_hits = up(sizeof(rpt_ray) * (size_t)n);
+    const size_t off_surfaces = off_hits + up(sizeof(rpt_hit) * (size_t)n);
+    const size_t off_guides = off_surfaces + up(sizeof(rpt_surface) * (size_t)n);
+    RPT_CHECK_RC(ensure_fb(ctx, d, off_guides + sizeof(rpt_guide) * (size_t)n));
+    unsigned char* base = reinterpret_cast<unsigned char*>(d.fb);
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(base, rays, sizeof(rpt_ray) * (size_t)n, hipMemcpyHostToDevice, d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + off_hits, hits, sizeof(rpt_hit) * (size_t)n, hipMemcpyHostToDevice, d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(base + off_surfaces, surfaces, sizeof(rpt_surface) * (size_t)n, hipMemcpyHostToDevice, d.stream));
+    RPT_HIP_CHECK(ctx, rptlaunch::gdn_pack(reinterpret_cast<const rpt_ray*>(base), reinterpret_cast<const rpt_hit*>(base + off_hits),
+                                           reinterpret_cast<const rpt_surface*>(base + off_surfaces), n, reinterpret_cast<rpt_guide*>(base + off_guides), d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(guides, base + off_guides, sizeof(rpt_guide) * (size_t)n, hipMemcpyDeviceToHost, d.stream));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    return RPT_OK;
+}
+
+// The filter's arguments, pointers aside: the ranges of include/rpt.h (a NaN fails every comparison).
+static bool guided_args_ok(uint32_t width, uint32_t height, uint32_t iterations, float edge_k, float normal_k, float plane_k, uint32_t flags)
+{
+    return width != 0 && height != 0 && iterations >= 1u && iterations <= 6u && edge_k > 0.0f && std::isfinite(edge_k) &&
+           normal_k >= 0.0f && std::isfinite(normal_k) && plane_k >= 0.0f && std::isfinite(plane_k) && flags == 0u;
+}
+
+int rpt_denoise_guided_device(rpt_ctx* ctx, const float* pixels_dev, const rpt_guide* guides_dev, float* out_dev, uint32_t width, uint32_t height,
+                              uint32_t iterations, float edge_k, float normal_k, float plane_k, uint32_t flags, void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_denoise_guided_device: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (!pixels_dev || !guides_dev || !out_dev || !guided_args_ok(width, height, iterations, edge_k, normal_k, plane_k, flags)) {
+        set_err(ctx, "rpt_denoise_guided_device: invalid argument (iterations 1..6, edge_k > 0, normal_k and plane_k >= 0, all finite, flags 0)");
+        return RPT_ERR_INVALID_ARG;
+    }
+    if ((((uintptr_t)pixels_dev | (uintptr_t)guides_dev | (uintptr_t)out_dev) & 15u) != 0) {
+        set_err(ctx, "rpt_denoise_guided_device: buffers must be 16-byte aligned");
+        return RPT_ERR_INVALID_ARG;
+    }
+    const size_t bytes = (size_t)width * height * 16u;
+    const char *a = (const char*)pixels_dev, *b = (const char*)out_dev, *g = (const char*)guides_dev;
+    if ((a < b + bytes && b < a + bytes) || (g < b + bytes && b < g + 4u * bytes)) {
+        set_err(ctx, "rpt_denoise_guided_device: out_dev overlaps pixels_dev or guides_dev");
+        return RPT_ERR_INVALID_ARG;
+    }
+    RPT_ON_DEVICE(ctx);
+    DevState& d = ctx->devs[0];
+    const bool uses_scratch = iterations > 1u;                        // (the context's buffer of rpt_denoise_device, and its rule for streams)
+    if (uses_scratch && bytes > d.dn_bytes) {
+        if (d.dn) { RPT_HIP_CHECK(ctx, hipStreamSynchronize((hipStream_t)stream)); RPT_HIP_CHECK(ctx, hipFree(d.dn)); d.dn = nullptr; d.dn_bytes = 0; }
+        RPT_HIP_CHECK(ctx, hipMalloc((void**)&d.dn, bytes));
+        d.dn_bytes = bytes;
+    }
+    if (uses_scratch && d.dn_used && d.dn_stream != (hipStream_t)stream) RPT_HIP_CHECK(ctx, hipStreamWaitEvent((hipStream_t)stream, d.dn_done, 0));
+    RPT_HIP_CHECK(ctx, rptlaunch::gdn_filter(pixels_dev, guides_dev, out_dev, d.dn, width, height, iterations, edge_k, normal_k, plane_k, (hipStream_t)stream));
+    if (uses_scratch) {
+        RPT_HIP_CHECK(ctx, hipEventRecord(d.dn_done, (hipStream_t)stream));
+        d.dn_stream = (hipStream_t)stream;
+        d.dn_used = true;
+    }
+    return RPT_OK;
+}
+
+int rpt_denoise_guided(rpt_ctx* ctx, const float* pixels, const rpt_guide* guides, float* out, uint32_t width, uint32_t height, uint32_t iterations,
+                       float edge_k, float normal_k, float plane_k, uint32_t flags)
+{
+    if (!ctx) { set_err(nullptr, "rpt_denoise_guided: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (!pixels || !guides || !out || !guided_args_ok(width, height, iterations, edge_k, normal_k, plane_k, flags)) {
+        set_err(ctx, "rpt_denoise_guided: invalid argument (iterations 1..6, edge_k > 0, normal_k and plane_k >= 0, all finite, flags 0)");
+        return RPT_ERR_INVALID_ARG;
+    }
+    RPT_ON_DEVICE(ctx);
+    DevState& d = ctx->devs[0];
+    const size_t bytes = (size_t)width * height * 16u;
+    RPT_CHECK_RC(ensure_fb(ctx, d, 6u * bytes));                      // input, output and the guides (64 B a pixel), one allocation
+    float* out_dev = reinterpret_cast<float*>(reinterpret_cast<char*>(d.fb) + bytes);
+    rpt_guide* guides_dev = reinterpret_cast<rpt_guide*>(reinterpret_cast<char*>(d.fb) + 2u * bytes);
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(d.fb, pixels, bytes, hipMemcpyHostToDevice, d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(guides_dev, guides, 4u * bytes, hipMemcpyHostToDevice, d.stream));
+    RPT_CHECK_RC(rpt_denoise_guided_device(ctx, d.fb, guides_dev, out_dev, width, height, iterations, edge_k, normal_k, plane_k, flags, d.stream));
     RPT_HIP_CHECK(ctx, hipMemcpyAsync(out, out_dev, bytes, hipMemcpyDeviceToHost, d.stream));
     RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
     return RPT_OK;

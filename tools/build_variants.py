@@ -89,7 +89,8 @@ VARIANTS = {
     # round 5
     "perop": ["-DRPT_GUARD_PER_OP"],                           # every kernel with the range tests next to the operation (k_small too): the differential partner of the range trackers (tools/range_soak.py)
     "dn_unfused": ["-DRPT_DENOISE_UNFUSED"],                   # the denoiser one pass per iteration (round 4's form) against the fused first three
-    "cg_licm_on": [],        # (built with RPT_TUNING_FLAGS="-mllvm -amdgpu-sched-strategy=max-ilp": machine LICM back on)
+    "gdn_unfused": ["-DRPT_GDN_UNFUSED"],                      # the guided denoiser one pass per iteration against the fused first two (tools/denoise_guided_bench.py)
+    "cg_licm_on": [],      # (built with RPT_TUNING_FLAGS="-mllvm -amdgpu-sched-strategy=max-ilp": machine LICM back on)
 }
 
 if __name__ == "__main__":
