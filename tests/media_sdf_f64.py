@@ -121,7 +121,7 @@ class Material(P.Material):
 
 def phase_hg(c, g):
     """"phase_hg(c, g) = INV_4_PI * (1 - g*g) / (d * sqrt(d)),  d = 1 + g*g + 2*g*c"."""
-    d = 1.0 + g * g + 2.0 * g * c
+    d = P.noisy(1.0 + g * g + 2.0 * g * c)
     return dv(INV_4_PI * (1.0 - g * g), d * sqrt(d))
 
 
@@ -147,11 +147,11 @@ def transmittance(md, dist, mut=()):
     if md.type == MEDIUM_ABSORB:
         if "absorb_with_color" in mut:
             return tuple(exp(-((c * dist) * md.density)) for c in md.color)
-        return tuple(exp(-(((1.0 - c) * dist) * md.density)) for c in md.color)
+        return tuple(P.noisy(exp(-P.noisy(((1.0 - c) * dist) * md.density))) for c in md.color)
     if md.type == MEDIUM_SCATTER:
         if "scatter_transmittance_per_channel" in mut:
             return tuple(exp(-(((1.0 - c) * dist) * md.density)) for c in md.color)
-        e = exp(-(dist * md.density))
+        e = P.noisy(exp(-P.noisy(dist * md.density)))
         return (e, e, e)
     return ONE3
 
@@ -541,6 +541,7 @@ def sample_many(scene, oracle, seed, items, width, height, mut=(), roulette=Fals
     nd = n_draws_of(scene)
     for k, (c, r, f) in enumerate(items):
         dr = oracle.rng_f32(seed, int(f), int(r) * width + int(c), nd)
+        P.noise_begin(seed, int(f), int(r) * width + int(c))
         rad, ry, m = path.sample(int(c), int(r), width, height, dr)
         out[k] = rad
         marg[k] = m

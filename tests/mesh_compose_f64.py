@@ -32,7 +32,14 @@ both sides.  The composition rules, each where the code applies it:
     sampler's `c > 0`, the hit side's c, and the facing test.
 
 Faults a device could have in exactly one interaction are planted by keyword arguments, as fault= / no_hit_weight= are in the
-single-feature files; tests/test_gpu_mesh_compose_f64.py holds each to the draws that must see it."""
+single-feature files; tests/test_gpu_mesh_compose_f64.py holds each to the draws that must see it.  Three subtle ones, wrong in the
+second or third digit, are held to the samples' own f32 tolerances there (tests/f32_spread.py): ComposedPath's mesh_light_pdf_scale,
+the scene attribute env_pdf_from_next_row and this module's BILINEAR_SHIFT.
+
+Under pt_f64's noise mode the outputs computed here outside pt_f64's helpers, which the device computes in f32, carry the same
+noise: interp_uv's (s, t), the BILINEAR blends of tex_lookup (a NEAREST value is a table entry and is not perturbed), the bend's T,
+B and result, env_pdf, the mesh-light sampler's barycentrics, and the textured rgb; the triangle test's t, u and v term by term
+(test_gpu_mesh_f64.MeshDescScene.noisy_tuv).  With the mode off every function returns the bits it returned before."""
 import bisect
 import math
 
@@ -47,6 +54,7 @@ REPEAT, CLAMP, NEAREST, BILINEAR = 0, 1, 0, 1
 WRAPS = {"repeat": REPEAT, "clamp": CLAMP}
 FILTERS = {"nearest": NEAREST, "bilinear": BILINEAR}
 N_DRAWS = 128
+BILINEAR_SHIFT = 0.0                                                  # a planted fault: the BILINEAR lookup shifted by this many texels
 
 
 # ---- the triangle's own quantities ------------------------------------------------------------------------------------------------
@@ -59,7 +67,7 @@ def interp_uv(sc, k, u, v):
     """include/rpt.h, "mesh textures", lookup at the hit: (s, t) from the corners' UVs and the triangle test's u and v."""
     ua, ub, uc = (sc.uv[j] for j in sc.corner[k])
     s, t = ((1.0 - u) - v) * ua + u * ub + v * uc
-    return float(s), float(t)
+    return P.noisy(float(s)), P.noisy(float(t))
 
 
 # ---- mesh textures ------------------------------------------------------------------------------------------------------------------
@@ -81,7 +89,7 @@ def tex_axis(s, n, wrap, filt, M):
             M.of(p - np.round(p), 1.0)
         i = int(np.floor(p))
         return (min(i, n - 1) if wrap == CLAMP else i % n), None, None
-    p -= 0.5
+    p -= 0.5 - BILINEAR_SHIFT
     f0 = np.floor(p)
     i0, i1 = int(f0), int(f0) + 1
     if wrap == CLAMP:
@@ -95,10 +103,10 @@ def tex_lookup(texels, s, t, wrap, filt, M):
     i0, i1, fx = tex_axis(s, w, wrap, filt, M)
     j0, j1, fy = tex_axis(t, h, wrap, filt, M)
     if filt == NEAREST:
-        return texels[j0, i0]
-    top = (1.0 - fx) * texels[j0, i0] + fx * texels[j0, i1]
-    bot = (1.0 - fx) * texels[j1, i0] + fx * texels[j1, i1]
-    return (1.0 - fy) * top + fy * bot
+        return texels[j0, i0]                                         # (a table value: never perturbed)
+    top = P.noisy_array((1.0 - fx) * texels[j0, i0] + fx * texels[j0, i1])
+    bot = P.noisy_array((1.0 - fx) * texels[j1, i0] + fx * texels[j1, i1])
+    return P.noisy_array((1.0 - fy) * top + fy * bot)
 
 
 # ---- mesh cutouts -------------------------------------------------------------------------------------------------------------------
@@ -151,8 +159,8 @@ def bend(N, e1, e2, ua, ub, uc, xyz, M, swap=False):
     M.of(l2, float((T0 * T0).sum()))
     if not l2 > 0.0:
         return tuple(float(c) for c in N)
-    T = T1 / np.sqrt(l2)
-    B = np.cross(N, T)
+    T = P.noisy_array(T1 / np.sqrt(l2))
+    B = P.noisy_array(np.cross(N, T))
     side = float((B * B0).sum())
     M.of(side, float(np.sqrt((B0 * B0).sum())))
     if side < 0.0:
@@ -164,7 +172,7 @@ def bend(N, e1, e2, ua, ub, uc, xyz, M, swap=False):
     M.of(l2, x * x + y * y + z * z)
     if not l2 > 0.0:
         return tuple(float(c) for c in N)
-    return tuple(float(c) for c in m / np.sqrt(l2))
+    return tuple(float(c) for c in P.noisy_array(m / np.sqrt(l2)))
 
 
 # ---- mesh lights --------------------------------------------------------------------------------------------------------------------
@@ -184,9 +192,9 @@ def bind_mesh_lights(sc, desc, scene, on):
     sc.won = None
 
 
-def sample_mesh_light(sc, ordinal, n_f, scatter_pos, draw, M, normal_of=None):
+def sample_mesh_light(sc, ordinal, n_f, scatter_pos, draw, M, normal_of=None, pdf_scale=1.0):
     """include/rpt.h, "sampling an ON mesh" -> (LightSampleRec, light.area).  n_f: N_f, the number of pickable lights.  normal_of
-    (a planted fault): (flattened triangle, bu, bv) -> the normal to use where the flat one belongs."""
+    (a planted fault): (flattened triangle, bu, bv) -> the normal to use where the flat one belongs; pdf_scale (another): the pdf times it."""
     cdf, q_all, a_tot, tri, em, first = sc.mesh_lights[ordinal]
     r0a, r0b, r1, r2 = draw(), draw(), draw(), draw()
     ls = P.LightSampleRec()
@@ -200,8 +208,8 @@ def sample_mesh_light(sc, ordinal, n_f, scatter_pos, draw, M, normal_of=None):
     a, b, c = (tuple(float(x) for x in p) for p in tri[k])
     e1, e2 = P.sub(b, a), P.sub(c, a)
     su = P.sqrt(r1)
-    bu = 1.0 - su
-    bv = r2 * su
+    bu = P.noisy(1.0 - su)
+    bv = P.noisy(r2 * su)
     p = P.add(P.add(a, P.scale(bu, e1)), P.scale(bv, e2))
     direction = P.sub(p, scatter_pos)
     ls.dist = P.length(direction)
@@ -213,6 +221,8 @@ def sample_mesh_light(sc, ordinal, n_f, scatter_pos, draw, M, normal_of=None):
     ls.normal = P.neg(n) if cs > 0.0 else n
     ls.emission = P.scale(n_f, em)
     ls.pdf = P.dv(dist_sq, a_tot * abs(cs))
+    if pdf_scale != 1.0:
+        ls.pdf *= pdf_scale
     return ls, a_tot
 
 
@@ -260,8 +270,10 @@ def env_pdf(sc, k, p):
     s_f = float(sc.env_size)
     l2 = P.dot(p, p)
     ln = P.sqrt(l2)
+    if getattr(sc, "env_pdf_from_next_row", False):                  # a planted fault: the neighbouring texel row's quantum
+        k = k + sc.env_size if k + sc.env_size < sc.env_size * sc.env_size else k - sc.env_size
     sel = P.dv(float(env_quantum(sc, k)), float(sc.env_q))
-    return (sel * ((s_f * s_f) * 0.25)) * (l2 * ln), ln
+    return P.noisy((sel * ((s_f * s_f) * 0.25)) * (l2 * ln)), ln
 
 
 def env_lookup(sc, d, M):
@@ -421,6 +433,7 @@ def sample_pixels(path, oracle, seed, pixels, w, h, frame=0):
     out, marg = np.zeros((len(pixels), 3)), np.zeros(len(pixels))
     for k, (c, r) in enumerate(pixels):
         dr = oracle.rng_f32(seed, frame, int(r) * w + int(c), N_DRAWS)
+        P.noise_begin(seed, frame, int(r) * w + int(c))
         out[k], _, marg[k] = path.sample(int(c), int(r), w, h, dr)
     return out, marg
 
@@ -516,7 +529,7 @@ class ComposedMeshDescScene(SmoothMeshDescScene):
             if mesh in self.tex and not (self.no_texture_under_env and self.env_set):
                 texels, wrap, filt = self.tex[mesh]
                 tex = tex_lookup(texels, *interp_uv(self, k, u, v), wrap, filt, M)
-                mat.rgb = tuple(float(c) * float(x) for c, x in zip(mat.rgb, tex))
+                mat.rgb = tuple(P.noisy(float(c) * float(x)) for c, x in zip(mat.rgb, tex))
 
 
 class ComposedPath(P.Path):
@@ -524,9 +537,10 @@ class ComposedPath(P.Path):
     weight use the shading normal — smooth, bent — where the flat one belongs) and n_without_on_meshes_under_env (N leaves the ON
     meshes out while an environment is SAMPLED: they are never picked, and every pick is scaled by the smaller N)."""
 
-    def __init__(self, scene, light_uses_shading_normal=False, n_without_on_meshes_under_env=False):
+    def __init__(self, scene, light_uses_shading_normal=False, n_without_on_meshes_under_env=False, mesh_light_pdf_scale=1.0):
         super().__init__(scene)
         self.light_uses_shading_normal, self.n_without_on_meshes_under_env = light_uses_shading_normal, n_without_on_meshes_under_env
+        self.mesh_light_pdf_scale = mesh_light_pdf_scale             # (a subtle planted fault: 0.98)
 
     def picks(self):
         """include/rpt.h, "pickable lights": the rpt_lights, the ON meshes in ascending mesh index, the SAMPLED environment last."""
@@ -540,7 +554,8 @@ class ComposedPath(P.Path):
 
     def sample_mesh_light(self, ordinal, scatter_pos, draw, M):
         shading = (lambda k, bu, bv: self.scene.shading_normal(k, bu, bv, M)) if self.light_uses_shading_normal else None
-        return sample_mesh_light(self.scene, ordinal, float(len(self.picks())), scatter_pos, draw, M, normal_of=shading)
+        return sample_mesh_light(self.scene, ordinal, float(len(self.picks())), scatter_pos, draw, M, normal_of=shading,
+                                 pdf_scale=self.mesh_light_pdf_scale)
 
     def sample_env(self, draw, M):
         return sample_env(self.scene, float(len(self.picks())), draw, M)

@@ -44,7 +44,7 @@ class EmapMeshDescScene(MM.MmapMeshDescScene):
             return
         E = self.emission_factor(*won, M)
         if E is not None:
-            mat.emission = tuple(float(e) * x for e, x in zip(mat.emission, E))
+            mat.emission = tuple(P.noisy(float(e) * x) for e, x in zip(mat.emission, E))
 
 
 class EmapPath(ComposedPath):
@@ -70,7 +70,7 @@ class EmapPath(ComposedPath):
             k, bu, bv = picked[0]
             E = sc.emission_factor(k, bv, bu, M) if self.sampler_swaps_uv else sc.emission_factor(k, bu, bv, M)
             if E is not None:
-                ls.emission = P.scale(n_f, tuple(float(e) * x for e, x in zip(em, E)))
+                ls.emission = P.scale(n_f, tuple(P.noisy(float(e) * x) for e, x in zip(em, E)))
         return ls, area
 
 

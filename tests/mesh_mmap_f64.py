@@ -3,11 +3,12 @@ MmapMeshDescScene is ComposedMeshDescScene with one more step at a winning trian
 textured rgb), roughness *= fr and metallic *= fm, the factors looked up through the TEXTURE's UVs and wrap with the MAP's own filter
 and size by the same tex_lookup, NEAREST margins included.  The decode is k / 255, or exactly 1 for a channel that is None.
 
-`material_maps` is the very dict Tracer.set_mesh_material_maps takes.  One planted fault, factor_on_wrong_field: roughness takes the
-metallic factor and metallic the roughness one.  The scene and the maps the float64 tests use are here as well, so the GPU file and
+`material_maps` is the very dict Tracer.set_mesh_material_maps takes.  Planted faults: factor_on_wrong_field (roughness takes the
+metallic factor and metallic the roughness one) and the subtle factor_scale (fr and fm times its two values).  The scene and the maps the float64 tests use are here as well, so the GPU file and
 the CPU file hand both sides one value."""
 import numpy as np
 
+import pt_f64 as P
 from mesh_compose_f64 import FILTERS, ComposedMeshDescScene, interp_uv, tex_lookup
 
 OBJECT_METALLIC = 0.7
@@ -24,9 +25,9 @@ def decode_material_map_f64(rgba, roughness_channel=1, metallic_channel=2):
 
 
 class MmapMeshDescScene(ComposedMeshDescScene):
-    def __init__(self, desc, scene, material_maps=None, factor_on_wrong_field=False, **composed):
+    def __init__(self, desc, scene, material_maps=None, factor_on_wrong_field=False, factor_scale=(1.0, 1.0), **composed):
         super().__init__(desc, scene, **composed)
-        self.factor_on_wrong_field = factor_on_wrong_field
+        self.factor_on_wrong_field, self.factor_scale = factor_on_wrong_field, factor_scale
         self.mmaps = {}
         for m, mm in (material_maps or {}).items():
             assert m in self.tex, "a material map needs the mesh's UVs (include/rpt.h, \"mesh material maps\": Composition)"
@@ -47,8 +48,9 @@ class MmapMeshDescScene(ComposedMeshDescScene):
         fr, fm = (float(x) for x in tex_lookup(texels, *interp_uv(self, k, u, v), self.tex[mesh][1], filt, M))
         if self.factor_on_wrong_field:
             fr, fm = fm, fr
-        mat.roughness = mat.roughness * fr
-        mat.metallic = mat.metallic * fm
+        fr, fm = fr * self.factor_scale[0], fm * self.factor_scale[1]      # (a subtle planted fault: a factor times 1.02; x 1.0 keeps the bits)
+        mat.roughness = P.noisy(mat.roughness * fr)
+        mat.metallic = P.noisy(mat.metallic * fm)
 
 
 def scene():

@@ -47,7 +47,11 @@ either); the denoiser is out of scope here (tests/dn_f64.py).
 Outputs of sample(): the radiance (three doubles), the rays it queried in oracle_sample_rays' layout ({o, d, max_dist}, max_dist =
 -1 for closest_hit), and the smallest relative BRANCH MARGIN over every comparison the sample took: how far (relatively) the two
 sides of each test lay apart.  A sample whose margin is below the rounding error of the arithmetic compared against can take
-another branch there, legitimately; every other sample must agree to rounding."""
+another branch there, legitimately; every other sample must agree to rounding.
+
+The noise mode (perturbed(), below the constants): the same statements with f32-sized relative noise on the result of every vector
+and divide helper, from which tests/f32_spread.py takes each sample's own f32 error bound.  Off, nothing here changes a bit."""
+import contextlib
 import math
 
 import numpy as np
@@ -95,18 +99,85 @@ MUTANTS = {
 }
 
 
+# ---- the noise mode ----------------------------------------------------------------------------------------------------------
+# How much f32 rounding a sample amplifies is a property of the sample.  Within `with perturbed(seed, run):` the arithmetic helpers
+# below (PERTURBED) multiply every component of their result by 1 + delta, delta uniform in +-2^-24 (half an ulp of f32, relatively);
+# how far the sample moves is its sensitivity (tests/f32_spread.py).  Draws, table integers, scene data and the branch margins'
+# own arithmetic are never perturbed; comparisons see the perturbed values, as an f32 computation's do.  The generator is seeded
+# from (seed, run, the key noise_begin() is given): the sample's own seed, frame and stream index, so that a sample's noise does not
+# depend on which other samples were evaluated.  Outside the block _NOISE is None and every helper returns the bits it always did.
+NOISE_EPS = 2.0 ** -24
+PERTURBED = ("add", "sub", "mul", "scale", "dot", "cross", "dv", "sqrt", "mix3", "mix1", "length, normalize and div3 through sqrt and dv")
+_NOISE = None
+
+
+class Noise:
+    __slots__ = ("seed", "run", "rng", "buf", "i")
+
+    def __init__(self, seed, run):
+        self.seed, self.run = int(seed), int(run)
+        self.begin()
+
+    def begin(self, *key):
+        self.rng = np.random.default_rng([self.seed, self.run] + [int(k) & 0xFFFFFFFF for k in key])
+        self.buf, self.i = (), 0
+
+    def factor(self):
+        if self.i >= len(self.buf):
+            self.buf, self.i = (1.0 + self.rng.uniform(-NOISE_EPS, NOISE_EPS, 1024)).tolist(), 0
+        self.i += 1
+        return self.buf[self.i - 1]
+
+    def v3(self, r):
+        f = self.factor
+        return (r[0] * f(), r[1] * f(), r[2] * f())
+
+    def array(self, x):
+        x = np.asarray(x, np.float64)
+        return x * (1.0 + self.rng.uniform(-NOISE_EPS, NOISE_EPS, x.shape))
+
+
+@contextlib.contextmanager
+def perturbed(seed, run=0):
+    """Within the block the helpers in PERTURBED carry f32-sized relative noise."""
+    global _NOISE
+    saved, _NOISE = _NOISE, Noise(seed, run)
+    try:
+        yield
+    finally:
+        _NOISE = saved
+
+
+def noise_begin(*key):
+    """Called by every loop over samples before a sample starts, with what identifies the sample (its seed, frame and stream
+    index): re-seeds the noise for it.  Nothing happens outside perturbed()."""
+    if _NOISE is not None:
+        _NOISE.begin(*key)
+
+
+def noisy(x):
+    """A float computed outside the helpers (the mesh restatements' numpy arithmetic) that the device computes in f32."""
+    return x if _NOISE is None else x * _NOISE.factor()
+
+
+def noisy_array(x):
+    return x if _NOISE is None else _NOISE.array(x)
+
+
 # ---- IEEE helpers ------------------------------------------------------------------------------------------------------------
 def dv(a, b):
     try:
-        return a / b
+        r = a / b
     except ZeroDivisionError:
         if a != a or a == 0.0:
             return NAN
         return math.copysign(INF, a) * math.copysign(1.0, b)
+    return r if _NOISE is None else r * _NOISE.factor()
 
 
 def sqrt(x):
-    return math.sqrt(x) if x >= 0.0 else (x if x != x else NAN)
+    r = math.sqrt(x) if x >= 0.0 else (x if x != x else NAN)
+    return r if _NOISE is None else r * _NOISE.factor()
 
 
 def log2(x):
@@ -155,19 +226,23 @@ def clamp(x, lo, hi):                           # f32::clamp: NaN stays NaN
 
 
 def add(a, b):
-    return (a[0] + b[0], a[1] + b[1], a[2] + b[2])
+    r = (a[0] + b[0], a[1] + b[1], a[2] + b[2])
+    return r if _NOISE is None else _NOISE.v3(r)
 
 
 def sub(a, b):
-    return (a[0] - b[0], a[1] - b[1], a[2] - b[2])
+    r = (a[0] - b[0], a[1] - b[1], a[2] - b[2])
+    return r if _NOISE is None else _NOISE.v3(r)
 
 
 def mul(a, b):
-    return (a[0] * b[0], a[1] * b[1], a[2] * b[2])
+    r = (a[0] * b[0], a[1] * b[1], a[2] * b[2])
+    return r if _NOISE is None else _NOISE.v3(r)
 
 
 def scale(s, a):
-    return (s * a[0], s * a[1], s * a[2])
+    r = (s * a[0], s * a[1], s * a[2])
+    return r if _NOISE is None else _NOISE.v3(r)
 
 
 def neg(a):
@@ -175,32 +250,36 @@ def neg(a):
 
 
 def dot(a, b):
-    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
+    r = a[0] * b[0] + a[1] * b[1] + a[2] * b[2]
+    return r if _NOISE is None else r * _NOISE.factor()
 
 
 def cross(a, b):
-    return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+    r = (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
+    return r if _NOISE is None else _NOISE.v3(r)
 
 
-def length(a):
+def length(a):                                  # (perturbed through sqrt)
     return sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2])
 
 
-def normalize(a):                               # fx.rs: each component over the length
+def normalize(a):                               # fx.rs: each component over the length (perturbed through length and dv)
     n = length(a)
     return (dv(a[0], n), dv(a[1], n), dv(a[2], n))
 
 
-def div3(a, b):
+def div3(a, b):                                 # (perturbed through dv)
     return (dv(a[0], b[0]), dv(a[1], b[1]), dv(a[2], b[2]))
 
 
 def mix3(a, b, v):                              # math.rs mix: (1 - v) * a + b * v per channel
-    return ((1.0 - v) * a[0] + b[0] * v, (1.0 - v) * a[1] + b[1] * v, (1.0 - v) * a[2] + b[2] * v)
+    r = ((1.0 - v) * a[0] + b[0] * v, (1.0 - v) * a[1] + b[1] * v, (1.0 - v) * a[2] + b[2] * v)
+    return r if _NOISE is None else _NOISE.v3(r)
 
 
 def mix1(a, b, v):                              # tracer.rs mix_ptf
-    return (1.0 - v) * a + b * v
+    r = (1.0 - v) * a + b * v
+    return r if _NOISE is None else r * _NOISE.factor()
 
 
 ONE3 = (1.0, 1.0, 1.0)
@@ -1118,6 +1197,7 @@ def sample_many(scene, oracle, seed, items, width, height, mut=(), roulette=Fals
     rays = []
     for k, (c, r, f) in enumerate(items):
         dr = oracle.rng_f32(seed, int(f), int(r) * width + int(c), n_draws)
+        noise_begin(seed, int(f), int(r) * width + int(c))
         rad, ry, m = path.sample(int(c), int(r), width, height, dr)
         out[k] = rad
         marg[k] = m

@@ -81,6 +81,7 @@ def sample_rays(path, oracle, seed, frames_done, rays, first_index=0, fault=None
         if fault == "key_without_first_index":
             index = i
         dr = oracle.rng_f32(seed, int(frames_done), index, n_draws)
+        P.noise_begin(seed, int(frames_done), index)
         o, d = tuple(float(x) for x in r[0:3]), tuple(float(x) for x in r[4:7])
         out[i], _, marg[i] = sample(path, o, d, dr, fault)
     return out, marg

@@ -49,13 +49,24 @@ classes give the single-feature restatements' samples and margins bit for bit.
 
 The restatement's time on the CPU, measured: 1.9 ms per sample — 0.75 s for a case's 400 draws, 2 s for a mutation's two passes over
 the grid, 18 s for this file's CPU tests together.  On an MI355X each of the eight comparisons takes 2.3 to 2.7 s, the restatement
-included; the largest clean relative distance seen was 1.4e-4 (case E), next to REL_CLEAN = 5e-2."""
+included; the largest clean relative distance seen was 1.4e-4 (case E), next to REL_CLEAN = 5e-2.
+
+The first 150 clean samples of every case are also held to their own f32 tolerance (tests/f32_spread.py: Tally.add's spreads; the
+mesh kernels have no f32 twin, and REL_CLEAN is hundreds of times what they have ever shown), computed once per case beside
+_restated (1.7 to 2.9 s of CPU time; the case's two plain passes take 0.75 s).  test_the_spreads_of_the_restatement holds the
+conditions on the CPU (at least 100 clean samples with a spread, at most 5 % with a tolerance above 1e-3: 0 % in every case),
+test_the_spreads_see_a_subtle_fault three faults that stay within REL_CLEAN on every clean sample and leave their own tolerance on
+38 (the mesh light's pdf x 0.98), 119 (the environment's pdf from the neighbouring texel row) and 16 (a BILINEAR lookup 1/32 of a
+texel off).  The largest z seen on an MI355X, per case: A 0.94, B 1.34, C 1.58, D 1.46, E 1.47, F 1.37, G 1.84, H 1.68, next to
+Z_MAX = 8.3; the medians 0.13 to 0.32, next to Z_MEDIAN = 1.4.  Measurements, not bounds."""
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
+import f32_spread as S
+import mesh_compose_f64 as MC
 from kernel_census import (CUT_BIT, ENV_BIT, LIGHT_BIT, MESH_BIT, MESH_FORM_BITS, MESH_RENDER_KERNELS, NRM_BIT, SMOOTH_BIT, TEX_BIT,
                            mesh_kernel_of)
 from mesh_compose_f64 import ComposedMeshDescScene, ComposedPath, sample_pixels
@@ -93,6 +104,19 @@ MUTATIONS = {
     "n_without_on_meshes_under_env": ("B", "path", 292),
 }
 GRID = [(c, r) for r in range(2, 48, 2) for c in range(8, 56, 2)]  # the lamp, the object and the floor
+
+
+def object_pixels(sc, mesh=0):
+    """The pixels of GRID whose centre sees mesh `mesh` of the restated scene `sc` first: where a fault on that mesh shows."""
+    import pt_f64 as P
+    out = []
+    for c, r in GRID:
+        o, d = P.gen_ray(sc.cam, (float(c) / W, 1.0 - (float(H) - float(H - 1 - r)) / H), (0.5, 0.5), float(W), float(H))
+        st = P.State()
+        st.material = P.Material(1.5)
+        if sc.closest_hit(o, d, st, P.LightSampleRec(), frozenset(), P.Margin()) and sc.won is not None and sc.tri_mesh[sc.won] == mesh:
+            out.append((c, r))
+    return out
 
 
 @pytest.fixture(scope="module")
@@ -145,6 +169,15 @@ def _restated(oracle, case):
     return [(seed, pixels) + sample_pixels(path, oracle, seed, pixels, W, H) for seed, pixels in _draws(case)]
 
 
+@functools.lru_cache(maxsize=None)
+def _spreads(oracle, case):
+    """The f32 spreads (tests/f32_spread.py) of the case's first 150 clean samples, computed once beside _restated for the CPU and
+    the GPU leg: ([spreads per seed, NaN where there is none], CPU seconds)."""
+    s = _scene()
+    path = ComposedPath(ComposedMeshDescScene(s.describe(), s, **inputs(s, case)))
+    return S.spreads_of_draws(path, oracle, _restated(oracle, case), W, H)
+
+
 def _one_composed_sample(rpt, torch, scene, args, seed):
     """A one-sample render under the case's set calls into a fresh buffer -> (frame, kernel choice)."""
     t = rpt.Tracer(scene, device=0, seed=seed)
@@ -175,13 +208,15 @@ def test_composed_mesh_renders_against_the_restatement(rpt, oracle, torch_cuda, 
     s = _scene()
     args = inputs(s, case)
     t = Tally(TAU, NEAR_TIE_MAX)
-    for seed, pixels, restated, margins in _restated(oracle, case):
+    spreads, seconds = _spreads(oracle, case)
+    print("case %s: the spreads took %.2f s of CPU time" % (case, seconds))
+    for (seed, pixels, restated, margins), spread in zip(_restated(oracle, case), spreads):
         frame, choice = _one_composed_sample(rpt, torch_cuda, s, args, seed)
         assert choice & MESH_FORM_BITS == bits, "case %s: bits 25-31 are 0x%x, not 0x%x" % (case, choice & MESH_FORM_BITS, bits)
         assert mesh_kernel_of(choice) == kernel
         t.ran.add(mesh_kernel_of(choice))
         print("case %s (seed %d): %d of %d samples below TAU" % (case, seed, int((margins <= TAU).sum()), len(margins)))
-        t.add("case %s (seed %d, %s)" % (case, seed, kernel), frame, restated, margins, pixels)
+        t.add("case %s (seed %d, %s)" % (case, seed, kernel), frame, restated, margins, pixels, spreads=spread)
     t.check("case %s" % case)
     assert t.n == 400 and t.ran == {kernel}
 
@@ -198,6 +233,63 @@ def test_the_near_tie_count_of_the_restatement(rpt, oracle, case):
     print("case %s: %d of %d samples below TAU (%.2f %%), %d with radiance" % (case, below, total, 100.0 * below / total, lit))
     assert total == 400 and below <= NEAR_TIE_MAX * total and lit > total // 4
     assert (below, lit) == (BELOW_TAU[case], LIT[case])
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_the_spreads_of_the_restatement(rpt, oracle, case):
+    """The conditions of the comparison with spreads, on the restatement alone: at least 100 clean samples of the case have a spread,
+    and at most 5 % of them a tolerance above 1e-3 — for the others the bound is at least 50 times sharper than REL_CLEAN."""
+    spreads, seconds = _spreads(oracle, case)
+    S.case_conditions("case %s" % case, _restated(oracle, case), spreads, seconds)
+
+
+def _low_contrast_texture(args):
+    """Mesh 0's BILINEAR checker with two colours a tenth apart: a lookup 1/32 of a texel off is wrong by well under a percent."""
+    from rust_pathtracer_amd import scenes
+    args["textures"][0]["texels"] = scenes.checker_texture(5, 3, (200, 190, 180), (180, 185, 190), cells=5)
+
+
+def _smooth_sky(args):
+    """A sky that brightens by 2 % from one texel row to the next, in place of the sun's few texels: the neighbouring row's pdf
+    is wrong by 2 %."""
+    rows = (1.0 + 0.02 * np.arange(ENV_SIZE))[:, None, None]
+    args["environment"]["image"] = np.ascontiguousarray(rows * np.array([0.5, 0.6, 0.8]) * np.ones((ENV_SIZE, ENV_SIZE, 1)), np.float32)
+
+
+# fault -> (the case, what changes its inputs or None, the path's keyword arguments, the scene's attributes, mesh_compose_f64's values)
+SUBTLE = {
+    "mesh light pdf x 0.98": ("A", None, dict(mesh_light_pdf_scale=0.98), {}, {}),
+    "environment pdf from the neighbouring texel row": ("B", _smooth_sky, {}, dict(env_pdf_from_next_row=True), {}),
+    "bilinear lookup shifted by 1/32 texel": ("A", _low_contrast_texture, {}, {}, dict(BILINEAR_SHIFT=1.0 / 32.0)),
+}
+
+
+@pytest.mark.parametrize("fault", sorted(SUBTLE))
+def test_the_spreads_see_a_subtle_fault(rpt, oracle, monkeypatch, fault):
+    """A restatement that is wrong in the second or third digit, rounded to f32, stands in for a device: every clean sample stays
+    within REL_CLEAN, so the comparison without spreads passes it; held to its samples' own tolerances it fails on at least 10.
+    Where the case's own inputs would make the fault a gross one (a checker of high contrast, a sky with a sun) the input is
+    replaced by a gentle one, and the restatement and its spreads are computed for it here."""
+    case, change, path_args, scene_attrs, module_values = SUBTLE[fault]
+    s = _scene()
+    args = inputs(s, case)
+    if change is not None:
+        change(args)
+    good = ComposedPath(ComposedMeshDescScene(s.describe(), s, **args))
+    sc = ComposedMeshDescScene(s.describe(), s, **args)
+    for k, v in scene_attrs.items():
+        setattr(sc, k, v)
+    faulty = ComposedPath(sc, **path_args)
+    if change is not None or module_values:
+        draws, entries = _draws(case)[:1], None
+        entries = [(seed, pixels) + sample_pixels(good, oracle, seed, pixels, W, H) for seed, pixels in draws]
+        spreads, _ = S.spreads_of_draws(good, oracle, entries, W, H, count=None)
+    else:
+        entries, (spreads, _) = _restated(oracle, case), _spreads(oracle, case)
+    for k, v in module_values.items():                                # (from here on: the restatement and its spreads are made)
+        monkeypatch.setattr(MC, k, v)
+    moved = [sample_pixels(faulty, oracle, seed, pixels, W, H) for seed, pixels, _, _ in entries]
+    S.teeth("%s (case %s)" % (fault, case), entries, spreads, moved)
 
 
 @pytest.mark.parametrize("fault", sorted(MUTATIONS))

@@ -12,13 +12,21 @@ The planted fault (test_the_restatement_sees_the_wrong_field, CPU): the factors 
 samples beyond REL_CLEAN on case A over test_gpu_mesh_compose_f64's grid of 552 pixels at seed 7 — counted again on every run; the
 composed file asks more than 10 of its faults, and so does this one.  test_an_all_255_map_is_the_composed_restatement (CPU) closes the
 other side: with both factors exactly 1 the subclass gives the composed restatement's samples bit for bit (its margins can only
-narrow: the lamp's NEAREST map adds its texel borders)."""
+narrow: the lamp's NEAREST map adds its texel borders).
+
+The first 150 clean samples of every case are also held to their own f32 tolerance (tests/f32_spread.py, through Tally.add's
+spreads; 1.8 to 2.3 s of CPU time per case, computed once for both legs).  test_the_spreads_of_the_restatement holds the conditions
+on the CPU (at most 2 % of a case's clean samples have a tolerance above 1e-3), test_the_spreads_see_a_factor_two_percent_off the
+metallic factor times 1.02: within REL_CLEAN everywhere, beyond their own tolerance on 51 of 73 clean samples on the object.  The
+largest z seen on an MI355X, per case: A 1.37, B 1.21, C 0.89, D 1.62, E 1.68, F 1.29, G 1.25, H 1.34, next to Z_MAX = 8.3; the
+medians 0.12 to 0.33.  Measurements, not bounds."""
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
+import f32_spread as S
 import mesh_mmap_f64 as MM
 from mesh_compose_f64 import ComposedMeshDescScene, ComposedPath, sample_pixels
 from test_gpu_mesh_compose_f64 import CASES, GRID, H, W, inputs
@@ -54,6 +62,15 @@ def _restated(oracle, case):
     return [(seed, pixels) + sample_pixels(path, oracle, seed, pixels, W, H) for seed, pixels in _draws(case)]
 
 
+@functools.lru_cache(maxsize=None)
+def _spreads(oracle, case):
+    """The f32 spreads (tests/f32_spread.py) of the case's first 150 clean samples, computed once beside _restated for the CPU and
+    the GPU leg: ([spreads per seed, NaN where there is none], CPU seconds)."""
+    s = MM.scene()
+    path = ComposedPath(MM.MmapMeshDescScene(s.describe(), s, material_maps=MM.material_maps(), **inputs(s, case)))
+    return S.spreads_of_draws(path, oracle, _restated(oracle, case), W, H)
+
+
 def set_composed(t, args):
     """The composed file's set calls, in its order."""
     t.set_mesh_textures(args["textures"])
@@ -79,7 +96,9 @@ def test_material_mapped_renders_against_the_restatement(rpt, oracle, torch_cuda
     s = MM.scene()
     args = inputs(s, case)
     tally = Tally(TAU, NEAR_TIE_MAX)
-    for seed, pixels, restated, margins in _restated(oracle, case):
+    spreads, seconds = _spreads(oracle, case)
+    print("case %s: the spreads took %.2f s of CPU time" % (case, seconds))
+    for (seed, pixels, restated, margins), spread in zip(_restated(oracle, case), spreads):
         t = rpt.Tracer(s, device=0, seed=seed)
         try:
             set_composed(t, args)
@@ -93,13 +112,37 @@ def test_material_mapped_renders_against_the_restatement(rpt, oracle, torch_cuda
             t.close()
         tally.ran.add("form %d" % form_of(case))
         print("case %s (seed %d): %d of %d samples below TAU" % (case, seed, int((margins <= TAU).sum()), len(margins)))
-        tally.add("case %s (seed %d, form %d)" % (case, seed, form_of(case)), frame, restated, margins, pixels)
+        tally.add("case %s (seed %d, form %d)" % (case, seed, form_of(case)), frame, restated, margins, pixels, spreads=spread)
     tally.check("case %s" % case)
     assert tally.n == 400
 
 
 def test_the_forms_of_the_cases_are_12_to_19():
     assert [form_of(c) for c in sorted(CASES)] == list(range(12, 20))
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_the_spreads_of_the_restatement(rpt, oracle, case):
+    """The conditions of the comparison with spreads, on the restatement alone: at least 100 clean samples of the case have a spread,
+    and at most 5 % of them a tolerance above 1e-3."""
+    spreads, seconds = _spreads(oracle, case)
+    S.case_conditions("case %s" % case, _restated(oracle, case), spreads, seconds)
+
+
+def test_the_spreads_see_a_factor_two_percent_off(rpt, oracle):
+    """The metallic factor times 1.02, rounded to f32, as a device's samples, over the grid's pixels on the object under case A's
+    inputs: no clean sample leaves REL_CLEAN, so the comparison without spreads passes it; at least 10 leave their own tolerance.
+    The object's metallic is 0.3 here, so that 1 - metallic, which scales the diffuse lobe, moves by under a percent per bounce (at
+    the cases' 0.7 it moves by up to 4.7 %, and two bounces on the object take a sample beyond REL_CLEAN)."""
+    from rust_pathtracer_amd import scenes
+    from test_gpu_mesh_compose_f64 import object_pixels
+    s = MM.scene()
+    s.materials[0] = scenes.full_material(rgb=(0.8, 0.3, 0.25), roughness=0.9, metallic=0.3)
+    good = ComposedPath(MM.MmapMeshDescScene(s.describe(), s, material_maps=MM.material_maps(), **inputs(s, "A")))
+    bad = ComposedPath(MM.MmapMeshDescScene(s.describe(), s, material_maps=MM.material_maps(), factor_scale=(1.0, 1.02), **inputs(s, "A")))
+    pixels = object_pixels(good.scene)
+    print("%d pixels on the object" % len(pixels))
+    S.teeth_on("the metallic factor x 1.02 (case A)", good, bad, oracle, [(7, pixels)], W, H)
 
 
 def test_the_restatement_sees_the_wrong_field(rpt, oracle):

@@ -67,6 +67,8 @@ class SmoothMeshDescScene(MeshDescScene):
         s = o - self.ta[k]
         u = float((s * p).sum()) * inv
         v = float((d * np.cross(s, self.e1[k])).sum()) * inv
+        if P._NOISE is not None:
+            _, u, v = (float(x) for x in self.noisy_tuv(o, d, k))
         return u, v
 
     def triangle_normal(self, k, o, d, M):

@@ -8,12 +8,16 @@ tests/test_gpu_mesh_emission_map_f64.py compares the eight emission-mapped kerne
   beyond REL_CLEAN: a device with that fault would fail the GPU comparison.
 * With all-255 emission maps the subclass gives the material-map restatement's samples bit for bit.
 
+* spreads() computes each case's f32 spreads (tests/f32_spread.py) once, for the GPU comparison and for the conditions held here: at
+  least 100 clean samples with a spread, at most 5 % of them with a tolerance above 1e-3 (at most 1.33 %).
+
 The tolerances are test_path_f64's TAU / REL_CLEAN / NEAR_TIE_MAX: this file has none of its own."""
 import functools
 
 import numpy as np
 import pytest
 
+import f32_spread as S
 import mesh_emap_f64 as ME
 import mesh_mmap_f64 as MM
 from mesh_compose_f64 import ComposedPath, sample_pixels
@@ -46,6 +50,21 @@ def restated(oracle, case):
     s = ME.scene()
     path = path_of(s, case)
     return [(seed, pixels) + sample_pixels(path, oracle, seed, pixels, W, H) for seed, pixels in draws(case)]
+
+
+@functools.lru_cache(maxsize=None)
+def spreads(oracle, case):
+    """The f32 spreads (tests/f32_spread.py) of the case's first 150 clean samples, computed once beside restated() for the CPU and
+    the GPU leg: ([spreads per seed, NaN where there is none], CPU seconds)."""
+    return S.spreads_of_draws(path_of(ME.scene(), case), oracle, restated(oracle, case), W, H)
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_the_spreads_of_the_restatement(rpt, oracle, case):
+    """The conditions of the comparison with spreads, on the restatement alone: at least 100 clean samples of the case have a spread,
+    and at most 5 % of them a tolerance above 1e-3."""
+    spr, seconds = spreads(oracle, case)
+    S.case_conditions("case %s" % case, restated(oracle, case), spr, seconds)
 
 
 @pytest.mark.parametrize("case", sorted(CASES))

@@ -35,12 +35,18 @@ The last one needs a scene whose eps is a visible fraction of the mesh: a light 
 through the mask's holes from somewhere else, and the fault is worth about eps / distance.  At the scene's own eps = 0.005 against
 an icosphere of radius 0.6 it moved 0 to 3 clean samples over every case, density 2.5 to 12 and four to twelve bounces; at 0.02 it
 moves 11, at 0.05 21 (27 at density 12).  (On the device the question does not arise in this form: path_shade_medium calls
-nee_query<false>, whose scatter_pos is the point itself whatever normal it is handed.)"""
+nee_query<false>, whose scatter_pos is the point itself whatever normal it is handed.)
+
+The spreads (tests/f32_spread.py): spreads() computes each case's once, for the CPU conditions here and for the GPU comparison;
+two subtle faults — sigma_t x 1.02, the phase function at g + 0.01 — pass REL_CLEAN on every clean sample and fail the samples' own
+tolerances (34 of 63 and 15 of 50 clean samples on the icosphere)."""
 import functools
 
 import numpy as np
 import pytest
 
+import f32_spread as S
+import media_sdf_f64 as MS
 from mesh_compose_f64 import ComposedMeshDescScene, ComposedPath, sample_pixels
 from mesh_media_f64 import MediaMeshDescScene, MediaMeshPath
 from test_gpu_mesh_compose_f64 import CASES, GRID, H, W, inputs
@@ -96,6 +102,57 @@ def restated(oracle, case):
     s = scene()
     path = MediaMeshPath(MediaMeshDescScene(s.describe(), s, media={0: MEDIA[case]}, **inputs(s, case)))
     return [(seed, pixels) + sample_pixels(path, oracle, seed, pixels, W, H) for seed, pixels in draws(case)]
+
+
+def path_of(case, medium=None):
+    s = scene()
+    return MediaMeshPath(MediaMeshDescScene(s.describe(), s, media={0: MEDIA[case] if medium is None else medium}, **inputs(s, case)))
+
+
+@functools.lru_cache(maxsize=None)
+def spreads(oracle, case):
+    """The f32 spreads (tests/f32_spread.py) of the case's first 150 clean samples, computed once beside restated() for the CPU and
+    the GPU leg: ([spreads per seed, NaN where there is none], CPU seconds)."""
+    return S.spreads_of_draws(path_of(case), oracle, restated(oracle, case), W, H)
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_the_spreads_of_the_restatement(rpt, oracle, case):
+    """The conditions of the comparison with spreads, on the restatement alone: at least 100 clean samples of the case have a spread,
+    and at most 5 % of them a tolerance above 1e-3."""
+    spr, seconds = spreads(oracle, case)
+    S.case_conditions("case %s" % case, restated(oracle, case), spr, seconds)
+
+
+THIN_AMBER = dict(AMBER, density=0.75)
+DENSE_FOG = dict(fog(0.6), density=6.0)
+
+
+def test_the_spreads_see_sigma_t_two_percent_off(rpt, oracle):
+    """An ABSORB medium whose density is 1.02 times the scene's, rounded to f32, as a device's samples, over the grid's pixels on the icosphere under case A's
+    inputs.
+    The medium is AMBER at density 0.75: a path crosses the icosphere (radius 0.6) at most three times in four bounces, so the
+    fault is worth at most 3 * 1.2 * 0.7 * 0.75 * 0.02 = 3.8 % and no clean sample leaves REL_CLEAN — the comparison without spreads
+    passes it; at least 10 leave their own tolerance."""
+    from test_gpu_mesh_compose_f64 import object_pixels
+    bad = dict(THIN_AMBER, density=THIN_AMBER["density"] * 1.02)
+    good = path_of("A", THIN_AMBER)
+    S.teeth_on("sigma_t x 1.02 (case A, ABSORB at density 0.75)", good, path_of("A", bad), oracle, [(7, object_pixels(good.scene))], W, H)
+
+
+def test_the_spreads_see_the_phase_function_s_g_off_by_a_hundredth(rpt, oracle, monkeypatch):
+    """phase_hg evaluated at g + 0.01 (the sampler keeps g, so the paths stay where they are), rounded to f32, as a device's samples,
+    over the grid's pixels on the icosphere under case D's inputs and SCATTER at density 6, g = 0.6 (dense, so that many paths scatter; the mask's holes and the
+    sampled sky, because a light estimate from inside a closed mesh is always shadowed by it and the phase function's value then
+    reaches no pixel): within REL_CLEAN everywhere, beyond their own tolerance on at least 10 clean samples."""
+    from mesh_compose_f64 import sample_pixels as sp
+    from test_gpu_mesh_compose_f64 import object_pixels
+    good = path_of("D", DENSE_FOG)
+    entries = [(seed, pixels) + sp(good, oracle, seed, pixels, W, H) for seed, pixels in [(7, object_pixels(good.scene))]]
+    spr, _ = S.spreads_of_draws(good, oracle, entries, W, H, count=None)
+    plain = MS.phase_hg
+    monkeypatch.setattr(MS, "phase_hg", lambda c, g: plain(c, g + 0.01))
+    S.teeth("HG phase g + 0.01 (case D, density 6)", entries, spr, [sp(good, oracle, seed, pixels, W, H) for seed, pixels, _, _ in entries])
 
 
 @pytest.mark.parametrize("case", ["A", "D", "H"])
