@@ -20,7 +20,14 @@ bit-identical twin) against the restatement, never on the device.  Statements ho
   median                the median z over the clean samples with a non-zero spread <= Z_MEDIAN
   bias                  the signed mean relative difference over the clean samples is within BIAS_SIGMAS of its own standard
                         errors + BIAS_FLOOR, as f64_compare.Bounds states it for frames
-Only samples that have a spread (not NaN) take part; the others are held to REL_CLEAN by the caller as before."""
+Only samples that have a spread (not NaN) take part; the others are held to REL_CLEAN by the caller as before.
+
+Files that pass spreads to Tally.add: test_gpu_path_f64 (the small scenes), test_gpu_mesh_compose_f64, test_gpu_mesh_material_map_f64,
+test_gpu_mesh_emission_map_f64, test_gpu_mesh_media_f64, test_gpu_radiance_f64, and the single-feature files test_gpu_mesh_f64,
+test_gpu_mesh_smooth_f64, test_gpu_mesh_light_f64, test_gpu_mesh_texture_f64, test_gpu_mesh_env_f64, test_gpu_mesh_cutout_f64,
+test_gpu_mesh_normal_map_f64 (through Cases below) and test_gpu_mesh_frames_f64 (through test_mesh_frames_f64's noisy_samples, at
+64 x 48).  Each holds its CPU-side conditions and plants a subtle fault (teeth) without a GPU; the cutout file has no teeth of its
+own and says why."""
 import time
 
 import numpy as np
@@ -157,6 +164,42 @@ def spreads_of_draws(path, oracle, entries, w, h, count=MIN_CLEAN):
         s.setflags(write=False)
         out.append(s)
     return out, seconds
+
+
+class Cases:
+    """A file's cases, each restated and given its spreads once for the CPU and the GPU leg.  path_of(case) -> the restatement as a
+    path for mesh_compose_f64.sample_pixels (pt_f64.Path(scene) for the files that restate through pt_f64.sample_many: the same
+    sample from the same stream); draws_of(case) -> [(seed, pixels)], the file's own draws.  Nobody writes to what comes back."""
+
+    def __init__(self, path_of, draws_of, w=64, h=48):
+        self.path_of, self.draws_of, self.w, self.h = path_of, draws_of, w, h
+        self._path, self._restated, self._spreads = {}, {}, {}
+
+    def path(self, case):
+        if case not in self._path:
+            self._path[case] = self.path_of(case)
+        return self._path[case]
+
+    def restated(self, oracle, case):
+        """[(seed, pixels, radiance, margins)] over the case's draws."""
+        from mesh_compose_f64 import sample_pixels
+        if case not in self._restated:
+            entries = [(seed, pixels) + sample_pixels(self.path(case), oracle, seed, pixels, self.w, self.h) for seed, pixels in self.draws_of(case)]
+            for _, _, radiance, margins in entries:
+                radiance.setflags(write=False)
+                margins.setflags(write=False)
+            self._restated[case] = entries
+        return self._restated[case]
+
+    def spreads(self, oracle, case):
+        """([spreads per entry, NaN where there is none], CPU seconds): of the case's first MIN_CLEAN clean samples."""
+        if case not in self._spreads:
+            self._spreads[case] = spreads_of_draws(self.path(case), oracle, self.restated(oracle, case), self.w, self.h)
+        return self._spreads[case]
+
+    def conditions(self, oracle, what, case):
+        spreads, seconds = self.spreads(oracle, case)
+        case_conditions(what, self.restated(oracle, case), spreads, seconds)
 
 
 def case_conditions(what, entries, spreads, seconds=None):

@@ -19,15 +19,21 @@ Three planted faults, each by a keyword argument, each in one place:
   weight_off_by_one         v = 1 / f, and 1 at f = 0 (invisible in a one-sample launch at a frame so late that 1 / f and 1 / (f + 1)
                             are REL_CLEAN apart or less: the comparison scales the device's pixel by f + 1)
 tests/test_mesh_frames_f64.py (CPU) counts what each moves; tests/test_gpu_mesh_frames_f64.py holds the device to frame_f64.
+A fourth, subtle one: weight_late_from = F takes v = 1 / (f + 2) from frame F on (a running mean one frame off at high counts, a
+part in a thousand at f = 1000), which only the samples' own f32 tolerances see (tests/f32_spread.py).
+
+Under pt_f64's noise mode the blend carries what the device rounds in f32: the weight 1 / (f + 1), each of the two products and the
+sum.  With the mode off every value keeps its bits.
 
 Measured on the CPU: 1.5 ms per sample of the emission-mapped restatement (cases A .. H), 1.2 ms per sample of the flat one."""
 import numpy as np
 
+import pt_f64 as P
 from mesh_compose_f64 import sample_pixels
 
 
 def frame_f64(path, oracle, seed, pixels, w, h, frames_done, n, acc=None, sample_frame=None,
-              frame_ignored=False, key_without_frames_done=False, weight_off_by_one=False):
+              frame_ignored=False, key_without_frames_done=False, weight_off_by_one=False, weight_late_from=None):
     """A launch of `n` samples on top of `frames_done` earlier frames, for `pixels` [(col, row)] ->
     (mean [p, 4], margins [p], samples [p, n, 3]).
 
@@ -47,8 +53,10 @@ def frame_f64(path, oracle, seed, pixels, w, h, frames_done, n, acc=None, sample
         margins = np.minimum(margins, marg)
         if weight_off_by_one:
             v = 1.0 / frame if frame else 1.0
+        elif weight_late_from is not None and frame >= weight_late_from:
+            v = 1.0 / (frame + 2)
         else:
-            v = 1.0 / (frame + 1)
+            v = P.noisy(1.0 / (frame + 1))
         c = np.concatenate([np.where(np.isfinite(rad).all(axis=1, keepdims=True), rad, 0.0), np.ones((len(pixels), 1))], axis=1)
-        mean = (1.0 - v) * mean + c * v
+        mean = P.noisy_array(P.noisy_array((1.0 - v) * mean) + P.noisy_array(c * v))
     return mean, margins, samples

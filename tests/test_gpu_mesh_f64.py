@@ -3,16 +3,28 @@
 any_hit, with the normal normalize(cross(e1, e2)) and the triangle's full patch, and records the branch margins of det, u, v, u + v,
 t, the point check and t against the running distance.  One-sample renders at several seeds are compared sample by sample with
 test_path_f64's TAU / REL_CLEAN / NEAR_TIE_MAX, as tests/test_gpu_path_f64.py does for the other classes (needs an MI355X).  The
-oracle only supplies the random draws (rng_f32); it knows nothing of meshes."""
+oracle only supplies the random draws (rng_f32); it knows nothing of meshes.
+
+The first 150 clean samples of each scene are also held to their own f32 tolerance (tests/f32_spread.py, through Tally.add's
+spreads), computed once per scene (CASES) for the CPU and the GPU leg; this file has no tolerance of its own.  The flat normal,
+which the device computes at the hit in f32, carries noise term by term (MeshDescScene.flat_normal).  On the CPU
+(test_the_spreads_of_the_restatement): scene 0 median spread 3.3e-7, largest 2.8e-5, none with a tolerance above 1e-3, 6.8 s of CPU
+time; scene 1 median 4.7e-7, 0.67 % above 1e-3 (one grazing sample of spread 0.99, capped at REL_CLEAN), 4.3 s.  Teeth
+(test_the_spreads_see_a_tilted_normal): the flat normal tilted by 0.05 % of e1's direction leaves REL_CLEAN on no clean sample of
+scene 0 and its own tolerance on 55; the 1 % first thought of is no subtle fault on a mirror-like icosphere and a clearcoat torus
+(27 clean samples beyond REL_CLEAN; 0.2 % still 2).  On an MI355X: largest z 2.0 (scene 0) and 1.66 (scene 1) next to
+Z_MAX = 8.3, median z 0.29 and 0.33 next to Z_MEDIAN = 1.4, 7.0 s of wall time for the GPU test.  Measurements, not
+bounds."""
 import numpy as np
 import pytest
 
+import f32_spread as S
 import pt_f64 as P
 from kernel_census import mesh_kernel_of
 from test_gpu_path_f64 import Tally, _one_sample
 from test_path_f64 import NEAR_TIE_MAX, TAU
 
-pytestmark = pytest.mark.gpu
+W, H = 64, 48
 
 
 @pytest.fixture(scope="module")
@@ -37,6 +49,18 @@ class MeshDescScene(P.DescScene):
         lo = self.ta + np.minimum(np.minimum(0.0, self.e1), self.e2)
         hi = self.ta + np.maximum(np.maximum(0.0, self.e1), self.e2)
         self.lo, self.hi = lo, hi
+        self.normal_tilt = 0.0                                        # a planted fault: the flat normal tilted by this much of e1's direction
+
+    def flat_normal(self, k):
+        """normalize(cross(e1, e2)) of triangle k's row, which the device computes at the hit in f32: under pt_f64's noise mode every
+        product and every difference of the cross carries its own noise (the normalisation carries its own through P.normalize)."""
+        g = np.cross(self.e1[k], self.e2[k])
+        if P._NOISE is not None:
+            a, b, N = self.e1[k], self.e2[k], P.noisy
+            g = np.array([N(N(a[1] * b[2]) - N(a[2] * b[1])), N(N(a[2] * b[0]) - N(a[0] * b[2])), N(N(a[0] * b[1]) - N(a[1] * b[0]))])
+        if self.normal_tilt:
+            g = g + self.normal_tilt * np.sqrt((g * g).sum() / (self.e1[k] * self.e1[k]).sum()) * self.e1[k]
+        return P.normalize(tuple(float(x) for x in g))
 
     def _triangles(self, o, d, M):
         """include/rpt.h's triangle test over every triangle in float64 -> (hit mask, t); records each triangle's flip margin: the
@@ -138,8 +162,7 @@ class MeshDescScene(P.DescScene):
             k = int(idx[order[0]])                                     # least t, lowest index on ties
             t = float(tt[k])
             if t < dist:
-                n = P.normalize(tuple(float(x) for x in np.cross(self.e1[k], self.e2[k])))
-                st.hit_dist, st.normal = t, n
+                st.hit_dist, st.normal = t, self.flat_normal(k)
                 self.patch(int(self.tri_mat[k]), d, P.add(o, P.scale(t, d)), st.material, mut, M)
                 hit, dist = True, t
         if self.sample_lights(o, d, st, ls, mut, M):
@@ -174,24 +197,77 @@ def _scenes():
     return [("spheres, plane, meshes", a), ("plane and meshes, any_hit with max_dist", b)]
 
 
-def test_mesh_renders_against_the_restatement(rpt, oracle, torch_cuda, monkeypatch):
-    w, h = 64, 48
+def _draws():
+    """[(k, what, scene, seed, pixels)]: 200 random pixels x 3 seeds x 2 scenes, 64 x 48, from one generator."""
     rng = np.random.default_rng(35)
+    out = []
+    for k, (what, s) in enumerate(_scenes()):
+        for seed in (1, 2, 3):
+            out.append((k, what, s, 50 + 10 * k + seed, list(zip(rng.integers(0, W, 200).tolist(), rng.integers(0, H, 200).tolist()))))
+    return out
+
+
+def _path(k):
+    s = _scenes()[k][1]
+    return P.Path(MeshDescScene(s.describe(), s))
+
+
+# per scene: the restated draws and the f32 spreads of their first 150 clean samples, once for the CPU and the GPU leg
+CASES = S.Cases(_path, lambda k: [(seed, pixels) for j, _, _, seed, pixels in _draws() if j == k], W, H)
+
+
+@pytest.mark.gpu
+def test_mesh_renders_against_the_restatement(rpt, oracle, torch_cuda, monkeypatch):
     t = Tally(TAU, NEAR_TIE_MAX)
     for k, (what, s) in enumerate(_scenes()):
-        ref = MeshDescScene(s.describe(), s)
-        for seed in (1, 2, 3):
-            pixels = list(zip(rng.integers(0, w, 200).tolist(), rng.integers(0, h, 200).tolist()))
-            frame, choice = _one_sample(rpt, torch_cuda, s, w, h, 50 + 10 * k + seed, False, monkeypatch)
+        spreads, seconds = CASES.spreads(oracle, k)
+        print("%s: the spreads took %.2f s of CPU time" % (what, seconds))
+        per = Tally(TAU, NEAR_TIE_MAX)
+        for (seed, pixels, restated, margins), spread in zip(CASES.restated(oracle, k), spreads):
+            frame, choice = _one_sample(rpt, torch_cuda, s, W, H, seed, False, monkeypatch)
             assert choice & (1 << 25), "the mesh kernel ran"
             assert mesh_kernel_of(choice) == "mesh_regen_kernel"
             t.ran.add(mesh_kernel_of(choice))
-            restated, margins, _ = P.sample_many(ref, oracle, 50 + 10 * k + seed, [(c, r, 0) for c, r in pixels], w, h)
-            t.add("%s (seed %d)" % (what, 50 + 10 * k + seed), frame, restated, margins, pixels)
+            t.add("%s (seed %d)" % (what, seed), frame, restated, margins, pixels, spreads=spread)
+            per.add("%s (seed %d)" % (what, seed), frame, restated, margins, pixels, spreads=spread)
+        print("%s: %s" % (what, per.held.line()))
     t.check("mesh scenes")
     assert t.n == 2 * 3 * 200
 
 
+def test_the_restated_draws_are_sample_many_s(rpt, oracle):
+    """The cached restatement (mesh_compose_f64.sample_pixels over pt_f64.Path) gives pt_f64.sample_many's samples and margins bit
+    for bit, as this file compared them before, and the generator's draws are the ones it always made."""
+    rng = np.random.default_rng(35)
+    for k, (what, s) in enumerate(_scenes()):
+        for j, (seed, pixels, restated, margins) in enumerate(CASES.restated(oracle, k)):
+            assert pixels == list(zip(rng.integers(0, W, 200).tolist(), rng.integers(0, H, 200).tolist())) and seed == 50 + 10 * k + j + 1
+            if j == 0:
+                want, marg, _ = P.sample_many(CASES.path(k).scene, oracle, seed, [(c, r, 0) for c, r in pixels], W, H)
+                assert np.array_equal(want, restated, equal_nan=True) and np.array_equal(marg, margins)
+
+
+@pytest.mark.parametrize("k", (0, 1))
+def test_the_spreads_of_the_restatement(rpt, oracle, k):
+    """The conditions of the comparison with spreads, on the restatement alone: at least 100 clean samples of the scene have a
+    spread, and at most 5 % of them a tolerance above 1e-3."""
+    CASES.conditions(oracle, _scenes()[k][0], k)
+
+
+def test_the_spreads_see_a_tilted_normal(rpt, oracle):
+    """The flat normal tilted by 0.05 % of e1's direction, rounded to f32, as a device's samples over the first scene's draws: no
+    clean sample leaves REL_CLEAN, at least 10 leave their own tolerance.  (On this scene's mirror-like icosphere and clearcoat torus
+    a tilt of 1 % is no subtle fault: it takes 27 clean samples beyond REL_CLEAN, one of 0.2 % still 2.)"""
+    from mesh_compose_f64 import sample_pixels
+    s = _scenes()[0][1]
+    faulty = MeshDescScene(s.describe(), s)
+    faulty.normal_tilt = 0.0005
+    entries, (spreads, _) = CASES.restated(oracle, 0), CASES.spreads(oracle, 0)
+    S.teeth("the flat normal tilted by 0.05 %% of e1 (%s)" % _scenes()[0][0], entries, spreads,
+            [sample_pixels(P.Path(faulty), oracle, seed, pixels, W, H) for seed, pixels, _, _ in entries])
+
+
+@pytest.mark.gpu
 def test_the_restatement_sees_the_triangles(rpt, oracle):
     """A wrong normal or material in the restatement must show: flipping the normal or giving the triangles another material moves
     the restated samples far beyond REL_CLEAN (so the comparison above would catch those faults on the device)."""

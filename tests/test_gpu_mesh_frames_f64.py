@@ -16,8 +16,8 @@ test asserts rpt_debug_mesh_form and, for forms 0 .. 11, kernel_census.mesh_kern
     in 1, 5, 1000 a one-sample render into a zeroed buffer with buf.frames = k.  The device writes rad * v, v = f32(1 / (k + 1)), so
     the sample is (k + 1) * rgb — two f32 roundings, far below REL_CLEAN — and it is compared through Tally with the restated sample
     of frame k and its margin; alpha is the f32 1 / (k + 1) exactly ((1 - v) * 0 + 1 * v).  At k = 1000 this test cannot see a wrong
-    WEIGHT, only a wrong stream: 1 / 1000 and 1 / 1001 are 1e-3 apart, within REL_CLEAN, but for alpha.  k = 1, k = 5 and (c) see
-    the weight.
+    WEIGHT through REL_CLEAN, only a wrong stream: 1 / 1000 and 1 / 1001 are 1e-3 apart, within REL_CLEAN, but for alpha.  At
+    64 x 48 it sees it through the samples' own tolerances (below); k = 1, k = 5 and (c) see the weight either way.
 (b) test_one_launch_is_its_one_sample_launches, all 28 forms, both sizes: render_n(buf, n) in one launch against n launches of
     render_n(buf2, 1) from the same Tracer, as uint32 — n = 2, 5, 16 from frames_done = 0, and n = 5 on top of 3 earlier frames.
     This is the design's own statement ("which lane renders a sample never changes it ... what must not change is the ORDER",
@@ -32,6 +32,9 @@ test asserts rpt_debug_mesh_form and, for forms 0 .. 11, kernel_census.mesh_kern
 (c) test_a_two_sample_launch_against_the_restatement, the cases of (a): render_n(buf, 2) into a fresh buffer, and the same on top of
     one earlier frame whose device pixels are frame_f64's starting accumulator, against frame_f64's mean through Tally with the
     pixel's margin the smaller of its samples'.  Alpha is exactly 1 from a fresh buffer.
+(e) test_a_two_sample_launch_at_depth, the cases of (a) at 64 x 48: render_n(buf, 2) into a zeroed buffer whose .frames is 1000
+    (998 for case G: test_mesh_frames_f64.deep_of says why), against frame_f64's mean, both times frames_done + 2, through the
+    pixels' own tolerances: the weights of the launch's first and second sample (s_weight[s], s = 0 and s > 0) at high counts.
 (d) test_the_heaviest_form_does_not_depend_on_the_dispatch: test_gpu_mesh's four set_dispatch settings and the resident render on
     case H with both maps (form 27) at 50 x 37 x 6 samples, bit for bit.
 
@@ -43,7 +46,17 @@ Measured on an MI355X (written down, not asserted).  Largest clean relative dist
 64 x 48, frame 1000; every other comparison below 2e-3, most near 3e-5), (c) 1.5e-3 (case G, 64 x 48, from a fresh buffer).  Near-tie
 shares per Tally line equal to the CPU counts, 1 to 23 of 200.  Wall time per test: (a) 0.28 to 0.53 s and (c) 0.19 to 0.25 s, the
 restatement of its 600 and 400 new samples included (this file run alone; that host restates a sample in about 0.5 ms); (b) 0.01
-to 0.03 s; (d) 0.02 s; the file's 94 tests 13.5 s."""
+to 0.03 s; (d) 0.02 s; the file's 94 tests 13.5 s.
+
+The comparisons of (a), (c) and (e) at 64 x 48 are also held to each sample's or pixel's own f32 tolerance (tests/f32_spread.py,
+through Tally.add's spreads): the first 150 clean samples of a frame are restated in eight noisy runs once
+(test_mesh_frames_f64.noisy_samples, shared by every comparison that needs the frame, CPU or GPU), a launch's spread comes from those
+runs through frame_f64's blend, which carries noise on the weight, both products and the sum.  The 50 x 37 comparisons stay at
+REL_CLEAN: their forms and blends are the same, and their launches are held to the one-sample ones bit for bit by (b).  Conditions,
+teeth (v = 1 / (f + 2) from frame 500 on: within REL_CLEAN on every clean sample of case A's frame 1000, beyond their own tolerance
+on 94 of 150) and the blend's bits with the mode off are in tests/test_mesh_frames_f64.py.  Measured on an MI355X, over the 27 + 18 +
+9 comparisons with spreads: largest z 2.51 (the flat case, two samples on 1000 earlier frames), next to Z_MAX = 8.3; median z 0.13 to 0.45, next to Z_MEDIAN = 1.4; wall
+time per test with spreads (a) 3.1 to 4.0 s, (c) 2.0 to 2.5 s, (e) 1.0 to 2.6 s, the noisy runs included.  Measurements, not bounds."""
 import ctypes as C
 
 import numpy as np
@@ -63,6 +76,7 @@ from test_path_f64 import NEAR_TIE_MAX, TAU
 pytestmark = pytest.mark.gpu
 
 SIZES = TF.SIZES
+SPREAD_SIZE = SIZES[0]                                               # the size whose comparisons are also held to their own f32 tolerances
 SIZE_IDS = ["%dx%d" % s for s in SIZES]
 LATER = (1, 5, 1000)
 assert set(LATER) | {0, 1, 2} <= set(TF.FRAMES), "every frame compared here has its near ties counted on the CPU"
@@ -169,7 +183,7 @@ def test_a_later_frame_is_that_frame_s_sample(rpt, oracle, torch_cuda, case, siz
             restated, margins = TF.restated(oracle, case, size, k)
             tally.ran.add("form %d" % form)
             tally.add("case %s, %d x %d, frame %d (form %d)" % ((case,) + size + (k, form)), frame.astype(np.float64) * float(k + 1),
-                      restated, margins, pixels)
+                      restated, margins, pixels, spreads=TF.sample_spreads(oracle, case, size, k) if size == SPREAD_SIZE else None)
             tally.check("case %s, %d x %d, frame %d" % ((case,) + size + (k,)))
             assert tally.n == TF.N and tally.near == TF.COUNTS[(case, size[0])][0][TF.FRAMES.index(k)]
     finally:
@@ -226,12 +240,40 @@ def test_a_two_sample_launch_against_the_restatement(rpt, oracle, torch_cuda, ca
             tally = Tally(TAU, NEAR_TIE_MAX)
             tally.ran.add("form %d" % form)
             what = "case %s, %d x %d, two samples on %d earlier" % ((case,) + size + (frames_done,))
-            tally.add("%s (form %d)" % (what, form), frame, mean[:, :3], margins, pixels)
+            tally.add("%s (form %d)" % (what, form), frame, mean[:, :3], margins, pixels,
+                      spreads=TF.launch_spreads(oracle, case, size, frames_done, 2, acc=acc) if size == SPREAD_SIZE else None)
             tally.check(what)
             assert tally.n == TF.N and tally.near == TF.COUNTS[(case, size[0])][2][launch]
             assert np.abs(np.array([frame[r, c, 3] for c, r in pixels], dtype=np.float64) - mean[:, 3]).max() < 1e-6
     finally:
         t.close()
+
+
+# ---- (e) a two-sample launch at depth ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", TF.ALL_CASES)
+def test_a_two_sample_launch_at_depth(rpt, oracle, torch_cuda, case):
+    """render_n(buf, 2) into a zeroed buffer whose .frames is about 1000 (TF.deep_of), 64 x 48, against frame_f64's mean, both
+    times frames_done + 2 — the sum of the two samples, but for a part in a thousand — and held to the pixels' own tolerances: a
+    stale or off-by-one weight of the launch's first or second sample is a part in a thousand of one of them."""
+    size, deep = SPREAD_SIZE, TF.deep_of(case)
+    pixels = TF.draws(case)[size]
+    t, form = case_tracer(rpt, case)
+    try:
+        buf, frame = render(rpt, torch_cuda, t, size, 2, frames=deep)
+        assert_form(rpt, t, form)
+        assert buf.frames == deep + 2
+    finally:
+        t.close()
+    scale = float(deep + 2)
+    mean, margins, _ = TF.launch_f64(oracle, case, size, deep, 2)
+    tally = Tally(TAU, NEAR_TIE_MAX)
+    tally.ran.add("form %d" % form)
+    what = "case %s, %d x %d, two samples on %d earlier" % ((case,) + size + (deep,))
+    tally.add("%s (form %d)" % (what, form), frame.astype(np.float64) * scale, mean[:, :3] * scale, margins, pixels,
+              spreads=TF.launch_spreads(oracle, case, size, deep, 2, scale=scale))
+    tally.check(what)
+    assert tally.n == TF.N and tally.near == TF.DEEP_NEAR[case]
+    assert np.abs(np.array([frame[r, c, 3] for c, r in pixels], dtype=np.float64) - mean[:, 3]).max() < 1e-9
 
 
 # ---- (d) dispatch independence of the heaviest form --------------------------------------------------------------------------------------

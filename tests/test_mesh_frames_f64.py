@@ -46,14 +46,26 @@ A device with one of them would fail the GPU comparison.
 The other side (test_one_sample_from_a_fresh_buffer_is_the_sample): frame_f64(frames_done=0, n=1) is sample_pixels' sample and margin
 bit for bit with alpha exactly 1, and a launch of three samples is a launch of one and a launch of two on top of it, bit for bit.
 
-The tolerances are test_path_f64's TAU / REL_CLEAN / NEAR_TIE_MAX: this file has none of its own.  Measured on the CPU: 1.5 ms per
+The spreads (tests/f32_spread.py), at 64 x 48.  noisy_samples restates the first 150 clean samples of a frame in eight noisy runs,
+once; sample_spreads and launch_spreads turn them into the tolerances the GPU file's comparisons (a), (c) and (e) use.
+test_the_spreads_of_the_restatement holds the conditions per case and comparison — at least 100 clean samples or pixels with a
+spread (139 to 150), at most 5 % of them with a tolerance above 1e-3 (at most 2.1 %: case G, whose frame 1 has two samples of spread
+0.3 and 0.6) — and the near-tie cap of the launch at depth (DEEP_NEAR; case G launches from 998, deep_of).  The noisy runs of a
+case's six frames take 10 to 18 s of CPU time.  test_the_spreads_see_a_weight_one_frame_off_at_depth: v = 1 / (f + 2) from frame
+500 on moves case A's frame 1000 by a part in a thousand — no clean sample beyond REL_CLEAN, 94 of 150 beyond their own tolerance.
+test_the_blend_keeps_its_bits_with_the_noise_mode_off: frame_f64's blend is the plain float64 running mean bit for bit, and moves
+under the noise.
+
+The tolerances are test_path_f64's TAU / REL_CLEAN / NEAR_TIE_MAX (and Z_MAX / Z_MEDIAN): this file has none of its own.  Measured on the CPU: 1.5 ms per
 sample of cases A .. H, 1.2 ms of the flat case; one size of a case, 1 200 samples, takes 1.5 to 2.2 s, a mutation's passes over the
 grid 1.7 to 2.4 s, this file 37 s."""
 import functools
+import time
 
 import numpy as np
 import pytest
 
+import f32_spread as S
 import mesh_emap_f64 as ME
 import mesh_mmap_f64 as MM
 import pt_f64 as P
@@ -92,6 +104,8 @@ COUNTS = {
     (FLAT, 64): ((6, 3, 2, 3, 3, 4), (110, 118, 113, 115, 105, 113), (8, 5)),
     (FLAT, 50): ((1, 5, 2, 3, 2, 2), (102, 105, 100, 101, 102, 99), (6, 7)),
 }
+# case -> pixels of the two-sample launch at depth with either sample at or below TAU; test_the_spreads_of_the_restatement prints them
+DEEP_NEAR = {"A": 14, "B": 11, "C": 16, "D": 11, "E": 9, "F": 14, "G": 18, "H": 9, FLAT: 5}
 # fault -> (case, frames_done, clean pixels moved beyond REL_CLEAN); test_the_restatement_sees_each_fault prints them
 MOVED = {"frame_ignored": ("A", 0, 300), "weight_off_by_one": ("A", 0, 300), "key_without_frames_done": ("B", 1, 273)}
 
@@ -141,6 +155,62 @@ def launch_f64(oracle, case, size, frames_done, n, acc=None):
     w, h = size
     return frame_f64(None, oracle, SEED, draws(case)[size], w, h, frames_done, n, acc=acc,
                      sample_frame=lambda f: restated(oracle, case, size, f))
+
+
+# ---- the samples' and the launches' own f32 tolerances (tests/f32_spread.py), at 64 x 48 ------------------------------------------------
+DEEP = 1000                                                          # frames_done of the two-sample launch at depth
+
+
+def deep_of(case):
+    """frames_done of the case's two-sample launch at depth: 1000, but 998 for G, 26 of whose 200 pixels have frame 1000 or 1001 at
+    or below TAU (the cap is 24; 25 from 999, 22 from 1001, 18 from 998).  Its mean over a zeroed accumulator times frames_done + 2
+    is the sum of the two samples, but for a part in a thousand."""
+    return 998 if case == "G" else DEEP
+
+
+@functools.lru_cache(maxsize=None)
+def noisy_samples(oracle, case, size, frame):
+    """The first MIN_CLEAN clean samples of restated(oracle, case, size, frame) restated again in f32_spread.RUNS noisy runs, once
+    for every comparison that needs them, CPU or GPU -> (their indices, radiance [RUNS, n, 3] blended as black, CPU seconds)."""
+    w, h = size
+    idx = S.first_clean(restated(oracle, case, size, frame)[1], S.MIN_CLEAN)
+    sf = sample_frame_of(oracle, case, SEED, [draws(case)[size][i] for i in idx], w, h)
+    t0 = time.process_time()
+    runs = []
+    for run in range(S.RUNS):
+        with P.perturbed(0, run):
+            runs.append(S._radiance(sf(frame)[0]))
+    out = np.stack(runs)
+    out.setflags(write=False)
+    return idx, out, time.process_time() - t0
+
+
+def sample_spreads(oracle, case, size, frame):
+    """The spreads of the frame's first MIN_CLEAN clean samples, NaN elsewhere: [N]."""
+    idx, runs, _ = noisy_samples(oracle, case, size, frame)
+    plain = S._radiance(restated(oracle, case, size, frame)[0])[idx]
+    return S.subset_spreads(N, idx, np.max([rel_distance(plain, r) for r in runs], axis=0))
+
+
+def launch_spreads(oracle, case, size, frames_done, n, acc=None, scale=1.0):
+    """The spreads of a launch's means (times `scale`), for the pixels every one of whose samples has noisy runs, NaN elsewhere: the
+    noisy samples of each run through frame_f64's noisy blend, against launch_f64's plain mean.  acc: the accumulator before the
+    launch, as launch_f64 takes it; it is an input and carries no noise."""
+    w, h = size
+    frames = range(frames_done, frames_done + n)
+    idx = functools.reduce(np.intersect1d, [noisy_samples(oracle, case, size, f)[0] for f in frames])
+    at = {f: np.searchsorted(noisy_samples(oracle, case, size, f)[0], idx) for f in frames}
+    pixels = [draws(case)[size][i] for i in idx]
+    sub = None if acc is None else np.asarray(acc, np.float64)[idx]
+    plain = launch_f64(oracle, case, size, frames_done, n, acc=acc)[0][idx, :3] * scale
+    out = np.zeros(len(idx))
+    for run in range(S.RUNS):
+        with P.perturbed(0, run):
+            P.noise_begin(SEED, frames_done, n)
+            sf = lambda f: (noisy_samples(oracle, case, size, f)[1][run][at[f]], restated(oracle, case, size, f)[1][idx])      # noqa: E731
+            mean = frame_f64(None, oracle, SEED, pixels, w, h, frames_done, n, acc=sub, sample_frame=sf)[0]
+        out = np.maximum(out, rel_distance(plain, mean[:, :3] * scale))
+    return S.subset_spreads(N, idx, out)
 
 
 @pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d" % s)
@@ -204,3 +274,67 @@ def test_one_sample_from_a_fresh_buffer_is_the_sample(rpt, oracle, case):
     rest = frame_f64(path, oracle, 9, pixels, 64, 48, 1, 2, acc=mean, sample_frame=sf)
     assert np.array_equal(whole[0], rest[0]) and np.array_equal(whole[1], np.minimum(marg, rest[1]))
     assert np.array_equal(whole[2][:, 1:], rest[2]) and not np.array_equal(whole[2][:, 0], whole[2][:, 1], equal_nan=True)
+
+
+# ---- the spreads: conditions, teeth, and the blend's bits ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ALL_CASES)
+def test_the_spreads_of_the_restatement(rpt, oracle, case):
+    """The conditions of the GPU file's comparisons with spreads (64 x 48), on the restatement alone: in each of them at least 100
+    clean samples or pixels have a spread and at most 5 % of those a tolerance above 1e-3 — the later frames of (a), the two
+    launches of (c) (the second on top of the restated first frame, where the device test has the device's) and the launch at
+    depth, whose near ties stay under the cap as well (DEEP_NEAR pins the count)."""
+    size = SIZES[0]
+    seconds = 0.0
+    for k in (1, 5, DEEP):
+        S.case_conditions("case %s, frame %d" % (case, k), [(None, None, None, restated(oracle, case, size, k)[1])], [sample_spreads(oracle, case, size, k)])
+    for frames_done, _ in LAUNCHES:
+        acc = launch_f64(oracle, case, size, 0, frames_done)[0] if frames_done else None
+        _, margins, _ = launch_f64(oracle, case, size, frames_done, 2, acc=acc)
+        S.case_conditions("case %s, two samples on %d earlier" % (case, frames_done), [(None, None, None, margins)],
+                          [launch_spreads(oracle, case, size, frames_done, 2, acc=acc)])
+    deep = deep_of(case)
+    _, margins, _ = launch_f64(oracle, case, size, deep, 2)
+    near = int((margins <= TAU).sum())
+    print("DEEP_NEAR[%r] = %d" % (case, near))
+    S.case_conditions("case %s, two samples on %d earlier" % (case, deep), [(None, None, None, margins)],
+                      [launch_spreads(oracle, case, size, deep, 2, scale=float(deep + 2))])
+    frames = sorted({0, 1, 2, 5, DEEP, deep, deep + 1})
+    for f in frames:
+        seconds += noisy_samples(oracle, case, size, f)[2]
+    print("case %s: the noisy runs of %d frames took %.2f s of CPU time" % (case, len(frames), seconds))
+    assert near <= NEAR_TIE_MAX * N and near == DEEP_NEAR[case]
+
+
+def test_the_spreads_see_a_weight_one_frame_off_at_depth(rpt, oracle):
+    """v = 1 / (f + 2) from frame 500 on, rounded to f32, as a device's frame 1000 of case A scaled as the GPU comparison (a) scales
+    it: a part in a thousand, within REL_CLEAN on every clean sample — the blind spot that comparison had — and beyond their own
+    tolerance on at least 10.  At frame 5 the fault is not there and nothing moves."""
+    size = SIZES[0]
+    pixels = draws("A")[size]
+    for k, sees in ((DEEP, True), (5, False)):
+        rad, marg = restated(oracle, "A", size, k)
+        mean = frame_f64(None, oracle, SEED, pixels, 64, 48, k, 1, sample_frame=lambda f: restated(oracle, "A", size, f), weight_late_from=500)[0]
+        entries, spreads, faulty = [(SEED, pixels, rad, marg)], [sample_spreads(oracle, "A", size, k)], [(mean[:, :3] * float(k + 1), marg)]
+        if sees:
+            S.teeth("v = 1 / (f + 2) from frame 500 (case A, frame %d)" % k, entries, spreads, faulty)
+        else:
+            assert np.array_equal(faulty[0][0], S._radiance(rad) * (1.0 / (k + 1)) * float(k + 1))
+
+
+def test_the_blend_keeps_its_bits_with_the_noise_mode_off(rpt, oracle):
+    """frame_f64's blend with the noise mode off is the plain float64 running mean, bit for bit; with it on, it moves."""
+    pixels = GRID[::6]
+    sf = sample_frame_of(oracle, FLAT, 9, pixels, 64, 48)
+    samples = {f: sf(f) for f in (DEEP, DEEP + 1, DEEP + 2)}
+    acc = np.random.default_rng(5).uniform(0.0, 2.0, (len(pixels), 4))
+    want = acc.copy()
+    for f in sorted(samples):
+        v = 1.0 / (f + 1)
+        c = np.concatenate([np.nan_to_num(samples[f][0]), np.ones((len(pixels), 1))], axis=1)
+        want = (1.0 - v) * want + c * v
+    assert np.isfinite(np.concatenate([r for r, _ in samples.values()])).all()
+    got = frame_f64(None, oracle, 9, pixels, 64, 48, DEEP, 3, acc=acc, sample_frame=lambda f: samples[f])[0]
+    assert np.array_equal(got, want)
+    with P.perturbed(0, 0):
+        moved = frame_f64(None, oracle, 9, pixels, 64, 48, DEEP, 3, acc=acc, sample_frame=lambda f: samples[f])[0]
+    assert not np.array_equal(moved, want) and np.abs(moved / want - 1.0).max() < 16 * P.NOISE_EPS
