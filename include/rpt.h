@@ -1773,6 +1773,103 @@ int rpt_denoise_guided_device(rpt_ctx* ctx, const float* pixels_dev, const rpt_g
 int rpt_denoise_guided(rpt_ctx* ctx, const float* pixels, const rpt_guide* guides, float* out, uint32_t width, uint32_t height,
                        uint32_t iterations, float edge_k, float normal_k, float plane_k, uint32_t flags);                                   /* host memory, blocks */
 
+/* ---- temporal accumulation — PROJECT-DEFINED -------------------------------------------------------------------------------------------
+ * Carries samples from one redraw to the next while the camera (or the geometry) moves.  A ColorBuffer's running mean is valid only
+ * while the camera stands still; this step reprojects each pixel's first hit (its rpt_guide of "guided denoiser") into the PREVIOUS
+ * frame, fetches the previous frame's accumulated colour where the previous guides say the same surface was seen, blends the new frame
+ * into it, and carries a per-pixel sample count and the first two moments of luminance in an rpt_history record.  No scene is needed:
+ * the result is a function of the pixels, the two sets of guides, the previous history and the two cameras alone.  The caller keeps
+ * two history buffers and two guide buffers and swaps them every frame.
+ *
+ * Every operation is f32, rounded once, in this order; dot(a, b) = fma(a.x, b.x, fma(a.y, b.y, a.z * b.z)); every quotient is the IEEE
+ * one; min(a, b) = a < b ? a : b; W = (float)width, H = (float)height.
+ *
+ * Host part, once per call.
+ *   From prev_camera, exactly as a render prepares a camera for (prev_camera, width, height) (camera/pinhole.rs:38-54; nothing fused):
+ *     half_width = tan(to_radians(fov_deg) * 0.5)  (the strict tan);  half_height = half_width / (W / H);  o = origin;
+ *     w = (origin - center) / |origin - center|, the length sqrt(x*x + y*y + z*z) summed left to right, three quotients;
+ *     u = cross((0, 1, 0), w);  v = cross(w, u)  (cross(a, b).x = a.y*b.z - a.z*b.y, ...).
+ *   Then gx = 0.5f / (half_width * dot(u, u)) and gy = 0.5f / (half_height * dot(v, v)).  (The reference's camera does not normalise u
+ *   and v: both have the length sqrt(w.x^2 + w.z^2), which is 1 only for a camera that looks horizontally.  A ray through the screen
+ *   point (sx, sy) is u*half_width*(2 sx - 1) + v*half_height*(2 sy - 1) - w, so its u coordinate over its depth is dot(u, u) times
+ *   half_width*(2 sx - 1): the factor belongs in the inverse.)
+ *   From camera: the frame-invariant part of a render's camera ray for (camera, width, height): rd0 = lower_left - origin, horizontal,
+ *   vertical, psx = 1 / W, psy = 1 / H.
+ *   IDENTITY mode: the two rpt_camera records are equal word for word and prev_positions is NULL.
+ *
+ * Per pixel (x, y), row 0 on top, i = y * width + x, g = guides[i]:
+ *   1 what to reproject.  g.kind != RPT_HIT_NONE: src = prev_positions[i] (xyz) if given, else g.position; d = src - o.
+ *     g.kind == RPT_HIT_NONE (the sky): d is the CURRENT camera's unnormalised ray direction through the pixel's centre, as
+ *     rpt_camera_rays_device computes it before normalising: px = (float)x / W;  py = 1 - ((float)(y + 1) / H);
+ *     s = psx * 0.5f + px;  t = psy * 0.5f + py;  d = (rd0 + horizontal * s) + vertical * t, per component.  The sky reprojects as a
+ *     point at infinity: by the previous camera's orientation only.
+ *   2 project.  lam = -dot(w, d); no history unless lam > 0.  a = dot(u, d) / lam;  b = dot(v, d) / lam;
+ *     sx = fma(a, gx, 0.5f);  sy = fma(b, gy, 0.5f);  fx = fma(sx, W, -0.5f);  fy = fma(1 - sy, H, -0.5f)  — the inverse of the
+ *     camera ray: row 0 on top, pixel centres at integers.  No history unless -1 < fx < W and -1 < fy < H (false for a NaN).
+ *   3 taps.  x0 = floor(fx), wx = fx - x0, likewise y0, wy; taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) in this order with the
+ *     weights (1-wx)*(1-wy), wx*(1-wy), (1-wx)*wy, wx*wy.  In IDENTITY mode steps 2 and 3 are replaced by the single tap q = (x, y)
+ *     with weight 1.
+ *   4 a tap q is VALID when it lies inside the image; prev_history[q].n >= 1 and its rgb, m1 and m2 are all finite;
+ *     prev_guides[q].key == g.key; and, for g.kind != RPT_HIT_NONE, dot(g.ns, prev_guides[q].ns) >= normal_min and
+ *     fma(-(dpl*dpl), kx, 1) > 0 with r = prev_guides[q].position - src, dpl = dot(g.ng, r), kx = plane_k > 0 ? plane_k / dot(d, d) : 0.
+ *     A NaN fails either test.  The distance from the pixel's tangent plane is measured relative to the distance from the previous
+ *     camera, so plane_k is dimensionless as in "guided denoiser".
+ *   5 history.  wsum = the sum of the valid taps' weights, from 0, in tap order; there is history when wsum > 0.  Each of r, g, b, n,
+ *     m1, m2: acc = fma(value_q, weight_q, acc) over the valid taps in order, from 0; h = acc / wsum.
+ *   6 blend.  c = the pixel's rgb; if any channel's exponent bits are all ones (NaN, +-inf) c is black, as in a render's blend.
+ *     L = fma(0.2126f, c.r, fma(0.7152f, c.g, 0.0722f * c.b)).
+ *     With history:    n' = min(n_h + 1, n_max);  al = 1 / n';  out = (1 - al) * h + c * al  (two products and one sum, nothing fused:
+ *                      a render's blend); m1' likewise from m1_h and L, m2' from m2_h and L * L.
+ *     Without history: n' = 1;  out = c;  m1' = L;  m2' = L * L.
+ *     out.alpha = the pixel's alpha;  history[i] = {out.rgb, n', m1', m2', 0, 0}.
+ * Consequences:
+ *   - a static camera (IDENTITY) with n_max >= the number of frames gives the running mean of the frames in a render's blend order,
+ *     bit for bit; max(m2 - m1*m1, 0) is the luminance variance of the samples behind a pixel;
+ *   - once n' reaches n_max the mean becomes an exponential one with al = 1 / n_max;
+ *   - a disoccluded pixel — no valid tap — starts again at n = 1, and so does one whose history holds a NaN or an infinity;
+ *   - a tap of weight 0 (fx or fy an integer) is valid or not like any other and contributes nothing;
+ *   - what a mirror shows is reprojected as if it were painted on the mirror: first-hit guides describe only the first surface, as in
+ *     "guided denoiser"; shadows and highlights that move over a surface lag by about n_max frames.
+ * n_max >= 1 and finite, -1 <= normal_min <= 1, plane_k >= 0 and finite (0 switches the plane test off), both cameras' fields finite
+ * and origin != center, width and height 1..65535 (a tile row or column per workgroup index), flags reserved: 0.  prev_guides, prev_history and prev_camera all NULL: the first frame, no pixel has history
+ * (prev_positions is then ignored).  Defaults that serve 1 spp per redraw: n_max 32, normal_min 0.9, plane_k 1000 (DESIGN.md has what
+ * was tried).
+ *
+ * prev_positions (n x 4 f32, the fourth word ignored) says, per pixel, where the surface point seen there WAS in the previous frame, in
+ * world space: for geometry that moves.  NULL: static geometry.  The library has no producer of it yet: a caller who moves meshes
+ * gathers it from the rpt_hit records (mesh, triangle, u, v) and the previous vertices.
+ *
+ * Arguments and errors.  Every pointer 16-byte aligned and (the _device form) on the context's device; out and history must overlap no
+ * input and not each other.  RPT_ERR_INVALID_ARG for a NULL ctx, a NULL pixels, guides, camera, out or history, some but not all of
+ * prev_guides, prev_history and prev_camera NULL, a misaligned pointer, an argument out of the ranges above or a NaN, flags != 0, and
+ * a width or height of zero or above 65535.  A rejected call writes nothing.  The _device form enqueues one kernel on `stream` and returns; it uses no
+ * memory of the context.  The host form stages through device memory of the context and blocks.
+ *
+ * The kernels (csrc/k_tacc.hip, a code object library of their own) are three forms of one template — first frame, IDENTITY,
+ * reprojecting — one pixel per lane on 32 x 8 tiles; a tap reads 32 of a guide's 64 bytes (position + key, ns + t) and the 32-byte
+ * history record, everything as 16-byte loads and stores.  DESIGN.md ("temporal accumulation") has their registers and rates. */
+typedef struct rpt_history {
+    float rgb[3]; float n;                 /* the accumulated colour; the number of samples behind it, at most n_max */
+    float m1, m2;                          /* the first and second moment of luminance */
+    uint32_t reserved[2];                  /* written 0 */
+} rpt_history;                             /* 32 B */
+
+#if defined(__cplusplus)
+static_assert(sizeof(rpt_history) == 32, "a history record is 32 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(rpt_history) == 32, "a history record is 32 bytes");
+#endif
+
+int rpt_temporal_accumulate_device(rpt_ctx* ctx, const float* pixels_dev, const rpt_guide* guides_dev, const rpt_camera* camera,
+                                   const rpt_guide* prev_guides_dev, const rpt_history* prev_history_dev, const rpt_camera* prev_camera,
+                                   const float* prev_positions_dev /* n x 4 f32, or NULL */, float* out_dev, rpt_history* history_dev,
+                                   uint32_t width, uint32_t height, float n_max, float normal_min, float plane_k, uint32_t flags /* reserved: 0 */,
+                                   void* stream);
+int rpt_temporal_accumulate(rpt_ctx* ctx, const float* pixels, const rpt_guide* guides, const rpt_camera* camera, const rpt_guide* prev_guides,
+                            const rpt_history* prev_history, const rpt_camera* prev_camera, const float* prev_positions /* or NULL */, float* out,
+                            rpt_history* history, uint32_t width, uint32_t height, float n_max, float normal_min, float plane_k,
+                            uint32_t flags);                                                                                             /* host memory, blocks */
+
 /* The same on HOST buffers (upload, convert, download; blocks): what ColorBuffer::convert_to_u8
  * does for a caller that owns a host ColorBuffer (buffer.rs:55-64, frame = width*height*4 bytes). */
 int rpt_convert_to_u8(rpt_ctx* ctx, const float* pixels, uint8_t* frame, uint32_t width, uint32_t height);

@@ -217,6 +217,10 @@ class rpt_guide(C.Structure):
                 ("albedo", F3), ("reserved", C.c_uint32)]
 
 
+class rpt_history(C.Structure):
+    _fields_ = [("rgb", F3), ("n", C.c_float), ("m1", C.c_float), ("m2", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 class rpt_scene_desc(C.Structure):
     _fields_ = [
         ("abi_version", C.c_uint32), ("flags", C.c_uint32),
@@ -320,6 +324,11 @@ SYMBOLS = {
                                             C.c_float, C.c_uint32, C.c_void_p]),
     "rpt_denoise_guided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float,
                                      C.c_uint32]),
+    # temporal accumulation (include/rpt.h, "temporal accumulation"): the two cameras are pointers to rpt_camera
+    "rpt_temporal_accumulate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_void_p]),
+    "rpt_temporal_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_uint32]),
     "rpt_synchronize": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 

@@ -389,6 +389,130 @@ def _convert_to_u8_tensor(pixels, width, height):
     return out
 
 
+def _c_camera(camera):
+    """An rpt_camera from a Pinhole (or an rpt_camera, returned as it is)."""
+    if isinstance(camera, _abi.rpt_camera):
+        return camera
+    c = _abi.rpt_camera()
+    c.origin = _abi.F3(*camera.origin)
+    c.center = _abi.F3(*camera.center)
+    c.fov_deg = camera.fov
+    return c
+
+
+# The defaults of temporal accumulation (DESIGN.md, "temporal accumulation", has what was tried)
+TEMPORAL_N_MAX, TEMPORAL_NORMAL_MIN, TEMPORAL_PLANE_K = 32.0, 0.9, 1000.0
+
+
+class TemporalAccumulator:
+    """Temporal accumulation on the device (include/rpt.h, "temporal accumulation"): carries a frame's samples into the next one while
+    the camera moves.  Owns the two history tensors it swaps, the previous frame's guides and the previous camera.
+
+        acc = TemporalAccumulator(w, h)
+        for each redraw:
+            buf = DeviceColorBuffer(w, h); tracer.render(buf)          # 1 spp of this camera alone
+            shown = acc.accumulate(buf, tracer.denoise_guides(w, h), camera)
+    """
+
+    def __init__(self, width, height, device="cuda:0", n_max=TEMPORAL_N_MAX, normal_min=TEMPORAL_NORMAL_MIN, plane_k=TEMPORAL_PLANE_K):
+        import torch
+        self.width, self.height = int(width), int(height)
+        self.device = torch.device(device)
+        self.n_max, self.normal_min, self.plane_k = float(n_max), float(normal_min), float(plane_k)
+        n = self.width * self.height
+        self._history = [torch.zeros((n, 8), dtype=torch.float32, device=self.device) for _ in range(2)]
+        self._cur = 0                                              # the history tensor the last call wrote
+        self._prev_guides = None
+        self._prev_camera = None
+
+    def reset(self):
+        """Start over: the next accumulate() is a first frame."""
+        self._prev_guides = None
+        self._prev_camera = None
+
+    def accumulate(self, buffer, guides, camera, prev_positions=None, out=None):
+        """Blend `buffer` (a DeviceColorBuffer holding this frame alone) into the reprojected history, on torch's current stream: a new
+        DeviceColorBuffer, or `out` (same size).  `guides`: this frame's rpt_guide records, a contiguous float32 CUDA tensor
+        [height * width, 16] (Tracer.denoise_guides); the accumulator keeps the tensor until the next call, so the caller must not
+        write into it.  `camera`: the Pinhole the frame was rendered with.  `prev_positions`: [height * width, 4] float32 on the
+        device, where each pixel's surface point was in the previous frame, for geometry that moved; None: static geometry."""
+        import torch
+        n = self.width * self.height
+        if not (buffer.width == self.width and buffer.height == self.height and buffer.pixels.device == self.device and buffer.pixels.is_contiguous()):
+            raise ValueError("buffer must be a %d x %d DeviceColorBuffer on %s" % (self.width, self.height, self.device))
+        if not (isinstance(guides, torch.Tensor) and guides.device == self.device and guides.dtype == torch.float32 and tuple(guides.shape) == (n, 16) and
+                guides.is_contiguous()):
+            raise ValueError("guides must be a contiguous float32 CUDA tensor [%d, 16] on the accumulator's device" % n)
+        if prev_positions is not None and not (isinstance(prev_positions, torch.Tensor) and prev_positions.device == self.device and
+                                               prev_positions.dtype == torch.float32 and tuple(prev_positions.shape) == (n, 4) and
+                                               prev_positions.is_contiguous()):
+            raise ValueError("prev_positions must be a contiguous float32 CUDA tensor [%d, 4] on the accumulator's device" % n)
+        if out is None:
+            out = DeviceColorBuffer(self.width, self.height, device=self.device)
+        assert out.width == self.width and out.height == self.height
+        cam = _c_camera(camera)
+        first = self._prev_guides is None
+        prev_hist, hist = self._history[self._cur], self._history[1 - self._cur]
+        ctx = _ctx_for(self.device.index or 0)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        check(lib().rpt_temporal_accumulate_device(
+            ctx, buffer.pixels.data_ptr(), guides.data_ptr(), C.addressof(cam), None if first else self._prev_guides.data_ptr(),
+            None if first else prev_hist.data_ptr(), None if first else C.addressof(self._prev_camera),
+            None if prev_positions is None else prev_positions.data_ptr(), out.pixels.data_ptr(), hist.data_ptr(), self.width, self.height,
+            self.n_max, self.normal_min, self.plane_k, 0, C.c_void_p(stream)), ctx)
+        self._cur = 1 - self._cur
+        self._prev_guides, self._prev_camera = guides, cam
+        out.frames = buffer.frames
+        return out
+
+    def history(self):
+        """The rpt_history records the last accumulate() wrote: float32 [height * width, 8] (rgb, n, m1, m2, 0, 0)."""
+        return self._history[self._cur]
+
+    def samples(self):
+        """The number of samples behind each pixel after the last accumulate(): float32 [height, width]."""
+        return self.history()[:, 3].reshape(self.height, self.width)
+
+    def variance(self):
+        """max(m2 - m1^2, 0): the luminance variance of the samples behind each pixel, float32 [height, width]."""
+        h = self.history()
+        return (h[:, 5] - h[:, 4] * h[:, 4]).clamp_min(0.0).reshape(self.height, self.width)
+
+
+def temporal_accumulate(pixels, guides, camera, prev_guides=None, prev_history=None, prev_camera=None, prev_positions=None,
+                        n_max=TEMPORAL_N_MAX, normal_min=TEMPORAL_NORMAL_MIN, plane_k=TEMPORAL_PLANE_K, device=0):
+    """rpt_temporal_accumulate on numpy arrays (the host form; blocks): `pixels` float32 [height, width, 4], `guides` [height * width,
+    16], the previous frame's `prev_guides`, `prev_history` [height * width, 8] and `prev_camera` all None (the first frame) or all
+    given.  Returns (out [height, width, 4], history [height * width, 8])."""
+    if not (isinstance(pixels, np.ndarray) and pixels.dtype == np.float32 and pixels.ndim == 3 and pixels.shape[2] == 4):
+        raise ValueError("pixels must be a float32 numpy array [height, width, 4]")
+    h, w = pixels.shape[:2]
+    n = w * h
+    pixels = np.ascontiguousarray(pixels)
+    guides = _host_guides(guides, n)
+    if sum(x is None for x in (prev_guides, prev_history, prev_camera)) not in (0, 3):
+        raise ValueError("prev_guides, prev_history and prev_camera must be all None or all given")
+    ptr = lambda a: None if a is None else a.ctypes.data           # noqa: E731
+    if prev_guides is not None:
+        prev_guides = _host_guides(prev_guides, n)
+        if not (isinstance(prev_history, np.ndarray) and prev_history.dtype == np.float32 and prev_history.shape == (n, 8)):
+            raise ValueError("prev_history must be a float32 numpy array [%d, 8]" % n)
+        prev_history = np.ascontiguousarray(prev_history)
+    if prev_positions is not None:
+        if not (isinstance(prev_positions, np.ndarray) and prev_positions.dtype == np.float32 and prev_positions.shape == (n, 4)):
+            raise ValueError("prev_positions must be a float32 numpy array [%d, 4]" % n)
+        prev_positions = np.ascontiguousarray(prev_positions)
+    cam = _c_camera(camera)
+    pcam = None if prev_camera is None else _c_camera(prev_camera)
+    out = np.empty((h, w, 4), np.float32)
+    history = np.empty((n, 8), np.float32)
+    ctx = _ctx_for(device)
+    check(lib().rpt_temporal_accumulate(ctx, pixels.ctypes.data, guides.ctypes.data, C.addressof(cam), ptr(prev_guides), ptr(prev_history),
+                                        None if pcam is None else C.addressof(pcam), ptr(prev_positions), out.ctypes.data, history.ctypes.data, w, h,
+                                        n_max, normal_min, plane_k, 0), ctx)
+    return out, history
+
+
 def comm_unique_id():
     """128 opaque bytes from rank 0 that every rank passes to Tracer(..., rank=, world=, unique_id=) (ncclGetUniqueId)."""
     uid = _abi.rpt_unique_id()

@@ -163,6 +163,17 @@ def gdn_lib_of(lib):
 
 GDN_LIB = gdn_lib_of(LIB)
 
+
+# The kernels of temporal accumulation (k_tacc.hip: tacc_*) are an eighteenth, named, linked and found like the guided denoiser's and
+# for the same reason one directory down, in tacc/ ($ORIGIN/tacc is on the run path of the libraries that load it):
+# tests/test_temporal.py keeps its census.
+def tacc_lib_of(lib):
+    d, base = os.path.split(os.path.abspath(lib))
+    return os.path.join(d, "tacc", os.path.splitext(base)[0] + "_tacc.so")
+
+
+TACC_LIB = tacc_lib_of(LIB)
+
 # One translation unit per kernel class (csrc/kernel_common.h says what each build of them is):
 #   strict    k_small tracks the range tests of the short divide / sqrt; k_compact, k_sdf, k_large, k_mesh test next to every operation
 #   relaxed   the four render TUs once more with hipcc's fast divide / sqrt and FMA contraction: what RPT_RENDER_FAST_MATH selects
@@ -212,6 +223,8 @@ OBJECTS = [
     ("denoise", "denoise.hip", ["-fslp-vectorize"] + PEROP, "both"),
     # the guided denoiser: the pack kernel and the filter's fused and step kernels; GDN_LIB.  Built like denoise.hip
     ("k_gdn", "k_gdn.hip", ["-fslp-vectorize"] + PEROP, "gdn"),
+    # temporal accumulation: one kernel in three forms (first frame, identity, reprojecting); TACC_LIB.  Built like denoise.hip
+    ("k_tacc", "k_tacc.hip", ["-fslp-vectorize"] + PEROP, "tacc"),
     ("capi", "capi.hip", [], "product"),
     ("capi_test", "capi.hip", ["-DRPT_TEST_HOOKS"], "test"),
     ("k_probes", "k_probes.hip", [], "test"),
@@ -265,14 +278,14 @@ def _deps():
 
 
 def needs_build(lib=LIB, mesh_lib=None, refit_lib=None, build_lib=None, move_lib=None, smooth_lib=None, light_lib=None, tex_lib=None, env_lib=None,
-                cut_lib=None, nrm_lib=None, mmap_lib=None, emap_lib=None, med_lib=None, query_lib=None, rad_lib=None, gdn_lib=None):
-    """`mesh_lib`, `refit_lib`, `build_lib`, `move_lib`, `smooth_lib`, `light_lib`, `tex_lib`, `env_lib`, `cut_lib`, `nrm_lib`, `mmap_lib`, `emap_lib`, `med_lib`, `query_lib`, `rad_lib`, `gdn_lib`: the
+                cut_lib=None, nrm_lib=None, mmap_lib=None, emap_lib=None, med_lib=None, query_lib=None, rad_lib=None, gdn_lib=None, tacc_lib=None):
+    """`mesh_lib`, `refit_lib`, `build_lib`, `move_lib`, `smooth_lib`, `light_lib`, `tex_lib`, `env_lib`, `cut_lib`, `nrm_lib`, `mmap_lib`, `emap_lib`, `med_lib`, `query_lib`, `rad_lib`, `gdn_lib`, `tacc_lib`: the
     code object libraries `lib` loads (default mesh_lib_of(lib), refit_lib_of(lib), build_lib_of(lib), move_lib_of(lib), smooth_lib_of(lib), light_lib_of(lib),
-    tex_lib_of(lib), env_lib_of(lib), cut_lib_of(lib), nrm_lib_of(lib), mmap_lib_of(lib), emap_lib_of(lib), med_lib_of(lib), query_lib_of(lib), rad_lib_of(lib), gdn_lib_of(lib); the test build loads the product's)."""
+    tex_lib_of(lib), env_lib_of(lib), cut_lib_of(lib), nrm_lib_of(lib), mmap_lib_of(lib), emap_lib_of(lib), med_lib_of(lib), query_lib_of(lib), rad_lib_of(lib), gdn_lib_of(lib), tacc_lib_of(lib); the test build loads the product's)."""
     parts = [lib, mesh_lib or mesh_lib_of(lib), refit_lib or refit_lib_of(lib), build_lib or build_lib_of(lib), move_lib or move_lib_of(lib),
              smooth_lib or smooth_lib_of(lib), light_lib or light_lib_of(lib), tex_lib or tex_lib_of(lib), env_lib or env_lib_of(lib),
              cut_lib or cut_lib_of(lib), nrm_lib or nrm_lib_of(lib), mmap_lib or mmap_lib_of(lib), emap_lib or emap_lib_of(lib), med_lib or med_lib_of(lib), query_lib or query_lib_of(lib),
-             rad_lib or rad_lib_of(lib), gdn_lib or gdn_lib_of(lib)]
+             rad_lib or rad_lib_of(lib), gdn_lib or gdn_lib_of(lib), tacc_lib or tacc_lib_of(lib)]
     if not all(os.path.exists(p) for p in parts):
         return True
     t = min(os.path.getmtime(p) for p in parts)
@@ -286,7 +299,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
     if not force and not needs_build(lib) and (test_lib is None or not needs_build(test_lib, mesh_lib_of(lib), refit_lib_of(lib), build_lib_of(lib), move_lib_of(lib),
                                                                          smooth_lib_of(lib), light_lib_of(lib), tex_lib_of(lib), env_lib_of(lib), cut_lib_of(lib),
                                                                          nrm_lib_of(lib), mmap_lib_of(lib), emap_lib_of(lib), med_lib_of(lib), query_lib_of(lib), rad_lib_of(lib),
-                                                                         gdn_lib_of(lib))):
+                                                                         gdn_lib_of(lib), tacc_lib_of(lib))):
         return lib
     objdir = os.path.join(HERE, objdir_name)
     os.makedirs(objdir, exist_ok=True)
@@ -318,11 +331,12 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
     mesh_lib, refit_lib, build_lib, move_lib, smooth_lib = mesh_lib_of(lib), refit_lib_of(lib), build_lib_of(lib), move_lib_of(lib), smooth_lib_of(lib)
     light_lib, tex_lib, env_lib, cut_lib, nrm_lib = light_lib_of(lib), tex_lib_of(lib), env_lib_of(lib), cut_lib_of(lib), nrm_lib_of(lib)
     mmap_lib, emap_lib, med_lib, query_lib = mmap_lib_of(lib), emap_lib_of(lib), med_lib_of(lib), query_lib_of(lib)
-    rad_lib, gdn_lib = rad_lib_of(lib), gdn_lib_of(lib)
+    rad_lib, gdn_lib, tacc_lib = rad_lib_of(lib), gdn_lib_of(lib), tacc_lib_of(lib)
     os.makedirs(os.path.dirname(gdn_lib), exist_ok=True)
+    os.makedirs(os.path.dirname(tacc_lib), exist_ok=True)
     for part, kind in ((mesh_lib, "mesh"), (refit_lib, "refit"), (build_lib, "bvhbuild"), (move_lib, "move"), (smooth_lib, "smooth"), (light_lib, "light"),
                        (tex_lib, "tex"), (env_lib, "env"), (cut_lib, "cut"), (nrm_lib, "nrm"), (mmap_lib, "mmap"), (emap_lib, "emap"), (med_lib, "med"), (query_lib, "query"),
-                       (rad_lib, "rad"), (gdn_lib, "gdn")):
+                       (rad_lib, "rad"), (gdn_lib, "gdn"), (tacc_lib, "tacc")):
         link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w == kind] + [
             "-Wl,-soname," + os.path.basename(part), "-o", part]
         if verbose:
@@ -334,7 +348,7 @@ def build(force=False, verbose=False, extra_flags=(), lib=LIB, objdir_name="buil
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared"] + [o for o, w in objs.values() if w in kinds] + [
             mesh_lib, refit_lib, build_lib, move_lib, smooth_lib, light_lib, tex_lib, env_lib, cut_lib, nrm_lib, mmap_lib, emap_lib, med_lib, query_lib, rad_lib, gdn_lib,
-            "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/gdn", "-ldl", "-o", out]
+            tacc_lib, "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/gdn", "-Wl,-rpath,$ORIGIN/tacc", "-ldl", "-o", out]
         if verbose:
             print(" ".join(link))
         subprocess.run(link, check=True, cwd=CSRC)

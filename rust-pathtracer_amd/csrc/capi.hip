@@ -31,6 +31,7 @@
 #include "host_nrm.h"
 #include "host_refit.h"
 #include "host_smooth.h"
+#include "host_tacc.h"
 #include "host_tex.h"
 #include "host_upload.h"
 #include "knobs.h"
@@ -48,6 +49,7 @@
 #include "launch_query.h"
 #include "launch_rad.h"
 #include "launch_smooth.h"
+#include "launch_tacc.h"
 #include "launch_tex.h"
 #include "mesh_args.h"
 #include "mesh_args_mmap.h"
@@ -3028,6 +3030,92 @@ int rpt_denoise_guided(rpt_ctx* ctx, const float* pixels, const rpt_guide* guide
     RPT_HIP_CHECK(ctx, hipMemcpyAsync(guides_dev, guides, 4u * bytes, hipMemcpyHostToDevice, d.stream));
     RPT_CHECK_RC(rpt_denoise_guided_device(ctx, d.fb, guides_dev, out_dev, width, height, iterations, edge_k, normal_k, plane_k, flags, d.stream));
     RPT_HIP_CHECK(ctx, hipMemcpyAsync(out, out_dev, bytes, hipMemcpyDeviceToHost, d.stream));
+    RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
+    return RPT_OK;
+}
+
+// ---- temporal accumulation (include/rpt.h, "temporal accumulation") ---------------------------------------------------------------------
+// Everything but alignment and overlap: the NULL rules, the ranges (a NaN fails every comparison), the cameras.  NULL: acceptable.
+static const char* tacc_args_bad(const void* pixels, const void* guides, const rpt_camera* camera, const void* prev_guides, const void* prev_history,
+                                 const rpt_camera* prev_camera, const void* out, const void* history, uint32_t width, uint32_t height, float n_max,
+                                 float normal_min, float plane_k, uint32_t flags)
+{
+    if (!pixels || !guides || !camera || !out || !history) return "pixels, guides, camera, out and history must not be NULL";
+    const int prevs = (prev_guides ? 1 : 0) + (prev_history ? 1 : 0) + (prev_camera ? 1 : 0);
+    if (prevs != 0 && prevs != 3) return "prev_guides, prev_history and prev_camera must be all NULL (the first frame) or all given";
+    if (width == 0 || height == 0 || width > 65535u || height > 65535u) return "width and height must be 1..65535";
+    if (!(n_max >= 1.0f) || !std::isfinite(n_max) || !(normal_min >= -1.0f && normal_min <= 1.0f) || !(plane_k >= 0.0f) || !std::isfinite(plane_k) || flags != 0u)
+        return "invalid argument (n_max >= 1, -1 <= normal_min <= 1, plane_k >= 0, all finite, flags 0)";
+    if (!rpthost::tacc_camera_ok(*camera) || (prev_camera && !rpthost::tacc_camera_ok(*prev_camera))) return "a camera's fields must be finite and origin != center";
+    return nullptr;
+}
+
+int rpt_temporal_accumulate_device(rpt_ctx* ctx, const float* pixels_dev, const rpt_guide* guides_dev, const rpt_camera* camera, const rpt_guide* prev_guides_dev,
+                                   const rpt_history* prev_history_dev, const rpt_camera* prev_camera, const float* prev_positions_dev, float* out_dev,
+                                   rpt_history* history_dev, uint32_t width, uint32_t height, float n_max, float normal_min, float plane_k, uint32_t flags,
+                                   void* stream)
+{
+    if (!ctx) { set_err(nullptr, "rpt_temporal_accumulate_device: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (const char* why = tacc_args_bad(pixels_dev, guides_dev, camera, prev_guides_dev, prev_history_dev, prev_camera, out_dev, history_dev, width, height, n_max,
+                                        normal_min, plane_k, flags)) {
+        set_err(ctx, "rpt_temporal_accumulate_device: %s", why);
+        return RPT_ERR_INVALID_ARG;
+    }
+    if ((((uintptr_t)pixels_dev | (uintptr_t)guides_dev | (uintptr_t)prev_guides_dev | (uintptr_t)prev_history_dev | (uintptr_t)prev_positions_dev |
+          (uintptr_t)out_dev | (uintptr_t)history_dev) & 15u) != 0) {
+        set_err(ctx, "rpt_temporal_accumulate_device: buffers must be 16-byte aligned");
+        return RPT_ERR_INVALID_ARG;
+    }
+    const size_t px = (size_t)width * height;
+    const struct { const void* p; size_t bytes; } ins[5] = {{pixels_dev, 16u * px}, {guides_dev, 64u * px}, {prev_guides_dev, 64u * px},
+                                                           {prev_history_dev, 32u * px}, {prev_positions_dev, 16u * px}};
+    const auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+        const char *x = (const char*)a, *y = (const char*)b;
+        return x < y + nb && y < x + na;
+    };
+    bool clash = overlap(out_dev, 16u * px, history_dev, 32u * px);
+    for (const auto& in : ins)
+        if (in.p) clash = clash || overlap(in.p, in.bytes, out_dev, 16u * px) || overlap(in.p, in.bytes, history_dev, 32u * px);
+    if (clash) { set_err(ctx, "rpt_temporal_accumulate_device: out_dev or history_dev overlaps an input or each other"); return RPT_ERR_INVALID_ARG; }
+    RPT_ON_DEVICE(ctx);
+    rptscene::TaccArgs args;
+    const rptscene::TaccForm form = rpthost::tacc_args(*camera, prev_camera, prev_camera && prev_positions_dev, width, height, n_max, normal_min, plane_k, args);
+    RPT_HIP_CHECK(ctx, rptlaunch::tacc_accumulate(form, args, pixels_dev, guides_dev, prev_guides_dev, prev_history_dev,
+                                                  form == rptscene::kTaccReproject ? prev_positions_dev : nullptr, out_dev, history_dev, (hipStream_t)stream));
+    return RPT_OK;
+}
+
+int rpt_temporal_accumulate(rpt_ctx* ctx, const float* pixels, const rpt_guide* guides, const rpt_camera* camera, const rpt_guide* prev_guides,
+                            const rpt_history* prev_history, const rpt_camera* prev_camera, const float* prev_positions, float* out, rpt_history* history,
+                            uint32_t width, uint32_t height, float n_max, float normal_min, float plane_k, uint32_t flags)
+{
+    if (!ctx) { set_err(nullptr, "rpt_temporal_accumulate: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
+    if (const char* why = tacc_args_bad(pixels, guides, camera, prev_guides, prev_history, prev_camera, out, history, width, height, n_max, normal_min, plane_k, flags)) {
+        set_err(ctx, "rpt_temporal_accumulate: %s", why);
+        return RPT_ERR_INVALID_ARG;
+    }
+    RPT_ON_DEVICE(ctx);
+    DevState& d = ctx->devs[0];
+    const size_t unit = (size_t)width * height * 16u;                 // one 16-byte line per pixel
+    // pixels 1, guides 4, prev_guides 4, prev_history 2, prev_positions 1, out 1, history 2 lines per pixel: one allocation
+    RPT_CHECK_RC(ensure_fb(ctx, d, 15u * unit));
+    char* base = reinterpret_cast<char*>(d.fb);
+    char *px_d = base, *g_d = base + unit, *pg_d = base + 5u * unit, *ph_d = base + 9u * unit, *pp_d = base + 11u * unit, *out_d = base + 12u * unit,
+         *hist_d = base + 13u * unit;
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(px_d, pixels, unit, hipMemcpyHostToDevice, d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(g_d, guides, 4u * unit, hipMemcpyHostToDevice, d.stream));
+    if (prev_guides) {
+        RPT_HIP_CHECK(ctx, hipMemcpyAsync(pg_d, prev_guides, 4u * unit, hipMemcpyHostToDevice, d.stream));
+        RPT_HIP_CHECK(ctx, hipMemcpyAsync(ph_d, prev_history, 2u * unit, hipMemcpyHostToDevice, d.stream));
+        if (prev_positions) RPT_HIP_CHECK(ctx, hipMemcpyAsync(pp_d, prev_positions, unit, hipMemcpyHostToDevice, d.stream));
+    }
+    RPT_CHECK_RC(rpt_temporal_accumulate_device(ctx, reinterpret_cast<const float*>(px_d), reinterpret_cast<const rpt_guide*>(g_d), camera,
+                                                prev_guides ? reinterpret_cast<const rpt_guide*>(pg_d) : nullptr,
+                                                prev_guides ? reinterpret_cast<const rpt_history*>(ph_d) : nullptr, prev_camera,
+                                                prev_guides && prev_positions ? reinterpret_cast<const float*>(pp_d) : nullptr, reinterpret_cast<float*>(out_d),
+                                                reinterpret_cast<rpt_history*>(hist_d), width, height, n_max, normal_min, plane_k, flags, d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(out, out_d, unit, hipMemcpyDeviceToHost, d.stream));
+    RPT_HIP_CHECK(ctx, hipMemcpyAsync(history, hist_d, 2u * unit, hipMemcpyDeviceToHost, d.stream));
     RPT_HIP_CHECK(ctx, hipStreamSynchronize(d.stream));
     return RPT_OK;
 }
