@@ -1568,7 +1568,8 @@ int rpt_occluded(rpt_ctx* ctx, const rpt_ray* rays, uint64_t n, uint8_t* occlude
  *
  * Errors.  RPT_ERR_NO_SCENE without a scene; RPT_ERR_UNSUPPORTED for a scene that is not a mesh scene and for a context with more
  * than one local device (an rpt_create_rank context has one and works); RPT_ERR_INVALID_ARG for a NULL ctx, a NULL array with n > 0,
- * a misaligned pointer, flags != 0 (reserved), zero width or height, and more rays than a grid of 0x7FFFFFFF workgroups of 256 holds.
+ * a misaligned pointer, flags != 0 (reserved), zero width or height, more rays than a grid of 0x7FFFFFFF workgroups of 256 holds, and
+ * frames_done + spp > 2^64 - 1 (the launch domain, rpt_render: frames_done is a stream selector here, and every 64-bit value is one).
  * A rejected call writes nothing.  rpt_debug_mesh_form and rpt_debug_kernel_choice (rpt_test.h) keep reporting the last RENDER launch.
  *
  * The kernels (csrc/k_rad.hip, a code object library of their own) are nine: the render's path-regenerating state machine over a
@@ -1586,7 +1587,15 @@ int rpt_camera_sample_rays_device(rpt_ctx* ctx, uint32_t width, uint32_t height,
  *   spp         number of render() calls to fold into this one; spp = 1 is exactly
  *               one reference render(); spp = S is bit-identical to S calls
  *   seed        RNG seed (the reference's thread_rng, tracer.rs:44, is unseedable)
- * Blocks until `pixels` holds the result. */
+ * Blocks until `pixels` holds the result.
+ *
+ * The launch domain — PROJECT-DEFINED.  Every 64-bit value of frames_done and of seed is a frame and a seed of its own: both words
+ * of either enter the stream's key (frame_key), and sample s is frame frames_done + s in 64-bit arithmetic wherever a call is cut
+ * into launches or chunks.  The weight of frame f is 1 / (float)(f + 1), the conversion rounded to nearest even (exact below 2^24).
+ * The domain ends at frames_done + spp <= 2^64 - 1: one sample further f + 1 wraps to 0, the weight is infinite and the pixel NaN
+ * for good.  Beyond it rpt_render, rpt_render_device, rpt_resident_render (against the resident counter) and
+ * rpt_radiance / rpt_radiance_device return RPT_ERR_INVALID_ARG and write nothing; spp == 0 is inside it for every frames_done.
+ * width or height may be 1.  tests/test_launch_domain.py and tests/test_gpu_launch_domain.py hold the ends of this domain. */
 int rpt_render(rpt_ctx* ctx, float* pixels, uint32_t width, uint32_t height,
                uint64_t frames_done, uint32_t spp, uint64_t seed, uint32_t flags);
 
@@ -1596,6 +1605,7 @@ int rpt_render(rpt_ctx* ctx, float* pixels, uint32_t width, uint32_t height,
  * (pixels + frames, buffer.rs:6-14): render accumulates into it, and the host fetches either the f32 pixels or
  * directly the gamma-encoded u8 frame (4 B per pixel).  Changing width/height or calling rpt_resident_reset
  * starts a new buffer (ColorBuffer::new, buffer.rs:18-26). */
+/* (the launch domain, rpt_render: resident frames + spp <= 2^64 - 1, else RPT_ERR_INVALID_ARG and neither the buffer nor the counter changes) */
 int rpt_resident_render(rpt_ctx* ctx, uint32_t width, uint32_t height, uint32_t spp, uint64_t seed, uint32_t flags);
 int rpt_resident_frames(const rpt_ctx* ctx, uint64_t* frames);          /* ColorBuffer.frames */
 /* Device time of the last rpt_resident_render's launches (HIP events on the stream they ran on; the slowest of this
@@ -1630,6 +1640,7 @@ int rpt_resident_upload(rpt_ctx* ctx, const float* pixels, uint32_t width, uint3
  * Calls on one context are ordered by the caller (one thread at a time).  The wavefront form of large scenes keeps its paths in
  * buffers of the context: a launch on another stream than the previous one waits (on the device) for that one to finish with
  * them; use one context per render that is to run concurrently. */
+/* (the launch domain, rpt_render: frames_done + spp <= 2^64 - 1, else RPT_ERR_INVALID_ARG and nothing is enqueued) */
 int rpt_render_device(rpt_ctx* ctx, float* pixels_dev, uint32_t width, uint32_t height,
                       uint64_t frames_done, uint32_t spp, uint64_t seed, uint32_t flags,
                       uint32_t tile_rows, uint32_t rank, uint32_t world, void* stream);

@@ -2416,6 +2416,15 @@ int rpt_tile_copy_plan(uint32_t height, uint32_t tile_rows, uint32_t rank, uint3
     return tile_copy_plan(height, tile_rows, rank, world, out);
 }
 
+// The launch domain (include/rpt.h, "the launch domain"): the last frame's count, frames_done + spp, fits 64 bits.  One past it the
+// blend's frames + 1 wraps to 0, the weight is infinite and the pixel NaN for good.
+static bool frames_in_domain(rpt_ctx* ctx, const char* who, uint64_t frames_done, uint32_t spp)
+{
+    if ((uint64_t)spp <= UINT64_MAX - frames_done) return true;
+    set_err(ctx, "%s: frames_done + spp exceeds 2^64 - 1 (frames_done=%llu spp=%u)", who, (unsigned long long)frames_done, spp);
+    return false;
+}
+
 int rpt_render_device(rpt_ctx* ctx, float* pixels_dev, uint32_t width, uint32_t height, uint64_t frames_done, uint32_t spp,
                       uint64_t seed, uint32_t flags, uint32_t tile_rows, uint32_t rank, uint32_t world, void* stream)
 {
@@ -2428,6 +2437,7 @@ int rpt_render_device(rpt_ctx* ctx, float* pixels_dev, uint32_t width, uint32_t 
     }
     if ((uint64_t)width * height > 0xFFFFFFFFull) { set_err(ctx, "rpt_render_device: image too large for 32-bit pixel indices"); return RPT_ERR_INVALID_ARG; }
     if (((uintptr_t)pixels_dev & 15u) != 0) { set_err(ctx, "rpt_render_device: pixels must be 16-byte aligned"); return RPT_ERR_INVALID_ARG; }
+    if (!frames_in_domain(ctx, "rpt_render_device", frames_done, spp)) return RPT_ERR_INVALID_ARG;
     if (spp == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
     return launch_render(ctx, ctx->devs[0], pixels_dev, width, height, frames_done, spp, seed, flags, tile_rows, rank, world, (hipStream_t)stream);
@@ -2439,6 +2449,7 @@ int rpt_render(rpt_ctx* ctx, float* pixels, uint32_t width, uint32_t height, uin
     if (!ctx) { set_err(nullptr, "rpt_render: ctx is NULL"); return RPT_ERR_INVALID_ARG; }
     if (!pixels || width == 0 || height == 0) { set_err(ctx, "rpt_render: invalid argument"); return RPT_ERR_INVALID_ARG; }
     if ((uint64_t)width * height > 0xFFFFFFFFull) { set_err(ctx, "rpt_render: image too large for 32-bit pixel indices"); return RPT_ERR_INVALID_ARG; }
+    if (!frames_in_domain(ctx, "rpt_render", frames_done, spp)) return RPT_ERR_INVALID_ARG;
     if (ctx->scene.kind == SceneKind::none) { set_err(ctx, "rpt_render: no scene uploaded"); return RPT_ERR_NO_SCENE; }
     if ((size_t)ctx->world != ctx->devs.size()) {
         set_err(ctx, "rpt_render: a host ColorBuffer needs every rank in this process (rpt_create / rpt_create_multi); "
@@ -2562,12 +2573,19 @@ int rpt_resident_reset(rpt_ctx* ctx)
     return RPT_OK;
 }
 
+// whether the resident buffer is one of this size and tiling: resident_begin then keeps it, and its frame counter
+static bool resident_matches(const rpt_ctx* ctx, uint32_t width, uint32_t height)
+{
+    const uint32_t tile_rows = ctx->plain() ? height : ctx->tile_rows;
+    return ctx->has_res && ctx->res_w == width && ctx->res_h == height && ctx->res_tile_rows == tile_rows;
+}
+
 // ColorBuffer::new(width, height) (buffer.rs:18-26) as per-rank tiles
 static int resident_begin(rpt_ctx* ctx, uint32_t width, uint32_t height)
 {
     const uint32_t world = (uint32_t)ctx->world;
     const uint32_t tile_rows = ctx->plain() ? height : ctx->tile_rows;
-    if (ctx->has_res && ctx->res_w == width && ctx->res_h == height && ctx->res_tile_rows == tile_rows) return RPT_OK;
+    if (resident_matches(ctx, width, height)) return RPT_OK;
     int rc = rpt_resident_reset(ctx);
     if (rc != RPT_OK) return rc;
     const uint32_t rows_padded = rows_padded_for(height, tile_rows, world);
@@ -2590,6 +2608,8 @@ int rpt_resident_render(rpt_ctx* ctx, uint32_t width, uint32_t height, uint32_t 
     if (width == 0 || height == 0) { set_err(ctx, "rpt_resident_render: invalid argument"); return RPT_ERR_INVALID_ARG; }
     if ((uint64_t)width * height > 0xFFFFFFFFull) { set_err(ctx, "rpt_resident_render: image too large for 32-bit pixel indices"); return RPT_ERR_INVALID_ARG; }
     if (ctx->scene.kind == SceneKind::none) { set_err(ctx, "rpt_resident_render: no scene uploaded"); return RPT_ERR_NO_SCENE; }
+    // against the resident counter, which a buffer of another size starts again from 0; checked before resident_begin touches anything
+    if (!frames_in_domain(ctx, "rpt_resident_render", resident_matches(ctx, width, height) ? ctx->res_frames : 0u, spp)) return RPT_ERR_INVALID_ARG;
     int rc = resident_begin(ctx, width, height);
     if (rc != RPT_OK) return rc;
     DeviceGuard guard(ctx->devs[0].device);
@@ -3391,6 +3411,7 @@ int rpt_radiance_device(rpt_ctx* ctx, const rpt_ray* rays_dev, uint64_t n, float
     int rc;
     const void* const ptrs[2] = {rays_dev, out_dev};
     if (!query_ready(ctx, "rpt_radiance_device", flags, ptrs, 2, nullptr, n, true, &rc)) return rc;
+    if (!frames_in_domain(ctx, "rpt_radiance_device", frames_done, spp)) return RPT_ERR_INVALID_ARG;
     if (spp == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
     return launch_radiance(ctx, ctx->devs[0], rays_dev, n, out_dev, frames_done, spp, seed, first_index, (hipStream_t)stream);
@@ -3402,6 +3423,7 @@ int rpt_radiance(rpt_ctx* ctx, const rpt_ray* rays, uint64_t n, float* out, uint
     int rc;
     const void* const ptrs[2] = {rays, out};
     if (!query_ready(ctx, "rpt_radiance", flags, ptrs, 2, nullptr, n, false, &rc)) return rc;
+    if (!frames_in_domain(ctx, "rpt_radiance", frames_done, spp)) return RPT_ERR_INVALID_ARG;
     if (spp == 0) return RPT_OK;
     RPT_ON_DEVICE(ctx);
     DevState& d = ctx->devs[0];

@@ -19,7 +19,9 @@ Three planted faults, each by a keyword argument, each in one place:
   weight_off_by_one         v = 1 / f, and 1 at f = 0 (invisible in a one-sample launch at a frame so late that 1 / f and 1 / (f + 1)
                             are REL_CLEAN apart or less: the comparison scales the device's pixel by f + 1)
 tests/test_mesh_frames_f64.py (CPU) counts what each moves; tests/test_gpu_mesh_frames_f64.py holds the device to frame_f64.
-A fourth, subtle one: weight_late_from = F takes v = 1 / (f + 2) from frame F on (a running mean one frame off at high counts, a
+A fourth, for the ends of the launch domain (tests/test_launch_domain.py): frame_low_word_only keys sample s by
+(frames_done + s) & 0xFFFFFFFF, a frame counter truncated to 32 bits (invisible below 2^32).
+A fifth, subtle one: weight_late_from = F takes v = 1 / (f + 2) from frame F on (a running mean one frame off at high counts, a
 part in a thousand at f = 1000), which only the samples' own f32 tolerances see (tests/f32_spread.py).
 
 Under pt_f64's noise mode the blend carries what the device rounds in f32: the weight 1 / (f + 1), each of the two products and the
@@ -33,7 +35,7 @@ from mesh_compose_f64 import sample_pixels
 
 
 def frame_f64(path, oracle, seed, pixels, w, h, frames_done, n, acc=None, sample_frame=None,
-              frame_ignored=False, key_without_frames_done=False, weight_off_by_one=False, weight_late_from=None):
+              frame_ignored=False, key_without_frames_done=False, weight_off_by_one=False, weight_late_from=None, frame_low_word_only=False):
     """A launch of `n` samples on top of `frames_done` earlier frames, for `pixels` [(col, row)] ->
     (mean [p, 4], margins [p], samples [p, n, 3]).
 
@@ -47,7 +49,7 @@ def frame_f64(path, oracle, seed, pixels, w, h, frames_done, n, acc=None, sample
     samples = np.zeros((len(pixels), n, 3))
     for s in range(n):
         frame = frames_done + s
-        stream = 0 if frame_ignored else s if key_without_frames_done else frame
+        stream = 0 if frame_ignored else s if key_without_frames_done else frame & 0xFFFFFFFF if frame_low_word_only else frame
         rad, marg = sample_frame(stream)
         samples[:, s] = rad
         margins = np.minimum(margins, marg)
